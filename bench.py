@@ -14,11 +14,16 @@ synthetic data are generated outside it.  `resident` in the JSON line is the sam
 clock (what the rules call the kernel-side figure).  With N GPUs every rank refines its own batch per step (weak scaling, no
 data-path collective) and the value is the whole-job rate N * R * region_kb * K / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--length L] [--events E] [--regions-per-gpu R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--length L] [--events E] [--regions-per-gpu R] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 with
+A plain run generates the inputs (seeded: the same arguments give the same inputs), runs W warm-up and K timed steps and prints
+ONE JSON line on rank 0: metric, value (kb/s), unit, higher_is_better, dtype, ms_per_step (one timed step), steps, warmup, config.
+--dump-outputs DIR writes what the last timed step returned for rank 0's regions (consensus sequences and accuracies) as .npy
+files (see dump_outputs).  --full measures and checks everything else as well, adding to the line
+  resident        the same measurement with the load left out of the clock (above)
+  batch_done_s, library, device_memory, accuracy
   roofline        the dominant kernel class: HIP events around every launch on the launching stream INSIDE the timed steps
                   (queued, read after each host thread's work): algorithmic bytes per launch / average launch duration
                   against the HBM peak; `traffic` from the committed rocprofv3 PMC measurement of the same command
@@ -96,6 +101,76 @@ def _cpu_baseline_children(args):
     return {"cpu": cpu, "t1k": t1k, "use_ref": use_ref}
 
 
+def _region_unaligned(job):
+    """synth.make_region up to its Smith-Waterman call, which needs the GPU: (draft, events before mapaligns, truth).  Pure numpy
+    on seeded streams, so it runs in worker processes: make_region(draft_error=0) builds the same truth and events without aligning
+    anything, and the draft is drawn from the same child stream (kids[1]) make_region draws it from"""
+    import numpy as np
+    from poreseq_amd import synth
+    from poreseq_amd.util import DEFAULT_PARAMS
+    length, events, seed, draft_error = job
+    params = dict(DEFAULT_PARAMS, verbose=0)
+    truth, evs, _ = synth.make_region(length, events, seed, None, params, draft_error=0.0)
+    rngd = np.random.default_rng(np.random.SeedSequence(seed).spawn(events + 2)[1])
+    return synth.corrupt(rngd, truth, draft_error, draft_error, draft_error), evs, truth
+
+
+def _align_region(part, swalign):
+    """the rest of synth.make_region: the events' truth alignment re-mapped onto the draft"""
+    import numpy as np
+    draft, evs, truth = part
+    pairs = np.array(swalign(truth, draft)[1])
+    for ev in evs:
+        ev.mapaligns(pairs)
+    return draft, evs, truth
+
+
+def _unaligned_regions(jobs, local_world=1):
+    """An iterator over _region_unaligned of every job, in order, computed by up to 16 worker processes per GPU of the node.  The
+    workers start at this call (before this process touches the GPU, like the CPU baseline's) and keep working while the caller
+    sets up the GPU and consumes the first results."""
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:   # pragma: no cover
+        cpus = os.cpu_count() or 1
+    nproc = max(1, min(16, cpus // max(1, local_world), len(jobs)))
+    if nproc == 1:
+        return (_region_unaligned(j) for j in jobs)
+    import multiprocessing as mp
+    pool = mp.get_context("spawn").Pool(nproc)
+    parts = pool.imap(_region_unaligned, jobs, chunksize=max(1, len(jobs) // (8 * nproc)))
+
+    def results():
+        try:
+            yield from parts
+            pool.close()
+            pool.join()
+        finally:
+            pool.terminate()
+    return results()
+
+
+def dump_outputs(path, results, limit_bytes=64 << 20):
+    """What the timed path hands its caller for the regions of one step, [(consensus sequence, accuracy %)] in region order, as
+    .npy files under `path`: consensus_bases.npy (float32, regions x longest sequence: the ASCII code of every base, 0 past the
+    end), consensus_lengths.npy and consensus_accuracy.npy (float64), region_index.npy (float64: the regions written).  When the
+    bases would exceed `limit_bytes`, a fixed seeded sample of the regions is written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = len(results)
+    width = max([len(s) for s, _ in results] + [1])
+    keep = max(1, min(n, (limit_bytes - 64 * n) // (4 * width + 24)))
+    idx = np.arange(n) if keep >= n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    bases = np.zeros((len(idx), width), dtype=np.float32)
+    for row, i in enumerate(idx):
+        s = np.frombuffer(results[i][0].encode("ascii"), dtype=np.uint8)
+        bases[row, :s.size] = s
+    np.save(os.path.join(path, "consensus_bases.npy"), bases)
+    np.save(os.path.join(path, "consensus_lengths.npy"), np.array([len(results[i][0]) for i in idx], dtype=np.float64))
+    np.save(os.path.join(path, "consensus_accuracy.npy"), np.array([results[i][1] for i in idx], dtype=np.float64))
+    np.save(os.path.join(path, "region_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,10 +185,18 @@ def main():
     ap.add_argument("--stream", action="store_true",
                     help="let the timed steps' batches stream through the slots (default: every step finishes before the next one's batches "
                          "start; measured the same on one MI355X: 141.1 against 140.5 kb/s)")
-    ap.add_argument("--cpu-length", type=int, default=1000, help="region length of the CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true", help="skip everything that touches the CPU checkers (oracle / reference)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-region, 1 kb and profiled passes (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: CPU baseline, single-region / 1 kb / variant passes, per-launch kernel "
+                         "profile of the timed steps and roofline, parity against the reference's digests, accuracy, resident rate, "
+                         "library and device-memory report")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's regions) as DIR/<name>.npy")
+    ap.add_argument("--cpu-length", type=int, default=1000, help="region length of the CPU baseline sample (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="skip everything that touches the CPU checkers (oracle / reference) (--full)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the single-region, 1 kb and profiled passes (profiling runs) (--full)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus != world_env:
@@ -124,8 +207,20 @@ def main():
     # The CPU baseline runs in child processes (the reference is single-threaded; its only parallel mode is one process per
     # region, README.md:48-54).  They are started HERE, before anything in this process touches the GPU.
     cpu_pre = None
-    if world_env == 1 and not args.no_cpu:
+    if args.full and world_env == 1 and not args.no_cpu:
         cpu_pre = _cpu_baseline_children(args)
+
+    # synthetic inputs for every step of this rank, generated outside the timed region: (at most three distinct sets: generating
+    # 25 x 280 regions would take longer than refining them; later steps go round the sets — every step recomputes everything,
+    # nothing is cached between steps).  The numpy part of synth.make_region runs in worker processes, also started before this
+    # process touches the GPU; the alignment onto the draft follows in a batch slot below, as their results arrive.
+    R = max(1, args.regions_per_gpu)
+    nsteps = args.warmup + args.steps
+    nsets = min(nsteps, 3)
+    rank_env = int(os.environ.get("RANK", "0"))
+    seeds = [1002 + 100000 * rank_env + 1000 * k + s for s in range(nsets) for k in range(R)]
+    unaligned = _unaligned_regions([(args.length, args.events, sd, 0.04) for sd in seeds],
+                                   int(os.environ.get("LOCAL_WORLD_SIZE", str(world_env))))
 
     from poreseq_amd import dist as psdist
     rank, local, world = psdist.init()
@@ -214,8 +309,10 @@ def main():
                 items.append({"step": si, "k": k, "n": n, "pas": pas, "rb": RegionBatch(pas), "out": None, "done": 0.0, "load": 0.0})
         profs = []
         plock = threading.Lock()
+        prof = timed and args.full
         if timed:
-            on_every_slot(lambda: (api.prof_reset(), api.prof_enable(2)))   # HIP events around every hot-kernel launch, read after the work
+            if prof:
+                on_every_slot(lambda: (api.prof_reset(), api.prof_enable(2)))   # HIP events around every hot-kernel launch, read after the work
             psdist.barrier()
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
@@ -237,6 +334,9 @@ def main():
         if errs:
             raise errs[0]
         if timed:
+            batch_done_s.append(sorted(round(it["done"], 3) for it in items))
+            load_s.append(sum(it["load"] for it in items) / NB)
+        if prof:
             def collect():
                 p = {c: list(api.prof_get(c)) + [api.prof_units(c)] for c in KERNEL_OF}
                 p["_forms"] = [api.prof_get(c)[1] for c in ("sweep_w2", "sweep_w4", "sweep_kept")]   # host-side launch counts by form
@@ -244,8 +344,6 @@ def main():
                 with plock:
                     profs.append(p)
             on_every_slot(collect)
-            batch_done_s.append(sorted(round(it["done"], 3) for it in items))
-            load_s.append(sum(it["load"] for it in items) / NB)
             live_prof.append({c: [sum(p[c][i] for p in profs) for i in range(4)] for c in KERNEL_OF})
             live_prof[-1]["_forms"] = [sum(p["_forms"][i] for p in profs) for i in range(3)]
         outs = []
@@ -261,17 +359,15 @@ def main():
         dt, outs = run_steps([regs], nb=nb)
         return dt, outs[0]
 
-    # synthetic inputs for every step of this rank, generated outside the timed region
-    R = max(1, args.regions_per_gpu)
-    nsteps = args.warmup + args.steps
-    # (at most three distinct sets: generating 25 x 64 regions would take longer than refining them; later steps go round the sets —
-    #  every step recomputes everything, nothing is cached between steps)
-    nsets = min(nsteps, 3)
-    sets = in_slot(lambda: [[make(1002 + 100000 * rank + 1000 * k + s) for k in range(R)] for s in range(nsets)])
+    # the inputs generated above, aligned onto their drafts: what make(seed) returns for the same seeds
+    assert rank == rank_env
+    aligned = in_slot(lambda: [_align_region(p, swalign) for p in unaligned])
+    del unaligned
+    sets = [aligned[s * R:(s + 1) * R] for s in range(nsets)]
     regions = [sets[s % nsets] for s in range(nsteps)]
 
     pre = {}
-    if rank == 0 and not args.no_extras:
+    if args.full and rank == 0 and not args.no_extras:
         # ---- one region alone (latency) ----
         run_batch(regions[0][:1])                      # warm: device pools, code objects
         lone = sorted(run_batch(regions[0][k:k + 1])[0] for k in range(min(3, R)))   # schedules differ in length from region to region
@@ -355,6 +451,24 @@ def main():
                                               "the event arrays) and reading the queued HIP-event pairs of the finished step",
                    "parallelism": "%d regions x %d GPU(s), %d host thread(s) per GPU, no data-path collective" % (R, world, NB)},
     }
+    if not args.full:
+        out["config"]["not_timed_between_steps"] = ("construction of the next step's PSAlign objects from the pre-generated synthetic "
+                                                    "regions (a deep copy of the event arrays)")
+
+    def finish():
+        for _ in slots:          # the slot threads leave (and hand their runtimes back) before the process group goes
+            jobs.put(None)
+        for t in slots:
+            t.join()
+        psdist.finalize()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        finish()
+        return
 
     out["resident"] = {"value": world * R * kb * args.steps / dt_res, "unit": "kb/s", "ms_per_step": 1000.0 * dt_res / max(args.steps, 1),
                        "load_ms_per_step": 1000.0 * sum(load_s) / max(args.steps, 1),
@@ -574,11 +688,7 @@ def main():
         flat["variant_config3.frac_of_hbm_peak"] = (out.get("variant_config3") or {}).get("frac_of_hbm_peak")
         out.update(flat)
         print(json.dumps(out), flush=True)
-    for _ in slots:          # the slot threads leave (and hand their runtimes back) before the process group goes
-        jobs.put(None)
-    for t in slots:
-        t.join()
-    psdist.finalize()
+    finish()
 
 
 if __name__ == "__main__":

@@ -17,7 +17,7 @@ def test_bench_under_torchrun_single_rank():
     out = subprocess.check_output([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                                    "--master-addr", "127.0.0.1", "--master-port", "29517", os.path.join(B.ROOT, "bench.py"),
                                    "--gpus", "1", "--steps", "1", "--warmup", "0", "--length", "1000", "--regions-per-gpu", "6",
-                                   "--batches-in-flight", "2", "--no-cpu"],
+                                   "--batches-in-flight", "2", "--no-cpu", "--full"],
                                   env=env, timeout=900, stderr=subprocess.STDOUT)
     line = [l for l in out.decode().splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
@@ -26,6 +26,27 @@ def test_bench_under_torchrun_single_rank():
     assert r["north_star_1kb"]["lock_step_kb_s"] > r["north_star_1kb"]["single_region_kb_s"] > 0
     assert r["config"]["batches_in_flight"] == 2 and r["single_region_s"] > 0
     assert r["accuracy"]["consensus_percent"] > 97.0
+
+
+def test_bench_plain_run_and_dump(tmp_path):
+    """a plain run reports the headline only, and --dump-outputs writes the last timed step's results: the same from run to run"""
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        out = subprocess.check_output([sys.executable, os.path.join(B.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                                       "--length", "1000", "--regions-per-gpu", "6", "--batches-in-flight", "2",
+                                       "--dump-outputs", str(tmp_path / d)], timeout=900, stderr=subprocess.STDOUT)
+        lines.append(json.loads([l for l in out.decode().splitlines() if l.startswith("{")][-1]))
+    r = lines[0]
+    assert r["steps"] == 2 and r["warmup"] == 1 and r["unit"] == "kb/s" and r["higher_is_better"] is True and r["dtype"] == "f64"
+    assert abs(r["value"] - 6 * 1.0 / (r["ms_per_step"] / 1e3)) < 1e-6 * r["value"]
+    assert not {"roofline", "resident", "accuracy", "parity_in_run", "cpu_baseline", "north_star_1kb"} & set(r)
+    for name in ("consensus_bases", "consensus_lengths", "consensus_accuracy", "region_index"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    # sequences lose end_trim (150) bases at both ends; the accuracy is the identity against the ~90 % draft the region was loaded with
+    lens, acc = np.load(tmp_path / "a" / "consensus_lengths.npy"), np.load(tmp_path / "a" / "consensus_accuracy.npy")
+    assert lens.shape == acc.shape == (6,) and np.all(lens > 600) and np.all(lens < 800) and np.all((acc > 80.0) & (acc <= 100.0))
 
 
 def test_bench_refuses_gpus_without_matching_world():
@@ -69,7 +90,7 @@ def test_bench_two_ranks_share_the_gpu_over_gloo():
     out = subprocess.check_output([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                                    "--master-addr", "127.0.0.1", "--master-port", "29519", os.path.join(B.ROOT, "bench.py"),
                                    "--gpus", "2", "--steps", "1", "--warmup", "0", "--length", "1000", "--regions-per-gpu", "6",
-                                   "--batches-in-flight", "2", "--no-cpu", "--no-extras"],
+                                   "--batches-in-flight", "2", "--no-cpu", "--no-extras", "--full"],
                                   env=env, timeout=900, stderr=subprocess.STDOUT)
     line = [l for l in out.decode().splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
@@ -89,7 +110,7 @@ def test_bench_eight_ranks_share_the_gpu_over_gloo():
     out = subprocess.check_output([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                                    "--master-addr", "127.0.0.1", "--master-port", "29523", os.path.join(B.ROOT, "bench.py"),
                                    "--gpus", "8", "--steps", "2", "--warmup", "0", "--length", "1000", "--regions-per-gpu", "4",
-                                   "--batches-in-flight", "2", "--no-cpu", "--no-extras"],
+                                   "--batches-in-flight", "2", "--no-cpu", "--no-extras", "--full"],
                                   env=env, timeout=1500, stderr=subprocess.STDOUT)
     line = [l for l in out.decode().splitlines() if l.startswith("{")][-1]
     r = json.loads(line)

@@ -3,7 +3,7 @@
 # usage (GPU box): bash tools/ab_nw.sh
 for cfg in "PORESEQ_SWEEP_NW=1" "PORESEQ_SWEEP_NW=2" "PORESEQ_SWEEP_NW=1" "PORESEQ_SWEEP_NW=2"; do
   echo "== $cfg"
-  env $cfg timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu --no-extras 2>/dev/null | python -c "
+  env $cfg timeout 600 python bench.py --steps 3 --warmup 1 --full --no-cpu --no-extras 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,10 +2,11 @@
 # HBM-side traffic of bench.py's default command from the rocprofv3 PMC counters (separate passes, kernel-trace only, as the
 # pool requires), next to the algorithmic bytes per k_fill launch that the same command reports.
 # usage on the GPU box: bash tools/pmc_bench.sh <tag>   -> gpurun_out/prof/<tag>_traffic.json (+ printed table)
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 TAG=${1:-r02}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof; mkdir -p $OUT
-python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu > /tmp/pmcb_plain.log 2>&1
+python3 "$REPO/bench.py" --steps 1 --warmup 1 --full --no-cpu > /tmp/pmcb_plain.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmcb_$c
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d /tmp/pmcb_$c -o r -- python3 $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu --no-extras > /tmp/pmcb_$c.log 2>&1

@@ -5,10 +5,11 @@
 # usage on the GPU box: bash tools/pmc_round.sh <tag>   -> gpurun_out/prof/<tag>_traffic.json, <tag>_valu.json, <tag>_bench_line.json
 set -euo pipefail
 : "${GRAFT_REPO_ROOT:?run on the GPU box (gpurun exports it)}"
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 TAG=${1:-r05}
 OUT="$GRAFT_REPO_ROOT/gpurun_out/prof"; mkdir -p "$OUT"
-python3 "$GRAFT_REPO_ROOT/bench.py" --steps 1 --warmup 1 --no-cpu > /tmp/pmcr_plain.log 2>&1
+python3 "$REPO/bench.py" --steps 1 --warmup 1 --full --no-cpu > /tmp/pmcr_plain.log 2>&1
 grep -q '^{' /tmp/pmcr_plain.log || { echo "pmc_round: the plain bench run printed no JSON line" >&2; tail -5 /tmp/pmcr_plain.log >&2; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf "/tmp/pmcr_$c"

@@ -41,11 +41,11 @@ else
       l=${spec%%@*}; envs=""; [ "$spec" != "$l" ] && envs=$(echo "${spec#*@}" | tr ',' ' ')
       v=$(echo "$spec" | tr '@=,/' '____')
       if [ "$l" = "." ]; then cp /tmp/lib_keep.so $lib; else cp tools/_libs/lib_$l.so $lib || continue; fi
-      env $envs timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu --no-extras "$@" > gpurun_out/ab_${v}_$r.json 2> gpurun_out/ab_${v}_$r.err
-      echo "$v rep $r: $(python - gpurun_out/ab_${v}_$r.json <<'PY'
-import json, sys
+      line=$(env $envs timeout 900 python bench.py --steps 2 --warmup 1 --full --no-cpu --no-extras "$@" 2> /dev/null | grep '^{' | tail -1)
+      echo "$v rep $r: $(BENCH_LINE="$line" python - <<'PY'
+import json, os
 try:
-    d = [json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")][-1]
+    d = json.loads(os.environ["BENCH_LINE"])
     r = d.get("roofline", {})
     print("%.1f kb/s, %.0f ms/step; sweep class avg launch %.1f ms, classes ms/step %s" % (d["value"], d["ms_per_step"], r.get("avg_launch_ms", 0), {k: round(v) for k, v in r.get("all_kernel_classes_ms_per_step", {}).items()}))
 except Exception as e:

@@ -13,6 +13,5 @@ fi
 bash tools/forms_bench.sh ${tag} "20 240" "4,2 2,4" > /dev/null 2>&1
 cat gpurun_out/forms_${tag}.txt
 if [[ " $* " != *" nobench "* ]]; then
-  timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu --no-extras > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err
-  python tools/show_bench.py gpurun_out/${tag}_bench.json 2>&1 | head -30
+  timeout 900 python bench.py --steps 2 --warmup 1 --full --no-cpu --no-extras 2> /dev/null | python tools/show_bench.py /dev/stdin 2>&1 | head -30
 fi
