@@ -367,6 +367,14 @@ class CApi:
                                       i1.ctypes.data_as(c_i32p), i2.ctypes.data_as(c_i32p), cap, C.byref(n)))
         return int(score.value), float(acc.value), i1[:n.value].copy(), i2[:n.value].copy()
 
+    def debug_sw_band(self):
+        """cumulative Smith-Waterman band counters: banded, fell_back, edge, band_cells, full_cells"""
+        fn = self.lib.ps_debug_sw_band   # (the HIP library only: not part of the ABI the checkers export)
+        fn.restype, fn.argtypes = C.c_int, [c_i64p]
+        out = np.zeros(5, dtype=np.int64)
+        self.check(fn(out.ctypes.data_as(c_i64p)))
+        return dict(zip(("banded", "fell_back", "edge", "band_cells", "full_cells"), (int(v) for v in out)))
+
     def seq_to_states(self, s):
         b = s.encode("ascii")
         st = np.zeros(max(len(b), 1), dtype=np.int32)

@@ -302,6 +302,14 @@ int ps_seq_to_states(const char* seq, int64_t n, int32_t* st, int64_t* ns) {
     return PS_OK;
 }
 
+// Smith-Waterman band mode counters (process-wide, cumulative; a test hook outside the public header): out[0] pairs run in band mode,
+// out[1] of them redone on the full matrix after a failed certificate, out[2] certified pairs whose maximum lies within 64 of the band
+// edge, out[3] cells the fills computed, out[4] full-matrix cells of the same pairs
+int ps_debug_sw_band(int64_t* out) {
+    if (!out) return fail(PS_ERR_BAD_ARG, "ps_debug_sw_band");
+    sw_band_counters(out);
+    return PS_OK;
+}
 int ps_debug_fill(ps_align* a, int32_t e, int32_t dir, double* main, double* stay, uint8_t* sm, uint8_t* ss) {
     if (!a || e < 0 || e >= a->a.E || !main || dir < 0 || dir > 1) return fail(PS_ERR_BAD_ARG, "ps_debug_fill");
     NEED_RT();

@@ -141,10 +141,10 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     // The batch's checkpoint rows / columns (~13 MB per 10 kb pair) are a pool like the DP matrices: at most an eighth of this
     // runtime's share goes into one launch.  The first chunk overlaps with the base realign; what is left (large lock-step batches
     // only) follows it, chunk by chunk, and a chunk the device has no memory for is cut in two.
-    auto sw_bytes = [&](size_t k) {
-        const double n1 = (double)pairs[k].first->size(), n2 = (double)pairs[k].second->size();
-        return 4.0 * ((n1 / 64 + 1) * (n2 + 8) + (n2 / 64 + 1) * (n1 + 1)) + 8.0 * (n1 + n2 + 2);
-    };
+    // Pairs whose alignment hugs the main diagonal (the Viterbi seeds) run in band mode (ps_sw.hip), with checkpoints sized from the band.
+    std::vector<int> wbs(pairs.size());
+    for (size_t k = 0; k < pairs.size(); k++) wbs[k] = sw_band_choice(*pairs[k].first, *pairs[k].second);
+    auto sw_bytes = [&](size_t k) { return sw_pair_bytes((int)pairs[k].first->size(), (int)pairs[k].second->size(), wbs[k]); };
     double sw_cap = device_share_bytes() / 8;
     auto sw_chunk_end = [&](size_t k0) {
         double acc = 0;
@@ -156,7 +156,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     SwJob swjob;
     size_t sw_first = sw_chunk_end(0);
     {
-        const int rc = sw_launch(rt, SwIn(pairs.begin(), pairs.begin() + sw_first), &swjob);
+        const int rc = sw_launch(rt, SwIn(pairs.begin(), pairs.begin() + sw_first), &swjob, wbs.data());
         if (rc == PS_ERR_NOMEM && sw_first > 1) { sw_first = 0; swjob = SwJob(); }   // nothing enqueued: everything goes the chunked way below
         else PS_TRY(rc);
     }
@@ -177,7 +177,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     for (size_t k0 = sw_first; k0 < pairs.size();) {
         const size_t k1 = sw_chunk_end(k0);
         std::vector<SwResult> part;
-        const int rc = sw_batch(rt, SwIn(pairs.begin() + k0, pairs.begin() + k1), &part);
+        const int rc = sw_batch(rt, SwIn(pairs.begin() + k0, pairs.begin() + k1), &part, wbs.data() + k0);
         if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { sw_cap *= 0.5; continue; }
         PS_TRY(rc);
         for (SwResult& r : part) als_all.push_back(std::move(r));

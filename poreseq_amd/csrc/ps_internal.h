@@ -255,6 +255,7 @@ int launch_gather_best(Runtime* rt, const BatchD& b, double* out);   // out[job]
 // Smith-Waterman (ps_sw.hip)
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,
               std::vector<int>* inds1, std::vector<int>* inds2);
+void sw_band_counters(int64_t out[5]);   // band mode: pairs banded, fell back, maxima near a band edge, band cells, full-matrix cells
 
 // Viterbi (ps_viterbi.hip): one region of a batched ViterbiMutate call, host side
 struct VitRegionH {

@@ -21,6 +21,15 @@
 // and the traceback kernel recomputes the 64 x 64 tiles its path crosses (the same row routine with one column
 // per lane, this time deriving the 4-bit step codes into LDS) — about 300 of the 25 000 tiles of a 10 kb pair.
 // The starting cell is located by recomputing only the strips whose block maximum equals the global maximum.
+//
+// Band mode (SwPair::wb > 0, the packed fill only).  Strips of 512 columns, one wave each, four waves per pair; strip s computes only its
+// rows [512 s + 1 - wb, 512 s + 512 + wb] (whole 64-row blocks), every cell outside them counts as 0.  That region holds the band
+// |i - j| <= wb, so the banded value Hb is a lower bound of the true H*, and any path the region misses leaves the band, with at most
+// min(i, j) matches and at least wb + 1 - |i - j| gap steps:  H* <= max(Hb, B),  B(i, j) = 5 min(i, j) - 8 max(0, wb + 1 - |i - j|).
+// So a cell with Hb >= B is exact.  The result is certified by the traceback kernel: the banded maximum must exceed
+// U = max B over all cells (then it is the true maximum and its first cell the reference's), and every cell the walk reads (the path
+// cell and its left, upper and diagonal neighbours) must pass Hb >= B.  A pair that fails is redone on the full matrix (sw_finish).
+#include <atomic>
 #include <cstring>
 
 #include "ps_sw.h"
@@ -30,6 +39,26 @@ namespace ps {
 constexpr int SWB = 8;    // rows per pipeline step
 constexpr int SWW = 8;    // waves per workgroup of the chained form: two per SIMD keeps one pair's strips issue-balanced over several CUs
 constexpr int SWW1 = 16;  // waves per workgroup of the one-workgroup-per-pair form (below)
+constexpr int SWBS = 512; // columns per strip of the band mode (one wave of 64 lanes x 8 columns)
+constexpr int SWBW = 4;   // waves per pair in band mode (one strip each at a time)
+
+// band-mode geometry (p.wb > 0): strip s keeps row blocks band_lo(s) .. band_lo(s) + nbb - 1 (those in 0 .. nrb - 1); full matrix:
+// one "strip" of all row blocks.  Row block q's top boundary H(64q, *), column 64c's values H(i, 64c) and block maxima live at:
+__device__ __forceinline__ int band_lo(const SwPair& p, int s) { return p.wb ? s * (SWBS / 64) - p.wb / 64 : 0; }
+__device__ __forceinline__ int64_t rs_index(const SwPair& p, int q, int j) {   // H(64q, j + 1)
+    if (!p.wb) return p.row_off + (int64_t)q * p.pitch + j;
+    const int s = j / SWBS;
+    return p.row_off + ((int64_t)s * p.nbb + q - band_lo(p, s)) * SWBS + (j - s * SWBS);
+}
+// colsave of column 64c as a base index: entry i (H(i, 64c)) at [col_base + i], for rows cs_lo <= i <= cs_hi (outside: 0)
+__device__ __forceinline__ int64_t col_base(const SwPair& p, int c) { return p.col_off + (int64_t)c * p.cpitch - (p.wb ? 64 * band_lo(p, (64 * c - 1) / SWBS) : 0); }
+__device__ __forceinline__ int col_hi(const SwPair& p, int c) { return p.wb ? min(p.n1, 64 * (band_lo(p, (64 * c - 1) / SWBS) + p.nbb)) : p.n1; }
+__device__ __forceinline__ int64_t bm_index(const SwPair& p, int q, int gw) {
+    return p.wb ? p.blk_off + (int64_t)gw * p.nbb + q - band_lo(p, gw) : p.blk_off + (int64_t)q * p.ngw + gw;
+}
+__device__ __forceinline__ int band_q0(const SwPair& p, int gw) { return max(0, band_lo(p, gw)); }            // first row block of a strip
+__device__ __forceinline__ int band_q1(const SwPair& p, int gw) { return p.wb ? min(p.nrb, band_lo(p, gw) + p.nbb) : p.nrb; }   // one past its last
+__device__ __forceinline__ int band_bound(int i, int j, int wb) { return 5 * min(i, j) - 8 * max(0, wb + 1 - abs(i - j)); }
 
 // inclusive prefix maximum over the 64 lanes of a wave: six v_max_i32 with a DPP-shifted first operand; a lane without a source
 // (the first lanes of a row for row_shr, the rows a row_mask leaves out) is disabled for that instruction and keeps its value.
@@ -53,7 +82,8 @@ __device__ __forceinline__ int wave_scan_max(int v) {
 //   bprev  H(i-1, first column - 1) (uniform)         lane   lane index, lane0 = lane ? -2^29 : 0
 //   c2[] and c1 hold characters shifted left by 4
 // MODE 0: values only.  MODE 1: also track the column-major first cell equal to `target` in (fc, fr).
-// MODE 2 (K == 1): also return the cell's step code  step | 4*(score > 0) | 8*(characters equal).
+// MODE 2 (K == 1): also return the cell's step code  step | 4*(score > 0) | 8*(characters equal) | 16*(exact), where exact means
+// that the cell and the three neighbours its step compares pass the band certificate Hb >= B (target = wb; always set when wb = 0).
 template <int K, int MODE>
 __device__ __forceinline__ unsigned sw_row(int (&G)[K], const int (&c2)[K], const int c1, const int bl, const int bprev,
                                            const int lane, const int lane0, const int target, const int i, const int jfirst, int& fc, int& fr) {
@@ -97,6 +127,10 @@ __device__ __forceinline__ unsigned sw_row(int (&G)[K], const int (&c2)[K], cons
             const int l0 = max(hl8, 0), m = max(l0, up0);
             const unsigned step = sd0 >= m ? 3u : (up0 > l0 ? 2u : (hl8 > 0 ? 1u : 0u));
             code = step | (gn > 0 ? 4u : 0u) | (c2[0] == c1 ? 8u : 0u);
+            const int j = jfirst + 1;
+            if (!target || (gn >= band_bound(i, j, target) && hl8 + 8 >= band_bound(i, j - 1, target) &&
+                            up0 + 8 >= band_bound(i - 1, j, target) && d0 >= band_bound(i - 1, j - 1, target)))
+                code |= 16u;
         }
         if (MODE == 1) {
             const int col = jfirst + k + 1;
@@ -276,21 +310,37 @@ __device__ __forceinline__ void sw_row_pk(unsigned (&P)[4], const unsigned (&sp)
 }
 
 // (at most 64 registers: a wave then fits beside two 224-register sweep waves on a SIMD; the compiler takes 79 when left alone)
-template <int WW>
+// BAND: one workgroup of WW waves per pair; wave w runs the pair's 512-column strips w, w + WW, ... one after the other, each over its rows
+// [r0 + 1, rend] only; rows of the left neighbour's boundary column beyond its last row (pend) and the row above r0 + 1 count as 0.  A
+// strip waits for its left neighbour (the previous wave) through an LDS progress word, 64 rows at a time; the neighbour starts 512 rows
+// earlier and a strip spans 512 + 2 wb rows, so with WW <= 1 + 2 wb / 512 no wave waits once the pipeline is full.  Full matrix: r0 = 0,
+// rend = pend = n1.  (Measured: band strips chained as one-wave workgroups through global memory, like the full fill's, made the whole
+// bench 1.5x slower: strip s waits for 512 s rows, so a 10 kb pair holds twenty wave slots that mostly poll, beside the strip sweeps.
+// One wave per pair over all its strips: no faster than the full fill, its launches twice as long.)
+template <int WW, bool BAND>
 __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sw_fill_pk(const SwPair* pairs, const char* chars, int* rowsave, int* colsave,
                                                        int* blkmax, int* prog, int* ticket, int* res) {
     constexpr int K = PKK;
-    __shared__ int s_ticket;
-    if (threadIdx.x == 0) s_ticket = atomicAdd(&ticket[blockIdx.y], 1);
+    static_assert(!BAND || 64 * K == SWBS, "band strips are one wave");
+    constexpr int WP = BAND ? 1 : WW;   // waves in one strip's row pipeline
+    constexpr int KEY = 32768;          // band progress word: strip x KEY + rows done in it (at most 64 nbb < KEY)
+    __shared__ int s_ticket, s_key[WW];
+    if (!BAND) {
+        if (threadIdx.x == 0) s_ticket = atomicAdd(&ticket[blockIdx.y], 1);
+    } else if (threadIdx.x < WW) {
+        s_key[threadIdx.x] = 0;
+    }
     __syncthreads();
-    const int ss = s_ticket;
     const SwPair p = pairs[blockIdx.y];
-    if (p.n1 <= 0 || p.n2 <= 0 || ss * WW * 64 * K >= p.n2) return;
+    const int nstrip = BAND ? (p.n2 + SWBS - 1) / SWBS : 1;
+    for (int it = BAND ? (int)(threadIdx.x >> 6) : 0; it < nstrip; it += BAND ? WW : 1) {
+    const int ss = BAND ? it : s_ticket;
+    if (p.n1 <= 0 || p.n2 <= 0 || ss * WP * 64 * K >= p.n2) return;
     int* prog_my = prog + (int64_t)blockIdx.y * gridDim.x + ss;
-    const bool has_next = (ss + 1) * WW * 64 * K < p.n2;
+    const bool has_next = !BAND && (ss + 1) * WW * 64 * K < p.n2;
     int seen = 0;
-    const int t = threadIdx.x, w = t >> 6, l = t & 63;
-    const int gw = ss * WW + w;
+    const int t = threadIdx.x, w = t >> 6, l = t & 63, wp = BAND ? 0 : w;
+    const int gw = BAND ? ss : ss * WW + w;
     const int wfirst = gw * 64 * K;
     const bool wave_on = wfirst < p.n2;
     const int jbase = wfirst + l * K;
@@ -317,16 +367,28 @@ __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     const int lane0 = l ? -(1 << 29) : 0, lane8k = 8 * K * l;
     __shared__ int hand[WW][2][SWB];
     const bool keeps = ((jbase + K) & 63) == 0 && jbase + K <= p.n2;
-    int* csave = colsave + p.col_off + (int64_t)((jbase + K) >> 6) * (p.n1 + 1);
-    const int* cprev = colsave + p.col_off + (int64_t)(wfirst >> 6) * (p.n1 + 1);
-    if (wave_on && keeps) csave[0] = 0;
+    const int lo = BAND ? band_lo(p, ss) : 0, q0 = max(0, lo), r0 = 64 * q0;
+    const int rend = BAND ? min(p.n1, 64 * (lo + p.nbb)) : p.n1;
+    const int pend = BAND ? min(p.n1, 64 * (lo - SWBS / 64 + p.nbb)) : p.n1;   // last row of the left neighbour's boundary column
+    int* csave = colsave + p.col_off + (int64_t)((jbase + K) >> 6) * p.cpitch - 64 * lo;
+    const int* cprev = colsave + p.col_off + (int64_t)(wfirst >> 6) * p.cpitch - (BAND ? 64 * (lo - SWBS / 64) : 0);
+    if (wave_on && keeps) csave[r0] = 0;
     int bprev = 0;
-    const int nchunks = (p.n1 + SWB - 1) / SWB;
+    const int cb = r0 / SWB, ce = (rend + SWB - 1) / SWB;   // chunks of this strip
     auto fetch = [&](int c, int& ch, int& bd) {
         ch = 1; bd = 0;
         const int i0 = c * SWB;
-        if (w == 0 && ss > 0 && c >= 0 && c < nchunks) {
-            const int need = min(p.n1, (i0 + SWB + 63) & ~63);
+        if (BAND && ss > 0 && c >= cb && c < ce) {      // the previous wave's strip: rows relative to its first
+            const int want = (ss - 1) * KEY + min(pend, (i0 + SWB + 63) & ~63) - 64 * max(0, lo - SWBS / 64);
+            int spins = 0;
+            for (; seen < want && spins < SW_SPIN_LIMIT; spins++) {
+                seen = __hip_atomic_load(&s_key[(w + WW - 1) % WW], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (seen < want) __builtin_amdgcn_s_sleep(2);
+            }
+            if (seen < want && l == 0) atomicOr(&res[p.res_off + 5], 1);
+        }
+        if (!BAND && w == 0 && ss > 0 && c >= cb && c < ce) {
+            const int need = min(pend, (i0 + SWB + 63) & ~63);
             int spins = 0;
             for (; seen < need && spins < SW_SPIN_LIMIT; spins++) {
                 seen = __hip_atomic_load(prog_my - 1, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
@@ -334,27 +396,28 @@ __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8)))
             }
             if (seen < need && l == 0) atomicOr(&res[p.res_off + 5], 1);
         }
-        if (wave_on && c >= 0 && c < nchunks && l < SWB && i0 + l < p.n1) {
+        if (wave_on && c >= cb && c < ce && l < SWB && i0 + l < rend) {
             ch = (int)(unsigned char)s1[i0 + l];
-            if (w == 0 && gw > 0) bd = cprev[i0 + 1 + l];
+            if (wp == 0 && gw > 0 && i0 + 1 + l <= pend) bd = cprev[i0 + 1 + l];
         }
     };
     int ch_nx, bd_nx;
-    fetch(0 - w, ch_nx, bd_nx);
-    for (int s = 0; s < nchunks + WW - 1; s++) {
-        const int c = s - w;
+    fetch(cb - wp, ch_nx, bd_nx);
+    if (BAND && gw > 0 && r0 > 0 && r0 <= pend) bprev = cprev[r0];   // the corner H(r0, first column - 1): published with the first chunk's rows
+    for (int s = 0; s < ce - cb + WP - 1; s++) {
+        const int c = cb + s - wp;
         const int ch1 = ch_nx, bd1 = bd_nx;
         fetch(c + 1, ch_nx, bd_nx);
-        if (wave_on && c >= 0 && c < nchunks) {
+        if (wave_on && c >= cb && c < ce) {
             const int i0 = c * SWB;
             int bnd = bd1;
-            if (w > 0 && l < SWB && i0 + l < p.n1) bnd = hand[w - 1][(s - 1) & 1][l];
+            if (wp > 0 && l < SWB && i0 + l < rend) bnd = hand[w - 1][(s - 1) & 1][l];
             int hl[SWB];
 #pragma unroll
             for (int r = 0; r < SWB; r++) hl[r] = 0;
 #pragma unroll
             for (int r = 0; r < SWB; r++) {
-                if (i0 + r < p.n1) {
+                if (i0 + r < rend) {
                     const int bl = __builtin_amdgcn_readlane(bnd, r), c1 = __builtin_amdgcn_readlane(ch1, r);   // c1: the row's base (uniform)
                     const int bidx = c1 == 'A' ? 0 : c1 == 'C' ? 1 : c1 == 'G' ? 2 : c1 == 'T' ? 3 : -1;       // (scalar selects)
                     unsigned sp[4];
@@ -371,24 +434,24 @@ __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8)))
 #pragma unroll
                     for (int m = 0; m < 4; m++) bmk[m] = un_pk(__builtin_elementwise_max(pk_of(bmk[m]), pk_of(P[m])));
                     const int hlast = (int)(P[3] >> 16) - 8 * K;
-                    if (l == 63) hand[w][s & 1][r] = hlast;
+                    if (!BAND && l == 63) hand[w][s & 1][r] = hlast;
                     hl[r] = hlast;
                 }
             }
             // the kept boundary column's rows of this chunk in two 16-byte stores (round 6: one 4-byte store per row and kept column was
             // 101 G of a bench step's 225 G L1 -> L2 write requests, profiles/r06_mem.json)
             if (keeps) {
-                if (i0 + SWB <= p.n1) {
+                if (i0 + SWB <= rend) {
                     typedef int v4i_a4 __attribute__((ext_vector_type(4), aligned(4)));
                     *(v4i_a4*)(csave + i0 + 1) = (v4i_a4){hl[0], hl[1], hl[2], hl[3]};
                     *(v4i_a4*)(csave + i0 + 5) = (v4i_a4){hl[4], hl[5], hl[6], hl[7]};
                 } else {
 #pragma unroll
-                    for (int r = 0; r < SWB; r++) if (i0 + r < p.n1) csave[i0 + r + 1] = hl[r];
+                    for (int r = 0; r < SWB; r++) if (i0 + r < rend) csave[i0 + r + 1] = hl[r];
                 }
             }
-            const int iend = min(i0 + SWB, p.n1);
-            if ((iend & 63) == 0 || iend == p.n1) {   // row block q complete
+            const int iend = min(i0 + SWB, rend);
+            if ((iend & 63) == 0 || iend == rend) {   // row block q complete
                 const int q = (iend - 1) >> 6;
                 int bm = 0;
 #pragma unroll
@@ -398,10 +461,12 @@ __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8)))
                     bmk[m] = 0u;
                 }
                 for (int o = 32; o; o >>= 1) bm = max(bm, __shfl_xor(bm, o));
-                if (l == 0) blkmax[p.blk_off + (int64_t)q * p.ngw + gw] = bm;
+                if (l == 0) blkmax[BAND ? p.blk_off + (int64_t)gw * p.nbb + q - lo : p.blk_off + (int64_t)q * p.ngw + gw] = bm;
                 if (has_next && w == WW - 1 && l == 63) __hip_atomic_store(prog_my, iend, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                if (iend < p.n1) {
-                    int* rs = rowsave + p.row_off + (int64_t)(q + 1) * p.pitch + jbase;
+                if (BAND && l == 63) __hip_atomic_store(&s_key[w], ss * KEY + iend - r0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (iend < rend) {
+                    int* rs = rowsave + (BAND ? p.row_off + ((int64_t)ss * p.nbb + q + 1 - lo) * SWBS + (jbase - ss * SWBS)
+                                              : p.row_off + (int64_t)(q + 1) * p.pitch + jbase);
 #pragma unroll
                     for (int m = 0; m < 4; m++) {
                         if (jbase + 2 * m < p.n2) rs[2 * m] = (int)(P[m] & 0xffffu) - 8 * (2 * m + 1);
@@ -410,7 +475,9 @@ __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8)))
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (!BAND) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+    if (BAND && l == 63) __hip_atomic_store(&s_key[w], (ss + 1) * KEY, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // strip done
     }
 }
 
@@ -421,17 +488,19 @@ __device__ __forceinline__ void sw_tile(const SwPair& p, const char* s1, const c
                                         unsigned char (*codes)[64]) {
     const int jbase = c0 + l * K;
     int c2[K], G[K];
-    const int* rs = rowsave + p.row_off + (int64_t)q * p.pitch + jbase;
+    const int* rs = rowsave + rs_index(p, q, jbase);
+    const bool top = q > band_q0(p, c0 / SWBS);   // (band mode: a tile never crosses a strip; the strip's top boundary is 0)
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const bool ok = jbase + k < p.n2;
         c2[k] = ok ? (int)(unsigned char)s2[jbase + k] << 4 : 0;
-        G[k] = ((ok && q > 0) ? rs[k] : 0) + 8 * k;
+        G[k] = ((ok && top) ? rs[k] : 0) + 8 * k;
     }
-    const int* cprev = colsave + p.col_off + (int64_t)(c0 >> 6) * (p.n1 + 1);   // H(*, c0)
-    int bprev = c0 > 0 ? cprev[64 * q] : 0;
+    const int* cprev = colsave + col_base(p, c0 >> 6);   // H(*, c0): rows up to chi, 0 below
+    const int chi = c0 > 0 ? col_hi(p, c0 >> 6) : 0;
+    int bprev = c0 > 0 && 64 * q <= chi ? cprev[64 * q] : 0;
     int bnd = 0, ch1 = 1;
-    if (l < nrows) { ch1 = (int)(unsigned char)s1[64 * q + l] << 4; if (c0 > 0) bnd = cprev[64 * q + 1 + l]; }
+    if (l < nrows) { ch1 = (int)(unsigned char)s1[64 * q + l] << 4; if (c0 > 0 && 64 * q + 1 + l <= chi) bnd = cprev[64 * q + 1 + l]; }
     const int lane0 = l ? -(1 << 29) : 0;
     for (int r = 0; r < nrows; r++) {
         const int bl = __builtin_amdgcn_readlane(bnd, r), c1 = __builtin_amdgcn_readlane(ch1, r);
@@ -458,8 +527,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
     const int* bmx = blkmax + p.blk_off;
     int best = 0;
     if (p.n1 > 0 && p.n2 > 0)
-        for (int k = l; k < p.nrb * p.ngw; k += 64) best = max(best, bmx[k]);
+        for (int k = l; k < (p.wb ? p.nbb : p.nrb) * p.ngw; k += 64) best = max(best, bmx[k]);
     for (int s = 32; s; s >>= 1) best = max(best, __shfl_xor(best, s));
+    if (p.wb) {   // the banded maximum is the true one only above U = max over all cells of B (out-of-band cells at |i - j| = wb + 1)
+        const int u = 5 * max(0, max(min(p.n1, p.n2 - p.wb - 1), min(p.n2, p.n1 - p.wb - 1)));
+        if (best <= u) {
+            if (l == 0) o[6] = 1;
+            return;
+        }
+    }
     if (best <= 0) {
         if (l == 0) { o[0] = 0; o[1] = 0; o[2] = 0; o[3] = 0; o[4] = 0; }
         return;
@@ -468,9 +544,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
     int bi = 0, bj = 0;
     for (int gw = 0; gw < p.ngw && !bj; gw++) {
         int fc = 0x7fffffff, fr = 0x7fffffff;
-        for (int q0 = 0; q0 < p.nrb; q0 += 64) {
+        const int qa = band_q0(p, gw), qb = band_q1(p, gw);
+        for (int q0 = qa; q0 < qb; q0 += 64) {
             const int q = q0 + l;
-            unsigned long long hit = __ballot(q < p.nrb && bmx[(int64_t)q * p.ngw + gw] == best);
+            unsigned long long hit = __ballot(q < qb && blkmax[bm_index(p, q, gw)] == best);
             while (hit) {
                 const int qq = q0 + (int)__builtin_ctzll(hit);
                 hit &= hit - 1;
@@ -486,13 +563,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
     int* oi = out + p.out_off;
     int* oj = oi + (p.n1 + p.n2 + 2);
     int i = bi, j = bj, np = 0, nm = 0;
-    bool done = false;
+    bool done = false, inexact = false;
     while (!done && i > 0 && j > 0) {
         const int q = (i - 1) >> 6, cb = (j - 1) >> 6;   // 64 x 64 tile holding (i, j), one column per lane
         const int r0 = 64 * q + 1, cfirst = 64 * cb + 1;
         int dc = 0, dr = 0;
         __syncthreads();
-        sw_tile<1, 2>(p, s1, s2, rowsave, colsave, q, 64 * cb, i - 64 * q, l, 0, dc, dr, codes);
+        sw_tile<1, 2>(p, s1, s2, rowsave, colsave, q, 64 * cb, i - 64 * q, l, p.wb, dc, dr, codes);
         __syncthreads();
         // lane m looks m cells ahead on the diagonal: a run of diagonal steps is emitted at once
         while (true) {
@@ -503,6 +580,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             if (ii >= r0 && jj >= cfirst) code = codes[ii - r0][jj - cfirst];
             const unsigned long long dm = __ballot((code & 7u) == 7u);   // diagonal step from a cell with score > 0
             const int run = __builtin_amdgcn_readfirstlane(dm == ~0ull ? 64 : (int)__builtin_ctzll(~dm));
+            if (__ballot(l < run && !(code & 16u))) { inexact = true; done = true; break; }   // band certificate
             if (l < run) { oi[np + l] = ii; oj[np + l] = jj; }
             nm += (int)__popcll(__ballot((code & 8u) && l < run));
             np += run; i -= run; j -= run;
@@ -510,6 +588,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             if (!(i > 0 && j > 0)) { done = true; break; }
             if (i < r0 || j < cfirst) break;
             const unsigned cr = __builtin_amdgcn_readlane(code, run);
+            if (!(cr & 16u)) { inexact = true; done = true; break; }
             if (!(cr & 4u)) { done = true; break; }   // score <= 0
             const unsigned stp = cr & 3u;
             if (stp == 1u) { if (l == 0) { oi[np] = 0; oj[np] = j; } np++; j--; }
@@ -517,7 +596,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             else { done = true; break; }
         }
     }
-    if (l == 0) { o[0] = best; o[1] = bi; o[2] = bj; o[3] = np; o[4] = nm; }
+    if (l == 0) { o[0] = best; o[1] = bi; o[2] = bj; o[3] = np; o[4] = nm; o[6] = inexact ? 1 : 0; }
 }
 
 // the packed fill (8 columns per lane, 8 waves) with the traceback of the 8-column build
@@ -526,7 +605,18 @@ static int sw_run_pk(Runtime* rt, hipStream_t st, int np, int nss, const SwPair*
     // PORESEQ_SW_LDS_PAD_KB (tuning): dynamic LDS a strip's workgroup claims on top of its own, i.e. a cap on the strips resident per CU: a
     // batch of 340 pairs is 1 700 chained strips of eight waves that mostly wait for their left neighbours and would take every free wave slot
     static const size_t pad = getenv("PORESEQ_SW_LDS_PAD_KB") ? (size_t)atoi(getenv("PORESEQ_SW_LDS_PAD_KB")) * 1024 : 0;
-    hipLaunchKernelGGL((k_sw_fill_pk<SWW>), dim3(nss, np), dim3(64 * SWW), pad, st, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_res);
+    hipLaunchKernelGGL((k_sw_fill_pk<SWW, false>), dim3(nss, np), dim3(64 * SWW), pad, st, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_res);
+    PS_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_sw_trace<8>, dim3(np), dim3(64), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, d_out, d_res);
+    PS_HIP(hipGetLastError());
+    return PS_OK;
+}
+
+// band mode: the packed fill, one workgroup of SWBW waves per pair over its 512-column strips, the same traceback (band-aware
+// through SwPair::wb)
+static int sw_run_band(Runtime* rt, hipStream_t st, int np, const SwPair* d_pairs, const char* d_chars, int* d_row, int* d_col,
+                       int* d_blk, int* d_out, int* d_res) {
+    hipLaunchKernelGGL((k_sw_fill_pk<SWBW, true>), dim3(1, np), dim3(64 * SWBW), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, nullptr, nullptr, d_res);
     PS_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_sw_trace<8>, dim3(np), dim3(64), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, d_out, d_res);
     PS_HIP(hipGetLastError());
@@ -544,16 +634,100 @@ static int sw_run(Runtime* rt, hipStream_t st, int np, int nss, const SwPair* d_
 }
 
 // -------------------------------------------------------------------------------------------------
+// band choice.  PORESEQ_SW_BAND = off / auto (default) / force, PORESEQ_SW_BAND_W = half-width (a multiple of 64, default 1024); both
+// read per call (test hooks).  auto bands a pair when the band computes at most half the matrix, the lengths differ by at most wb / 2
+// and a k-mer sample says the alignment is close and near the diagonal (high-identity seeds pass, reads against the draft do not:
+// a failed certificate costs the band fill on top of the full one).  force bands every pair the packed fill can take.
+constexpr int SW_BAND_W = 1024;
+
+static int band_width_env() {
+    const char* e = getenv("PORESEQ_SW_BAND_W");
+    const int w = e ? atoi(e) : SW_BAND_W;
+    return w >= 64 ? std::min(w, 8192) / 64 * 64 : SW_BAND_W;   // (8192: the fill's progress word holds 64 nbb < 32768 rows)
+}
+
+static double band_cells(int n1, int n2, int wb) {   // cells the band fill computes
+    const int nbb = SWBS / 64 + 2 * wb / 64, ns = (n2 + SWBS - 1) / SWBS, nrb = (n1 + 63) / 64;
+    double c = 0;
+    for (int s = 0; s < ns; s++) {
+        const int lo = s * (SWBS / 64) - wb / 64, r0 = 64 * std::max(0, lo), r1 = std::min(n1, 64 * std::min(nrb, lo + nbb));
+        c += (double)std::max(0, r1 - r0) * std::min(SWBS, n2 - s * SWBS);
+    }
+    return c;
+}
+
+// 12-mers of s1 at ~256 evenly spaced positions, each looked up in s2 within +-32 of the diagonal offset the previous hit left (indels
+// drift it); a pair is close when >= 60 % are found and no hit lies further than wb / 2 from the main diagonal (~96 % identity and up:
+// a loss 5 min(n1, n2) - M below the certificate's 5 (wb + 1 - |n1 - n2|) at wb = 1024)
+static bool band_close(const std::string& s1, const std::string& s2, int wb) {
+    constexpr int KM = 12, WIN = 32, NS = 256;
+    const int n1 = (int)s1.size(), n2 = (int)s2.size();
+    if (n1 < 4 * KM || n2 < 4 * KM) return false;
+    auto code = [](const std::string& x, int at) {
+        uint32_t v = 0;
+        for (int k = 0; k < KM; k++) v = (v << 2) | ((x[at + k] >> 1) & 3);   // A C G T -> 0 1 3 2 (other bytes: some code)
+        return v;
+    };
+    std::vector<uint32_t> c2(n2 - KM + 1);
+    {
+        uint32_t v = 0;
+        for (int k = 0; k < n2; k++) {
+            v = ((v << 2) | ((s2[k] >> 1) & 3)) & ((1u << (2 * KM)) - 1);
+            if (k >= KM - 1) c2[k - KM + 1] = v;
+        }
+    }
+    const int step = std::max(1, (n1 - KM) / NS);
+    int hits = 0, tries = 0, d = 0, dmax = 0;
+    for (int p = 0; p + KM <= n1; p += step) {
+        tries++;
+        const uint32_t v = code(s1, p);
+        int best = -1;
+        for (int o = 0; o <= WIN && best < 0; o++)
+            for (int sg = 0; sg < 2 && best < 0; sg++) {
+                const int q = p + d + (sg ? -o : o);
+                if (q >= 0 && q + KM <= n2 && c2[q] == v) best = q;
+            }
+        if (best >= 0) { hits++; d = best - p; dmax = std::max(dmax, std::abs(d)); }
+    }
+    return hits * 10 >= tries * 6 && 2 * dmax <= wb;
+}
+
+int sw_band_choice(const std::string& s1, const std::string& s2) {
+    const char* e = getenv("PORESEQ_SW_BAND");
+    const int mode = !e || !strcmp(e, "auto") ? 1 : (!strcmp(e, "force") ? 2 : 0);
+    const int n1 = (int)s1.size(), n2 = (int)s2.size();
+    if (!mode || n1 <= 0 || n2 <= 0 || std::min(n1, n2) > SW_PK_MAXLEN) return 0;
+    if (const char* k = getenv("PORESEQ_SW_PK")) if (atoi(k) == 0) return 0;   // the band fill is a form of the packed one
+    const int wb = band_width_env();
+    if (mode == 2) return wb;
+    if (2 * std::abs(n1 - n2) > wb || band_cells(n1, n2, wb) > 0.5 * (double)n1 * n2) return 0;
+    return band_close(s1, s2, wb) ? wb : 0;
+}
+
+double sw_pair_bytes(int n1, int n2, int wb) {
+    const double out = 8.0 * ((double)n1 + n2 + 2);
+    if (!wb) return 4.0 * (((double)n1 / 64 + 1) * (n2 + 8) + ((double)n2 / 64 + 1) * (n1 + 1)) + out;
+    const double nbb = SWBS / 64 + 2 * wb / 64, ns = (n2 + SWBS - 1) / SWBS;
+    return 4.0 * (ns * nbb * (SWBS + 1) + ((double)n2 / 64 + 1) * (64 * nbb + 1)) + out;
+}
+
+static std::atomic<int64_t> g_band[5];   // pairs banded, fell back, maxima near a band edge, band cells, full-matrix cells
+
+void sw_band_counters(int64_t out[5]) { for (int k = 0; k < 5; k++) out[k] = g_band[k].load(); }
+
+// -------------------------------------------------------------------------------------------------
 // enqueue a batch of pairwise alignments on the runtime's second stream (asynchronous)
-int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, SwJob* job) {
+int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, SwJob* job, const int* wbs) {
     const int np = (int)in.size();
     job->np = np;
     if (!np) return PS_OK;
     std::vector<SwPair>& pairs = job->pairs;
     std::string& pool = job->pool;
     pairs.assign(np, SwPair());
+    std::vector<int> wb(np);
+    for (int k = 0; k < np; k++) wb[k] = wbs ? wbs[k] : sw_band_choice(*in[k].first, *in[k].second);
     int maxn2 = 1;
-    for (int k = 0; k < np; k++) maxn2 = std::max(maxn2, (int)in[k].second->size());
+    for (int k = 0; k < np; k++) if (!wb[k]) maxn2 = std::max(maxn2, (int)in[k].second->size());
     // 4 columns per lane = 2048 per workgroup: a 10 kb pair runs as five chained workgroups, all but the last full (8 columns per
     // lane: three, the last 44 % used, 7.8 instead of 6.6 ms per pair).  8 columns per lane spread the row scan over twice the cells:
     // 17 % fewer vector instructions per pair — with several lock-step batches in flight the chip is short of vector issue, not of
@@ -570,30 +744,53 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     }
     const int sswidth = WW * 64 * K;
     const int nss = (maxn2 + sswidth - 1) / sswidth;
+    // device order: the full-matrix pairs, then the band pairs (each group one fill and one traceback launch); results by res_off
+    std::vector<int> order;
+    for (int pass = 0; pass < 2; pass++)
+        for (int k = 0; k < np; k++) if ((wb[k] != 0) == (pass == 1)) order.push_back(k);
+    const int nf = np - (int)std::count_if(wb.begin(), wb.end(), [](int w) { return w != 0; }), nb = np - nf;
     int64_t row_tot = 0, col_tot = 0, blk_tot = 0, out_tot = 0;
+    job->nband = nb; job->cells = 0; job->band_cells = 0;
     for (int k = 0; k < np; k++) {
         SwPair& p = pairs[k];
         p.n1 = (int)in[k].first->size(); p.n2 = (int)in[k].second->size();
+        p.wb = wb[k];
         p.nrb = std::max(1, (p.n1 + 63) / 64);
-        p.ngw = WW * std::max(1, (p.n2 + sswidth - 1) / sswidth);
-        p.pitch = ((p.n2 + 3) / 4) * 4 + 4;
         p.s1_off = (int64_t)pool.size(); pool += *in[k].first;
         p.s2_off = (int64_t)pool.size(); pool += *in[k].second;
-        p.row_off = row_tot; row_tot += (int64_t)p.nrb * p.pitch;
-        p.col_off = col_tot; col_tot += ((int64_t)p.n2 / 64 + 1) * (p.n1 + 1);
-        p.blk_off = blk_tot; blk_tot += (int64_t)p.nrb * p.ngw;
+        if (!p.wb) {
+            p.ngw = WW * std::max(1, (p.n2 + sswidth - 1) / sswidth);
+            p.pitch = ((p.n2 + 3) / 4) * 4 + 4;
+            p.nbb = p.nrb;
+            p.cpitch = p.n1 + 1;
+            p.row_off = row_tot; row_tot += (int64_t)p.nrb * p.pitch;
+            p.blk_off = blk_tot; blk_tot += (int64_t)p.nrb * p.ngw;
+            job->band_cells += (double)p.n1 * p.n2;
+        } else {
+            p.ngw = std::max(1, (p.n2 + SWBS - 1) / SWBS);
+            p.pitch = SWBS;
+            p.nbb = SWBS / 64 + 2 * p.wb / 64;
+            p.cpitch = 64 * p.nbb + 1;
+            p.row_off = row_tot; row_tot += (int64_t)p.ngw * p.nbb * SWBS;
+            p.blk_off = blk_tot; blk_tot += (int64_t)p.ngw * p.nbb;
+            job->band_cells += band_cells(p.n1, p.n2, p.wb);
+        }
+        p.col_off = col_tot; col_tot += ((int64_t)p.n2 / 64 + 1) * p.cpitch;
         p.out_off = out_tot; out_tot += 2 * ((int64_t)p.n1 + p.n2 + 2);
         p.res_off = (int64_t)k * 8;
         job->cells += (double)p.n1 * p.n2;
     }
     pool.push_back(0);
     job->out_tot = out_tot;
+    std::vector<SwPair> dev(np);
+    for (int k = 0; k < np; k++) dev[k] = pairs[order[k]];
+    const size_t nprog = (size_t)nf * (nss + 1) + 1;   // progress per strip + one ticket counter per pair (full-matrix pairs)
     PS_TRY(rt->buf("sw_pairs").ensure(np * sizeof(SwPair)));
     PS_TRY(rt->buf("sw_chars").ensure(pool.size()));
     PS_TRY(rt->buf("sw_row").ensure(row_tot * sizeof(int)));
     PS_TRY(rt->buf("sw_col").ensure(col_tot * sizeof(int)));
     PS_TRY(rt->buf("sw_blk").ensure(blk_tot * sizeof(int)));
-    PS_TRY(rt->buf("sw_prog").ensure((size_t)np * (nss + 1) * sizeof(int)));   // progress per strip + one ticket counter per pair
+    PS_TRY(rt->buf("sw_prog").ensure(nprog * sizeof(int)));
     PS_TRY(rt->buf("sw_out").ensure(out_tot * sizeof(int)));
     PS_TRY(rt->buf("sw_res").ensure((size_t)np * 8 * sizeof(int)));
     SwPair* d_pairs = rt->buf("sw_pairs").as<SwPair>();
@@ -602,37 +799,46 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     int* d_col = rt->buf("sw_col").as<int>();
     int* d_blk = rt->buf("sw_blk").as<int>();
     int* d_prog = rt->buf("sw_prog").as<int>();
-    int* d_ticket = d_prog + (size_t)np * nss;
+    int* d_ticket = d_prog + (size_t)nf * nss;
     int* d_out = rt->buf("sw_out").as<int>();
     int* d_res = rt->buf("sw_res").as<int>();
     hipStream_t st = nullptr;
     PS_TRY(second_stream(rt, &st));
     job->stream = st;
-    PS_TRY(rt->up(d_pairs, pairs.data(), np * sizeof(SwPair), st));
+    PS_TRY(rt->up(d_pairs, dev.data(), np * sizeof(SwPair), st));
     PS_TRY(rt->up(d_chars, pool.data(), pool.size(), st));
     PS_HIP(hipMemsetAsync(d_res, 0, (size_t)np * 8 * sizeof(int), st));
     PS_HIP(hipMemsetAsync(d_blk, 0, blk_tot * sizeof(int), st));   // waves beyond a pair's last column never write theirs
-    PS_HIP(hipMemsetAsync(d_prog, 0, (size_t)np * (nss + 1) * sizeof(int), st));
+    PS_HIP(hipMemsetAsync(d_prog, 0, nprog * sizeof(int), st));
     if (rt->prof_on) PS_HIP(hipEventRecord(rt->sw0, st));
-    // the packed 16-bit fill serves the 8-column build whenever every pair's scores fit 16 bits (PORESEQ_SW_PK=0: never; tests)
-    bool packed = K == 8 && WW == SWW;
-    for (int k = 0; k < np && packed; k++) if (std::min(pairs[k].n1, pairs[k].n2) > SW_PK_MAXLEN) packed = false;
-    if (const char* e = getenv("PORESEQ_SW_PK")) if (atoi(e) == 0) packed = false;
-    if (packed) {
-        PS_TRY(sw_run_pk(rt, st, np, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res));
-        if (rt->prof_on) rt->prof["sw_pk8"].launches++;   // (which fill ran: a host-side count, no event pair)
-    } else if (WW == SWW1) {
-        switch (K) {
-            case 8: PS_TRY((sw_run<8, SWW1>(rt, st, np, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-            default: PS_TRY((sw_run<16, SWW1>(rt, st, np, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-        }
-    } else {
-        switch (K) {
-            case 4: PS_TRY((sw_run<4, SWW>(rt, st, np, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-            case 16: PS_TRY((sw_run<16, SWW>(rt, st, np, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-            default: PS_TRY((sw_run<8, SWW>(rt, st, np, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
+    bool packed_all = true;   // every pair of the batch on a packed 8-column fill (the band fill is one)
+    if (nf) {
+        // the packed 16-bit fill serves the 8-column build whenever every pair's scores fit 16 bits (PORESEQ_SW_PK=0: never; tests)
+        bool packed = K == 8 && WW == SWW;
+        for (int k = 0; k < nf && packed; k++) if (std::min(dev[k].n1, dev[k].n2) > SW_PK_MAXLEN) packed = false;
+        if (const char* e = getenv("PORESEQ_SW_PK")) if (atoi(e) == 0) packed = false;
+        if (packed) {
+            PS_TRY(sw_run_pk(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res));
+        } else if (WW == SWW1) {
+            packed_all = false;
+            switch (K) {
+                case 8: PS_TRY((sw_run<8, SWW1>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
+                default: PS_TRY((sw_run<16, SWW1>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
+            }
+        } else {
+            packed_all = false;
+            switch (K) {
+                case 4: PS_TRY((sw_run<4, SWW>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
+                case 16: PS_TRY((sw_run<16, SWW>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
+                default: PS_TRY((sw_run<8, SWW>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
+            }
         }
     }
+    if (nb) {
+        PS_TRY(sw_run_band(rt, st, nb, d_pairs + nf, d_chars, d_row, d_col, d_blk, d_out, d_res));
+        if (rt->prof_on) rt->prof["sw_band"].launches++;
+    }
+    if (rt->prof_on && packed_all) rt->prof["sw_pk8"].launches++;   // (which fill ran: a host-side count per batch, no event pair)
     if (rt->prof_on) PS_HIP(hipEventRecord(rt->sw1, st));
     PS_TRY(rt->hbuf("sw_res").ensure((size_t)np * 8 * sizeof(int)));
     PS_TRY(rt->hbuf("sw_out").ensure((size_t)out_tot * sizeof(int)));
@@ -657,6 +863,14 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
     }
     for (int k = 0; k < np; k++)
         if (job->res[k * 8 + 5]) return fail(PS_ERR_HIP, "Smith-Waterman: a strip gave up waiting for its left neighbour (result discarded)");
+    std::vector<int> redo;
+    int edge = 0;
+    for (int k = 0; k < np; k++) {
+        const SwPair& p = job->pairs[k];
+        if (!p.wb) continue;
+        if (job->res[k * 8 + 6]) { redo.push_back(k); continue; }
+        if (job->res[k * 8 + 0] > 0 && std::abs(job->res[k * 8 + 1] - job->res[k * 8 + 2]) > p.wb - 64) edge++;
+    }
     for (int k = 0; k < np; k++) {
         const int n = job->res[k * 8 + 3], nm = job->res[k * 8 + 4];
         const SwPair& p = job->pairs[k];
@@ -668,12 +882,32 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
         std::reverse(r.a.begin(), r.a.end()); std::reverse(r.b.begin(), r.b.end());
         r.accuracy = 100.0 * nm / (double)n;  // NaN for an empty alignment, as the reference computes it
     }
+    g_band[0] += job->nband; g_band[1] += (int64_t)redo.size(); g_band[2] += edge;
+    g_band[3] += (int64_t)job->band_cells; g_band[4] += (int64_t)job->cells;
+    static const bool trace = getenv("PORESEQ_TRACE") != nullptr;
+    if (trace && job->nband)
+        fprintf(stderr, "[ps] smith-waterman band: %d of %d pairs banded, %zu fell back, %d maxima near a band edge, %.3g of %.3g cells\n",
+                job->nband, np, redo.size(), edge, job->band_cells, job->cells);
+    if (redo.empty()) return PS_OK;
+    // pairs whose band certificate failed: the full matrix, in one follow-up batch (the job's staging is free again after the sync above)
+    std::vector<std::string> s(2 * redo.size());
+    SwInput in2;
+    for (size_t k = 0; k < redo.size(); k++) {
+        const SwPair& p = job->pairs[redo[k]];
+        s[2 * k].assign(job->pool, (size_t)p.s1_off, (size_t)p.n1);
+        s[2 * k + 1].assign(job->pool, (size_t)p.s2_off, (size_t)p.n2);
+    }
+    for (size_t k = 0; k < redo.size(); k++) in2.push_back({&s[2 * k], &s[2 * k + 1]});
+    const std::vector<int> full(redo.size(), 0);
+    std::vector<SwResult> part;
+    PS_TRY(sw_batch(rt, in2, &part, full.data()));
+    for (size_t k = 0; k < redo.size(); k++) (*out)[redo[k]] = std::move(part[k]);
     return PS_OK;
 }
 
-int sw_batch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, std::vector<SwResult>* out) {
+int sw_batch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, std::vector<SwResult>* out, const int* wb) {
     SwJob job;
-    PS_TRY(sw_launch(rt, in, &job));
+    PS_TRY(sw_launch(rt, in, &job, wb));
     return sw_finish(rt, &job, out);
 }
 
