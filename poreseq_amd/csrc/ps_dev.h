@@ -15,19 +15,9 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // Serial single-wave kernels of a launch chain (the backtrace walkers, the path-score pass, the per-job maxima: < 3 % of the vector
 // work, a fifth of a ScoreMutations chain's latency under load) can raise their waves' issue priority at entry: beside three sweep
 // waves on its SIMD a lone walker wave otherwise gets a quarter of the issue slots and runs 4x slower than alone, while its batch
-// offers the chip nothing else.  PS_WALKER_PRIO: the serial walkers; PS_WIDE_PRIO: the short chip-wide table builders between them.
-#ifndef PS_WALKER_PRIO
-#define PS_WALKER_PRIO 3
-#endif
-#ifndef PS_WIDE_PRIO
-#define PS_WIDE_PRIO 0
-#endif
-__device__ __forceinline__ void chain_priority() {
-    if (PS_WALKER_PRIO > 0) __builtin_amdgcn_s_setprio(PS_WALKER_PRIO);
-}
-__device__ __forceinline__ void chain_priority_wide() {
-    if (PS_WIDE_PRIO > 0) __builtin_amdgcn_s_setprio(PS_WIDE_PRIO);
-}
+// offers the chip nothing else.  (Raising the short chip-wide table builders between them as well takes the gain away again.)
+constexpr int PS_WALKER_PRIO = 3;
+__device__ __forceinline__ void chain_priority() { __builtin_amdgcn_s_setprio(PS_WALKER_PRIO); }
 
 // std::lower_bound(double*, int) exactly as libstdc++ walks it (cpp/EventData.h:178)
 __device__ inline int lower_bound_d(const double* __restrict__ a, int n, int v) {
@@ -184,6 +174,8 @@ __device__ __forceinline__ void bt_load(unsigned short (*__restrict__ dst)[BT + 
         }
         return;
     }
+    // (a source that decodes picks its column's tables by lane, StripCodes::prep / decode: a column's threads must be one wave)
+    static_assert(!SRC::TWO_PASS || (BT == 64 && NT % 64 == 0), "bt_load: a two-pass source needs 64-row tiles and whole waves of loaders");
     unsigned raw[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
@@ -208,7 +200,7 @@ __device__ __forceinline__ void bt_walk(const JobD& J, SRC& src) {
     const int tid = threadIdx.x, n0 = J.n0;
     // (wave priority for the WALKER wave only: with the tile loaders raised too, the kernel alone was 14 % slower than without any
     //  priority — 1.24 against 1.08 ms per 10 kb job — the loaders' decode work then competes with the walk it feeds)
-    if (PS_WALKER_PRIO > 0 && tid < 64) __builtin_amdgcn_s_setprio(PS_WALKER_PRIO);
+    if (tid < 64) __builtin_amdgcn_s_setprio(PS_WALKER_PRIO);
     double* __restrict__ ra = J.ra;
     long long* __restrict__ rlw = (long long*)J.rl;
     for (int t = tid; t < n0; t += 256) { ra[t] = 0.0; rlw[t] = 0ll; }
@@ -227,7 +219,7 @@ __device__ __forceinline__ void bt_walk(const JobD& J, SRC& src) {
         }
         const int pi = ti - (BT - BTM), pj = tj - (BT - BTM);
         unsigned short (*t_step)[BT + 2] = t_buf[cur];
-        if (tid >= 64) bt_load<192>(t_buf[cur ^ 1], src, pi, pj, tid - 64);
+        if (tid >= 64) bt_load<192>(t_buf[cur ^ 1], src, pi, pj, tid - 64);   // (the loaders' offset is a multiple of 64: thread mod 64 stays the lane, as a two-pass source's prep / decode need)
         if (tid < 64) {
             // wave 0 walks; (i, j, arr) are wave-uniform.  Lane l looks l cells ahead on the diagonal, so a run of
             // MATCH steps (the common case) is emitted by one LDS read + one ballot with coalesced stores; the

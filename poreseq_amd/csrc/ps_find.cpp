@@ -183,7 +183,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
         for (SwResult& r : part) als_all.push_back(std::move(r));
         k0 = k1;
     }
-    if (sw_first < pairs.size()) { static const bool trace = getenv("PORESEQ_TRACE") != nullptr; if (trace) fprintf(stderr, "[ps] smith-waterman: %zu pairs, %zu with the realign, the rest in chunks\n", pairs.size(), sw_first); }
+    if (sw_first < pairs.size()) { if (trace_on()) fprintf(stderr, "[ps] smith-waterman: %zu pairs, %zu with the realign, the rest in chunks\n", pairs.size(), sw_first); }
     if (pairs.empty()) return PS_OK;
     // the reference's progress line under `verbose` (cpp/FindMutations.cpp:34-35, 100-109: "Finding mutations", a dot per seed sequence, a
     // newline); single-handle calls only (a lock-step call has no single line to write)
@@ -290,7 +290,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             {
                 const int rc = realign(rt, b, q1 - q0 > 1 ? 1.2 * cap : 0.0);
                 if (rc == PS_SPLIT) {   // wider bands than guessed: cut the chunk again with the width it asked for
-                    { static const bool trace = getenv("PORESEQ_TRACE") != nullptr; if (trace) fprintf(stderr, "[ps] seed chunk of %zu cut again: %d slots per anti-diagonal, %d guessed\n", q1 - q0, b.P, std::max(p_seen, 0)); }
+                    { if (trace_on()) fprintf(stderr, "[ps] seed chunk of %zu cut again: %d slots per anti-diagonal, %d guessed\n", q1 - q0, b.P, std::max(p_seen, 0)); }
                     p_seen = std::max(p_seen, b.P);
                     limit = std::max<size_t>(1, (q1 - q0) / 2);
                     PS_HIP(hipStreamSynchronize(rt->stream));

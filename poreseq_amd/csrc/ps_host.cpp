@@ -30,7 +30,8 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
 const char* last_error() { return g_err.c_str(); }
 
 static double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
-Tick::Tick(const char* w) : what(w), t0(now_s()) { static int e = getenv("PORESEQ_TRACE") ? 1 : 0; on = e; }
+bool trace_on() { static const bool on = getenv("PORESEQ_TRACE") != nullptr; return on; }
+Tick::Tick(const char* w) : what(w), t0(now_s()), on(trace_on()) {}
 void Tick::lap(const char* label) {
     if (!on) return;
     const double t = now_s();
@@ -46,8 +47,7 @@ static std::atomic<long long> g_pool_bytes(0);   // device memory held by the po
 
 int DBuf::ensure(size_t bytes) {
     if (bytes <= cap && p) return PS_OK;
-    static const bool trace = getenv("PORESEQ_TRACE") != nullptr;
-    if (trace) fprintf(stderr, "[ps] pool grow %zu -> %zu bytes\n", cap, bytes);
+    if (trace_on()) fprintf(stderr, "[ps] pool grow %zu -> %zu bytes\n", cap, bytes);
     if (p) { PS_HIP(hipFree(p)); p = nullptr; g_pool_bytes -= (long long)cap; cap = 0; }
     size_t want = std::max<size_t>(bytes + std::min<size_t>(bytes / 4, (size_t)1 << 30), 1 << 16);   // growth slack, at most 1 GB
     // never into the last 6 % of the device: a launch that finds no memory for the HSA runtime's own needs aborts the process
@@ -69,7 +69,7 @@ int DBuf::ensure(size_t bytes) {
             // runtimes on the free list (their threads are gone) keep their pools for the next thread: take them back first
             (void)hipGetLastError();
             const size_t got = trim_idle_runtimes();
-            if (trace) fprintf(stderr, "[ps] out of device memory: %zu bytes taken back from idle runtimes\n", got);
+            if (trace_on()) fprintf(stderr, "[ps] out of device memory: %zu bytes taken back from idle runtimes\n", got);
             p = nullptr;
             e = got ? hipMalloc(&p, want) : e;
         }
@@ -531,8 +531,10 @@ static size_t device_plan_bytes() { return (size_t)(device_fraction() * (double)
 // band tables, edit tables): 1.4 x share + 2.5 GB, measured at 7, 10 and 14 batches in flight.  Share: 31 GB up to four threads,
 // 17 GB with seven batches in flight, 7.7 GB with fourteen.  It sizes the chunks of FindMutations' candidate alignments (7 MB of
 // step codes each), of Smith-Waterman batches and of the Viterbi tables.
+// PORESEQ_MAX_BATCH_GB in bytes (read at every call: tests change it); 0: set without a budget, < 0: not set
+static double max_batch_env() { const char* e = getenv("PORESEQ_MAX_BATCH_GB"); return e ? std::max(atof(e), 0.0) * 1e9 : -1.0; }
 double device_share_bytes() {
-    if (const char* e = getenv("PORESEQ_MAX_BATCH_GB")) { const double g = atof(e); if (g > 0) return g * 1e9; }
+    if (const double g = max_batch_env(); g > 0) return g;
     const size_t tot = device_plan_bytes();
     if (!tot) return 32e9;
     const int nrt = std::max(4, peak_runtimes());
@@ -566,7 +568,7 @@ double dense_cap_bytes() {
     // (the smallest slab actually allocated, when one came out smaller than planned: sub-batches are cut to fit any of them)
     size_t cap = slab_bytes();
     { std::lock_guard<std::mutex> lk(g_slab_mu); for (const Slab* sl : g_slabs) cap = std::min(cap, sl->bytes); }
-    if (const char* e = getenv("PORESEQ_MAX_BATCH_GB")) { const double g = atof(e); if (g > 0) return std::min(g * 1e9, (double)cap); }
+    if (const double g = max_batch_env(); g > 0) return std::min(g, (double)cap);
     return (double)cap;
 }
 void SlabHold::release() {
@@ -621,7 +623,7 @@ static int ensure_matrix_pools(Runtime* rt, const Batch& bt, size_t need_rec, si
     DBuf& rec = rt->buf("rec");
     DBuf& flg = rt->buf("flg");
     size_t tot = device_plan_bytes();
-    if (!getenv("PORESEQ_MAX_BATCH_GB") && rec.p && (double)rec.cap > 1.5 * device_share_bytes() + 2e9 && need_rec < rec.cap) {
+    if (max_batch_env() < 0 && rec.p && (double)rec.cap > 1.5 * device_share_bytes() + 2e9 && need_rec < rec.cap) {
         PS_HIP(hipStreamSynchronize(rt->stream));
         PS_HIP(hipFree(rec.p)); g_pool_bytes -= (long long)rec.cap; rec.p = nullptr; rec.cap = 0;
         if (flg.p) { PS_HIP(hipFree(flg.p)); g_pool_bytes -= (long long)flg.cap; flg.p = nullptr; flg.cap = 0; }
@@ -862,6 +864,9 @@ int Align::refs_to_host(Runtime* rt) {
     return PS_OK;
 }
 
+// slots per anti-diagonal a band of half-width W will probably need: footprint ~ (2W + 1) / 1.9 for about one level per base, + 9
+static int guess_slots_w(int W) { return std::min(1024, std::max(64, (((2 * W + 1) * 10 / 19 + 9 + 63) / 64) * 64)); }
+
 // forward fill + backtrace + updaterefs of a batch (the body of ScoreAlignments per event,
 // cpp/MakeMutations.cpp:148-195, and of Alignment::update with ndir == 2, cpp/Alignment.cpp:63-73)
 static int sweep_min_default() { static const int v = getenv("PORESEQ_SWEEP_MIN") ? atoi(getenv("PORESEQ_SWEEP_MIN")) : 400; return v; }
@@ -881,13 +886,15 @@ void sparse_min_set(int n) { g_sparse_min.store(n); }
 static int sparse_min() { return g_sparse_min.load() >= 0 ? g_sparse_min.load() : sparse_min_default(); }
 bool sweep_enabled() { static const bool off = getenv("PORESEQ_NO_SWEEP") != nullptr; return !off; }
 
+// PORESEQ_DEBUG_SWEEP_K (tests: a given strip height, i.e. a wrong guess; read per call); < 0: not set
+static int debug_sweep_k() { const char* e = getenv("PORESEQ_DEBUG_SWEEP_K"); return e ? std::max(atoi(e), 0) : -1; }
+
 // device bytes one forward-only job of AlignData a (n0 levels against C states) will probably take: step codes of a strip sweep,
 // or the skewed {record, step word} matrix of k_fill
 double fwd_job_bytes(const Align* a, int n0, int C) {
     SweepForm f;
     if (sweep_enabled()) f = sweep_guess_form(a->par.realign_width, 1);
-    static const int dbg = getenv("PORESEQ_DEBUG_SWEEP_K") ? atoi(getenv("PORESEQ_DEBUG_SWEEP_K")) : 0;   // tests: a wrong guess
-    if (f.ok() && dbg > 0) f.K = dbg;
+    if (f.ok() && debug_sweep_k() > 0) f.K = debug_sweep_k();
     if (f.ok()) return 1.15 * sweep_job_bytes(n0, C, f);   // (the multi-wavefront forms take up to a tenth more: more steps, fewer rows per lane)
     return ((double)n0 + C + 1 + MAT_FRONT + MAT_BACK) * guess_slots(a) * 18.0;
 }
@@ -913,14 +920,13 @@ static SweepForm pick_form(int W, int nsweeps, bool fastdiv) {
     // Two wavefronts per sweep by default: the SIMD time of one (K = 10) in half the time and three wavefronts per SIMD instead of two
     // (measured: 2 400 sweeps of 10 kb in 50 ms against 58; 20 in 13 ms against 23).  Four — a quarter more SIMD time, 11 ms — only for
     // a lone driver thread's small launches: with several lock-step batches in flight the chip is shared and SIMD time is what counts.
-    static const int nw_env = getenv("PORESEQ_SWEEP_NW") ? atoi(getenv("PORESEQ_SWEEP_NW")) : 0;       // tuning: wavefronts per sweep
-    static const int w4_max = getenv("PORESEQ_SWEEP_W4_MAX") ? atoi(getenv("PORESEQ_SWEEP_W4_MAX")) : 256;   // sweeps per launch up to which four wavefronts each pay
-    int nw = nw_env > 0 ? nw_env : (live_runtimes() <= 1 && nsweeps <= w4_max ? 4 : 2);
+    constexpr int W4_MAX = 256;   // sweeps per launch up to which four wavefronts each pay
+    int nw = live_runtimes() <= 1 && nsweeps <= W4_MAX ? 4 : 2;
     if (!fastdiv) nw = 1;                                         // (the multi-wavefront builds exist with tabulated reciprocals only)
     for (; nw >= 1; nw >>= 1) {
         f = sweep_guess_form(W, nw);
         // a narrow band on many wavefronts leaves most lanes without a strip: at least half of them busy, else fewer wavefronts
-        if (f.ok() && (nw == 1 || ((2 * W + 1) / (f.K + 1) + 3) * 2 >= 64 * nw)) return f;
+        if (f.ok() && (nw == 1 || sweep_guess_window(W, f.K) * 2 >= 64 * nw)) return f;
     }
     return sweep_guess_form(W, 1);
 }
@@ -932,7 +938,7 @@ static int realign_sweep(Runtime* rt, Batch& b, double cap) {
     int W = 0;
     for (const JobD& j : b.jobs) W = std::max(W, j.W);
     SweepForm f = pick_form(W, b.d.njobs * b.ndir, b.d.fastdiv != 0);
-    if (const char* e = getenv("PORESEQ_DEBUG_SWEEP_K")) { f.K = atoi(e); f.NW = 1; }   // tests: a given strip height first
+    if (const int dbg = debug_sweep_k(); dbg >= 0) { f.K = dbg; f.NW = 1; }   // tests: a given strip height first
     if (!f.ok()) return -1;
     PS_TRY(launch_begin(rt, b.d));
     PS_TRY(launch_lb(rt, b.d, 0, b.maxlbn));
@@ -941,7 +947,7 @@ static int realign_sweep(Runtime* rt, Batch& b, double cap) {
         int* w = nullptr;
         PS_TRY(rt->down(&w, b.sd.maxwin, (size_t)1));
         PS_HIP(hipStreamSynchronize(rt->stream));
-        { static const bool trace = getenv("PORESEQ_TRACE") != nullptr; if (trace) fprintf(stderr, "[ps] realign (strip sweep%s): %d jobs x %d, K = %d on %d wavefronts, widest window %d strips\n", b.sparse ? ", kept columns" : "", b.d.njobs, b.ndir, f.K, f.NW, *w); }
+        { if (trace_on()) fprintf(stderr, "[ps] realign (strip sweep%s): %d jobs x %d, K = %d on %d wavefronts, widest window %d strips\n", b.sparse ? ", kept columns" : "", b.d.njobs, b.ndir, f.K, f.NW, *w); }
         if (*w <= sweep_win_max(f.NW)) break;
         f = sweep_next_form(f, *w);
         if (!f.ok()) { for (JobD& j : b.jobs) j.K = 0; return -1; }
@@ -949,8 +955,7 @@ static int realign_sweep(Runtime* rt, Batch& b, double cap) {
     const int K = f.K;
     const double bytes = (double)b.sweep_code_bytes + 16.0 * (double)b.sweep_recs;
     if (cap > 0 && bytes > cap) {
-        static const bool trace = getenv("PORESEQ_TRACE") != nullptr;
-        if (trace) fprintf(stderr, "[ps] realign (strip sweep): %.2f GB of step codes%s at K = %d, over the share: split\n", bytes * 1e-9, b.ndir == 2 ? (b.sparse ? " and kept columns" : " and records") : "", K);
+        if (trace_on()) fprintf(stderr, "[ps] realign (strip sweep): %.2f GB of step codes%s at K = %d, over the share: split\n", bytes * 1e-9, b.ndir == 2 ? (b.sparse ? " and kept columns" : " and records") : "", K);
         b.P = 0;
         return PS_SPLIT;
     }
@@ -991,7 +996,7 @@ int realign(Runtime* rt, Batch& b, double cap) {
     bool too_big = false;
     if (b.ndir == 1 && sweep_enabled() && b.d.njobs < sweep_min) {
         double est = 0;
-        for (const JobD& j : b.jobs) est += (double)(j.S + MAT_FRONT + MAT_BACK) * std::min(1024, std::max(64, (((2 * j.W + 1) * 10 / 19 + 9 + 63) / 64) * 64)) * 18.0;
+        for (const JobD& j : b.jobs) est += (double)(j.S + MAT_FRONT + MAT_BACK) * guess_slots_w(j.W) * 18.0;   // (not guess_slots: the tests' override of the guess does not reach here)
         too_big = est > device_share_bytes();
     }
     if (sweep_enabled() && (b.d.njobs * b.ndir >= sweep_min || too_big)) {
@@ -1011,15 +1016,14 @@ int realign(Runtime* rt, Batch& b, double cap) {
     if (std::max(*w, 1) + 2 > 2048)
         return fail(PS_ERR_UNSUPPORTED, "band footprint of " + std::to_string(*w) + " rows on one anti-diagonal: wider than two slots per lane of one "
                                         "workgroup (2046); realign_width up to 1022 fits for any input");
-    { static const bool trace = getenv("PORESEQ_TRACE") != nullptr; if (trace) fprintf(stderr, "[ps] realign: %d jobs x %d, widest footprint %d\n", b.d.njobs, b.ndir, *w); }
+    { if (trace_on()) fprintf(stderr, "[ps] realign: %d jobs x %d, widest footprint %d\n", b.d.njobs, b.ndir, *w); }
     const int Pneed = std::max(*w, 1) + 9 <= 1024 ? std::max(*w, 1) + 9 : ((std::max(*w, 1) + 2 + 127) / 128) * 128;
     if (cap > 0) {   // the caller sized this batch on a guess of the footprint: let it split when the real one is much wider
         const int Pr = std::min(b.Pmax, std::max(64, ((Pneed + 63) / 64) * 64));
         double bytes = 0;
         for (const JobD& j : b.jobs) bytes += (double)(j.S + MAT_FRONT + MAT_BACK) * Pr * 18.0 * b.ndir;
         if (bytes > cap) {
-            static const bool trace2 = getenv("PORESEQ_TRACE") != nullptr;
-            if (trace2) fprintf(stderr, "[ps] realign: %.1f GB of matrices at %d slots per anti-diagonal, over the share: split\n", bytes * 1e-9, Pr);
+            if (trace_on()) fprintf(stderr, "[ps] realign: %.1f GB of matrices at %d slots per anti-diagonal, over the share: split\n", bytes * 1e-9, Pr);
             b.P = Pr;
             return PS_SPLIT;
         }
@@ -1111,8 +1115,7 @@ void par_for(int n, const std::function<void(int)>& fn) {
 // and split when it answers PS_SPLIT.  PORESEQ_DEBUG_GUESS_P overrides it (tests: a wrong guess).
 int guess_slots(const Align* a) {
     static const int dbg = getenv("PORESEQ_DEBUG_GUESS_P") ? atoi(getenv("PORESEQ_DEBUG_GUESS_P")) : 0;
-    const int g = dbg > 0 ? dbg : (((2 * a->par.realign_width + 1) * 10 / 19 + 9 + 63) / 64) * 64;
-    return std::min(1024, std::max(64, g));
+    return dbg > 0 ? std::min(1024, std::max(64, dbg)) : guess_slots_w(a->par.realign_width);
 }
 
 // Where the sub-batch of AlignData that starts at as[k0] ends when each event takes `ndir` sweeps: everything if it fits this
@@ -1338,10 +1341,9 @@ static void plan_tables(const Align* a, const std::vector<Mut>& muts, EditPlan* 
         p->oldidx[i] = at;
     }
     p->nr0 = (int)p->r0s.size();
-    static const int lim7 = getenv("PORESEQ_NO_SCORE7") ? -1 : 7;   // (tuning / A-B: point edits on the 8-lane class as before round 5)
     for (int i = 0; i < M; i++) {
         const int nc = p->ncol[i];
-        p->cls[nc <= lim7 ? 4 : nc <= 8 ? 0 : nc <= 16 ? 1 : nc <= 32 ? 2 : 3].push_back(i);
+        p->cls[nc <= 7 ? 4 : nc <= 8 ? 0 : nc <= 16 ? 1 : nc <= 32 ? 2 : 3].push_back(i);
     }
 }
 
@@ -1381,10 +1383,6 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         for (int e = 0; e < as[0]->E; e++) fputc('.', stderr);
         fputc('\n', stderr);
         fflush(stderr);
-    }
-    {   // experiment: how much of a bench step is the latency of a chain?  PORESEQ_DEBUG_SLEEP_US of host sleep per ScoreMutations call
-        static const int us = getenv("PORESEQ_DEBUG_SLEEP_US") ? atoi(getenv("PORESEQ_DEBUG_SLEEP_US")) : 0;
-        if (us > 0) std::this_thread::sleep_for(std::chrono::microseconds(us));
     }
     // Which columns of the score matrices will the edit lists read?  A short list (FindMutations' found edits, the rounds of
     // MakeMutations' recursion: tens to hundreds of edits per region) reads a few percent of them: the fills then run as strip

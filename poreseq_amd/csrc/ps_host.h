@@ -98,8 +98,15 @@ std::string apply_edit(const std::string& b, const Mut& m);
 void accumulate_likes(const double* ra, const double* rl, int n, int C, double* likes);
 
 // strip sweeps (ps_sweep.hip, ps_sweepw.hip): K rows per lane on NW wavefronts per sweep
+// The forms that are built, X(K, on one wavefront, on two, on four) by ascending K: the one list that the form search, the sweep
+// launchers of both files and the backtrace launcher are made from (PS_FORM_1(code): code, PS_FORM_0(code): nothing)
+#define PS_SWEEP_HEIGHTS(X) \
+    X(2, 0, 0, 1) X(3, 0, 0, 1) X(4, 1, 1, 1) X(5, 0, 1, 0) X(6, 1, 1, 1) X(10, 1, 1, 0) X(16, 1, 0, 0) X(24, 1, 0, 0) X(32, 1, 0, 0)
+#define PS_FORM_1(...) __VA_ARGS__
+#define PS_FORM_0(...)
 struct SweepForm { int K = 0, NW = 1; bool ok() const { return K > 0; } };
 int sweep_guess_k(int W);                         // strip height of the one-wavefront form for realign_width W (0: too wide for a strip sweep)
+int sweep_guess_window(int W, int K);             // strips in band on one step, probably, at realign_width W
 SweepForm sweep_guess_form(int W, int NW);        // form to try first on NW wavefronts (K = 0: none)
 SweepForm sweep_next_form(SweepForm f, int win);  // next larger one after a window of `win` strips did not fit (K = 0: none)
 bool sweep_form_exists(int K, int NW);

@@ -16,6 +16,7 @@
 
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/poreseq_hip.h"
@@ -27,12 +28,14 @@ constexpr double BIG = 1e300;  // "inf" of the reference, cpp/AlignUtil.h:20
 
 // ---- error plumbing ------------------------------------------------------------------------
 int fail(int code, const std::string& msg);
+bool trace_on();   // PORESEQ_TRACE is set (read once): diagnostics on stderr
 #define PS_HIP(expr)                                                                          \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
         if (_e != hipSuccess)                                                                 \
             return ps::fail(PS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
     } while (0)
+#define PS_LAUNCH_CHECK() PS_HIP(hipGetLastError())
 #define PS_TRY(expr)            \
     do {                        \
         int _rc = (expr);       \
@@ -214,6 +217,9 @@ struct LikeGroup {
     int C, len;             // states of the sequence; doubles of its vector (bases)
     int64_t out_off;        // into the output pool
 };
+
+// the runtime BatchD.fastdiv as a kernel's template argument: launch(std::true_type / std::false_type)
+template <class F> void with_fastdiv(int fastdiv, F&& launch) { if (fastdiv) launch(std::true_type()); else launch(std::false_type()); }
 
 // ---- kernel launchers (ps_kernels.hip) ------------------------------------------------------
 int launch_updaterefs(Runtime* rt, const BatchD& b);

@@ -40,7 +40,6 @@ __device__ __forceinline__ int slot_of(int i, int P) { return i % P; }
 // one 256-thread block per job; each thread owns a contiguous chunk of levels
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_updaterefs(BatchD b) {
-    chain_priority_wide();
     const JobD& J = b.jobs[blockIdx.x];
     JobOut* O = J.out;
     const int n = J.n0, tid = threadIdx.x;
@@ -92,7 +91,6 @@ __global__ __launch_bounds__(256) void k_updaterefs(BatchD b) {
 
 // lb[j] = getrefstate(j) for j = 0 .. lbn-1 (or -1 when ref_index is empty)
 __global__ void k_lb(BatchD b, int which) {
-    chain_priority_wide();
     const JobD& J = b.jobs[blockIdx.y];
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= J.lbn) return;
@@ -110,7 +108,6 @@ __global__ void k_lb(BatchD b, int which) {
 // Entries [S, S + LO_PAD) are -1: the fill pipeline looks a few anti-diagonals past the end.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lo(BatchD b, int ndir) {
-    chain_priority_wide();
     const int jd = blockIdx.y, job = jd / ndir, dir = jd % ndir;
     const JobD& J = b.jobs[job];
     if (J.out->inert) return;
@@ -849,7 +846,6 @@ __device__ double colmax_pair(const BatchD& b, const JobD& J, int raf, int rab, 
 
 // old score for each distinct r0 = max(start - 3, 1) ; grid (nr0, njobs), block 64
 __global__ __launch_bounds__(64) void k_old(BatchD b, const ScoreArgs* __restrict__ A) {
-    chain_priority_wide();
     const ScoreArgs& a = A[blockIdx.z];
     if (a.oldall || (int)blockIdx.x >= a.nr0 || (int)blockIdx.y >= a.njobs) return;
     const JobD& J = b.jobs[a.job0 + blockIdx.y];
@@ -1261,7 +1257,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) voi
 
 // score[m] = -1e-6 + sum over events in order (cpp/AlignUtil.h:86, cpp/MakeMutations.cpp:51)
 __global__ void k_reduce(const ScoreArgs* __restrict__ A) {
-    chain_priority_wide();
     const ScoreArgs& a = A[blockIdx.y];
     const int njobs = a.njobs;
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1273,7 +1268,6 @@ __global__ void k_reduce(const ScoreArgs* __restrict__ A) {
 
 // latch the reference's "stripe_width == 0" decision (cpp/Alignment.cpp:51-59) for this API call
 __global__ void k_begin(BatchD b) {
-    chain_priority_wide();
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j == 0) *b.maxw = 0;
     if (j >= b.njobs) return;
@@ -1285,7 +1279,6 @@ __global__ void k_begin(BatchD b) {
 // out[job] = JobOut.best of every job of the batch (the results live in their AlignData's own slabs: gathered here so that one copy
 // returns them)
 __global__ void k_gather_best(BatchD b, double* __restrict__ out) {
-    chain_priority_wide();
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < b.njobs) out[j] = b.jobs[j].out->best;
 }
@@ -1293,8 +1286,6 @@ __global__ void k_gather_best(BatchD b, double* __restrict__ out) {
 // =================================================================================================
 // launchers
 // =================================================================================================
-#define PS_LAUNCH_CHECK() PS_HIP(hipGetLastError())
-
 int launch_updaterefs(Runtime* rt, const BatchD& b) {
     if (!b.njobs) return PS_OK;
     hipLaunchKernelGGL(k_updaterefs, dim3(b.njobs), dim3(256), 0, rt->stream, b);
@@ -1332,8 +1323,7 @@ template <int MAXT, bool PAIR, bool CMP>
 static void fill_launch(Runtime* rt, const BatchD& b, const int* d_pairs, int nwg, int ndir, int P, int64_t maxS, size_t lds) {
     const dim3 grid(nwg), block(PAIR ? 2 * P : P);
     const int rc = fill_ring_cols(P), sw = fill_slow_words(maxS), hb = fill_half_bytes(P, maxS);
-    if (b.fastdiv) hipLaunchKernelGGL((k_fill<MAXT, PAIR, true, CMP>), grid, block, lds, rt->stream, b, d_pairs, ndir, P, rc, sw, hb);
-    else hipLaunchKernelGGL((k_fill<MAXT, PAIR, false, CMP>), grid, block, lds, rt->stream, b, d_pairs, ndir, P, rc, sw, hb);
+    with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL((k_fill<MAXT, PAIR, fd.value, CMP>), grid, block, lds, rt->stream, b, d_pairs, ndir, P, rc, sw, hb); });
 }
 
 int launch_fill(Runtime* rt, const BatchD& b, const std::vector<JobD>& jobs, int ndir, int64_t maxS, int P, int64_t ncols) {
@@ -1359,8 +1349,7 @@ int launch_fill(Runtime* rt, const BatchD& b, const std::vector<JobD>& jobs, int
         const int rc = 4096;
         const size_t lds = (size_t)2 * P * 24 + (size_t)rc * 8;
         prof_begin(rt);
-        if (b.fastdiv) hipLaunchKernelGGL(k_fill_wide<true>, dim3(b.njobs * ndir), dim3(P / 2), lds, rt->stream, b, ndir, rc);
-        else hipLaunchKernelGGL(k_fill_wide<false>, dim3(b.njobs * ndir), dim3(P / 2), lds, rt->stream, b, ndir, rc);
+        with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL(k_fill_wide<fd.value>, dim3(b.njobs * ndir), dim3(P / 2), lds, rt->stream, b, ndir, rc); });
         PS_LAUNCH_CHECK();
         prof_end(rt, "fill", 0.0);
         hipLaunchKernelGGL(k_prefix, dim3(b.njobs * ndir), dim3(64), 0, rt->stream, b, ndir);
@@ -1482,8 +1471,7 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
         if (!n) continue;
         const int G = k == 4 ? 7 : 8 << k, ipb = 4 * (64 / G);
         dim3 grid((n + ipb - 1) / ipb, maxE, R), block(256);
-#define PS_SCORE(GG) do { if (b.fastdiv) hipLaunchKernelGGL((k_score<GG, true>), grid, block, 0, rt->stream, b, d_sas); \
-                          else hipLaunchKernelGGL((k_score<GG, false>), grid, block, 0, rt->stream, b, d_sas); } while (0)
+#define PS_SCORE(GG) with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL((k_score<GG, fd.value>), grid, block, 0, rt->stream, b, d_sas); })
         if (k == 4) PS_SCORE(7); else if (k == 0) PS_SCORE(8); else if (k == 1) PS_SCORE(16); else if (k == 2) PS_SCORE(32); else PS_SCORE(64);
 #undef PS_SCORE
         PS_LAUNCH_CHECK();

@@ -32,6 +32,7 @@
 #include <atomic>
 #include <cstring>
 
+#include "ps_dev.h"
 #include "ps_sw.h"
 
 namespace ps {
@@ -515,10 +516,7 @@ template <int K>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 : 4, 8))) void k_sw_trace(const SwPair* pairs, const char* chars, const int* rowsave, const int* colsave,
                                                  const int* blkmax, int* out, int* res) {
     __shared__ unsigned char codes[64][64];
-#ifndef PS_WALKER_PRIO
-#define PS_WALKER_PRIO 3
-#endif
-    if (PS_WALKER_PRIO > 0) __builtin_amdgcn_s_setprio(PS_WALKER_PRIO);   // one serial wave per pair at the end of FindMutations' chain (ps_dev.h, chain_priority)
+    __builtin_amdgcn_s_setprio(PS_WALKER_PRIO);   // one serial wave per pair at the end of FindMutations' chain (ps_dev.h, chain_priority)
     const SwPair p = pairs[blockIdx.x];
     const int l = threadIdx.x;
     int* o = res + p.res_off;
@@ -599,38 +597,33 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
     if (l == 0) { o[0] = best; o[1] = bi; o[2] = bj; o[3] = np; o[4] = nm; o[6] = inexact ? 1 : 0; }
 }
 
-// the packed fill (8 columns per lane, 8 waves) with the traceback of the 8-column build
-static int sw_run_pk(Runtime* rt, hipStream_t st, int np, int nss, const SwPair* d_pairs, const char* d_chars, int* d_row, int* d_col,
-                     int* d_blk, int* d_prog, int* d_ticket, int* d_out, int* d_res) {
-    // PORESEQ_SW_LDS_PAD_KB (tuning): dynamic LDS a strip's workgroup claims on top of its own, i.e. a cap on the strips resident per CU: a
-    // batch of 340 pairs is 1 700 chained strips of eight waves that mostly wait for their left neighbours and would take every free wave slot
-    static const size_t pad = getenv("PORESEQ_SW_LDS_PAD_KB") ? (size_t)atoi(getenv("PORESEQ_SW_LDS_PAD_KB")) * 1024 : 0;
-    hipLaunchKernelGGL((k_sw_fill_pk<SWW, false>), dim3(nss, np), dim3(64 * SWW), pad, st, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_res);
-    PS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_sw_trace<8>, dim3(np), dim3(64), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, d_out, d_res);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
+// the device pointers of an enqueued batch
+struct SwDev { const SwPair* pairs; const char* chars; int *row, *col, *blk, *prog, *ticket, *out, *res; };
 
-// band mode: the packed fill, one workgroup of SWBW waves per pair over its 512-column strips, the same traceback (band-aware
-// through SwPair::wb)
-static int sw_run_band(Runtime* rt, hipStream_t st, int np, const SwPair* d_pairs, const char* d_chars, int* d_row, int* d_col,
-                       int* d_blk, int* d_out, int* d_res) {
-    hipLaunchKernelGGL((k_sw_fill_pk<SWBW, true>), dim3(1, np), dim3(64 * SWBW), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, nullptr, nullptr, d_res);
-    PS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_sw_trace<8>, dim3(np), dim3(64), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, d_out, d_res);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
-}
-
-template <int K, int WW>
-static int sw_run(Runtime* rt, hipStream_t st, int np, int nss, const SwPair* d_pairs, const char* d_chars, int* d_row, int* d_col,
-                  int* d_blk, int* d_prog, int* d_ticket, int* d_out, int* d_res) {
-    hipLaunchKernelGGL((k_sw_fill<K, WW>), dim3(nss, np), dim3(64 * WW), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_res);
-    PS_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_sw_trace<K>, dim3(np), dim3(64), 0, st, d_pairs, d_chars, d_row, d_col, d_blk, d_out, d_res);
-    PS_HIP(hipGetLastError());
-    return PS_OK;
+// Fill and traceback of np pairs in one form: K columns per lane on `waves` waves per workgroup, chained over nss strips
+// (sw_launch on why each exists).  packed: the 16-bit fill (8 columns per lane, SWW waves) with the traceback of the 8-column build;
+// band: the packed fill, one workgroup of SWBW waves per pair over its 512-column strips, the same traceback (band-aware through
+// SwPair::wb).
+static int sw_run(hipStream_t st, const SwDev& d, int np, int nss, int K, int waves, bool packed, bool band) {
+    auto run = [&](auto fill, dim3 grid, int wv, int* prog, int* ticket, auto trace) -> int {
+        hipLaunchKernelGGL(fill, grid, dim3(64 * wv), 0, st, d.pairs, d.chars, d.row, d.col, d.blk, prog, ticket, d.res);
+        PS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(trace, dim3(np), dim3(64), 0, st, d.pairs, d.chars, d.row, d.col, d.blk, d.out, d.res);
+        PS_LAUNCH_CHECK();
+        return PS_OK;
+    };
+    const dim3 strips(nss, np);
+    // (kernels come out in the code object in the order they are first named here)
+    if (packed && !band) return run(k_sw_fill_pk<SWW, false>, strips, SWW, d.prog, d.ticket, k_sw_trace<8>);
+    if (band) return run(k_sw_fill_pk<SWBW, true>, dim3(1, np), SWBW, nullptr, nullptr, k_sw_trace<8>);
+    switch (100 * waves + K) {
+        case 100 * SWW1 + 8: return run(k_sw_fill<8, SWW1>, strips, SWW1, d.prog, d.ticket, k_sw_trace<8>);
+        case 100 * SWW1 + 16: return run(k_sw_fill<16, SWW1>, strips, SWW1, d.prog, d.ticket, k_sw_trace<16>);
+        case 100 * SWW + 4: return run(k_sw_fill<4, SWW>, strips, SWW, d.prog, d.ticket, k_sw_trace<4>);
+        case 100 * SWW + 16: return run(k_sw_fill<16, SWW>, strips, SWW, d.prog, d.ticket, k_sw_trace<16>);
+        case 100 * SWW + 8: return run(k_sw_fill<8, SWW>, strips, SWW, d.prog, d.ticket, k_sw_trace<8>);
+    }
+    return fail(PS_ERR_BAD_ARG, "Smith-Waterman: no fill of " + std::to_string(K) + " columns per lane on " + std::to_string(waves) + " waves is built");
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -692,12 +685,15 @@ static bool band_close(const std::string& s1, const std::string& s2, int wb) {
     return hits * 10 >= tries * 6 && 2 * dmax <= wb;
 }
 
+// PORESEQ_SW_PK=0 (tests): never the packed 16-bit fill
+static bool packed_allowed() { const char* e = getenv("PORESEQ_SW_PK"); return !e || atoi(e) != 0; }
+
 int sw_band_choice(const std::string& s1, const std::string& s2) {
-    const char* e = getenv("PORESEQ_SW_BAND");
+    const char* e = getenv("PORESEQ_SW_BAND");   // (per call, as PORESEQ_SW_BAND_W and PORESEQ_SW_PK: test hooks)
     const int mode = !e || !strcmp(e, "auto") ? 1 : (!strcmp(e, "force") ? 2 : 0);
     const int n1 = (int)s1.size(), n2 = (int)s2.size();
     if (!mode || n1 <= 0 || n2 <= 0 || std::min(n1, n2) > SW_PK_MAXLEN) return 0;
-    if (const char* k = getenv("PORESEQ_SW_PK")) if (atoi(k) == 0) return 0;   // the band fill is a form of the packed one
+    if (!packed_allowed()) return 0;   // the band fill is a form of the packed one
     const int wb = band_width_env();
     if (mode == 2) return wb;
     if (2 * std::abs(n1 - n2) > wb || band_cells(n1, n2, wb) > 0.5 * (double)n1 * n2) return 0;
@@ -795,13 +791,11 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     PS_TRY(rt->buf("sw_res").ensure((size_t)np * 8 * sizeof(int)));
     SwPair* d_pairs = rt->buf("sw_pairs").as<SwPair>();
     char* d_chars = rt->buf("sw_chars").as<char>();
-    int* d_row = rt->buf("sw_row").as<int>();
-    int* d_col = rt->buf("sw_col").as<int>();
     int* d_blk = rt->buf("sw_blk").as<int>();
     int* d_prog = rt->buf("sw_prog").as<int>();
-    int* d_ticket = d_prog + (size_t)nf * nss;
     int* d_out = rt->buf("sw_out").as<int>();
     int* d_res = rt->buf("sw_res").as<int>();
+    SwDev dv = {d_pairs, d_chars, rt->buf("sw_row").as<int>(), rt->buf("sw_col").as<int>(), d_blk, d_prog, d_prog + (size_t)nf * nss, d_out, d_res};
     hipStream_t st = nullptr;
     PS_TRY(second_stream(rt, &st));
     job->stream = st;
@@ -813,29 +807,15 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     if (rt->prof_on) PS_HIP(hipEventRecord(rt->sw0, st));
     bool packed_all = true;   // every pair of the batch on a packed 8-column fill (the band fill is one)
     if (nf) {
-        // the packed 16-bit fill serves the 8-column build whenever every pair's scores fit 16 bits (PORESEQ_SW_PK=0: never; tests)
-        bool packed = K == 8 && WW == SWW;
+        // the packed 16-bit fill serves the 8-column build whenever every pair's scores fit 16 bits
+        bool packed = K == 8 && WW == SWW && packed_allowed();
         for (int k = 0; k < nf && packed; k++) if (std::min(dev[k].n1, dev[k].n2) > SW_PK_MAXLEN) packed = false;
-        if (const char* e = getenv("PORESEQ_SW_PK")) if (atoi(e) == 0) packed = false;
-        if (packed) {
-            PS_TRY(sw_run_pk(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res));
-        } else if (WW == SWW1) {
-            packed_all = false;
-            switch (K) {
-                case 8: PS_TRY((sw_run<8, SWW1>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-                default: PS_TRY((sw_run<16, SWW1>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-            }
-        } else {
-            packed_all = false;
-            switch (K) {
-                case 4: PS_TRY((sw_run<4, SWW>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-                case 16: PS_TRY((sw_run<16, SWW>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-                default: PS_TRY((sw_run<8, SWW>(rt, st, nf, nss, d_pairs, d_chars, d_row, d_col, d_blk, d_prog, d_ticket, d_out, d_res))); break;
-            }
-        }
+        packed_all = packed;
+        PS_TRY(sw_run(st, dv, nf, nss, K, WW, packed, false));
     }
     if (nb) {
-        PS_TRY(sw_run_band(rt, st, nb, d_pairs + nf, d_chars, d_row, d_col, d_blk, d_out, d_res));
+        dv.pairs += nf;
+        PS_TRY(sw_run(st, dv, nb, nss, 8, SWBW, true, true));
         if (rt->prof_on) rt->prof["sw_band"].launches++;
     }
     if (rt->prof_on && packed_all) rt->prof["sw_pk8"].launches++;   // (which fill ran: a host-side count per batch, no event pair)
@@ -884,8 +864,7 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
     }
     g_band[0] += job->nband; g_band[1] += (int64_t)redo.size(); g_band[2] += edge;
     g_band[3] += (int64_t)job->band_cells; g_band[4] += (int64_t)job->cells;
-    static const bool trace = getenv("PORESEQ_TRACE") != nullptr;
-    if (trace && job->nband)
+    if (trace_on() && job->nband)
         fprintf(stderr, "[ps] smith-waterman band: %d of %d pairs banded, %zu fell back, %d maxima near a band edge, %.3g of %.3g cells\n",
                 job->nband, np, redo.size(), edge, job->band_cells, job->cells);
     if (redo.empty()) return PS_OK;

@@ -35,7 +35,6 @@ namespace ps {
 // column C + 1 an empty sentinel.  grid (ceil((maxC + 2) / 256), njobs)
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_band(BatchD b, SweepD sw) {
-    chain_priority_wide();
     const int jd = blockIdx.y, dir = jd % sw.ndir;
     const JobD& J = b.jobs[jd / sw.ndir];
     const SweepJob& SJ = sw.sj[jd];
@@ -51,7 +50,6 @@ __global__ __launch_bounds__(256) void k_band(BatchD b, SweepD sw) {
 // Strip q works on column t - q; it is in band iff  i0(t-q) <= qK + K  (true from some q on: i0 falls as the column does)
 // and  i1(t-q) >= qK + 1  (true up to some q).  grid (ceil((maxT + Q_PAD) / 256), njobs * ndir)
 __global__ __launch_bounds__(256) void k_qlo(BatchD b, SweepD sw) {
-    chain_priority_wide();
     const int jd = blockIdx.y;
     const JobD& J = b.jobs[jd / sw.ndir];
     const SweepJob& SJ = sw.sj[jd];
@@ -224,7 +222,6 @@ __device__ __forceinline__ double cell_emission(const BatchD& b, const JobD& J, 
 
 template <bool FD>
 __global__ __launch_bounds__(256) void k_like_a(BatchD b) {
-    chain_priority_wide();
     const JobD& J = b.jobs[blockIdx.y];
     if (J.out->inert) return;
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -285,7 +282,6 @@ __global__ __launch_bounds__(64) void k_like_b(BatchD b) {
 // ------------------------------------------------------------------------------------------------
 constexpr int LK_MAXC = 12 * 1024;      // bases per sequence the LDS index table holds (longer sequences take the host loop)
 __global__ __launch_bounds__(256) void k_likes(BatchD b, const LikeGroup* __restrict__ groups, double* __restrict__ out) {
-    chain_priority_wide();
     __shared__ int s_idx[LK_MAXC];
     __shared__ int s_part[256];
     const LikeGroup G = groups[blockIdx.x];
@@ -321,7 +317,7 @@ __global__ __launch_bounds__(256) void k_likes(BatchD b, const LikeGroup* __rest
 int launch_likes(Runtime* rt, const BatchD& b, const LikeGroup* d_groups, int ngroups, double* d_out) {
     if (!ngroups) return PS_OK;
     hipLaunchKernelGGL(k_likes, dim3(ngroups), dim3(256), 0, rt->stream, b, d_groups, d_out);
-    PS_HIP(hipGetLastError());
+    PS_LAUNCH_CHECK();
     return PS_OK;
 }
 int likes_max_states() { return LK_MAXC - 4; }
@@ -329,8 +325,6 @@ int likes_max_states() { return LK_MAXC - 4; }
 // =================================================================================================
 // host side
 // =================================================================================================
-#define PS_LAUNCH_CHECK() PS_HIP(hipGetLastError())
-
 // Forms of the strip sweep: K rows per lane on NW wavefronts per sweep (NL = 64 NW lanes).  The strips in band on one step form a
 // window of about (2W + 1) / (K + levels per base) + 2 strips, which must fit NL - 1 lanes (sweep_win_max).
 //   NW = 1   one wavefront per sweep: the fewest instructions per cell at K = 10 for the default width (57 of 64 lanes busy), ~27 ms
@@ -338,59 +332,51 @@ int likes_max_states() { return LK_MAXC - 4; }
 //   NW = 2   K = 4: the same SIMD time per sweep (120 of 128 lanes busy; the per-step overhead of a lane is spread over 4 cells
 //            instead of 10) in half the time, 80 registers fewer (the level records of six rows)
 //   NW = 4   K = 2: a quarter more SIMD time, a third of the time: launches that leave most of the chip idle
-static const int K_LIST1[] = {4, 6, 10, 16, 24, 32, 0};
-static const int K_LIST2[] = {4, 5, 6, 10, 0};
-static const int K_LIST4[] = {2, 3, 4, 6, 0};
-static const int* k_list(int NW) { return NW == 1 ? K_LIST1 : NW == 2 ? K_LIST2 : NW == 4 ? K_LIST4 : nullptr; }
+struct SweepHeight { int K; bool on[3]; };   // on[0 / 1 / 2]: built for one / two / four wavefronts
+static const SweepHeight HEIGHTS[] = {
+#define PS_X(K, W1, W2, W4) {K, {W1, W2, W4}},
+    PS_SWEEP_HEIGHTS(PS_X)
+#undef PS_X
+};
+// the smallest strip height built for NW wavefronts that `ok` accepts (0: none)
+template <class F>
+static int first_height(int NW, F ok) {
+    const int c = NW == 1 ? 0 : NW == 2 ? 1 : NW == 4 ? 2 : -1;
+    for (const SweepHeight& h : HEIGHTS) if (c >= 0 && h.on[c] && ok(h.K)) return h.K;
+    return 0;
+}
 // The strips in band on one step must leave ONE lane of the sweep idle: the lane above the lowest strip in band then holds a strip
 // that is out of band, so what the first row of a band reads as its upper neighbour is the absent-cell value (a band's top row has no
 // neighbour above: cpp/Alignment.cpp:226-236; the kernels do not mask it, they rely on that value).  With a window of NL - 1 strips at
 // most, the strip NL above the one a lane has just left cannot be in band yet.  (Rounds 3-4 kept two lanes idle; the bench's windows
 // at K = 4 sit at 125-128 strips of 128 lanes, and every window of 127 took the next larger strip height at +16 % instructions.)
 int sweep_win_max(int NW) { return 64 * NW - 1; }
-static int guess_window(int W, int K) { return (2 * W + 1) / (K + 1) + 3; }
+int sweep_guess_window(int W, int K) { return (2 * W + 1) / (K + 1) + 3; }
 
 // smallest strip height on NW wavefronts whose window probably fits (K = 0: none)
 SweepForm sweep_guess_form(int W, int NW) {
     SweepForm f;
-    const int* l = k_list(NW);
-    if (!l) return f;
-    for (; *l; l++) if (guess_window(W, *l) <= sweep_win_max(NW)) { f.K = *l; f.NW = NW; return f; }
+    f.K = first_height(NW, [&](int K) { return sweep_guess_window(W, K) <= sweep_win_max(NW); });
+    if (f.K) f.NW = NW;
     return f;
 }
 // the next larger form after a window that did not fit: the next strip height on the same number of wavefronts, else the
 // single-wavefront form of that capacity
 SweepForm sweep_next_form(SweepForm f, int win) {
     SweepForm n;
-    for (const int* l = k_list(f.NW); l && *l; l++) if (*l > f.K) { n.K = *l; n.NW = f.NW; return n; }
-    if (f.NW > 1)
-        for (const int* l = K_LIST1; *l; l++) if (*l * sweep_win_max(1) > f.K * win) { n.K = *l; n.NW = 1; return n; }
+    n.K = first_height(f.NW, [&](int K) { return K > f.K; });
+    if (n.K) n.NW = f.NW;
+    else if (f.NW > 1) n.K = first_height(1, [&](int K) { return K * sweep_win_max(1) > f.K * win; });
     return n;
 }
-bool sweep_form_exists(int K, int NW) {
-    for (const int* l = k_list(NW); l && *l; l++) if (*l == K) return true;
-    return false;
-}
+bool sweep_form_exists(int K, int NW) { return first_height(NW, [&](int k) { return k == K; }) != 0; }
 int sweep_guess_k(int W) { return sweep_guess_form(W, 1).K; }
 
 template <int K>
 static void sweep_launch_k(Runtime* rt, const BatchD& b, const SweepD& sw) {
-    if (sw.ndir == 2 && sw.sparse) {
-        if (b.fastdiv) hipLaunchKernelGGL((k_sweeps<K, true>), dim3(b.njobs * 2), dim3(64), 0, rt->stream, b, sw);
-        else hipLaunchKernelGGL((k_sweeps<K, false>), dim3(b.njobs * 2), dim3(64), 0, rt->stream, b, sw);
-        return;
-    }
-    if (sw.ndir == 2) {
-        if (b.fastdiv) hipLaunchKernelGGL((k_sweep2<K, true>), dim3(b.njobs * 2), dim3(64), 0, rt->stream, b, sw);
-        else hipLaunchKernelGGL((k_sweep2<K, false>), dim3(b.njobs * 2), dim3(64), 0, rt->stream, b, sw);
-        return;
-    }
-    if (b.fastdiv) hipLaunchKernelGGL((k_sweep<K, true>), dim3(b.njobs), dim3(64), 0, rt->stream, b, sw);
-    else hipLaunchKernelGGL((k_sweep<K, false>), dim3(b.njobs), dim3(64), 0, rt->stream, b, sw);
-}
-template <int K>
-static void bt_launch_k(Runtime* rt, const BatchD& b, const SweepD& sw) {
-    hipLaunchKernelGGL((k_backtrace_s<K>), dim3(b.njobs), dim3(256), 0, rt->stream, b, sw);
+    if (sw.ndir == 2 && sw.sparse) with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL((k_sweeps<K, fd.value>), dim3(b.njobs * 2), dim3(64), 0, rt->stream, b, sw); });
+    else if (sw.ndir == 2) with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL((k_sweep2<K, fd.value>), dim3(b.njobs * 2), dim3(64), 0, rt->stream, b, sw); });
+    else with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL((k_sweep<K, fd.value>), dim3(b.njobs), dim3(64), 0, rt->stream, b, sw); });
 }
 
 // bytes one job takes in form f: step codes (forward), and with full = true the records of both directions
@@ -462,19 +448,16 @@ int sweep_run(Runtime* rt, Batch& bt) {
     const BatchD& b = bt.d;
     SweepD& sw = bt.sd;
     const int K = bt.sweep_K, NW = bt.sweep_NW;
+    if (!sweep_form_exists(K, NW)) return fail(PS_ERR_BAD_ARG, "sweep_run: no strip sweep of " + std::to_string(K) + " rows per lane on " + std::to_string(NW) + " wavefronts is built");
     PS_HIP(hipMemsetAsync(sw.sb, 0, (size_t)std::max<int64_t>(bt.sweep_sb, 1) * sizeof(StripBest), rt->stream));
     prof_begin(rt);
     if (NW > 1) {
         if (!b.fastdiv || !sweepw_launch(rt, b, sw, K, NW)) return fail(PS_ERR_BAD_ARG, "sweep_run: no such multi-wavefront form");
     } else {
         switch (K) {
-            case 4: sweep_launch_k<4>(rt, b, sw); break;
-            case 6: sweep_launch_k<6>(rt, b, sw); break;
-            case 10: sweep_launch_k<10>(rt, b, sw); break;
-            case 16: sweep_launch_k<16>(rt, b, sw); break;
-            case 24: sweep_launch_k<24>(rt, b, sw); break;
-            case 32: sweep_launch_k<32>(rt, b, sw); break;
-            default: return fail(PS_ERR_BAD_ARG, "sweep_run: strip height");
+#define PS_X(K, W1, W2, W4) PS_FORM_##W1(case K: sweep_launch_k<K>(rt, b, sw); break;)
+            PS_SWEEP_HEIGHTS(PS_X)
+#undef PS_X
         }
     }
     PS_LAUNCH_CHECK();
@@ -485,26 +468,17 @@ int sweep_run(Runtime* rt, Batch& bt) {
     }
     hipLaunchKernelGGL(k_best, dim3(b.njobs), dim3(64), 0, rt->stream, b, sw);
     if (bt.ndir == 2) PS_TRY(launch_prefix(rt, b, 2));   // running MaxInfo per column of both directions (the strip jobs' best cell is k_best's)
-    switch (K) {
-        case 2: bt_launch_k<2>(rt, b, sw); break;
-        case 3: bt_launch_k<3>(rt, b, sw); break;
-        case 4: bt_launch_k<4>(rt, b, sw); break;
-        case 5: bt_launch_k<5>(rt, b, sw); break;
-        case 6: bt_launch_k<6>(rt, b, sw); break;
-        case 10: bt_launch_k<10>(rt, b, sw); break;
-        case 16: bt_launch_k<16>(rt, b, sw); break;
-        case 24: bt_launch_k<24>(rt, b, sw); break;
-        default: bt_launch_k<32>(rt, b, sw); break;
+    switch (K) {   // (K is one of the heights: checked above)
+#define PS_X(K, W1, W2, W4) case K: hipLaunchKernelGGL((k_backtrace_s<K>), dim3(b.njobs), dim3(256), 0, rt->stream, b, sw); break;
+        PS_SWEEP_HEIGHTS(PS_X)
+#undef PS_X
     }
     PS_LAUNCH_CHECK();
     if (bt.maxn > 0) {
-        if (b.fastdiv) {
-            hipLaunchKernelGGL(k_like_a<true>, dim3((bt.maxn + 255) / 256, b.njobs), dim3(256), 0, rt->stream, b);
-            hipLaunchKernelGGL(k_like_b<true>, dim3(b.njobs), dim3(64), 0, rt->stream, b);
-        } else {
-            hipLaunchKernelGGL(k_like_a<false>, dim3((bt.maxn + 255) / 256, b.njobs), dim3(256), 0, rt->stream, b);
-            hipLaunchKernelGGL(k_like_b<false>, dim3(b.njobs), dim3(64), 0, rt->stream, b);
-        }
+        with_fastdiv(b.fastdiv, [&](auto fd) {
+            hipLaunchKernelGGL(k_like_a<fd.value>, dim3((bt.maxn + 255) / 256, b.njobs), dim3(256), 0, rt->stream, b);
+            hipLaunchKernelGGL(k_like_b<fd.value>, dim3(b.njobs), dim3(64), 0, rt->stream, b);
+        });
         PS_LAUNCH_CHECK();
     }
     return PS_OK;

@@ -7,10 +7,6 @@
 #include "ps_host.h"
 #include "ps_codes.h"
 
-#ifndef PS_SWEEP_STRAIGHT
-#define PS_SWEEP_STRAIGHT 1
-#endif
-
 namespace ps {
 
 #ifdef __HIPCC__
@@ -49,11 +45,8 @@ __device__ __forceinline__ double wave_ror1(double v) {
 // row is fetched ONCE per sweep into a ring in LDS indexed by column (slot = column mod 2 NL, 80-byte pitch: eight consecutive slots
 // cover all 32 banks, a 16-byte read per lane is conflict-free) by wave 0, sixteen columns per batch (64 lanes x 16 bytes), NL columns
 // ahead of the newest column in use; the lanes read their rows from LDS.  640 KB of model rows per 10 kb sweep leave L2 instead of 100 MB.
-#ifndef PS_MODEL_RING
-#define PS_MODEL_RING 1
-#endif
 __host__ __device__ constexpr int mring_slots(int nw) { return 128 * nw; }          // 2 NL columns
-__host__ __device__ constexpr int mring_bytes(int nw) { return PS_MODEL_RING ? (mring_slots(nw) + 1) * MODEL_ROW_BYTES : 16; }   // (+ a spare slot: f_write)
+__host__ __device__ constexpr int mring_bytes(int nw) { return (mring_slots(nw) + 1) * MODEL_ROW_BYTES; }   // (+ a spare slot: f_write)
 
 // columns of the LDS ring of per-column maxima: the widest window (NL - 1 strips) + the 64 steps between two flushes, rounded up
 __host__ __device__ constexpr int ring_cols(int nw) { return nw <= 2 ? 256 : 512; }
@@ -119,18 +112,12 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
         // (forward column j holds states[j - 1], backward column j states[C - j]; ints of -1 around the list)
         a.sc = *(const PS_GLOBAL int*)(st_c + (unsigned)(4 * (DIR == 0 ? j : C - j)));
         a.kc = MODE == 2 ? *(const PS_GLOBAL int*)(keep_c + (unsigned)(4 * j)) : -1;
-        a.ro = PS_MODEL_RING ? (j & (RM - 1)) * MODEL_ROW_BYTES : 0;
+        a.ro = (j & (RM - 1)) * MODEL_ROW_BYTES;
         return a;
     };
     auto model_row = [&](const Ahead& a, double (&m)[8]) {
-        v2d q0, q1, q2, q3;
-        if (PS_MODEL_RING) {
-            const v2d* row = (const v2d*)(mring + a.ro);
-            q0 = row[0]; q1 = row[1]; q2 = row[2]; q3 = row[3];
-        } else {
-            const PS_GLOBAL v2d* row = (const PS_GLOBAL v2d*)(model + (unsigned)max(a.sc, 0) * (unsigned)MODEL_ROW_BYTES);
-            q0 = row[0]; q1 = row[1]; q2 = row[2]; q3 = row[3];
-        }
+        const v2d* row = (const v2d*)(mring + a.ro);
+        const v2d q0 = row[0], q1 = row[1], q2 = row[2], q3 = row[3];
         m[0] = q0.x; m[1] = q0.y; m[2] = q1.x; m[3] = q1.y; m[4] = q2.x; m[5] = q2.y; m[6] = q3.x; m[7] = q3.y;
     };
 
@@ -144,7 +131,7 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
     // a strip that has left the band does not come back) — i.e. NL columns ahead of jn.  At the start of a sweep and on the step
     // after a stretch without any strip in band, the columns the next step reads may not be there yet: all 64 lanes then load
     // sixteen columns at a time on the spot (two dependent round trips each: rare).
-    const bool feeder = PS_MODEL_RING && wv == 0;
+    const bool feeder = wv == 0;
     typedef const __attribute__((address_space(4))) int* kst_t;
     kst_t st_k = (kst_t)uni_ptr(J.st);
     int jf = 0;                         // columns 1 .. jf are in the ring (visible behind the next barrier)
@@ -218,11 +205,9 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
     int ql0 = QLO[1], ql1 = QLO[2], ql2 = QLO[3];   // qlo of step t, t + 1, t + 2 (scalar registers; T + Q_PAD entries, -1 behind T)
     Ahead aA = fetch(1, ql0), aB = fetch(2, ql1), aC = aB;   // three pipeline stages whose roles rotate with the step (the loop is unrolled by three)
     double mr[8];
-    if (PS_MODEL_RING) {
-        // the rows of step 1's columns (every lane's column is clamped into 1 .. C: column 1 where its strip has not started)
-        if (feeder) { feed_now(min(max(C, 1), ql0 >= 0 ? max(1 - ql0, 1) : 1)); if (jf < C) { fsb = jf; fs0 = st_of(min(jf + 1, C)); fs1 = st_of(min(jf + 2, C)); } }
-        if (NW > 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
+    // the rows of step 1's columns (every lane's column is clamped into 1 .. C: column 1 where its strip has not started)
+    if (feeder) { feed_now(min(max(C, 1), ql0 >= 0 ? max(1 - ql0, 1) : 1)); if (jf < C) { fsb = jf; fs0 = st_of(min(jf + 1, C)); fs1 = st_of(min(jf + 2, C)); } }
+    if (NW > 1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     model_row(aA, mr);
     // The level records of the strip a lane works on at step t + 1 are fetched during step t, behind the step's emissions (the last
     // readers of the old ones): a strip's rows are read once per sweep, so the loads miss every cache, and issued at the top of
@@ -271,12 +256,7 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
                 v.x = cw[r0 / 4]; v.y = cw[r0 / 4 + 1];
                 *(PS_GLOBAL v2i*)p = v;
             } else if (sz == 4) {
-#ifndef PS_CODES_NT
-#define PS_CODES_NT 0
-#endif
-                // (PS_CODES_NT: the codes as non-temporal stores — 7 MB per sweep that only the backtrace reads, sparsely, a kernel later)
-                if (PS_CODES_NT) __builtin_nontemporal_store(cw[r0 / 4], (PS_GLOBAL unsigned*)p);
-                else *(PS_GLOBAL unsigned*)p = cw[r0 / 4];
+                *(PS_GLOBAL unsigned*)p = cw[r0 / 4];
             } else {
                 // a register with nrow < 4 rows holds its first row in field nrow - 1: the plane's rows r0 .. r0 + sz - 1 are the sz
                 // fields from field nrow - (r0 mod 4) - sz on, last row lowest
@@ -315,11 +295,9 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
 #pragma unroll
             for (int r = 0; r < K; r++) { pm[r] = NINF; if (DIR) pe[r] = NINF; }
         }
-        if (PS_MODEL_RING) f_top(ql1 >= 0 ? t + 1 - ql1 : 0, ql >= 0 ? t - ql : 0);   // (before the step's barrier: what it writes now is read behind it)
+        f_top(ql1 >= 0 ? t + 1 - ql1 : 0, ql >= 0 ? t - ql : 0);   // (before the step's barrier: what it writes now is read behind it)
         // (qlo one step further ahead than it is needed: the scalar load's latency stays off the step.  With the model rows in LDS the
         //  emissions below wait for LDS reads — the same counter as scalar loads — so the load is issued behind them, further down)
-        int ql3 = 0;
-        if (!PS_MODEL_RING) ql3 = QLO[t + 3];
         a2 = fetch(t + 2, ql2);
         __builtin_amdgcn_sched_barrier(0);                           // (the step's loads are issued before its first emission waits for the model row)
         // emissions of the lane's K cells first: the model row is then free to receive the next column's (one step of lead).  NW > 1:
@@ -347,11 +325,11 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
         put_pending(t - 1);
         load_levels(ql1);
         model_row(a1, mr);
-        if (PS_MODEL_RING) ql3 = QLO[t + 3];
+        const int ql3 = QLO[t + 3];
         pend = live;
         // (a step without a strip in band — the steps a last round of three adds behind T - 1 — runs the cells too, on no band: a uniform
         //  branch around them makes every loop-carried value a phi of two definitions, eight register copies per step)
-        if ((PS_SWEEP_STRAIGHT && MODE != 1) || live) {   // (MODE 1 stores a record per cell and step: behind T - 1 there is no room for them)
+        if (MODE != 1 || live) {   // (MODE 1 stores a record per cell and step: behind T - 1 there is no room for them)
             const int base = q * K + 1;
             const bool valid = live && j >= 1 && j <= C && a0.sc >= 0;     // (a column whose 5-mer is invalid is all zero: no cell takes part, cpp/Alignment.cpp:162-163)
             const int ra = valid ? a0.i0 - base : K, rb = valid ? a0.i1 - base : -1;   // band rows relative to the strip
@@ -466,10 +444,7 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
                     asm("v_max_f64 %0, %1, %2" : "=v"(lbest) : "v"(lbest), "v"(nmx));   // (= gt ? nmx : lbest: one v_max instead of two selects; no canonicalisation of the operands)
                     lbr = gt ? r : lbr;
                 }
-#ifndef PS_SWEEP_ROW_FENCE
-#define PS_SWEEP_ROW_FENCE 1
-#endif
-                if (PS_SWEEP_ROW_FENCE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
             bot_m = um; bot_s = us; bot_e = ue;
             if (DIR == 0) lbt = lbest > lbefore ? t : lbt;
@@ -495,17 +470,15 @@ __device__ __forceinline__ void sweep_body(const BatchD& b, const SweepD& sw, co
             *(v2d*)h = (v2d){bot_m, bot_s};
             if (DIR) h[2] = bot_e;
         }
-        if (PS_MODEL_RING) f_end();
+        f_end();
         ql0 = ql1; ql1 = ql2; ql2 = ql3;
     };
 
-#ifndef PS_SWEEP_UNROLL_MAXK
-#define PS_SWEEP_UNROLL_MAXK 5
-#endif
-    if (K <= PS_SWEEP_UNROLL_MAXK) {
-        // steps 1 .. T - 1, three to a round so that the pipeline stages need no copies; the steps a last round adds behind T - 1 find
-        // no strip in band (qlo = -1 there: Q_PAD) and do nothing.  (Taller strips keep one copy of the body: three of K = 10's
-        // would be most of the instruction cache two CUs share.)
+    // steps 1 .. T - 1, three to a round so that the pipeline stages need no copies; the steps a last round adds behind T - 1 find
+    // no strip in band (qlo = -1 there: Q_PAD) and do nothing.  (Taller strips keep one copy of the body: three of K = 10's
+    // would be most of the instruction cache two CUs share.)
+    constexpr int UNROLL_MAXK = 5;
+    if (K <= UNROLL_MAXK) {
         for (int t = 1; t < T; t += 3) {
             step(t, aA, aB, aC);
             step(t + 1, aB, aC, aA);

@@ -60,24 +60,19 @@ void k_sweeps_w(BatchD b, SweepD sw) {
 
 template <int K, int NW>
 static void launch_w(Runtime* rt, const BatchD& b, const SweepD& sw) {
-    // PORESEQ_SWEEP_LDS_PAD_KB (tuning): dynamic LDS a sweep's workgroup claims on top of its own, i.e. a cap on the sweeps resident per CU
-    // (160 KB of LDS per CU) that leaves registers and wave slots to the short kernels of the other batches' chains
-    static const size_t pad = getenv("PORESEQ_SWEEP_LDS_PAD_KB") ? (size_t)atoi(getenv("PORESEQ_SWEEP_LDS_PAD_KB")) * 1024 : 0;
-    if (sw.ndir == 2 && sw.sparse) hipLaunchKernelGGL((k_sweeps_w<K, NW>), dim3(b.njobs * 2), dim3(64 * NW), pad, rt->stream, b, sw);
-    else if (sw.ndir == 2) hipLaunchKernelGGL((k_sweep2_w<K, NW>), dim3(b.njobs * 2), dim3(64 * NW), pad, rt->stream, b, sw);
-    else hipLaunchKernelGGL((k_sweep_w<K, NW>), dim3(b.njobs), dim3(64 * NW), pad, rt->stream, b, sw);
+    if (sw.ndir == 2 && sw.sparse) hipLaunchKernelGGL((k_sweeps_w<K, NW>), dim3(b.njobs * 2), dim3(64 * NW), 0, rt->stream, b, sw);
+    else if (sw.ndir == 2) hipLaunchKernelGGL((k_sweep2_w<K, NW>), dim3(b.njobs * 2), dim3(64 * NW), 0, rt->stream, b, sw);
+    else hipLaunchKernelGGL((k_sweep_w<K, NW>), dim3(b.njobs), dim3(64 * NW), 0, rt->stream, b, sw);
 }
 
 bool sweepw_launch(Runtime* rt, const BatchD& b, const SweepD& sw, int K, int NW) {
     switch (NW * 100 + K) {
-        case 204: launch_w<4, 2>(rt, b, sw); return true;
-        case 205: launch_w<5, 2>(rt, b, sw); return true;
-        case 206: launch_w<6, 2>(rt, b, sw); return true;
-        case 210: launch_w<10, 2>(rt, b, sw); return true;
-        case 402: launch_w<2, 4>(rt, b, sw); return true;
-        case 403: launch_w<3, 4>(rt, b, sw); return true;
-        case 404: launch_w<4, 4>(rt, b, sw); return true;
-        case 406: launch_w<6, 4>(rt, b, sw); return true;
+#define PS_X(K, W1, W2, W4) PS_FORM_##W2(case 200 + K: launch_w<K, 2>(rt, b, sw); return true;)
+        PS_SWEEP_HEIGHTS(PS_X)
+#undef PS_X
+#define PS_X(K, W1, W2, W4) PS_FORM_##W4(case 400 + K: launch_w<K, 4>(rt, b, sw); return true;)
+        PS_SWEEP_HEIGHTS(PS_X)
+#undef PS_X
     }
     return false;
 }

@@ -475,7 +475,7 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
     else hipLaunchKernelGGL(k_vit_obs<256>, dim3((unsigned)ttot), dim3(256), 0, rt->stream, d_regs, d_posreg, d_in, std::log(2 * M_PI), d_obs, d_eobs);
     hipLaunchKernelGGL(k_vit_steps, dim3(R), dim3(1024), 0, rt->stream, d_regs, d_obs, d_eobs, skip, stay, std::log(skip), std::log(stay),
                        std::log(0.25), d_bp, d_fwd, d_lik, nkeep ? 1 : 0);
-    PS_HIP(hipGetLastError());
+    PS_LAUNCH_CHECK();
     double* lik = nullptr;
     PS_TRY(rt->down(&lik, d_lik, (size_t)R * NS));
     // the uniform deviates of the stochastic back-traces are drawn on the host while the recursion runs: per region in the
@@ -511,7 +511,7 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
     hipLaunchKernelGGL(k_vit_log, dim3((unsigned)(((size_t)ttot * NS + 255) / 256)), dim3(256), 0, rt->stream, d_fwd, (size_t)ttot * NS);
     hipLaunchKernelGGL(k_vit_trace, dim3(nkeep, R), dim3(VT_THREADS), 0, rt->stream, d_regs, d_fwd, rt->buf("vit_start").as<int>(), skip, stay,
                        rt->buf("vit_att").as<double>(), rt->buf("vit_rnd").as<double>(), rt->buf("vit_path").as<short>());
-    PS_HIP(hipGetLastError());
+    PS_LAUNCH_CHECK();
     prof_end(rt, "viterbi", (double)ttot * NS * (8.0 * maxE + 8 + 2 + 8 + 8.0 * nkeep));
     short* hp = nullptr;
     PS_TRY(rt->down(&hp, rt->buf("vit_path").p, (size_t)nkeep * ttot));

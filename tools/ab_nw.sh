@@ -1,7 +1,8 @@
 #!/bin/bash
-# A/B of the strip sweep's form in the bench: one and two wavefronts per sweep, alternating, three timed steps each (one box, one call).
+# A/B of the strip sweep's form in the bench: one and two wavefronts per sweep (PORESEQ_SWEEP_FORM=0,NW: the smallest strip height
+# that fits on NW wavefronts), alternating, three timed steps each (one box, one call).
 # usage (GPU box): bash tools/ab_nw.sh
-for cfg in "PORESEQ_SWEEP_NW=1" "PORESEQ_SWEEP_NW=2" "PORESEQ_SWEEP_NW=1" "PORESEQ_SWEEP_NW=2"; do
+for cfg in "PORESEQ_SWEEP_FORM=0,1" "PORESEQ_SWEEP_FORM=0,2" "PORESEQ_SWEEP_FORM=0,1" "PORESEQ_SWEEP_FORM=0,2"; do
   echo "== $cfg"
   env $cfg timeout 600 python bench.py --steps 3 --warmup 1 --full --no-cpu --no-extras 2>/dev/null | python -c "
 import sys, json

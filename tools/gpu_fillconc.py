@@ -29,7 +29,6 @@ def work(t):
     res[t] = (sum(ts) / N, api.prof_get("fill"), ts)
 th = [threading.Thread(target=work, args=(t,)) for t in range(T)]
 [x.start() for x in th]; [x.join() for x in th]
-print("threads %d x %d regions: %.1f ms per call; fill launch avg %.1f ms (%s)" % (
-    T, R, 1e3 * sum(r[0] for r in res) / T, sum(r[1][0] for r in res) / max(1, sum(r[1][1] for r in res)),
-    os.environ.get("PORESEQ_EXPERIMENT_NOSTORE") and "NO STORES" or "stores"))
+print("threads %d x %d regions: %.1f ms per call; fill launch avg %.1f ms" % (
+    T, R, 1e3 * sum(r[0] for r in res) / T, sum(r[1][0] for r in res) / max(1, sum(r[1][1] for r in res))))
 print("   thread 0 calls (ms):", " ".join("%.0f" % (1e3 * x) for x in res[0][2]))
