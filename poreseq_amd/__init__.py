@@ -31,7 +31,7 @@ def _want_hw_queues():
     has opened the GPU yet (torch.cuda.is_available(), another HIP library ...: the variable would be ignored, and the library, told
     that it is in force, would put every stream on one priority level: seven streams on four queues).  PORESEQ_HWQ_SET_BY_PACKAGE=1
     tells the library that the value can be trusted; otherwise it deals its streams over the device's priority levels
-    (ps_host.cpp, hwq_mode; `poreseq_amd._capi.load_hip().info()` says which mode a process is in)."""
+    (ps_runtime.cpp, hwq_mode; `poreseq_amd._capi.load_hip().info()` says which mode a process is in)."""
     if "GPU_MAX_HW_QUEUES" in _os.environ:
         return
     if _gpu_opened():

@@ -14,7 +14,7 @@
 
 namespace ps {
 
-// cap on the DP-matrix bytes of one batch of candidate-sequence alignments: this runtime's share of the device (ps_host.cpp)
+// cap on the DP-matrix bytes of one batch of candidate-sequence alignments: this runtime's share of the device (ps_mem.cpp)
 static double max_batch_bytes() { return device_share_bytes(); }
 
 static void fillinds(SwResult& al) {  // cpp/swlib.cpp:342-365
@@ -145,7 +145,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     std::vector<int> wbs(pairs.size());
     for (size_t k = 0; k < pairs.size(); k++) wbs[k] = sw_band_choice(*pairs[k].first, *pairs[k].second);
     auto sw_bytes = [&](size_t k) { return sw_pair_bytes((int)pairs[k].first->size(), (int)pairs[k].second->size(), wbs[k]); };
-    double sw_cap = device_share_bytes() / 8;
+    double sw_cap = device_share_bytes() / PLAN_SW_PART;
     auto sw_chunk_end = [&](size_t k0) {
         double acc = 0;
         size_t k = k0;
@@ -233,7 +233,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
                 double add = 0;
                 for (int e = 0; e < a->E; e++)
                     add += sweep_enabled() && sweep_guess_k(a->par.realign_width) ? fwd_job_bytes(a, a->n[e], (int)need[q1].states.size())
-                                                                                  : ((double)a->n[e] + need[q1].states.size() + 1 + MAT_FRONT + MAT_BACK) * P * 18.0;
+                                                                                  : matrix_bytes((int64_t)a->n[e] + (int64_t)need[q1].states.size() + 1, P, 1);
                 if (q1 > q0 && (bytes + add > cap || q1 - q0 >= limit)) break;
                 bytes += add; nref += (size_t)a->ntot; q1++;
             }
@@ -275,8 +275,8 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             for (size_t q = q0; q < q1; q++) {
                 Align* a = as[need[q].r];
                 for (int e = 0; e < a->E; e++) {
-                    JobSpec s;
-                    s.a = a; s.ev = e; s.states = &need[q].states;
+                    JobSpec s = a->job(e);   // the event's data; the candidate's states and its remapped alignment on top
+                    s.states = &need[q].states;
                     const size_t o = roff[q - q0] + a->off[e];
                     s.ra = d_ra + o; s.rl = d_rl + o; s.ri = d_ri + o;
                     s.out = ob.as<JobOut>() + specs.size();
@@ -288,7 +288,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             PS_TRY(launch_updaterefs(rt, b.d));  // MapAlignments ends with updaterefs (cpp/EventUtil.cpp:51)
             tk.lap("seed batch build");
             {
-                const int rc = realign(rt, b, q1 - q0 > 1 ? 1.2 * cap : 0.0);
+                const int rc = realign(rt, b, q1 - q0 > 1 ? PLAN_OVER_GUESS * cap : 0.0);
                 if (rc == PS_SPLIT) {   // wider bands than guessed: cut the chunk again with the width it asked for
                     { if (trace_on()) fprintf(stderr, "[ps] seed chunk of %zu cut again: %d slots per anti-diagonal, %d guessed\n", q1 - q0, b.P, std::max(p_seen, 0)); }
                     p_seen = std::max(p_seen, b.P);
@@ -529,7 +529,7 @@ int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::
         // probabilities: 26 KB per position; ~270 MB per 10 kb region); the regions' generators keep the results the same however
         // the batch is cut; a sub-batch the device has no memory for is cut in two
         auto need = [&](size_t k) { return 26.0 * 1024.0 * (double)regs[k].T + 32.0 * (double)regs[k].T * regs[k].E; };
-        double cap = std::max(1e9, 0.9 * device_share_bytes());   // (the tables live in the runtime's matrix pool, which no alignment uses during this call)
+        double cap = std::max(1e9, PLAN_VITERBI_FRAC * device_share_bytes());   // (the tables live in the runtime's matrix pool, which no alignment uses during this call)
         for (size_t k0 = 0; k0 < regs.size();) {
             size_t k1 = k0;
             double acc = 0;

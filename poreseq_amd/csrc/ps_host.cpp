@@ -1,389 +1,23 @@
-// ps_host.cpp — host side of libporeseq_hip.so: runtime, AlignData, batching, and the
-// refinement-loop logic that the reference keeps in C++ above its Alignment class
-// (cpp/MakeMutations.cpp, cpp/FindMutations.cpp, cpp/EventUtil.cpp, cpp/Sequence.h).
+// ps_host.cpp — host side of libporeseq_hip.so above the runtime: sequences, AlignData, alignment batches and realign() (which
+// fill runs for a batch, in which form), and the refinement-loop logic that the reference keeps in C++ above its Alignment class
+// (cpp/MakeMutations.cpp, cpp/FindMutations.cpp, cpp/EventUtil.cpp, cpp/Sequence.h): ScoreAlignments, ScoreMutations with its edit
+// plans, FindPointMutations, MakeMutations.  The runtime, its streams and par_for are in ps_runtime.cpp; device memory — pools,
+// shares, slabs, the AlignData slab cache — in ps_mem.cpp, its arithmetic in ps_plan.h.
 // All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_sw.hip,
 // ps_viterbi.hip); there is no CPU implementation of it in this library.
 #include "ps_host.h"
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <array>
-#include <functional>
 #include <iterator>
 #include <numeric>
-#include <mutex>
-#include <deque>
-#include <memory>
-#include <condition_variable>
 #include <thread>
-#include <cstdio>
-#include <ctime>
 
 namespace ps {
-
-static thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-const char* last_error() { return g_err.c_str(); }
-
-static double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
-bool trace_on() { static const bool on = getenv("PORESEQ_TRACE") != nullptr; return on; }
-Tick::Tick(const char* w) : what(w), t0(now_s()), on(trace_on()) {}
-void Tick::lap(const char* label) {
-    if (!on) return;
-    const double t = now_s();
-    fprintf(stderr, "[ps] %-18s %-22s %8.3f ms\n", what, label, 1e3 * (t - t0));
-    t0 = t;
-}
-
-// ------------------------------------------------------------------------------------------ runtime
-static size_t trim_idle_runtimes();   // below: hands back the device pools of runtimes no thread owns
-static size_t device_total_bytes();
-static size_t device_plan_bytes();   // this process's part of it (ps_set_device_fraction)
-static std::atomic<long long> g_pool_bytes(0);   // device memory held by the pools of all runtimes
-
-int DBuf::ensure(size_t bytes) {
-    if (bytes <= cap && p) return PS_OK;
-    if (trace_on()) fprintf(stderr, "[ps] pool grow %zu -> %zu bytes\n", cap, bytes);
-    if (p) { PS_HIP(hipFree(p)); p = nullptr; g_pool_bytes -= (long long)cap; cap = 0; }
-    size_t want = std::max<size_t>(bytes + std::min<size_t>(bytes / 4, (size_t)1 << 30), 1 << 16);   // growth slack, at most 1 GB
-    // never into the last 6 % of the device: a launch that finds no memory for the HSA runtime's own needs aborts the process
-    // (HSA_STATUS_ERROR_OUT_OF_RESOURCES) — refuse here instead, callers that can cut their batch do so on PS_ERR_NOMEM
-    if (const size_t tot = device_plan_bytes()) {
-        auto over = [&](size_t w) { return (double)g_pool_bytes.load() + (double)w > 0.94 * (double)tot; };
-        if (over(want)) want = std::max<size_t>(bytes, 1 << 16);
-        if (over(want)) (void)trim_idle_runtimes();
-        if (over(want))
-            return fail(PS_ERR_NOMEM, "device pools of this process would reach " + std::to_string((size_t)((g_pool_bytes.load() + (long long)want) >> 20)) + " MB of " +
-                                      std::to_string(tot >> 20) + " MB (a buffer of " + std::to_string(want >> 20) + " MB was asked for)");
-    }
-    if (hipMalloc(&p, want) != hipSuccess) {
-        p = nullptr;
-        (void)hipGetLastError();   // (sticky: the next launch check would report it)
-        want = std::max<size_t>(bytes, 1 << 16);
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            // runtimes on the free list (their threads are gone) keep their pools for the next thread: take them back first
-            (void)hipGetLastError();
-            const size_t got = trim_idle_runtimes();
-            if (trace_on()) fprintf(stderr, "[ps] out of device memory: %zu bytes taken back from idle runtimes\n", got);
-            p = nullptr;
-            e = got ? hipMalloc(&p, want) : e;
-        }
-        if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); 
-            size_t fr = 0, tt = 0;
-            (void)hipMemGetInfo(&fr, &tt);
-            return fail(PS_ERR_NOMEM, std::string("hipMalloc of ") + std::to_string(want >> 20) + " MB: " + hipGetErrorString(e) + " (" + std::to_string(fr >> 20) + " of " +
-                                      std::to_string(tt >> 20) + " MB free, " + std::to_string((long long)(g_pool_bytes.load() >> 20)) + " MB in this process's pools)");
-        }
-    }
-    cap = want;
-    g_pool_bytes += (long long)cap;
-    return PS_OK;
-}
-
-int HBuf::ensure(size_t bytes) {
-    if (bytes <= cap && p) return PS_OK;
-    if (p) { PS_HIP(hipHostFree(p)); p = nullptr; cap = 0; }
-    const size_t want = std::max<size_t>(bytes + bytes / 4, 1 << 16);
-    PS_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
-    cap = want;
-    return PS_OK;
-}
-
-void* Stage::alloc(size_t bytes) {
-    bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
-    if (chunks.empty() || used + bytes > chunks.back().cap) {
-        size_t want = std::max<size_t>(bytes, chunks.empty() ? (size_t)4 << 20 : 2 * chunks.back().cap);
-        void* p = nullptr;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-            want = bytes;
-            if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) return nullptr;
-        }
-        chunks.push_back({(char*)p, want});
-        used = 0;
-    }
-    void* r = chunks.back().p + used;
-    used += bytes;
-    dirty = true;
-    return r;
-}
-
-int Stage::reset() {
-    if (chunks.size() > 1) {   // grew during the last call: one chunk of the combined size from now on
-        size_t tot = 0;
-        for (Chunk& c : chunks) { tot += c.cap; PS_HIP(hipHostFree(c.p)); }
-        chunks.clear();
-        void* p = nullptr;
-        if (hipHostMalloc(&p, tot, hipHostMallocDefault) == hipSuccess) chunks.push_back({(char*)p, tot});
-    }
-    used = 0;
-    dirty = false;
-    return PS_OK;
-}
-
-int Runtime::up(void* dst, const void* src, size_t bytes, hipStream_t st) {
-    if (!bytes) return PS_OK;
-    void* h = stage.alloc(bytes);
-    if (!h) return fail(PS_ERR_NOMEM, "hipHostMalloc (staging arena)");
-    memcpy(h, src, bytes);
-    PS_HIP(hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, st ? st : stream));
-    return PS_OK;
-}
-
-int Runtime::down(void** hptr, const void* src, size_t bytes, hipStream_t st) {
-    void* h = stage.alloc(bytes);
-    if (!h) return fail(PS_ERR_NOMEM, "hipHostMalloc (staging arena)");
-    *hptr = h;
-    if (bytes) PS_HIP(hipMemcpyAsync(h, src, bytes, hipMemcpyDeviceToHost, st ? st : stream));
-    return PS_OK;
-}
-
-// One runtime (HIP streams + grow-only device pools) per host thread that is inside the library: independent
-// PSAlign pipelines driven from different threads run concurrently on the GPU — a single region keeps at most a
-// few dozen of the 256 CUs busy, and regions are independent work-items.  Runtimes live in a process-wide
-// free-list: a thread adopts one on its first call and hands it back when it exits, so short-lived worker
-// threads reuse the pools instead of re-allocating (or leaking) them.
-namespace {
-struct RtSlot { Runtime R; int state = 0; std::string why; };   // state: 0 untried, 1 ok, -1 failed
-std::mutex g_rt_mu;
-std::vector<RtSlot*> g_rt_free;
-struct RtHolder {
-    RtSlot* s = nullptr;
-    ~RtHolder();
-};
-thread_local RtHolder t_rt;
-std::atomic<int> g_rt_live(0);
-std::atomic<int> g_rt_peak(0);   // most threads that owned a runtime at the same time (forgotten a minute after the count was last that high)
-std::atomic<double> g_rt_peak_at(0.0);
-}  // namespace
-int live_runtimes() { return g_rt_live.load(); }
-int peak_runtimes() {
-    // a burst of threads long ago must not shrink a later lone caller's share for good
-    const double t = now_s();
-    if (t - g_rt_peak_at.load() > 60.0) { g_rt_peak.store(std::max(g_rt_live.load(), 1)); g_rt_peak_at.store(t); }
-    return g_rt_peak.load();
-}
-static size_t trim_idle_runtimes() {
-    std::lock_guard<std::mutex> lk(g_rt_mu);
-    size_t got = 0;
-    for (RtSlot* s : g_rt_free)
-        for (auto& kv : s->R.pool) {
-            DBuf& b = kv.second;
-            if (b.p && hipFree(b.p) == hipSuccess) got += b.cap;   // (the owning thread drained its streams before it left)
-            if (b.p) g_pool_bytes -= (long long)b.cap;
-            b.p = nullptr; b.cap = 0;
-        }
-    return got;
-}
-RtHolder::~RtHolder() {
-    if (!s) return;
-    if (getenv("PORESEQ_TRACE")) {   // what this thread's runtime holds, largest first
-        std::vector<std::pair<size_t, std::string>> v;
-        size_t tot = 0;
-        for (auto& kv : s->R.pool) { v.push_back({kv.second.cap, kv.first}); tot += kv.second.cap; }
-        std::sort(v.rbegin(), v.rend());
-        std::string line = "[ps] runtime handed back: " + std::to_string(tot >> 20) + " MB of device pools:";
-        for (size_t k = 0; k < v.size() && k < 12; k++) line += " " + v[k].second + " " + std::to_string(v[k].first >> 20);
-        fprintf(stderr, "%s\n", line.c_str());
-    }
-    std::lock_guard<std::mutex> lk(g_rt_mu);
-    g_rt_free.push_back(s);
-    g_rt_live--;
-}
-
-// How the runtimes' streams get hardware queues (see make_stream below).  GPU_MAX_HW_QUEUES only counts when HIP read it, i.e. when
-// it was in the environment before the HIP runtime started: either the process was started with it (/proc/self/environ is the
-// environment at exec, later setenv calls do not show there), or the poreseq_amd package exported it at import after checking that
-// nothing in the process had opened the GPU yet (it then sets PORESEQ_HWQ_SET_BY_PACKAGE=1).  A value that appeared any other way
-// is not trusted: seven streams on four queues of ONE priority level would be the slowest arrangement of all (108 against 141 kb/s).
-static int hwq_from_exec_env() {
-    static const int v = [] {
-        FILE* f = fopen("/proc/self/environ", "rb");
-        if (!f) return 0;
-        std::string all;
-        char buf[4096];
-        size_t n;
-        while ((n = fread(buf, 1, sizeof buf, f)) > 0) all.append(buf, n);
-        fclose(f);
-        const std::string key = "GPU_MAX_HW_QUEUES=";
-        for (size_t at = 0; at < all.size();) {
-            const size_t end = all.find('\0', at);
-            const std::string kv = all.substr(at, end == std::string::npos ? std::string::npos : end - at);
-            if (kv.compare(0, key.size(), key) == 0) return atoi(kv.c_str() + key.size());
-            if (end == std::string::npos) break;
-            at = end + 1;
-        }
-        return 0;
-    }();
-    return v;
-}
-int hwq_mode(std::string* why) {
-    static int mode = -1;
-    static std::string reason;
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lk(mu);
-    if (mode < 0) {
-        const char* e = getenv("GPU_MAX_HW_QUEUES");
-        const int now = e ? atoi(e) : 0;
-        const char* pk = getenv("PORESEQ_HWQ_SET_BY_PACKAGE");
-        if (getenv("PORESEQ_ONE_PRIORITY")) { mode = 1; reason = "one priority level (PORESEQ_ONE_PRIORITY)"; }
-        else if (getenv("PORESEQ_PRIORITY_LEVELS")) { mode = 0; reason = "streams dealt over the priority levels (PORESEQ_PRIORITY_LEVELS)"; }
-        else if (hwq_from_exec_env() >= 8) { mode = 1; reason = "one priority level, a hardware queue per stream (GPU_MAX_HW_QUEUES=" + std::to_string(hwq_from_exec_env()) + " in the process's start-up environment)"; }
-        else if (now >= 8 && pk && atoi(pk) == 1) { mode = 1; reason = "one priority level, a hardware queue per stream (GPU_MAX_HW_QUEUES=" + std::to_string(now) + " exported by the poreseq_amd package before HIP started)"; }
-        else {
-            mode = 0;
-            reason = now >= 8 ? "streams dealt over the priority levels (GPU_MAX_HW_QUEUES=" + std::to_string(now) + " appeared after start-up without the package's guarantee that HIP had not started: not trusted)"
-                              : "streams dealt over the priority levels (HIP's default of 4 hardware queues per level)";
-        }
-    }
-    if (why) *why = reason;
-    return mode;
-}
-
-int second_stream(Runtime* rt, hipStream_t* out) {
-    // One stream per runtime as soon as several host threads drive the GPU (lock-step batches in flight): HIP maps streams onto
-    // 4 hardware queues by default, and the 5th stream serialises behind another one — measured: 4 batches x 1 stream 101 kb/s,
-    // 4 batches x 2 streams 69 kb/s; the overlap a second stream buys comes from the other batches anyway.
-    // (PORESEQ_ONE_STREAM forces it for a lone thread too; read once: getenv races with setenv from other threads.)
-    static const bool one = getenv("PORESEQ_ONE_STREAM") != nullptr;
-    // PORESEQ_FORCE_STREAM2 (diagnostics only, tests/test_hip_variant.py and DESIGN.md section 9): second streams even with
-    // several threads inside the library; "prio" puts them on the next stream priority level, as round 2's experiment did
-    static const char* force = getenv("PORESEQ_FORCE_STREAM2");
-    if (!force && (one || live_runtimes() > 1)) { *out = rt->stream; return PS_OK; }
-    if (!rt->stream2 && force && !strcmp(force, "prio")) {
-        static std::atomic<int> seq(1);
-        int lo = 0, hi = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo > hi)
-            PS_HIP(hipStreamCreateWithPriority(&rt->stream2, hipStreamNonBlocking, hi + seq++ % (lo - hi + 1)));
-    }
-    if (!rt->stream2) PS_HIP(hipStreamCreateWithFlags(&rt->stream2, hipStreamNonBlocking));
-    *out = rt->stream2;
-    return PS_OK;
-}
-
-int runtime(Runtime** out) {
-    if (!t_rt.s) {
-        std::lock_guard<std::mutex> lk(g_rt_mu);
-        if (!g_rt_free.empty()) { t_rt.s = g_rt_free.back(); g_rt_free.pop_back(); }
-        else t_rt.s = new RtSlot();
-        {
-            const int n = ++g_rt_live;
-            int pk = g_rt_peak.load();
-            while (n > pk && !g_rt_peak.compare_exchange_weak(pk, n)) {}
-            if (n >= g_rt_peak.load()) g_rt_peak_at.store(now_s());
-        }
-        if (t_rt.s->state == 1) (void)hipSetDevice(t_rt.s->R.device);   // the current device is per-thread state
-    }
-    Runtime& R = t_rt.s->R;
-    int& state = t_rt.s->state;
-    std::string& why = t_rt.s->why;
-    if (state == 0) {
-        int n = 0;
-        hipError_t e = hipGetDeviceCount(&n);
-        if (e != hipSuccess || n <= 0) {
-            state = -1;
-            why = std::string("no HIP device available (") + (e != hipSuccess ? hipGetErrorString(e) : "count 0") +
-                  "); libporeseq_hip has no CPU fallback";
-        } else {
-            int dev = 0;
-            if (const char* s = getenv("PORESEQ_DEVICE")) dev = atoi(s);
-            else if (const char* s2 = getenv("LOCAL_RANK")) dev = atoi(s2) % n;
-            if (dev < 0 || dev >= n) dev = 0;
-            hipDeviceProp_t prop;
-            // One non-blocking stream for the alignment pipeline; a second one for Smith-Waterman batches (they
-            // overlap with the base realign inside FindMutations) is created on first use (second_stream()).
-            // Partitioning the CUs between them (hipExtStreamCreateWithCUMask) was measured and made no
-            // difference, so it is not used.
-            // Streams and hardware queues.  HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues per stream
-            // priority level (default 4), and streams that share a queue run their kernels one after the other: seven lock-step
-            // batches on one level = seven streams on four queues, three kernels in flight on average, 108 kb/s.
-            //  * GPU_MAX_HW_QUEUES >= 8 in force (hwq_mode() above: in the environment the process started with, or exported by the
-            //    poreseq_amd package before HIP started): every runtime's stream on the default level, a queue each — 146-147 kb/s.
-            //  * otherwise the streams are dealt round-robin to the device's three priority levels, not for the priorities' sake but
-            //    for the 3 x 4 queues: 141 kb/s — the two or three batches on the lowest level finish ~0.8 s after the others
-            //    (profiles/r03_d_sweep_forms.md).
-            // (PORESEQ_ONE_PRIORITY=1 forces the default level, PORESEQ_PRIORITY_LEVELS=1 the dealing.)
-            auto make_stream = [&](hipStream_t* st) {
-                static std::atomic<int> seq(0);
-                const bool one = hwq_mode(nullptr) == 1;
-                int lo = 0, hi = 0;
-                if (!one && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo > hi)
-                    return hipStreamCreateWithPriority(st, hipStreamNonBlocking, hi + seq++ % (lo - hi + 1));
-                return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-            };
-            if (hipSetDevice(dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess ||
-                make_stream(&R.stream) != hipSuccess ||
-                hipEventCreate(&R.ev0) != hipSuccess || hipEventCreate(&R.ev1) != hipSuccess ||
-                hipEventCreate(&R.sw0) != hipSuccess || hipEventCreate(&R.sw1) != hipSuccess) {
-                state = -1; why = "HIP device initialisation failed";
-            } else if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
-                state = -1; why = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
-            } else {
-                R.device = dev; R.ready = true; state = 1;
-            }
-        }
-    }
-    if (state < 0) return fail(PS_ERR_NO_DEVICE, why);
-    if (R.stage.dirty) {   // a new API call: nothing staged by the previous one may still be in flight
-        PS_HIP(hipStreamSynchronize(R.stream));
-        if (R.stream2) PS_HIP(hipStreamSynchronize(R.stream2));
-        PS_TRY(R.stage.reset());
-    }
-    *out = &R;
-    return PS_OK;
-}
-
-static hipEvent_t prof_event(Runtime* rt) {
-    hipEvent_t e = nullptr;
-    if (!rt->prof_spare.empty()) { e = rt->prof_spare.back(); rt->prof_spare.pop_back(); }
-    else if (hipEventCreate(&e) != hipSuccess) e = nullptr;
-    return e;
-}
-void prof_begin(Runtime* rt) {
-    if (!rt->prof_on) return;
-    if (rt->prof_defer) {
-        Runtime::ProfPend p{prof_event(rt), nullptr, nullptr, 0.0};
-        if (p.a) (void)hipEventRecord(p.a, rt->stream);
-        rt->prof_pend.push_back(p);
-        return;
-    }
-    (void)hipEventRecord(rt->ev0, rt->stream);
-}
-void prof_end(Runtime* rt, const char* name, double bytes) {
-    if (!rt->prof_on) return;
-    if (rt->prof_defer) {
-        if (rt->prof_pend.empty() || rt->prof_pend.back().b) return;
-        Runtime::ProfPend& p = rt->prof_pend.back();
-        p.b = prof_event(rt); p.name = name; p.bytes = bytes;   // (names are string literals)
-        if (p.b) (void)hipEventRecord(p.b, rt->stream);
-        return;
-    }
-    (void)hipEventRecord(rt->ev1, rt->stream);
-    (void)hipEventSynchronize(rt->ev1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, rt->ev0, rt->ev1);
-    Prof& p = rt->prof[name];
-    p.ms += ms; p.launches += 1; p.bytes += bytes;
-}
-// read the queued event pairs (deferred mode); the stream is drained first
-void prof_flush(Runtime* rt) {
-    if (rt->prof_pend.empty()) return;
-    (void)hipStreamSynchronize(rt->stream);
-    for (Runtime::ProfPend& q : rt->prof_pend) {
-        float ms = 0;
-        if (q.a && q.b && q.name && hipEventElapsedTime(&ms, q.a, q.b) == hipSuccess) {
-            Prof& p = rt->prof[q.name];
-            p.ms += ms; p.launches += 1; p.bytes += q.bytes;
-        }
-        if (q.a) rt->prof_spare.push_back(q.a);
-        if (q.b) rt->prof_spare.push_back(q.b);
-    }
-    rt->prof_pend.clear();
-}
 
 // ------------------------------------------------------------------------------------------ sequences
 // Sequence::populateStates, cpp/Sequence.h:64-100
@@ -491,154 +125,6 @@ int Batch::build(Runtime* rt, const std::vector<JobSpec>& specs, int ndir_, int 
     return PS_OK;
 }
 
-// This runtime's share of the device memory for DP matrices (rec + flg = 18 bytes per slot): PORESEQ_MAX_BATCH_GB when set (read
-// at every call), otherwise 65 % of the device divided by the most threads that owned a runtime at once (at least four; the maximum is
-// forgotten a minute after the count was last that high).  Within a run of a multi-threaded driver the count only goes up, so
-// shares only go down: pools sized under a larger share are given back at the owner's next Batch::place, and after the first
-// step every pool fits its share (no regrowth, no thrash).
-// 288 GB -> 47 GB per runtime up to four threads: a lone region's 170 candidate alignments (24 GB) stay one launch; a lock-step
-// batch of 16 regions takes ~170 workgroups of two 10 kb sweeps per launch.  Callers size their batches on a guess of the band
-// footprint (guess_slots) and split when realign() finds the matrices 20 % over the share, or the device short of memory.
-static size_t device_total_bytes() {
-    static std::atomic<size_t> dev_total(0);       // the device's memory size does not change: asked once
-    size_t tot = dev_total.load();
-    if (!tot) {
-        size_t fr = 0;
-        if (hipMemGetInfo(&fr, &tot) != hipSuccess || !tot) return 0;
-        dev_total.store(tot);
-    }
-    return tot;
-}
-
-// The part of the device this PROCESS plans for.  One process per GPU (the normal deployment) owns the device: 1.  Several ranks on one
-// device (poreseq_amd.dist.init with more ranks than GPUs; the 8-rank test of the driver's command line on one GPU) each plan for
-// their fraction — ps_set_device_fraction / PORESEQ_DEVICE_FRACTION — so that the slabs, the runtimes' shares and the 94 % guard of
-// the pools add up to one device, not to one device per rank.
-static std::atomic<double> g_dev_fraction(-1.0);
-void device_fraction_set(double f) { g_dev_fraction.store(f > 0.0 && f <= 1.0 ? f : -1.0); }
-double device_fraction() {
-    const double f = g_dev_fraction.load();
-    if (f > 0.0) return f;
-    static const double env = [] { const char* e = getenv("PORESEQ_DEVICE_FRACTION"); const double v = e ? atof(e) : 1.0; return v > 0.0 && v <= 1.0 ? v : 1.0; }();
-    return env;
-}
-static size_t device_plan_bytes() { return (size_t)(device_fraction() * (double)device_total_bytes()); }
-
-// Memory plan of the device (309 GB on an MI355X): 27 % in three slabs for full score matrices (below), 13 % left alone (the HSA
-// runtime aborts the process when a launch finds no memory for its own needs, and hipMalloc rounds: pools that sum to 302 GB left
-// 5 GB free), 60 % to the runtimes.  What a runtime holds follows its share: the matrix pool grows 6 % past it, small forward batches
-// (k_fill) add an eighth in step words, Smith-Waterman checkpoints a quarter, and ~2.5 GB do not depend on it (remapped alignments,
-// band tables, edit tables): 1.4 x share + 2.5 GB, measured at 7, 10 and 14 batches in flight.  Share: 31 GB up to four threads,
-// 17 GB with seven batches in flight, 7.7 GB with fourteen.  It sizes the chunks of FindMutations' candidate alignments (7 MB of
-// step codes each), of Smith-Waterman batches and of the Viterbi tables.
-// PORESEQ_MAX_BATCH_GB in bytes (read at every call: tests change it); 0: set without a budget, < 0: not set
-static double max_batch_env() { const char* e = getenv("PORESEQ_MAX_BATCH_GB"); return e ? std::max(atof(e), 0.0) * 1e9 : -1.0; }
-double device_share_bytes() {
-    if (const double g = max_batch_env(); g > 0) return g;
-    const size_t tot = device_plan_bytes();
-    if (!tot) return 32e9;
-    const int nrt = std::max(4, peak_runtimes());
-    return std::max(2e9, (0.60 * (double)tot / nrt - 2.5e9) / 1.4);
-}
-
-// ---- slabs for full score matrices -----------------------------------------------------------------------------------------
-// Only a ScoreMutations call whose edit list reads most columns (Refine / ScorePoints: point edits at every position, ~4 % of a
-// consensus schedule's calls) keeps full forward + backward matrices: 265 MB per 10 kb event, 53 GB for a lock-step call of 20
-// regions.  Sizing every runtime's pools for that (round 3: 65 % of the device divided by the batches in flight) made the number of
-// batches in flight a memory question.  Instead the process keeps a few slabs (PORESEQ_SLABS, default 3, of PORESEQ_SLAB_GB,
-// default 9 % of the device each: 28 GB on an MI355X = the matrices of 10 regions per launch), allocated on first use and never
-// freed; a dense call takes one for its
-// duration (fills, backtrace, edit scoring, read-back) and waits when all are taken.  Nothing is acquired while a slab is held.
-// A single AlignData whose matrices exceed a slab (a 48 kb region with 30 events: 41 GB) takes the calling runtime's own pools.
-namespace {
-struct Slab { char* p = nullptr; size_t bytes = 0; bool busy = false; };
-std::mutex g_slab_mu;
-std::condition_variable g_slab_cv;
-std::vector<Slab*> g_slabs;
-}  // namespace
-static int slab_count() { static const int n = getenv("PORESEQ_SLABS") ? std::max(1, atoi(getenv("PORESEQ_SLABS"))) : 3; return n; }
-size_t slab_bytes() {
-    static const double gb = getenv("PORESEQ_SLAB_GB") ? atof(getenv("PORESEQ_SLAB_GB")) : 0.0;
-    if (gb > 0) return (size_t)(gb * 1e9);
-    const size_t tot = device_plan_bytes();
-    return tot ? (size_t)(0.09 * (double)tot) : (size_t)24e9;
-}
-// bytes of full matrices one dense call may place: the slab, or PORESEQ_MAX_BATCH_GB when set (tests: tiny budgets)
-double dense_cap_bytes() {
-    // (the smallest slab actually allocated, when one came out smaller than planned: sub-batches are cut to fit any of them)
-    size_t cap = slab_bytes();
-    { std::lock_guard<std::mutex> lk(g_slab_mu); for (const Slab* sl : g_slabs) cap = std::min(cap, sl->bytes); }
-    if (const double g = max_batch_env(); g > 0) return std::min(g, (double)cap);
-    return (double)cap;
-}
-void SlabHold::release() {
-    if (!s) return;
-    if (drain) (void)hipStreamSynchronize(drain);   // (a no-op on the normal path: the call has read its results back)
-    { std::lock_guard<std::mutex> lk(g_slab_mu); ((Slab*)s)->busy = false; }
-    s = nullptr; p = nullptr; bytes = 0;
-    g_slab_cv.notify_one();
-}
-int slab_acquire(SlabHold* h) {
-    std::unique_lock<std::mutex> lk(g_slab_mu);
-    for (;;) {
-        for (Slab* sl : g_slabs) if (!sl->busy) { sl->busy = true; h->s = sl; h->p = sl->p; h->bytes = sl->bytes; return PS_OK; }
-        if ((int)g_slabs.size() < slab_count()) {
-            Slab* sl = new Slab();
-            size_t want = slab_bytes();
-            hipError_t e = hipMalloc((void**)&sl->p, want);
-            if (e != hipSuccess) {   // the device is fuller than expected: idle runtimes' pools first, then a smaller slab
-                (void)hipGetLastError();
-                (void)trim_idle_runtimes();
-                for (int k = 0; k < 3 && e != hipSuccess; k++) { if (k) want = want / 4 * 3; e = hipMalloc((void**)&sl->p, want); if (e != hipSuccess) (void)hipGetLastError(); }
-            }
-            if (e != hipSuccess) {
-                delete sl;
-                if (!g_slabs.empty()) { g_slab_cv.wait(lk); continue; }   // make do with the slabs there are
-                return fail(PS_ERR_NOMEM, std::string("hipMalloc of a ") + std::to_string(want >> 20) + " MB slab for full score matrices: " + hipGetErrorString(e));
-            }
-            sl->bytes = want; sl->busy = true;
-            g_pool_bytes += (long long)want;
-            g_slabs.push_back(sl);
-            h->s = sl; h->p = sl->p; h->bytes = sl->bytes;
-            return PS_OK;
-        }
-        g_slab_cv.wait(lk);
-    }
-}
-
-// The DP matrices ("rec": 16-byte records, or a strip sweep's step codes, which alias it; "flg": step words) are the only big pools,
-// and several runtimes size theirs at different times (the share depends on how many threads are inside the library).  Two rules
-// keep the sum below the device: a runtime whose pools were sized for a much larger share than today's gives them back before
-// re-sizing, and no matrix pool grows into the last 8 % of the device (small buffers of every runtime live there) — PS_ERR_NOMEM
-// instead, which callers that can split turn into smaller batches.
-static int ensure_matrix_pools(Runtime* rt, const Batch& bt, size_t need_rec, size_t need_flg, bool can_split, void** rec_out, void** flg_out) {
-    if (bt.ext) {   // full matrices of a dense ScoreMutations call: carved out of the slab the caller holds
-        const size_t r = (need_rec + 255) & ~(size_t)255;
-        if (r + need_flg > bt.ext_bytes)
-            return fail(PS_ERR_NOMEM, "the score matrices of this call (" + std::to_string((r + need_flg) >> 20) + " MB) do not fit a slab of " + std::to_string(bt.ext_bytes >> 20) +
-                                      " MB (PORESEQ_SLAB_GB)");
-        *rec_out = bt.ext; *flg_out = bt.ext + r;
-        return PS_OK;
-    }
-    DBuf& rec = rt->buf("rec");
-    DBuf& flg = rt->buf("flg");
-    size_t tot = device_plan_bytes();
-    if (max_batch_env() < 0 && rec.p && (double)rec.cap > 1.5 * device_share_bytes() + 2e9 && need_rec < rec.cap) {
-        PS_HIP(hipStreamSynchronize(rt->stream));
-        PS_HIP(hipFree(rec.p)); g_pool_bytes -= (long long)rec.cap; rec.p = nullptr; rec.cap = 0;
-        if (flg.p) { PS_HIP(hipFree(flg.p)); g_pool_bytes -= (long long)flg.cap; flg.p = nullptr; flg.cap = 0; }
-    }
-    if (tot && (need_rec > rec.cap || need_flg > flg.cap)) {
-        auto over = [&] { return (double)(g_pool_bytes.load() - (long long)rec.cap - (long long)flg.cap) + (double)need_rec + (double)need_flg > 0.92 * (double)tot; };
-        if (over()) (void)trim_idle_runtimes();
-        if (over() && can_split) return fail(PS_ERR_NOMEM, "the DP matrices of this batch do not fit beside the pools of the other threads' batches");
-    }
-    PS_TRY(rec.ensure(need_rec));
-    if (need_flg) PS_TRY(flg.ensure(need_flg));
-    *rec_out = rec.p; *flg_out = flg.p;
-    return PS_OK;
-}
-
 // second phase: the anti-diagonal footprint of every band is known, size the skewed matrices
 int Batch::place(Runtime* rt, int P_, bool can_split) {
     P = std::min(Pmax, std::max(64, ((P_ + 63) / 64) * 64));
@@ -647,7 +133,7 @@ int Batch::place(Runtime* rt, int P_, bool can_split) {
     for (JobD& j : jobs) {
         j.P = P;
         // spare anti-diagonals in front of and behind every matrix: k_fill's pipeline starts early and runs past S
-        for (int dd = 0; dd < ndir; dd++) { j.mat_off[dd] = mat_tot + (int64_t)MAT_FRONT * P; mat_tot += (j.S + MAT_FRONT + MAT_BACK) * P; }
+        for (int dd = 0; dd < ndir; dd++) { j.mat_off[dd] = mat_tot + (int64_t)MAT_FRONT * P; mat_tot += matrix_cells(j.S, P); }
     }
     cells = mat_tot;
     void *prec = nullptr, *pflg = nullptr;
@@ -668,70 +154,7 @@ double Batch::fill_alg_bytes() const {
 }
 
 // ------------------------------------------------------------------------------------------ AlignData
-// The slab of an AlignData (events, derived tables, results: ~13 MB for a 10 kb region at 10x) comes from a process-wide cache and goes
-// back to it.  hipFree waits for EVERY stream of the process (43 ms per call with fourteen lock-step batches in flight: 280 regions per
-// bench step were 12 s of blocked slot threads), hipMalloc takes ~2 ms; a cached slab costs an event: recorded on the stream that
-// last had work on the slab when its AlignData goes, waited for (on the device, not the host) by the stream of the next owner.
-namespace {
-struct CachedSlab { void* p; size_t cap; hipEvent_t ev; bool pending; };
-std::mutex g_aslab_mu;
-std::vector<CachedSlab> g_aslabs;
-size_t g_aslab_bytes = 0;
-size_t aslab_cache_limit() {
-    // 8 GB, at most 3 % of this process's part of the device (ranks that share a GPU: ps_set_device_fraction)
-    static const double env = getenv("PORESEQ_ALIGN_CACHE_GB") ? atof(getenv("PORESEQ_ALIGN_CACHE_GB")) * 1e9 : -1.0;
-    if (env >= 0) return (size_t)env;
-    const size_t plan = device_plan_bytes();
-    return plan ? std::min<size_t>((size_t)8e9, (size_t)(0.03 * (double)plan)) : (size_t)8e9;
-}
-}  // namespace
-
-Align::~Align() {
-    if (!slab) return;
-    CachedSlab c{slab, slab_cap, nullptr, false};
-    bool keep = slab_cap > 0 && hipEventCreateWithFlags(&c.ev, hipEventDisableTiming) == hipSuccess;
-    if (keep && last_stream) {
-        if (hipEventRecord(c.ev, (hipStream_t)last_stream) == hipSuccess) c.pending = true;
-        else { (void)hipGetLastError(); (void)hipEventDestroy(c.ev); keep = false; }
-    }
-    if (keep) {
-        std::lock_guard<std::mutex> lk(g_aslab_mu);
-        if (g_aslab_bytes + c.cap <= aslab_cache_limit()) { g_aslabs.push_back(c); g_aslab_bytes += c.cap; slab = nullptr; return; }
-    }
-    if (keep) (void)hipEventDestroy(c.ev);
-    (void)hipFree(slab);
-}
-
-// a slab of at least `bytes` for an AlignData on `rt`'s stream: the smallest cached one that fits without wasting more than half of
-// itself, else a fresh allocation (with an eighth of slack, so that regions of similar size find each other's slabs)
-static int align_slab_take(Runtime* rt, size_t bytes, void** out, size_t* cap) {
-    CachedSlab got{nullptr, 0, nullptr, false};
-    {
-        std::lock_guard<std::mutex> lk(g_aslab_mu);
-        int best = -1;
-        for (int k = 0; k < (int)g_aslabs.size(); k++)
-            if (g_aslabs[k].cap >= bytes && g_aslabs[k].cap <= 2 * bytes + (1 << 20) && (best < 0 || g_aslabs[k].cap < g_aslabs[best].cap)) best = k;
-        if (best >= 0) { got = g_aslabs[best]; g_aslabs[best] = g_aslabs.back(); g_aslabs.pop_back(); g_aslab_bytes -= got.cap; }
-    }
-    if (got.p) {
-        if (got.pending) PS_HIP(hipStreamWaitEvent(rt->stream, got.ev, 0));   // (the previous owner's last work on it, if any is still queued)
-        (void)hipEventDestroy(got.ev);   // (destruction is deferred by the runtime until the wait above has been honoured)
-        *out = got.p; *cap = got.cap;
-        return PS_OK;
-    }
-    const size_t want = (bytes + bytes / 8 + ((size_t)1 << 20) - 1) >> 20 << 20;
-    if (hipMalloc(out, want) != hipSuccess) {
-        (void)hipGetLastError();
-        {   // hand the cache back and try once more
-            std::lock_guard<std::mutex> lk(g_aslab_mu);
-            for (CachedSlab& c : g_aslabs) { (void)hipEventDestroy(c.ev); (void)hipFree(c.p); }
-            g_aslabs.clear(); g_aslab_bytes = 0;
-        }
-        PS_HIP(hipMalloc(out, want));
-    }
-    *cap = want;
-    return PS_OK;
-}
+Align::~Align() { align_slab_give(slab, slab_cap, last_stream); }   // (back to the cache of ps_mem.cpp, or freed)
 
 int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_events, const int64_t* level_off,
                   const double* mean, const double* stdv, const double* ref_align, const double* ref_like,
@@ -835,12 +258,17 @@ int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_event
 
 int Align::base_batch(Runtime* rt, Batch* b, int ndir, int lb_extra) {
     std::vector<JobSpec> specs(E);
-    for (int e = 0; e < E; e++) {
-        specs[e].a = this; specs[e].ev = e; specs[e].states = &states;
-        specs[e].ra = d_ra + off[e]; specs[e].rl = d_rl + off[e]; specs[e].ri = d_ri + off[e];
-        specs[e].out = d_out + e;
-    }
+    for (int e = 0; e < E; e++) specs[e] = job(e);
     return b->build(rt, specs, ndir, lb_extra);
+}
+
+// event e against this AlignData's own sequence, with the event's own reference arrays and result record
+JobSpec Align::job(int e) {
+    JobSpec s;
+    s.a = this; s.ev = e; s.states = &states;
+    s.ra = d_ra + off[e]; s.rl = d_rl + off[e]; s.ri = d_ri + off[e];
+    s.out = d_out + e;
+    return s;
 }
 
 // device -> host mirror of ref_align / ref_like in two halves, so that several AlignData can share one synchronisation
@@ -863,9 +291,6 @@ int Align::refs_to_host(Runtime* rt) {
     refs_finish();
     return PS_OK;
 }
-
-// slots per anti-diagonal a band of half-width W will probably need: footprint ~ (2W + 1) / 1.9 for about one level per base, + 9
-static int guess_slots_w(int W) { return std::min(1024, std::max(64, (((2 * W + 1) * 10 / 19 + 9 + 63) / 64) * 64)); }
 
 // forward fill + backtrace + updaterefs of a batch (the body of ScoreAlignments per event,
 // cpp/MakeMutations.cpp:148-195, and of Alignment::update with ndir == 2, cpp/Alignment.cpp:63-73)
@@ -896,7 +321,7 @@ double fwd_job_bytes(const Align* a, int n0, int C) {
     if (sweep_enabled()) f = sweep_guess_form(a->par.realign_width, 1);
     if (f.ok() && debug_sweep_k() > 0) f.K = debug_sweep_k();
     if (f.ok()) return 1.15 * sweep_job_bytes(n0, C, f);   // (the multi-wavefront forms take up to a tenth more: more steps, fewer rows per lane)
-    return ((double)n0 + C + 1 + MAT_FRONT + MAT_BACK) * guess_slots(a) * 18.0;
+    return matrix_bytes((int64_t)n0 + C + 1, guess_slots(a), 1);
 }
 
 // Which form a strip-sweep launch takes (ps_sweep.hip: K rows per lane on NW wavefronts per sweep).  Forced by
@@ -996,7 +421,7 @@ int realign(Runtime* rt, Batch& b, double cap) {
     bool too_big = false;
     if (b.ndir == 1 && sweep_enabled() && b.d.njobs < sweep_min) {
         double est = 0;
-        for (const JobD& j : b.jobs) est += (double)(j.S + MAT_FRONT + MAT_BACK) * guess_slots_w(j.W) * 18.0;   // (not guess_slots: the tests' override of the guess does not reach here)
+        for (const JobD& j : b.jobs) est += matrix_bytes(j.S, guess_slots_w(j.W), 1);   // (not guess_slots: the tests' override of the guess does not reach here)
         too_big = est > device_share_bytes();
     }
     if (sweep_enabled() && (b.d.njobs * b.ndir >= sweep_min || too_big)) {
@@ -1021,7 +446,7 @@ int realign(Runtime* rt, Batch& b, double cap) {
     if (cap > 0) {   // the caller sized this batch on a guess of the footprint: let it split when the real one is much wider
         const int Pr = std::min(b.Pmax, std::max(64, ((Pneed + 63) / 64) * 64));
         double bytes = 0;
-        for (const JobD& j : b.jobs) bytes += (double)(j.S + MAT_FRONT + MAT_BACK) * Pr * 18.0 * b.ndir;
+        for (const JobD& j : b.jobs) bytes += matrix_bytes(j.S, Pr, b.ndir);
         if (bytes > cap) {
             if (trace_on()) fprintf(stderr, "[ps] realign: %.1f GB of matrices at %d slots per anti-diagonal, over the share: split\n", bytes * 1e-9, Pr);
             b.P = Pr;
@@ -1042,75 +467,7 @@ int realign(Runtime* rt, Batch& b, double cap) {
     return PS_OK;
 }
 
-// run fn(k) for k in [0, n) on the calling thread plus helpers from a process-wide pool of host threads (disjoint outputs; the GPU
-// work of a batched call is enqueued by the caller).  The pool's threads live for the process: a lock-step schedule makes ~500 such
-// calls per batch, fourteen batches at once — creating up to 32 threads for each of them cost more than most of the loops.  Helpers
-// per call: PORESEQ_HOST_THREADS (poreseq_amd.dist.init sets it to this rank's share of the node's cores when several ranks share a
-// node), else up to 32; the pool holds twice that for callers that overlap.  A helper that is dequeued after the caller and the
-// other helpers have taken every index finds nothing to do and never touches the caller's frame.
-namespace {
-struct ParJob {
-    std::function<void(int)> fn;
-    int n = 0;
-    std::atomic<int> next{0}, done{0};
-    std::mutex mu;
-    std::condition_variable cv;
-    void run() {
-        int did = 0;
-        for (int k = next++; k < n; k = next++) { fn(k); did++; }
-        if (did && (done += did) >= n) { std::lock_guard<std::mutex> lk(mu); cv.notify_all(); }
-    }
-};
-struct ParPool {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<std::shared_ptr<ParJob>> q;
-    std::vector<std::thread> th;
-    int idle = 0;
-    size_t cap = 64;
-    void worker() {
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-            idle++;
-            cv.wait(lk, [&] { return !q.empty(); });
-            idle--;
-            std::shared_ptr<ParJob> j = q.front();
-            q.pop_front();
-            lk.unlock();
-            j->run();
-            j.reset();
-            lk.lock();
-        }
-    }
-    void submit(const std::shared_ptr<ParJob>& j, int helpers) {
-        std::lock_guard<std::mutex> lk(mu);
-        for (int k = 0; k < helpers; k++) q.push_back(j);
-        int need = (int)q.size() - idle;   // queued tasks no waiting worker will take: new workers, up to the pool's size
-        for (; need > 0 && th.size() < cap; need--) { th.emplace_back([this] { worker(); }); th.back().detach(); }
-        cv.notify_all();
-    }
-};
-static int par_cap() { static const int cap = [] { const char* e = getenv("PORESEQ_HOST_THREADS"); const int v = e ? atoi(e) : 32; return std::max(1, std::min(v, 64)); }(); return cap; }
-ParPool* par_pool() {   // (never destroyed: its threads are detached and may outlive main; its size is set once, here)
-    static ParPool* p = [] { ParPool* q = new ParPool(); q->cap = (size_t)std::max(2 * par_cap(), 8); return q; }();
-    return p;
-}
-}  // namespace
-
-void par_for(int n, const std::function<void(int)>& fn) {
-    if (n <= 1) { if (n == 1) fn(0); return; }
-    const int cap = par_cap();
-    const int nth = std::min(n, cap);
-    if (nth <= 1) { for (int k = 0; k < n; k++) fn(k); return; }
-    std::shared_ptr<ParJob> j = std::make_shared<ParJob>();
-    j->fn = fn; j->n = n;
-    par_pool()->submit(j, nth - 1);
-    j->run();
-    std::unique_lock<std::mutex> lk(j->mu);
-    j->cv.wait(lk, [&] { return j->done.load() >= n; });
-}
-
-// Slots per anti-diagonal realign() will probably need for this AlignData: footprint ~ (2W + 1) / 1.9 for about one level per base, + 9.
+// Slots per anti-diagonal realign() will probably need for this AlignData (guess_slots_w, ps_plan.h).
 // Only a guess (ragged remapped alignments, few levels per base: up to 2W + 1): callers that size batches on it pass realign() a cap
 // and split when it answers PS_SPLIT.  PORESEQ_DEBUG_GUESS_P overrides it (tests: a wrong guess).
 int guess_slots(const Align* a) {
@@ -1119,8 +476,7 @@ int guess_slots(const Align* a) {
 }
 
 // Where the sub-batch of AlignData that starts at as[k0] ends when each event takes `ndir` sweeps: everything if it fits this
-// runtime's device share; otherwise the batch is cut into the fewest sub-batches that fit, of about equal size (a remainder of
-// two regions behind two full sub-batches would cost a whole launch's latency for a tenth of the work)
+// runtime's device share; otherwise the fewest sub-batches that fit, of about equal size (share_cut, ps_plan.h)
 static size_t fit_share(const std::vector<Align*>& as, size_t k0, int ndir) {
     const double cap = ndir == 2 ? dense_cap_bytes() : device_share_bytes();   // (full forward + backward matrices live in a slab)
     auto need = [&](size_t k) {
@@ -1128,54 +484,44 @@ static size_t fit_share(const std::vector<Align*>& as, size_t k0, int ndir) {
         const int P = guess_slots(a);
         double add = 0;
         for (int e = 0; e < a->E; e++)
-            add += ndir == 1 ? fwd_job_bytes(a, a->n[e], (int)a->states.size()) : ((double)a->n[e] + a->states.size() + 1 + MAT_FRONT + MAT_BACK) * P * 18.0 * ndir;
+            add += ndir == 1 ? fwd_job_bytes(a, a->n[e], (int)a->states.size()) : matrix_bytes((int64_t)a->n[e] + (int64_t)a->states.size() + 1, P, ndir);
         return add;
     };
-    double total = 0;
-    for (size_t k = k0; k < as.size(); k++) total += need(k);
-    if (total <= cap) return as.size();
-    const double target = total / std::ceil(total / cap);      // bytes per sub-batch, all about equal
-    double bytes = 0;
-    size_t k = k0;
-    for (; k < as.size(); k++) {
-        const double add = need(k);
-        if (k > k0 && (bytes + add > cap || bytes + 0.5 * add > target)) break;
-        bytes += add;
+    return share_cut(k0, as.size(), cap, need);
+}
+
+// regions k0 .. k1 - 1 of a lock-step call as calls of their own, sub(k0, k1), one after the other: the sub-batches that fit this
+// runtime's share (fit_share), or two halves (a call whose bands came out wider than guessed)
+template <class Sub> static int in_share_chunks(const std::vector<Align*>& as, int ndir, Sub&& sub) {
+    for (size_t k0 = 0; k0 < as.size();) {
+        const size_t k1 = fit_share(as, k0, ndir);
+        PS_TRY(sub(k0, k1));
+        k0 = k1;
     }
-    return k;
+    return PS_OK;
+}
+template <class Sub> static int in_halves(size_t n, Sub&& sub) {
+    const size_t h = n / 2;
+    PS_TRY(sub(0, h));
+    return sub(h, n);
 }
 
 // ScoreAlignments, cpp/MakeMutations.cpp:148-195, for several AlignData in one launch chain (independent regions in lock-step)
 int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes) {
-    if (fit_share(as, 0, 1) < as.size()) {   // more matrices than this runtime's share of the device: sub-batches, one after the other
-        for (size_t k0 = 0; k0 < as.size();) {
-            const size_t k1 = fit_share(as, k0, 1);
-            PS_TRY(score_alignments_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
-                                          std::vector<double*>(likes.begin() + k0, likes.begin() + k1)));
-            k0 = k1;
-        }
-        return PS_OK;
-    }
+    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
+        return score_alignments_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
+                                      std::vector<double*>(likes.begin() + k0, likes.begin() + k1));
+    };
+    if (fit_share(as, 0, 1) < as.size()) return in_share_chunks(as, 1, sub);   // more matrices than this runtime's share of the device
     std::vector<JobSpec> specs;
     for (Align* a : as)
-        for (int e = 0; e < a->E; e++) {
-            JobSpec s;
-            s.a = a; s.ev = e; s.states = &a->states;
-            s.ra = a->d_ra + a->off[e]; s.rl = a->d_rl + a->off[e]; s.ri = a->d_ri + a->off[e]; s.out = a->d_out + e;
-            specs.push_back(s);
-        }
+        for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
     if (specs.empty()) return PS_OK;
     Batch b;
     PS_TRY(b.build(rt, specs, 1, 0));
     {
-        const int rc = realign(rt, b, as.size() > 1 ? 1.2 * device_share_bytes() : 0.0);
-        if (rc == PS_SPLIT) {   // bands wider than fit_share guessed: two halves, one after the other
-            const size_t h = as.size() / 2;
-            PS_TRY(score_alignments_multi(rt, std::vector<Align*>(as.begin(), as.begin() + h), std::vector<double*>(scores.begin(), scores.begin() + h),
-                                          std::vector<double*>(likes.begin(), likes.begin() + h)));
-            return score_alignments_multi(rt, std::vector<Align*>(as.begin() + h, as.end()), std::vector<double*>(scores.begin() + h, scores.end()),
-                                          std::vector<double*>(likes.begin() + h, likes.end()));
-        }
+        const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
+        if (rc == PS_SPLIT) return in_halves(as.size(), sub);   // bands wider than fit_share guessed: two halves, one after the other
         PS_TRY(rc);
     }
     // the jobs' scores, gathered into one array on the device: one copy back instead of one per AlignData
@@ -1418,20 +764,8 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
                                        std::vector<const std::vector<Mut>*>(muts.begin() + k0, muts.begin() + k1),
                                        std::vector<std::vector<Mut>*>(outs.begin() + k0, outs.begin() + k1), delta_out ? &dsub : nullptr, psub);
     };
-    auto halves = [&]() {
-        const size_t h = as.size() / 2;
-        PS_TRY(sub(0, h));
-        return sub(h, as.size());
-    };
-    if (sparse && R > 1 && sparse_bytes > device_share_bytes()) return halves();
-    if (!sparse && fit_share(as, 0, 2) < as.size()) {   // sub-batches that fit this runtime's share of the device
-        for (size_t k0 = 0; k0 < as.size();) {
-            const size_t k1 = fit_share(as, k0, 2);
-            PS_TRY(sub(k0, k1));
-            k0 = k1;
-        }
-        return PS_OK;
-    }
+    if (sparse && R > 1 && sparse_bytes > device_share_bytes()) return in_halves(as.size(), sub);
+    if (!sparse && fit_share(as, 0, 2) < as.size()) return in_share_chunks(as, 2, sub);   // sub-batches that fit a slab
     // the kept-column tables of all AlignData in one block (before the jobs are built: their descriptors point into it)
     std::vector<const int*> d_keep(2 * (size_t)R, nullptr);
     if (sparse) {
@@ -1454,9 +788,7 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         job0[k] = (int)specs.size();
         extra = std::max(extra, plan[k].extra);
         for (int e = 0; e < a->E; e++) {
-            JobSpec s;
-            s.a = a; s.ev = e; s.states = &a->states;
-            s.ra = a->d_ra + a->off[e]; s.rl = a->d_rl + a->off[e]; s.ri = a->d_ri + a->off[e]; s.out = a->d_out + e;
+            JobSpec s = a->job(e);
             if (sparse) for (int d = 0; d < 2; d++) { s.keep[d] = d_keep[2 * k + d]; s.nkeep[d] = plan[k].nkeep[d]; }
             specs.push_back(s);
         }
@@ -1465,7 +797,7 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
     Batch b;
     SlabHold slab;   // full matrices: one of the process's slabs for the duration of this call (released at every return)
     double lone_need = 0;   // a single AlignData cannot be split: matrices beyond a slab go to the runtime's own pools
-    if (!sparse && R == 1) for (int e = 0; e < as[0]->E; e++) lone_need += ((double)as[0]->n[e] + as[0]->states.size() + 1 + MAT_FRONT + MAT_BACK) * std::min(1024, 2 * as[0]->par.realign_width + 74) * 36.0;
+    if (!sparse && R == 1) for (int e = 0; e < as[0]->E; e++) lone_need += matrix_bytes((int64_t)as[0]->n[e] + (int64_t)as[0]->states.size() + 1, most_slots_w(as[0]->par.realign_width), 2);
     if (!sparse && lone_need <= (double)slab_bytes()) {
         PS_TRY(slab_acquire(&slab));
         if (R == 1 && lone_need > (double)slab.bytes) {
@@ -1481,8 +813,8 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
     }
     PS_TRY(b.build(rt, specs, 2, extra));
     {
-        const int rc = realign(rt, b, R > 1 ? (sparse ? 1.2 * device_share_bytes() : (double)b.ext_bytes) : 0.0);
-        if (rc == PS_SPLIT) { slab.release(); return halves(); }   // bands wider than guessed: two halves, one after the other
+        const int rc = realign(rt, b, R > 1 ? (sparse ? PLAN_OVER_GUESS * device_share_bytes() : (double)b.ext_bytes) : 0.0);
+        if (rc == PS_SPLIT) { slab.release(); return in_halves(as.size(), sub); }   // bands wider than guessed: two halves, one after the other
         PS_TRY(rc);
     }
     for (Align* a : as) a->host_refs_valid = false;
@@ -1706,18 +1038,6 @@ int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector
         active.swap(next);
     }
     return PS_OK;
-}
-
-// one line about the process-wide state of the library (ps_info): stream / hardware-queue mode, runtimes, memory plan
-std::string info_string() {
-    std::string why;
-    (void)hwq_mode(&why);
-    size_t nslab = 0, slab_b = 0;
-    { std::lock_guard<std::mutex> lk(g_slab_mu); nslab = g_slabs.size(); for (Slab* sl : g_slabs) slab_b += sl->bytes; }
-    char buf[512];
-    snprintf(buf, sizeof buf, "; device fraction of this process %.3f; runtimes: %d live, %d peak; share per runtime %.1f GB; slabs for full score matrices: %zu of %d allocated (%.1f GB, %.1f GB each by plan); device pools of this process %.1f GB",
-             device_fraction(), live_runtimes(), peak_runtimes(), device_share_bytes() * 1e-9, nslab, slab_count(), slab_b * 1e-9, slab_bytes() * 1e-9, (double)g_pool_bytes.load() * 1e-9);
-    return "hip-gfx950; streams: " + why + buf;
 }
 
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases) {

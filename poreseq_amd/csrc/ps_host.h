@@ -73,7 +73,7 @@ struct Align {
     bool host_refs_valid = true;
     void* slab = nullptr;
     size_t slab_cap = 0;
-    void* last_stream = nullptr;   // the stream that last had work on the slab enqueued (hipStream_t; Batch::build, create, refs_to_host): ~Align
+    void* last_stream = nullptr;   // the stream that last had work on the slab enqueued (hipStream_t; Batch::build, create, refs_to_host): align_slab_give
     double *d_mean = nullptr, *d_stdv = nullptr, *d_lsd = nullptr, *d_ra = nullptr, *d_rl = nullptr, *d_ri = nullptr;
     double *d_model = nullptr, *d_trans = nullptr;
     double *d_model8 = nullptr, *d_lev[2] = {nullptr, nullptr};   // k_fill's tables (ps_internal.h, JobD)
@@ -86,7 +86,8 @@ struct Align {
                const double* mean, const double* stdv, const double* ref_align, const double* ref_like,
                const double* model, const double* trans, const char* evseq, const int64_t* evseq_off,
                const ps_params* params);
-    int base_batch(Runtime* rt, Batch* b, int ndir, int lb_extra);
+    JobSpec job(int e);   // event e against this AlignData's own sequence
+    int base_batch(Runtime* rt, Batch* b, int ndir, int lb_extra);   // job(e) of every event
     int refs_to_host(Runtime* rt);
     int refs_to_host_async(Runtime* rt);   // enqueue; refs_finish() after the stream has been synchronised
     void refs_finish();
@@ -134,6 +135,9 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
 int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
                          double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs);
 std::string info_string();   // process-wide state in one line (ps_info)
+struct MemInfo { size_t slabs = 0, slab_bytes = 0; int slabs_planned = 0; long long pool_bytes = 0; };
+MemInfo mem_info();          // ps_mem.cpp's part of it: slabs allocated (and their bytes) of how many, bytes in the pools of this process
+void for_idle_runtimes(const std::function<void(Runtime&)>& fn);   // fn on every runtime no thread owns, under the free list's lock
 int hwq_mode(std::string* why);   // 1: every stream on one priority level (a hardware queue each), 0: streams dealt over the levels
 int peak_runtimes();   // most host threads that ever owned a runtime at the same time
 int live_runtimes();   // host threads that currently own a runtime
@@ -141,11 +145,15 @@ int guess_slots(const Align* a);   // anti-diagonal footprint realign() will pro
 void device_fraction_set(double f);   // the part of the device this process plans for (several ranks on one GPU); <= 0: PORESEQ_DEVICE_FRACTION, else 1
 double device_fraction();
 double device_share_bytes();   // this runtime's share of the device memory for its own pools (step codes, kept columns, small matrices)
-// a process-wide slab for the full score matrices of one Refine-sized ScoreMutations call (ps_host.cpp)
+// a process-wide slab for the full score matrices of one Refine-sized ScoreMutations call (ps_mem.cpp)
 struct SlabHold { void* s = nullptr; char* p = nullptr; size_t bytes = 0; hipStream_t drain = nullptr; void release(); ~SlabHold() { release(); } };   // release() drains `drain` first: nothing in flight may still use the slab
 int slab_acquire(SlabHold* h);    // blocks while all slabs are taken
 size_t slab_bytes();
 double dense_cap_bytes();         // bytes of full matrices one call may place
+// the matrix pools of a batch ("rec", "flg"): carved out of the slab the batch holds (bt.ext), else the runtime's own, re-sized
+int ensure_matrix_pools(Runtime* rt, const Batch& bt, size_t need_rec, size_t need_flg, bool can_split, void** rec_out, void** flg_out);
+int align_slab_take(Runtime* rt, size_t bytes, void** out, size_t* cap);   // an AlignData's slab, from the process-wide cache when one fits
+void align_slab_give(void* slab, size_t cap, void* last_stream);           // and back to it (or freed)
 int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector<std::vector<Mut>> muts, std::vector<int>* nbases);
 // delta_out (optional): per AlignData a host array [E][M] receiving every event's term of every edit's score
 int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,

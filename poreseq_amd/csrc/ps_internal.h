@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/poreseq_hip.h"
+#include "ps_plan.h"   // MAT_FRONT, MAT_BACK and the memory plan's arithmetic (host-only, no HIP)
 
 namespace ps {
 
@@ -47,6 +48,7 @@ struct DBuf {
     void* p = nullptr;
     size_t cap = 0;
     int ensure(size_t bytes);  // grow-only; contents are NOT preserved across growth
+    hipError_t release();      // frees and forgets the buffer and takes it off the process's pool count, whatever hipFree answers (returned)
     template <class T> T* as() const { return (T*)p; }
 };
 
@@ -105,9 +107,9 @@ struct Runtime {
 int runtime(Runtime** out);  // PS_ERR_NO_DEVICE when no usable GPU; never falls back
 // The stream Smith-Waterman batches should use: the runtime's second stream (created on first use), so that the batch overlaps with
 // the base realign of FindMutations — while the calling thread is the only one inside the library.  With several threads (lock-step
-// batches in flight) every runtime keeps to one stream: HIP maps streams onto 4 hardware queues by default (ps_host.cpp).
+// batches in flight) every runtime keeps to one stream: HIP maps streams onto 4 hardware queues by default (ps_runtime.cpp).
 int second_stream(Runtime* rt, hipStream_t* out);
-int live_runtimes();   // host threads that currently own a runtime (ps_host.cpp)
+int live_runtimes();   // host threads that currently own a runtime (ps_runtime.cpp)
 
 // ---- mutation list (vector<MutInfo>/vector<MutScore>, cpp/AlignUtil.h:69-91) ----------------
 struct Mut {
@@ -161,8 +163,6 @@ struct JobOut {
 };
 
 constexpr int MODEL_ROW_BYTES = 80;   // k_fill's model rows: 8 doubles + 16 bytes of padding (LDS bank spread)
-constexpr int MAT_FRONT = 8;   // spare anti-diagonals in front of every matrix (the fill pipeline starts 8 steps early)
-constexpr int MAT_BACK = 16;   // and behind it (the last loop body runs past S)
 constexpr int LO_PAD = 160;    // LO / HI entries behind S, all -1 (k_fill prefetches them in chunks of 64)
 
 struct SweepJob;

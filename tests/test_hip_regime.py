@@ -183,7 +183,7 @@ def test_sweep_matrices_where_the_band_shifts_every_column(nw, K):
 
 @pytest.mark.gpu
 def test_align_slabs_are_recycled_without_leaking_state():
-    """AlignData slabs come from a process-wide cache (ps_host.cpp, align_slab_take: no hipMalloc / hipFree per region): a handle that takes
+    """AlignData slabs come from a process-wide cache (ps_mem.cpp, align_slab_take: no hipMalloc / hipFree per region): a handle that takes
     over the slab of a destroyed one — same size, smaller, from another thread's stream — computes what a fresh process computes.  Regions of
     alternating sizes are created, scored and destroyed in turn, on two host threads at once; every result equals the oracle's."""
     import copy

@@ -102,7 +102,7 @@ def test_concurrent_regions_from_threads_match_oracle():
 
 
 def test_dense_calls_queue_for_one_small_slab_and_match_alone():
-    """Full score matrices live in process-wide slabs that a dense ScoreMutations call takes for its duration (ps_host.cpp).  With ONE
+    """Full score matrices live in process-wide slabs that a dense ScoreMutations call takes for its duration (ps_mem.cpp).  With ONE
     slab of 0.3 GB (a subprocess: the slab plan is read once), four threads of lock-step Refine calls wait for each other, a batch whose
     matrices exceed the slab is cut in halves, a single region larger than the slab takes the runtime's own pools — and every result equals
     the single-threaded default run's."""
