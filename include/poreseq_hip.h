@@ -179,6 +179,18 @@ int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, i
 /* swfull (cpp/swlib.h:36, cpp/swlib.cpp:211-340).  inds1/inds2 need room for n1+n2 entries. */
 int ps_swfull(const char* seq1, int64_t n1, const char* seq2, int64_t n2, int32_t* score,
               double* accuracy, int32_t* inds1, int32_t* inds2, int64_t cap, int64_t* n_pairs);
+/* swfull for n pairs in one call, each reduced to what the reference's consensus driver reads off the index lists (cpp/swlib.cpp:211-340;
+ * poreseq/Mutate.py:59-68 picks its `test` start from the first and last aligned pair, Mutate.py:96-98 counts the zero entries): the
+ * pairs run as batched launches cut by the device-memory plan, near-identical pairs banded, and no index list is stored or copied.
+ * Per pair, in terms of ps_swfull's inds1 / inds2: n_pairs their length, n_match the matching aligned pairs, first1 / first2 entry 0
+ * (0, 0 for an empty alignment), last1 / last2 entry n_pairs - 1, gap1 / gap2 the entries with inds1 == 0 / inds2 == 0,
+ * accuracy = 100.0 * n_match / n_pairs as ps_swfull forms it (NaN for an empty alignment). */
+typedef struct ps_sw_summary {
+    int32_t score, n_pairs, n_match, first1, first2, last1, last2, gap1, gap2;
+    double accuracy;
+} ps_sw_summary;
+int ps_batch_sw_summary(int64_t n, const char* const* seq1, const int64_t* n1, const char* const* seq2, const int64_t* n2,
+                        ps_sw_summary* out);
 /* Sequence::populateStates (cpp/Sequence.h:64-100); states needs max(n-4,0) entries. */
 int ps_seq_to_states(const char* seq, int64_t n, int32_t* states, int64_t* n_states);
 

@@ -5,6 +5,7 @@ binds `poreseq_amd/csrc/libporeseq_hip.so` (see `load_hip`), and raises if it is
 missing — there is no CPU fallback.  (The test-suite binds the oracle / reference
 shims through the same class, from tests/, never from here.)
 """
+import collections
 import ctypes as C
 import os
 
@@ -23,6 +24,12 @@ class PsParams(C.Structure):
     # AlignParams, cpp/AlignUtil.h:57-66
     _fields_ = [("lik_offset", C.c_double), ("scoring_width", C.c_int32),
                 ("realign_width", C.c_int32), ("verbose", C.c_int32)]
+
+
+class PsSwSummary(C.Structure):
+    # ps_sw_summary, include/poreseq_hip.h
+    _fields_ = [(k, C.c_int32) for k in ("score", "n_pairs", "n_match", "first1", "first2", "last1", "last2", "gap1", "gap2")] + \
+               [("accuracy", C.c_double)]
 
 
 class PoreseqError(Exception):
@@ -77,6 +84,8 @@ SYMBOLS = {
                                           C.c_double, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "ps_swfull": (C.c_int, [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, c_i32p, c_dp, c_i32p,
                             c_i32p, C.c_int64, c_i64p]),
+    "ps_batch_sw_summary": (C.c_int, [C.c_int64, C.POINTER(C.c_char_p), c_i64p, C.POINTER(C.c_char_p), c_i64p,
+                                      C.POINTER(PsSwSummary)]),
     "ps_seq_to_states": (C.c_int, [C.c_char_p, C.c_int64, c_i32p, c_i64p]),
     "ps_debug_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_dp, c_dp, c_u8p, c_u8p]),
     "ps_set_sweep_min": (C.c_int, [C.c_int32]),
@@ -91,12 +100,35 @@ SYMBOLS = {
 }
 
 
+# entry points of the header that a checker library (the oracle, the reference shim) may lack: CApi serves them from what the
+# library does export (sw_summaries from swfull)
+OPTIONAL = frozenset(["ps_batch_sw_summary"])
+
+# one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
+# entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
+SwSummary = collections.namedtuple("SwSummary", "score n_pairs n_match first1 first2 last1 last2 gap1 gap2 accuracy")
+
+
 def _dp(a):
     return a.ctypes.data_as(c_dp)
 
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def summary_from_lists(seq1, seq2, score, accuracy, i1, i2):
+    """the SwSummary of one swfull result (score, accuracy, inds1, inds2) of seq1 against seq2; n_match counted as the reference
+    does (cpp/swlib.cpp:317-319: aligned pairs whose characters are equal)"""
+    n = int(len(i1))
+    if not n:
+        return SwSummary(int(score), 0, 0, 0, 0, 0, 0, 0, 0, float(accuracy))
+    i1, i2 = np.asarray(i1), np.asarray(i2)
+    both = (i1 > 0) & (i2 > 0)
+    c1 = np.frombuffer(seq1.encode("ascii"), dtype=np.uint8)[i1[both] - 1]
+    c2 = np.frombuffer(seq2.encode("ascii"), dtype=np.uint8)[i2[both] - 1]
+    return SwSummary(int(score), n, int(np.count_nonzero(c1 == c2)), int(i1[0]), int(i2[0]), int(i1[-1]), int(i2[-1]),
+                     int(np.count_nonzero(i1 == 0)), int(np.count_nonzero(i2 == 0)), float(accuracy))
 
 
 class CApi:
@@ -108,8 +140,15 @@ class CApi:
                                "(build it with `python -c 'import __graft_entry__ as g; g.build()'`)" % path)
         self.path = path
         self.lib = C.CDLL(path)
+        self.missing = set()
         for name, (res, args) in SYMBOLS.items():
-            fn = getattr(self.lib, name)  # AttributeError if the symbol is missing
+            try:
+                fn = getattr(self.lib, name)  # AttributeError if the symbol is missing
+            except AttributeError:
+                if name not in OPTIONAL:
+                    raise
+                self.missing.add(name)
+                continue
             fn.restype = res
             fn.argtypes = args
 
@@ -366,6 +405,24 @@ class CApi:
         self.check(self.lib.ps_swfull(b1, len(b1), b2, len(b2), C.byref(score), C.byref(acc),
                                       i1.ctypes.data_as(c_i32p), i2.ctypes.data_as(c_i32p), cap, C.byref(n)))
         return int(score.value), float(acc.value), i1[:n.value].copy(), i2[:n.value].copy()
+
+    def sw_summaries(self, pairs):
+        """[SwSummary] of the (seq1, seq2) pairs: ONE ps_batch_sw_summary call where the library has it, otherwise the same
+        records derived from swfull's index lists pair by pair (the checkers)."""
+        pairs = list(pairs)
+        if "ps_batch_sw_summary" in self.missing:
+            return [summary_from_lists(a, b, *self.swfull(a, b)) for a, b in pairs]
+        n = len(pairs)
+        if not n:
+            return []
+        b1 = [a.encode("ascii") for a, _ in pairs]
+        b2 = [b.encode("ascii") for _, b in pairs]
+        p1, p2 = (C.c_char_p * n)(*b1), (C.c_char_p * n)(*b2)
+        n1 = np.array([len(x) for x in b1], dtype=np.int64)
+        n2 = np.array([len(x) for x in b2], dtype=np.int64)
+        out = (PsSwSummary * n)()
+        self.check(self.lib.ps_batch_sw_summary(n, p1, n1.ctypes.data_as(c_i64p), p2, n2.ctypes.data_as(c_i64p), out))
+        return [SwSummary(*(int(getattr(r, k)) for k in SwSummary._fields[:-1]), float(r.accuracy)) for r in out]
 
     def debug_sw_band(self):
         """cumulative Smith-Waterman band counters: banded, fell_back, edge, band_cells, full_cells"""

@@ -46,6 +46,14 @@ class RegionBatch:
                 pa.sequence = self.api.align_sequence(h)
                 self.api.align_update_events(h, pa.events)
 
+    def drop(self, idx=None):
+        """Forget the resident AlignData of the regions `idx` (default: all) WITHOUT writing anything back: the PSAlign objects
+        were changed from outside (a new start sequence) and the next call rebuilds the AlignData from them."""
+        for i in (list(self._h) if idx is None else idx):
+            h = self._h.pop(i, None)
+            if h is not None:
+                self.api.align_destroy(h)
+
     def close(self):
         self.sync()
         for h in self._h.values():

@@ -2,6 +2,7 @@
 `poreseqcpp.PSAlign`:
 
   consensus_region  <- poreseq/Mutate.py:8-101   (Mutate('self') then {Mutate('viterbi'), Refine()})
+  test_start        <- poreseq/Mutate.py:59-65   (`test`: start from the read that spans the most of the draft)
   variant_region    <- poreseq/Variant.py:66-95  (ScoreMutations / ScorePoints with start offsetting)
   split_regions     <- poreseq/split_fasta.py:94-101 (max_length pieces with 1 kb overlap)
 
@@ -20,7 +21,25 @@ def _report(verbose, text):
         sys.stderr.write(text + "\n")
 
 
-def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None):
+def test_start(events, refseq, summaries):
+    """The start sequence of the reference's `test` mode (Mutate.py:59-65): one of the events' own base-called sequences
+    instead of the draft.  `summaries[k]` is the Smith-Waterman summary of events[k].sequence against `refseq`
+    (poreseqcpp.swalign_summaries).  Returns (sequence, index of the event it was cut from; -1 and "" when no event wins).
+
+    The loop is the reference's, quirks included: an event's span on the DRAFT (last2 - first2) is compared with the LENGTH
+    of the best slice so far and has to be strictly greater, so the first of equals stays; the 1-based first1 / last1 are used
+    as 0-based slice bounds.  An empty alignment raises IndexError, as `pairs[-1]` of an empty list does there.
+    """
+    seq, chosen = "", -1
+    for k, (ev, s) in enumerate(zip(events, summaries)):
+        if s.n_pairs == 0:
+            raise IndexError("list index out of range")
+        if s.last2 - s.first2 > len(seq):
+            seq, chosen = ev.sequence[s.first1:s.last1], k
+    return seq, chosen
+
+
+def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False):
     """Run the consensus schedule in place on `pa`; returns (sequence, accuracy_vs_refseq).
 
     The call sequence is the reference's (Mutate.py:39-101) and has to be: a region with fewer than 5 events is handed
@@ -28,15 +47,25 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None):
     followed by Refine(), ending after the first Refine that changes nothing; `end_trim` bases come off both ends;
     the accuracy is the swalign identity against the sequence the region was loaded with.
     `log`, when given, receives (call, nbases, sequence) after every PSAlign call; `verbose` > 0 prints progress.
+    `test` (Mutate.py:45-46, 59-68; `poreseq consensus -T`, and `poreseq train` unless --descend): the loaded sequence is thrown
+    away and the schedule starts from `test_start`'s pick among the reads' own sequences, WITHOUT realignment — the events keep
+    the ref_align they were loaded with; the accuracy is still taken against the loaded sequence.  It turns `verbose` 0 into 1.
     """
     params = pa.params if params is None else params
     pa.params.setdefault('verbose', 0)
     identity = lambda a, b: poreseqcpp.swalign(a, b, pa._native)
     refseq = pa.sequence if refseq is None else refseq
+    if test and verbose == 0:
+        verbose = 1
     if len(pa.events) < 5:
         _report(verbose, "fewer than 5 events: region returned as loaded")
         return (refseq, 100)
     _report(verbose, "refining %d bases with %d events" % (len(refseq), len(pa.events)))
+    if test:
+        sums = poreseqcpp.swalign_summaries([(ev.sequence, refseq) for ev in pa.events], pa._native)
+        pa.sequence, chosen = test_start(pa.events, refseq, sums)
+        start = poreseqcpp.swalign_summaries([(pa.sequence, refseq)], pa._native)[0]
+        _report(verbose, "starting from event %d: %d bases, identity %.1f%%" % (chosen, len(pa.sequence), start.accuracy))
 
     def call(name, fn):
         n = fn()
@@ -65,13 +94,19 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None):
     return (pa.sequence, acc)
 
 
-def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True):
+def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True, test=False, accuracies=None):
     """The consensus schedule of `consensus_region` for several independent regions in lock-step (poreseq_amd.batch):
     every PSAlign call of the schedule is issued once for all regions that still take part in it, so each phase is one
     launch chain on the GPU.  Returns [(sequence, accuracy)] in the order of `pas`; each entry equals what
     `consensus_region(pa)` returns for that region run on its own from a fresh process.
     `logs`, when given, is a list of lists receiving (call, nbases, sequence) per region after every call.
     `batch`: an already loaded RegionBatch over `pas` (events resident on the GPU, see RegionBatch.load); it is closed here.
+    `test`: every region starts from `test_start`'s pick instead of its loaded sequence (see consensus_region); the picks of all
+    regions come from ONE batched Smith-Waterman call over all (read, draft) pairs.  Resident AlignData of a loaded `batch`
+    still hold the loaded sequence: they are dropped and rebuilt from the PSAlign objects.
+    `accuracies`, when given, is a list of lists receiving per region the identity against its refseq after Mutate('self') and
+    after every Refine (the "Accuracy:" lines of Mutate.py:72-83), each round's values from one batched call over the live regions.
+    The final accuracies likewise come from one batched call.
     """
     from .batch import RegionBatch
     n = len(pas)
@@ -88,13 +123,36 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
     if not todo and batch is not None:
         batch.close()                               # (every region had fewer than five events: nothing ran, the handles still go)
     if todo:
+        api = pas[todo[0]]._native
+
         def note(i, call, nb):
             if logs is not None:
                 logs[i].append((call, nb, pas[i].sequence))
+
+        def identities(idx):
+            if accuracies is not None and idx:
+                sums = poreseqcpp.swalign_summaries([(pas[i].sequence, refseqs[i]) for i in idx], api)
+                for i, s in zip(idx, sums):
+                    accuracies[i].append(s.accuracy)
+
+        if test:
+            try:
+                owner = [i for i in todo for _ in pas[i].events]
+                sums = poreseqcpp.swalign_summaries([(ev.sequence, refseqs[i]) for i in todo for ev in pas[i].events], api)
+                for i in todo:
+                    pas[i].sequence = test_start(pas[i].events, refseqs[i], [s for o, s in zip(owner, sums) if o == i])[0]
+                if batch is not None:
+                    batch.drop(todo)
+            except Exception:
+                if batch is not None:
+                    batch.drop()
+                    batch.close()
+                raise
         with (batch if batch is not None else RegionBatch(pas, resident=resident)) as rb:
             tot = rb.Mutate(todo, reps=reps)
             for i in todo:
                 note(i, "Mutate:self", tot[i])
+            identities(todo)
             live = list(todo)
             for _ in range(reps):
                 if not live:
@@ -105,14 +163,16 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
                 nb = rb.Refine(live)
                 for i in live:
                     note(i, "Refine", nb[i])
+                identities(live)
                 live = [i for i in live if nb[i] != 0]
-        api = pas[todo[0]]._native
         for i in todo:
             pa = pas[i]
             p = pa.params if params is None else params
             if 'end_trim' in p and len(pa.sequence) > 2 * p['end_trim']:
                 pa.sequence = pa.sequence[int(p['end_trim']):-int(p['end_trim'])]
-            out[i] = (pa.sequence, poreseqcpp.swalign(pa.sequence, refseqs[i], api)[0])
+        final = poreseqcpp.swalign_summaries([(pas[i].sequence, refseqs[i]) for i in todo], api)
+        for i, s in zip(todo, final):
+            out[i] = (pas[i].sequence, s.accuracy)
     return out
 
 
@@ -129,7 +189,7 @@ def variant_region(pa, muts, region_start=0, params=None, out=None):
     return mutscores
 
 
-def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None, in_flight=1, lock_step=False):
+def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None, in_flight=1, lock_step=False, test=False):
     """Transition-parameter search of `poreseq train` (cmdline.py:246-267): every iteration runs the consensus schedule
     (reps = 10) once per candidate parameter set (VaryParams: 16 of them) on the same region and keeps the most accurate.
 
@@ -146,6 +206,10 @@ def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None,
                        stopped, which is what the reference's single process does — bit-parity mode.
     Which candidate wins can differ between the first two and the last by the luck of the seeds; keep the default
     when comparing against the reference.
+
+    `test` is handed to the consensus schedule of every candidate, in all three modes.  The reference's command line runs
+    its candidates with test = not --descend (cmdline.py:242-244), i.e. `poreseq train` corresponds to test=True here and
+    `poreseq train --descend` to the default, test=False.
     """
     from .util import VaryParams, SaveParams
     best_accs = []
@@ -153,11 +217,11 @@ def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None,
         cands = paramlists[it] if paramlists is not None else VaryParams(params)
 
         def one(p):
-            return consensus_region(make_pa(p), p, reps=reps, refseq=refseq)[1]
+            return consensus_region(make_pa(p), p, reps=reps, refseq=refseq, test=test)[1]
 
         if lock_step:
             pas = [make_pa(p) for p in cands]
-            accs = [acc for _, acc in consensus_regions(pas, None, reps=reps, refseqs=[refseq] * len(pas))]
+            accs = [acc for _, acc in consensus_regions(pas, None, reps=reps, refseqs=[refseq] * len(pas), test=test)]
         elif in_flight > 1:
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=int(in_flight)) as pool:

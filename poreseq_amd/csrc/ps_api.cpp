@@ -5,6 +5,7 @@
 #include <memory>
 
 #include "ps_host.h"
+#include "ps_sw.h"
 
 using namespace ps;
 
@@ -292,6 +293,32 @@ int ps_swfull(const char* s1, int64_t n1, const char* s2, int64_t n2, int32_t* s
     if (acc) *acc = ac;
     for (size_t k = 0; k < a.size(); k++) { if (i1) i1[k] = a[k]; if (i2) i2[k] = b[k]; }
     *np = (int64_t)a.size();
+    return PS_OK;
+}
+int ps_batch_sw_summary(int64_t n, const char* const* seq1, const int64_t* n1, const char* const* seq2, const int64_t* n2,
+                        ps_sw_summary* out) {
+    if (n < 0 || (n && (!seq1 || !n1 || !seq2 || !n2 || !out))) return fail(PS_ERR_BAD_ARG, "ps_batch_sw_summary");
+    for (int64_t k = 0; k < n; k++)
+        if (n1[k] < 0 || n2[k] < 0 || (n1[k] && !seq1[k]) || (n2[k] && !seq2[k])) return fail(PS_ERR_BAD_ARG, "ps_batch_sw_summary: bad pair");
+    if (!n) return PS_OK;
+    NEED_RT();
+    std::vector<std::string> s(2 * (size_t)n);
+    SwInput in;
+    for (int64_t k = 0; k < n; k++) {
+        if (n1[k]) s[2 * k].assign(seq1[k], (size_t)n1[k]);
+        if (n2[k]) s[2 * k + 1].assign(seq2[k], (size_t)n2[k]);
+    }
+    for (int64_t k = 0; k < n; k++) in.push_back({&s[2 * k], &s[2 * k + 1]});
+    std::vector<SwResult> res;
+    PS_TRY(sw_summaries(rt, in, &res));
+    for (int64_t k = 0; k < n; k++) {
+        const SwResult& r = res[k];
+        ps_sw_summary& o = out[k];
+        o.score = r.score; o.n_pairs = r.n_pairs; o.n_match = r.n_match;
+        o.first1 = r.first1; o.first2 = r.first2; o.last1 = r.last1; o.last2 = r.last2;
+        o.gap1 = r.gap1; o.gap2 = r.gap2;
+        o.accuracy = r.accuracy;
+    }
     return PS_OK;
 }
 int ps_seq_to_states(const char* seq, int64_t n, int32_t* st, int64_t* ns) {

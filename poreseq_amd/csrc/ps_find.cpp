@@ -144,17 +144,9 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     // Pairs whose alignment hugs the main diagonal (the Viterbi seeds) run in band mode (ps_sw.hip), with checkpoints sized from the band.
     std::vector<int> wbs(pairs.size());
     for (size_t k = 0; k < pairs.size(); k++) wbs[k] = sw_band_choice(*pairs[k].first, *pairs[k].second);
-    auto sw_bytes = [&](size_t k) { return sw_pair_bytes((int)pairs[k].first->size(), (int)pairs[k].second->size(), wbs[k]); };
-    double sw_cap = device_share_bytes() / PLAN_SW_PART;
-    auto sw_chunk_end = [&](size_t k0) {
-        double acc = 0;
-        size_t k = k0;
-        for (; k < pairs.size(); k++) { const double add = sw_bytes(k); if (k > k0 && acc + add > sw_cap) break; acc += add; }
-        return k;
-    };
     typedef std::vector<std::pair<const std::string*, const std::string*>> SwIn;
     SwJob swjob;
-    size_t sw_first = sw_chunk_end(0);
+    size_t sw_first = sw_chunk_end(pairs, wbs.data(), SW_LISTS, 0, sw_chunk_cap());
     {
         const int rc = sw_launch(rt, SwIn(pairs.begin(), pairs.begin() + sw_first), &swjob, wbs.data());
         if (rc == PS_ERR_NOMEM && sw_first > 1) { sw_first = 0; swjob = SwJob(); }   // nothing enqueued: everything goes the chunked way below
@@ -174,15 +166,7 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     std::vector<SwResult> als_all;
     PS_TRY(sw_finish(rt, &swjob, &als_all));   // always drain the second stream, even on failure above
     PS_TRY(rc_base);
-    for (size_t k0 = sw_first; k0 < pairs.size();) {
-        const size_t k1 = sw_chunk_end(k0);
-        std::vector<SwResult> part;
-        const int rc = sw_batch(rt, SwIn(pairs.begin() + k0, pairs.begin() + k1), &part, wbs.data() + k0);
-        if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { sw_cap *= 0.5; continue; }
-        PS_TRY(rc);
-        for (SwResult& r : part) als_all.push_back(std::move(r));
-        k0 = k1;
-    }
+    PS_TRY(sw_chunks(rt, pairs, wbs.data(), SW_LISTS, sw_first, &als_all));
     if (sw_first < pairs.size()) { if (trace_on()) fprintf(stderr, "[ps] smith-waterman: %zu pairs, %zu with the realign, the rest in chunks\n", pairs.size(), sw_first); }
     if (pairs.empty()) return PS_OK;
     // the reference's progress line under `verbose` (cpp/FindMutations.cpp:34-35, 100-109: "Finding mutations", a dot per seed sequence, a

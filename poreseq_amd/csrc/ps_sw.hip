@@ -33,6 +33,8 @@
 #include <cstring>
 
 #include "ps_dev.h"
+#include "ps_host.h"
+#include "ps_plan.h"
 #include "ps_sw.h"
 
 namespace ps {
@@ -512,7 +514,10 @@ __device__ __forceinline__ void sw_tile(const SwPair& p, const char* s1, const c
 }
 
 // ---- locate the starting cell, then trace back; grid (pairs), block 64 ------------------------------------------
-template <int K>
+// SUMMARY: the same walk, counted instead of stored (SwForm, ps_sw.h): nothing goes to `out` (no buffer exists), and the record gets the
+// walk's ends and its gap steps next to the pair and match counts — what a caller would read off the reversed index lists.  In walk
+// order the first entry is the lists' last, the last entry their first; every value below is wave-uniform.
+template <int K, bool SUMMARY>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 : 4, 8))) void k_sw_trace(const SwPair* pairs, const char* chars, const int* rowsave, const int* colsave,
                                                  const int* blkmax, int* out, int* res) {
     __shared__ unsigned char codes[64][64];
@@ -558,9 +563,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
         }
         if (fc != 0x7fffffff) { bj = fc; bi = fr; }
     }
-    int* oi = out + p.out_off;
-    int* oj = oi + (p.n1 + p.n2 + 2);
+    int* oi = SUMMARY ? nullptr : out + p.out_off;
+    int* oj = SUMMARY ? nullptr : oi + (p.n1 + p.n2 + 2);
     int i = bi, j = bj, np = 0, nm = 0;
+    int w1 = 0, w2 = 0, e1 = 0, e2 = 0, g1 = 0, g2 = 0;   // summary: first and latest entry of the walk, entries with a 0 on either side
     bool done = false, inexact = false;
     while (!done && i > 0 && j > 0) {
         const int q = (i - 1) >> 6, cb = (j - 1) >> 6;   // 64 x 64 tile holding (i, j), one column per lane
@@ -579,7 +585,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             const unsigned long long dm = __ballot((code & 7u) == 7u);   // diagonal step from a cell with score > 0
             const int run = __builtin_amdgcn_readfirstlane(dm == ~0ull ? 64 : (int)__builtin_ctzll(~dm));
             if (__ballot(l < run && !(code & 16u))) { inexact = true; done = true; break; }   // band certificate
-            if (l < run) { oi[np + l] = ii; oj[np + l] = jj; }
+            if (!SUMMARY) { if (l < run) { oi[np + l] = ii; oj[np + l] = jj; } }
+            else if (run) { if (!np) { w1 = i; w2 = j; } e1 = i - run + 1; e2 = j - run + 1; }
             nm += (int)__popcll(__ballot((code & 8u) && l < run));
             np += run; i -= run; j -= run;
             if (run == 64) continue;
@@ -589,22 +596,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             if (!(cr & 16u)) { inexact = true; done = true; break; }
             if (!(cr & 4u)) { done = true; break; }   // score <= 0
             const unsigned stp = cr & 3u;
-            if (stp == 1u) { if (l == 0) { oi[np] = 0; oj[np] = j; } np++; j--; }
-            else if (stp == 2u) { if (l == 0) { oi[np] = i; oj[np] = 0; } np++; i--; }
-            else { done = true; break; }
+            if (stp == 1u) {
+                if (!SUMMARY) { if (l == 0) { oi[np] = 0; oj[np] = j; } }
+                else { if (!np) { w1 = 0; w2 = j; } e1 = 0; e2 = j; g1++; }
+                np++; j--;
+            } else if (stp == 2u) {
+                if (!SUMMARY) { if (l == 0) { oi[np] = i; oj[np] = 0; } }
+                else { if (!np) { w1 = i; w2 = 0; } e1 = i; e2 = 0; g2++; }
+                np++; i--;
+            } else { done = true; break; }
         }
     }
     if (l == 0) { o[0] = best; o[1] = bi; o[2] = bj; o[3] = np; o[4] = nm; o[6] = inexact ? 1 : 0; }
+    if (SUMMARY && l == 0) { o[8] = e1; o[9] = e2; o[10] = w1; o[11] = w2; o[12] = g1; o[13] = g2; }
 }
 
 // the device pointers of an enqueued batch
 struct SwDev { const SwPair* pairs; const char* chars; int *row, *col, *blk, *prog, *ticket, *out, *res; };
 
-// Fill and traceback of np pairs in one form: K columns per lane on `waves` waves per workgroup, chained over nss strips
+// Fill and traceback (list or summary build, SwForm) of np pairs in one form: K columns per lane on `waves` waves per workgroup, chained over nss strips
 // (sw_launch on why each exists).  packed: the 16-bit fill (8 columns per lane, SWW waves) with the traceback of the 8-column build;
 // band: the packed fill, one workgroup of SWBW waves per pair over its 512-column strips, the same traceback (band-aware through
 // SwPair::wb).
-static int sw_run(hipStream_t st, const SwDev& d, int np, int nss, int K, int waves, bool packed, bool band) {
+static int sw_run(hipStream_t st, const SwDev& d, int np, int nss, int K, int waves, bool packed, bool band, SwForm form) {
+    const bool sum = form == SW_SUMMARY;
+#define PS_SW_TRACE(K_) (sum ? k_sw_trace<K_, true> : k_sw_trace<K_, false>)
     auto run = [&](auto fill, dim3 grid, int wv, int* prog, int* ticket, auto trace) -> int {
         hipLaunchKernelGGL(fill, grid, dim3(64 * wv), 0, st, d.pairs, d.chars, d.row, d.col, d.blk, prog, ticket, d.res);
         PS_LAUNCH_CHECK();
@@ -614,15 +630,16 @@ static int sw_run(hipStream_t st, const SwDev& d, int np, int nss, int K, int wa
     };
     const dim3 strips(nss, np);
     // (kernels come out in the code object in the order they are first named here)
-    if (packed && !band) return run(k_sw_fill_pk<SWW, false>, strips, SWW, d.prog, d.ticket, k_sw_trace<8>);
-    if (band) return run(k_sw_fill_pk<SWBW, true>, dim3(1, np), SWBW, nullptr, nullptr, k_sw_trace<8>);
+    if (packed && !band) return run(k_sw_fill_pk<SWW, false>, strips, SWW, d.prog, d.ticket, PS_SW_TRACE(8));
+    if (band) return run(k_sw_fill_pk<SWBW, true>, dim3(1, np), SWBW, nullptr, nullptr, PS_SW_TRACE(8));
     switch (100 * waves + K) {
-        case 100 * SWW1 + 8: return run(k_sw_fill<8, SWW1>, strips, SWW1, d.prog, d.ticket, k_sw_trace<8>);
-        case 100 * SWW1 + 16: return run(k_sw_fill<16, SWW1>, strips, SWW1, d.prog, d.ticket, k_sw_trace<16>);
-        case 100 * SWW + 4: return run(k_sw_fill<4, SWW>, strips, SWW, d.prog, d.ticket, k_sw_trace<4>);
-        case 100 * SWW + 16: return run(k_sw_fill<16, SWW>, strips, SWW, d.prog, d.ticket, k_sw_trace<16>);
-        case 100 * SWW + 8: return run(k_sw_fill<8, SWW>, strips, SWW, d.prog, d.ticket, k_sw_trace<8>);
+        case 100 * SWW1 + 8: return run(k_sw_fill<8, SWW1>, strips, SWW1, d.prog, d.ticket, PS_SW_TRACE(8));
+        case 100 * SWW1 + 16: return run(k_sw_fill<16, SWW1>, strips, SWW1, d.prog, d.ticket, PS_SW_TRACE(16));
+        case 100 * SWW + 4: return run(k_sw_fill<4, SWW>, strips, SWW, d.prog, d.ticket, PS_SW_TRACE(4));
+        case 100 * SWW + 16: return run(k_sw_fill<16, SWW>, strips, SWW, d.prog, d.ticket, PS_SW_TRACE(16));
+        case 100 * SWW + 8: return run(k_sw_fill<8, SWW>, strips, SWW, d.prog, d.ticket, PS_SW_TRACE(8));
     }
+#undef PS_SW_TRACE
     return fail(PS_ERR_BAD_ARG, "Smith-Waterman: no fill of " + std::to_string(K) + " columns per lane on " + std::to_string(waves) + " waves is built");
 }
 
@@ -700,8 +717,8 @@ int sw_band_choice(const std::string& s1, const std::string& s2) {
     return band_close(s1, s2, wb) ? wb : 0;
 }
 
-double sw_pair_bytes(int n1, int n2, int wb) {
-    const double out = 8.0 * ((double)n1 + n2 + 2);
+double sw_pair_bytes(int n1, int n2, int wb, SwForm form) {
+    const double out = form == SW_SUMMARY ? 0.0 : 8.0 * ((double)n1 + n2 + 2);
     if (!wb) return 4.0 * (((double)n1 / 64 + 1) * (n2 + 8) + ((double)n2 / 64 + 1) * (n1 + 1)) + out;
     const double nbb = SWBS / 64 + 2 * wb / 64, ns = (n2 + SWBS - 1) / SWBS;
     return 4.0 * (ns * nbb * (SWBS + 1) + ((double)n2 / 64 + 1) * (64 * nbb + 1)) + out;
@@ -713,9 +730,11 @@ void sw_band_counters(int64_t out[5]) { for (int k = 0; k < 5; k++) out[k] = g_b
 
 // -------------------------------------------------------------------------------------------------
 // enqueue a batch of pairwise alignments on the runtime's second stream (asynchronous)
-int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, SwJob* job, const int* wbs) {
+int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, SwJob* job, const int* wbs, SwForm form) {
     const int np = (int)in.size();
+    const bool lists = form == SW_LISTS;
     job->np = np;
+    job->form = form;
     if (!np) return PS_OK;
     std::vector<SwPair>& pairs = job->pairs;
     std::string& pool = job->pool;
@@ -772,8 +791,8 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
             job->band_cells += band_cells(p.n1, p.n2, p.wb);
         }
         p.col_off = col_tot; col_tot += ((int64_t)p.n2 / 64 + 1) * p.cpitch;
-        p.out_off = out_tot; out_tot += 2 * ((int64_t)p.n1 + p.n2 + 2);
-        p.res_off = (int64_t)k * 8;
+        p.out_off = out_tot; if (lists) out_tot += 2 * ((int64_t)p.n1 + p.n2 + 2);   // (summary form: no index lists anywhere)
+        p.res_off = (int64_t)k * SW_RES;
         job->cells += (double)p.n1 * p.n2;
     }
     pool.push_back(0);
@@ -787,13 +806,13 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     PS_TRY(rt->buf("sw_col").ensure(col_tot * sizeof(int)));
     PS_TRY(rt->buf("sw_blk").ensure(blk_tot * sizeof(int)));
     PS_TRY(rt->buf("sw_prog").ensure(nprog * sizeof(int)));
-    PS_TRY(rt->buf("sw_out").ensure(out_tot * sizeof(int)));
-    PS_TRY(rt->buf("sw_res").ensure((size_t)np * 8 * sizeof(int)));
+    if (lists) PS_TRY(rt->buf("sw_out").ensure(out_tot * sizeof(int)));
+    PS_TRY(rt->buf("sw_res").ensure((size_t)np * SW_RES * sizeof(int)));
     SwPair* d_pairs = rt->buf("sw_pairs").as<SwPair>();
     char* d_chars = rt->buf("sw_chars").as<char>();
     int* d_blk = rt->buf("sw_blk").as<int>();
     int* d_prog = rt->buf("sw_prog").as<int>();
-    int* d_out = rt->buf("sw_out").as<int>();
+    int* d_out = lists ? rt->buf("sw_out").as<int>() : nullptr;
     int* d_res = rt->buf("sw_res").as<int>();
     SwDev dv = {d_pairs, d_chars, rt->buf("sw_row").as<int>(), rt->buf("sw_col").as<int>(), d_blk, d_prog, d_prog + (size_t)nf * nss, d_out, d_res};
     hipStream_t st = nullptr;
@@ -801,7 +820,7 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     job->stream = st;
     PS_TRY(rt->up(d_pairs, dev.data(), np * sizeof(SwPair), st));
     PS_TRY(rt->up(d_chars, pool.data(), pool.size(), st));
-    PS_HIP(hipMemsetAsync(d_res, 0, (size_t)np * 8 * sizeof(int), st));
+    PS_HIP(hipMemsetAsync(d_res, 0, (size_t)np * SW_RES * sizeof(int), st));
     PS_HIP(hipMemsetAsync(d_blk, 0, blk_tot * sizeof(int), st));   // waves beyond a pair's last column never write theirs
     PS_HIP(hipMemsetAsync(d_prog, 0, nprog * sizeof(int), st));
     if (rt->prof_on) PS_HIP(hipEventRecord(rt->sw0, st));
@@ -811,21 +830,23 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
         bool packed = K == 8 && WW == SWW && packed_allowed();
         for (int k = 0; k < nf && packed; k++) if (std::min(dev[k].n1, dev[k].n2) > SW_PK_MAXLEN) packed = false;
         packed_all = packed;
-        PS_TRY(sw_run(st, dv, nf, nss, K, WW, packed, false));
+        PS_TRY(sw_run(st, dv, nf, nss, K, WW, packed, false, form));
     }
     if (nb) {
         dv.pairs += nf;
-        PS_TRY(sw_run(st, dv, nb, nss, 8, SWBW, true, true));
+        PS_TRY(sw_run(st, dv, nb, nss, 8, SWBW, true, true, form));
         if (rt->prof_on) rt->prof["sw_band"].launches++;
     }
     if (rt->prof_on && packed_all) rt->prof["sw_pk8"].launches++;   // (which fill ran: a host-side count per batch, no event pair)
     if (rt->prof_on) PS_HIP(hipEventRecord(rt->sw1, st));
-    PS_TRY(rt->hbuf("sw_res").ensure((size_t)np * 8 * sizeof(int)));
-    PS_TRY(rt->hbuf("sw_out").ensure((size_t)out_tot * sizeof(int)));
+    PS_TRY(rt->hbuf("sw_res").ensure((size_t)np * SW_RES * sizeof(int)));
     job->res = rt->hbuf("sw_res").as<int>();
-    job->outbuf = rt->hbuf("sw_out").as<int>();
-    PS_HIP(hipMemcpyAsync(job->res, d_res, (size_t)np * 8 * sizeof(int), hipMemcpyDeviceToHost, st));
-    PS_HIP(hipMemcpyAsync(job->outbuf, d_out, (size_t)out_tot * sizeof(int), hipMemcpyDeviceToHost, st));
+    PS_HIP(hipMemcpyAsync(job->res, d_res, (size_t)np * SW_RES * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (lists) {
+        PS_TRY(rt->hbuf("sw_out").ensure((size_t)out_tot * sizeof(int)));
+        job->outbuf = rt->hbuf("sw_out").as<int>();
+        PS_HIP(hipMemcpyAsync(job->outbuf, d_out, (size_t)out_tot * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
     return PS_OK;
 }
 
@@ -842,24 +863,30 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
         }
     }
     for (int k = 0; k < np; k++)
-        if (job->res[k * 8 + 5]) return fail(PS_ERR_HIP, "Smith-Waterman: a strip gave up waiting for its left neighbour (result discarded)");
+        if (job->res[k * SW_RES + 5]) return fail(PS_ERR_HIP, "Smith-Waterman: a strip gave up waiting for its left neighbour (result discarded)");
     std::vector<int> redo;
     int edge = 0;
     for (int k = 0; k < np; k++) {
         const SwPair& p = job->pairs[k];
         if (!p.wb) continue;
-        if (job->res[k * 8 + 6]) { redo.push_back(k); continue; }
-        if (job->res[k * 8 + 0] > 0 && std::abs(job->res[k * 8 + 1] - job->res[k * 8 + 2]) > p.wb - 64) edge++;
+        if (job->res[k * SW_RES + 6]) { redo.push_back(k); continue; }
+        if (job->res[k * SW_RES + 0] > 0 && std::abs(job->res[k * SW_RES + 1] - job->res[k * SW_RES + 2]) > p.wb - 64) edge++;
     }
     for (int k = 0; k < np; k++) {
-        const int n = job->res[k * 8 + 3], nm = job->res[k * 8 + 4];
+        const int* rec = job->res + (size_t)k * SW_RES;
+        const int n = rec[3], nm = rec[4];
         const SwPair& p = job->pairs[k];
         SwResult& r = (*out)[k];
-        r.score = job->res[k * 8 + 0];
-        const int* oi = job->outbuf + p.out_off;
-        const int* oj = oi + (p.n1 + p.n2 + 2);
-        r.a.assign(oi, oi + n); r.b.assign(oj, oj + n);
-        std::reverse(r.a.begin(), r.a.end()); std::reverse(r.b.begin(), r.b.end());
+        r.score = rec[0];
+        r.n_pairs = n; r.n_match = nm;
+        if (job->form == SW_SUMMARY) {
+            r.first1 = rec[8]; r.first2 = rec[9]; r.last1 = rec[10]; r.last2 = rec[11]; r.gap1 = rec[12]; r.gap2 = rec[13];
+        } else {
+            const int* oi = job->outbuf + p.out_off;
+            const int* oj = oi + (p.n1 + p.n2 + 2);
+            r.a.assign(oi, oi + n); r.b.assign(oj, oj + n);
+            std::reverse(r.a.begin(), r.a.end()); std::reverse(r.b.begin(), r.b.end());
+        }
         r.accuracy = 100.0 * nm / (double)n;  // NaN for an empty alignment, as the reference computes it
     }
     g_band[0] += job->nband; g_band[1] += (int64_t)redo.size(); g_band[2] += edge;
@@ -879,15 +906,57 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
     for (size_t k = 0; k < redo.size(); k++) in2.push_back({&s[2 * k], &s[2 * k + 1]});
     const std::vector<int> full(redo.size(), 0);
     std::vector<SwResult> part;
-    PS_TRY(sw_batch(rt, in2, &part, full.data()));
+    PS_TRY(sw_batch(rt, in2, &part, full.data(), job->form));   // (in the form the batch was asked for)
     for (size_t k = 0; k < redo.size(); k++) (*out)[redo[k]] = std::move(part[k]);
     return PS_OK;
 }
 
-int sw_batch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, std::vector<SwResult>* out, const int* wb) {
+int sw_batch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, std::vector<SwResult>* out, const int* wb, SwForm form) {
     SwJob job;
-    PS_TRY(sw_launch(rt, in, &job, wb));
+    PS_TRY(sw_launch(rt, in, &job, wb, form));
     return sw_finish(rt, &job, out);
+}
+
+// The checkpoint rows / columns of a batch (~13 MB per full-matrix 10 kb pair) are a pool like the DP matrices: at most PLAN_SW_PART-th of
+// this runtime's share goes into one launch.  sw_chunk_end: one past the last pair of the chunk that starts at k0 under `cap` bytes
+// (always at least one pair).
+size_t sw_chunk_end(const SwInput& in, const int* wbs, SwForm form, size_t k0, double cap) {
+    double acc = 0;
+    size_t k = k0;
+    for (; k < in.size(); k++) {
+        const double add = sw_pair_bytes((int)in[k].first->size(), (int)in[k].second->size(), wbs[k], form);
+        if (k > k0 && acc + add > cap) break;
+        acc += add;
+    }
+    return k;
+}
+
+double sw_chunk_cap() { return device_share_bytes() / PLAN_SW_PART; }
+
+// pairs k0 .. end, chunk after chunk, appended to `out`; a chunk the device has no memory for is cut in two
+int sw_chunks(Runtime* rt, const SwInput& in, const int* wbs, SwForm form, size_t k0, std::vector<SwResult>* out, int* nchunks) {
+    double cap = sw_chunk_cap();
+    while (k0 < in.size()) {
+        const size_t k1 = sw_chunk_end(in, wbs, form, k0, cap);
+        std::vector<SwResult> part;
+        const int rc = sw_batch(rt, SwInput(in.begin() + k0, in.begin() + k1), &part, wbs + k0, form);
+        if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { cap *= 0.5; continue; }
+        PS_TRY(rc);
+        for (SwResult& r : part) out->push_back(std::move(r));
+        if (nchunks) ++*nchunks;
+        k0 = k1;
+    }
+    return PS_OK;
+}
+
+int sw_summaries(Runtime* rt, const SwInput& in, std::vector<SwResult>* out) {
+    out->clear();
+    std::vector<int> wbs(in.size());
+    for (size_t k = 0; k < in.size(); k++) wbs[k] = sw_band_choice(*in[k].first, *in[k].second);
+    int nchunks = 0;
+    PS_TRY(sw_chunks(rt, in, wbs.data(), SW_SUMMARY, 0, out, &nchunks));
+    if (trace_on()) fprintf(stderr, "[ps] smith-waterman summaries: %zu pairs in %d chunks\n", in.size(), nchunks);
+    return PS_OK;
 }
 
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,

@@ -323,7 +323,7 @@ def _gather_and_meet(local, n_regions, max_events):
     return got
 
 
-def refine_regions(regions, make_region_pa, params=None, batch=16, reps=4, max_events=64, in_flight=1):
+def refine_regions(regions, make_region_pa, params=None, batch=16, reps=4, max_events=64, in_flight=1, test=False):
     """Consensus for a list of (start, end) regions on all ranks: regions are dealt longest-first to the ranks
     (`shard` with weights), each rank refines its share in lock-step batches of `batch` regions on its GPU
     (poreseq_amd.batch), and every rank receives every region's result.  Returns [(sequence, accuracy)] in region order.
@@ -331,7 +331,8 @@ def refine_regions(regions, make_region_pa, params=None, batch=16, reps=4, max_e
     in_flight > 1 keeps that many lock-step batches on the GPU at once, one host thread (slot) each — the library gives every
     thread its own stream and device pools, and a slot takes the next batch when its own is done, so a rank's regions stream
     through the slots (bench.py: 14 slots of 20 regions on one MI355X).  Every region draws from its own random stream
-    (poreseq_amd.batch), so the results do not depend on batch, in_flight or on which slot refines a region."""
+    (poreseq_amd.batch), so the results do not depend on batch, in_flight or on which slot refines a region.
+    `test` goes to `consensus_regions`: every region starts from one of its reads instead of its draft (Mutate.py:59-68)."""
     from .consensus import consensus_regions
     from .poreseqcpp import PSAlign
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -357,7 +358,7 @@ def refine_regions(regions, make_region_pa, params=None, batch=16, reps=4, max_e
 
     def one(chunk):
         pas = [probe.pop(idx) if idx in probe else make_region_pa(a, b) for idx, (a, b) in chunk]
-        res = consensus_regions(pas, params, reps=reps)
+        res = consensus_regions(pas, params, reps=reps, test=test)
         return [(idx, seq, np.array([acc])) for (idx, _), (seq, acc) in zip(chunk, res)]
 
     local = [r for part in stream_batches(chunks, one, in_flight, enter=_enter_hip_library if hip_backend else None) for r in part]

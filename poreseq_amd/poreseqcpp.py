@@ -27,6 +27,19 @@ def swalign(seq1, seq2, _api=_api):
     return (acc, list(zip(i1.tolist(), i2.tolist())))
 
 
+def swalign_summaries(pairs, _api=_api):
+    """Smith-Waterman of every (seq1, seq2) pair in ONE batched call, each reduced to a `_capi.SwSummary`: what the consensus
+    driver reads off swalign's list (Mutate.py:59-68, 93-98) — first and last aligned pair, gap counts, identity — without the
+    list.  Identical pairs are aligned once (the replicas of `train` share reads and draft).  Returns the records in the order of `pairs`.
+    """
+    pairs = [(a, b) for a, b in pairs]
+    slot = {}
+    for p in pairs:
+        slot.setdefault(p, len(slot))
+    res = _api().sw_summaries(list(slot))
+    return [res[slot[p]] for p in pairs]
+
+
 def seqtostates(seq, _api=_api):
     """5-mer states [0, 1023] of a nucleotide string (pyx:176-187)."""
     return _api().seq_to_states(seq).tolist()
