@@ -136,6 +136,15 @@ int ps_score_mutation_deltas(ps_align* a, const ps_muts* muts, double* deltas);
 /* MakeMutations (cpp/MakeMutations.cpp:74-146): greedy application, returns mutated-base count. */
 int ps_make_mutations(ps_align* a, const ps_muts* scored, int32_t* n_bases);
 
+/* Variant.py:48-61 for n_seqs sequences: scores[s * n_events + e] = ScoreEvents()[e] of a copy of the AlignData realigned to
+ * sequence s (pyx:241-261, EventData.py:226-256); accuracy[s] = swalign's identity in %.  The AlignData is not modified.
+ * All sequences run as one chain: a Smith-Waterman batch whose traceback leaves, per sequence, a partner table on the device (no index
+ * list comes back), the events' ref_align re-mapped through it on the device by PSEvent.mapaligns' rule, and (sequence x event) forward
+ * alignments in chunks sized by the device-memory plan; identical sequences are aligned and scored once.  A sequence whose alignment
+ * with the current one is empty is PS_ERR_BAD_ARG, the message naming its index (the reference dies there with an IndexError).
+ * accuracy may be NULL.  Sequences as a CSR string pool, as ps_find_mutations takes its seeds. */
+int ps_score_sequences(ps_align* a, int32_t n_seqs, const int64_t* seq_off, const char* seq_pool, double* scores, double* accuracy);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -172,6 +181,9 @@ int ps_batch_find_mutations(int32_t n, ps_align* const* a, const ps_seqs* const*
 int ps_batch_score_mutations(int32_t n, ps_align* const* a, const ps_muts* const* muts, ps_muts** out);
 /* MakeMutations: greedy application per AlignData; the re-scoring rounds of the recursion are batched. */
 int ps_batch_make_mutations(int32_t n, ps_align* const* a, const ps_muts* const* scored, int32_t* n_bases);
+/* `poreseq variant -v` for every AlignData: seqs[i] are the candidate sequences of AlignData i (ps_seqs_create), scores[i] has
+ * count(seqs[i]) * n_events(i) doubles and accuracy[i] (or the whole array) may be NULL: ps_score_sequences for all of them in one chain. */
+int ps_batch_score_sequences(int32_t n, ps_align* const* a, const ps_seqs* const* seqs, double* const* scores, double* const* accuracy);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -233,7 +245,9 @@ int ps_set_device_fraction(double fraction);
 
 /* Hot-kernel instrumentation for bench.py: accumulated HIP-event time (ms), launches and
  * algorithmic bytes of the named kernel class ("fill" = k_fill, "sweep" = the strip sweeps k_sweep / k_sweeps / k_sweep2 and their _w builds,
- * "score", "viterbi", "sw") since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab". */
+ * "score", "viterbi", "sw") since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab";
+ * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =
+ * alignment chunks (launches) over distinct sequences (units) of ps_score_sequences. */
 /* ps_prof_enable(1) makes every hot-kernel launch be bracketed by HIP events on the library's stream
  * (one extra synchronisation per launch: use it in a separate, untimed pass); ps_prof_enable(2) queues the
  * event pairs instead and reads them when the profile is asked for (no synchronisation per launch: usable

@@ -67,6 +67,8 @@ SYMBOLS = {
     "ps_find_point_mutations": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "ps_find_mutations": (C.c_int, [C.c_void_p, C.c_int32, c_i64p, C.c_char_p, C.POINTER(C.c_void_p)]),
     "ps_score_mutations": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "ps_score_sequences": (C.c_int, [C.c_void_p, C.c_int32, c_i64p, C.c_char_p, c_dp, c_dp]),
+    "ps_batch_score_sequences": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_dp), C.POINTER(c_dp)]),
     "ps_score_mutation_deltas": (C.c_int, [C.c_void_p, C.c_void_p, c_dp]),
     "ps_make_mutations": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -101,8 +103,8 @@ SYMBOLS = {
 
 
 # entry points of the header that a checker library (the oracle, the reference shim) may lack: CApi serves them from what the
-# library does export (sw_summaries from swfull)
-OPTIONAL = frozenset(["ps_batch_sw_summary"])
+# library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents)
+OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
 # entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
@@ -301,6 +303,18 @@ class CApi:
         self.check(self.lib.ps_score_mutations(h, hm, C.byref(out)))
         return out
 
+    def score_sequences(self, h, seqs, n_events):
+        """-> (scores float64 [len(seqs)][n_events], accuracy float64 [len(seqs)]): ScoreEvents of the AlignData realigned to each
+        sequence, and swalign's identity in %; the AlignData is not modified"""
+        bs = [s.encode("ascii") for s in seqs]
+        off = np.zeros(len(bs) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(b) for b in bs])
+        scores = np.zeros((len(bs), int(n_events)), dtype=np.float64)
+        acc = np.zeros(len(bs), dtype=np.float64)
+        if bs:
+            self.check(self.lib.ps_score_sequences(h, len(bs), off.ctypes.data_as(c_i64p), b"".join(bs), _dp(scores), _dp(acc)))
+        return scores, acc
+
     def score_mutation_deltas(self, h, hm, n_events, n_muts):
         """[n_events][n_muts] float64: every event's term of every edit's score (their sum in event order + -1e-6 is the score)"""
         out = np.zeros((int(n_events), int(n_muts)), dtype=np.float64)
@@ -366,6 +380,21 @@ class CApi:
         out = (C.c_void_p * n)()
         self.check(self.lib.ps_batch_score_mutations(n, self._harr(handles), self._harr(muts_handles), out))
         return [C.c_void_p(out[i]) for i in range(n)]
+
+    def batch_score_sequences(self, handles, seqs, n_events):
+        """score_sequences for several AlignData in one chain; seqs[i]: the sequences of handles[i] -> [(scores, accuracy)]"""
+        n = len(handles)
+        hs = [self.seqs_create(list(sv)) for sv in seqs]
+        try:
+            scores = [np.zeros((len(sv), int(e)), dtype=np.float64) for sv, e in zip(seqs, n_events)]
+            acc = [np.zeros(len(sv), dtype=np.float64) for sv in seqs]
+            sp = (c_dp * n)(*[_dp(a) for a in scores])
+            ap = (c_dp * n)(*[_dp(a) for a in acc])
+            self.check(self.lib.ps_batch_score_sequences(n, self._harr(handles), self._harr(hs), sp, ap))
+        finally:
+            for h in hs:
+                self.seqs_destroy(h)
+        return list(zip(scores, acc))
 
     def batch_make_mutations(self, handles, muts_handles):
         n = len(handles)

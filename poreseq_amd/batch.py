@@ -138,6 +138,27 @@ class RegionBatch:
             self._close(idx, hs, write_back=False)
         return [s.tolist() for s in sc]
 
+    def ScoreSequences(self, seqs_per_region, idx=None):
+        """PSAlign.ScoreSequences for the regions `idx` on their resident AlignData, all regions' sequences in one chain:
+        seqs_per_region[k] are the candidate sequences of region idx[k] (may be empty).  Returns one ndarray
+        [sequences][events] per region; nothing is modified."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        seqs = [[str(s) for s in sv] for sv in seqs_per_region]
+        if len(seqs) != len(idx):
+            raise ValueError("one list of sequences per region")
+        if not idx:
+            return []
+        if "ps_batch_score_sequences" in self.api.missing:
+            return [self.pas[i].ScoreSequences(sv) for i, sv in zip(idx, seqs)]
+        hs = self._open(idx)
+        try:
+            res = self.api.batch_score_sequences(hs, seqs, [len(self.pas[i].events) for i in idx])
+        finally:
+            self._close(idx, hs, write_back=False)
+        for _, acc in res:
+            poreseqcpp._check_realign_accuracy(acc)
+        return [sc for sc, _ in res]
+
     def Mutate(self, idx=None, seqs='self', reps=4):
         """PSAlign.Mutate (pyx:378-435) for the regions `idx`; returns {region index: total mutated bases}."""
         idx = list(range(len(self.pas))) if idx is None else list(idx)

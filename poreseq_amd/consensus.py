@@ -4,6 +4,7 @@
   consensus_region  <- poreseq/Mutate.py:8-101   (Mutate('self') then {Mutate('viterbi'), Refine()})
   test_start        <- poreseq/Mutate.py:59-65   (`test`: start from the read that spans the most of the draft)
   variant_region    <- poreseq/Variant.py:66-95  (ScoreMutations / ScorePoints with start offsetting)
+  variant_sequences <- poreseq/Variant.py:48-63  (`variant -v`: whole candidate sequences, one batched ScoreSequences call)
   split_regions     <- poreseq/split_fasta.py:94-101 (max_length pieces with 1 kb overlap)
 
 fast5 / BAM loading is out of scope: callers hand over a PSAlign whose events are already
@@ -187,6 +188,24 @@ def variant_region(pa, muts, region_start=0, params=None, out=None):
         if out is not None:
             out.write(str(ms) + '\n')
     return mutscores
+
+
+def variant_sequences(pa, variants, out=None):
+    """Score whole candidate sequences against the reads as `poreseq variant -v` does (Variant.py:48-63): `variants` is a mapping
+    id -> sequence or an iterable of (id, sequence); returns {id: dscore}, dscore = sum of the events' scores after re-aligning a
+    copy of `pa` to the sequence, minus the same sum for `pa` as it is, and writes the reference's 'id, dscore' line per variant to
+    `out`.  All variants go through ONE `PSAlign.ScoreSequences` call; `pa` is not modified.  The sums are numpy's, on the host,
+    so the additions happen in the reference's order."""
+    items = list(variants.items()) if hasattr(variants, "items") else [(k, v) for k, v in variants]
+    basescore = np.sum(pa.ScoreEvents())
+    rows = pa.ScoreSequences([str(seq) for _, seq in items])
+    variantscores = {}
+    for (vid, _), row in zip(items, rows):
+        dscore = np.sum(row) - basescore
+        if out is not None:
+            out.write('{}, {}\n'.format(vid, dscore))
+        variantscores[vid] = dscore
+    return variantscores
 
 
 def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None, in_flight=1, lock_step=False, test=False):

@@ -235,6 +235,29 @@ int ps_batch_find_mutations(int32_t n, ps_align* const* a, const ps_seqs* const*
     for (int i = 0; i < n; i++) out[i] = m[i].release();
     return PS_OK;
 }
+int ps_score_sequences(ps_align* a, int32_t n_seqs, const int64_t* off, const char* pool, double* scores, double* accuracy) {
+    if (!a || n_seqs < 0 || (n_seqs && (!off || !pool)) || (n_seqs && a->a.E && !scores)) return fail(PS_ERR_BAD_ARG, "ps_score_sequences");
+    if (n_seqs && off[0] < 0) return fail(PS_ERR_BAD_ARG, "ps_score_sequences: negative offset");
+    for (int i = 0; i < n_seqs; i++) if (off[i + 1] < off[i]) return fail(PS_ERR_BAD_ARG, "ps_score_sequences: offsets not monotone");
+    NEED_RT();
+    std::vector<std::string> sv;
+    for (int i = 0; i < n_seqs; i++) sv.emplace_back(pool + off[i], pool + off[i + 1]);
+    return score_sequences_multi(rt, {&a->a}, {&sv}, {scores}, {accuracy});
+}
+int ps_batch_score_sequences(int32_t n, ps_align* const* a, const ps_seqs* const* seqs, double* const* scores, double* const* accuracy) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n && (!seqs || !scores)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_sequences");
+    NEED_RT();
+    std::vector<const std::vector<std::string>*> sv(n);
+    std::vector<double*> sc(n), ac(n);
+    for (int i = 0; i < n; i++) {
+        if (!seqs[i]) return fail(PS_ERR_BAD_ARG, "ps_batch_score_sequences: null sequences");
+        if (!scores[i] && as[i]->E && !seqs[i]->v.empty()) return fail(PS_ERR_BAD_ARG, "ps_batch_score_sequences: null scores");
+        sv[i] = &seqs[i]->v; sc[i] = scores[i]; ac[i] = accuracy ? accuracy[i] : nullptr;
+    }
+    return score_sequences_multi(rt, as, sv, sc, ac);
+}
 int ps_batch_score_mutations(int32_t n, ps_align* const* a, const ps_muts* const* muts, ps_muts** out) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

@@ -14,8 +14,9 @@
 
 namespace ps {
 
-// cap on the DP-matrix bytes of one batch of candidate-sequence alignments: this runtime's share of the device (ps_mem.cpp)
-static double max_batch_bytes() { return device_share_bytes(); }
+// cap on the DP-matrix bytes of one chunk of candidate-sequence alignments (FindMutations' seeds, ps_score_sequences): this runtime's
+// share of the device (ps_mem.cpp)
+double fwd_chunk_cap() { return device_share_bytes(); }
 
 static void fillinds(SwResult& al) {  // cpp/swlib.cpp:342-365
     if (al.a.empty()) return;
@@ -24,6 +25,28 @@ static void fillinds(SwResult& al) {  // cpp/swlib.cpp:342-365
         if (al.a[k] > 0) i1 = al.a[k]; else al.a[k] = i1;
         if (al.b[k] > 0) i2 = al.b[k]; else al.b[k] = i2;
     }
+}
+
+// Where the chunk of forward-only (region, candidate sequence) units that starts at unit q0 ends: as many units as the matrix budget
+// `cap` holds (typical anti-diagonal footprint ~ half the band; p_seen: the widest one a chunk of this call turned out to need), at
+// most `limit` of them, always at least one.  *nref: levels of the chunk's units (their ref_align / ref_like / ref_index arrays).
+// Shared by FindMutations' candidate sequences and ps_score_sequences (ps_variant.hip).
+size_t fwd_chunk_end(const std::vector<FwdUnit>& units, size_t q0, double cap, int p_seen, size_t limit, size_t* nref) {
+    size_t q1 = q0;
+    double bytes = 0;
+    *nref = 0;
+    while (q1 < units.size()) {
+        const Align* a = units[q1].a;
+        // slots per anti-diagonal as realign will probably size them (the first chunk finds out and is cut again if not)
+        const int P = std::max(p_seen, guess_slots(a));
+        double add = 0;
+        for (int e = 0; e < a->E; e++)
+            add += sweep_enabled() && sweep_guess_k(a->par.realign_width) ? fwd_job_bytes(a, a->n[e], units[q1].C)
+                                                                          : matrix_bytes((int64_t)a->n[e] + (int64_t)units[q1].C + 1, P, 1);
+        if (q1 > q0 && (bytes + add > cap || q1 - q0 >= limit)) break;
+        bytes += add; *nref += (size_t)a->ntot; q1++;
+    }
+    return q1;
 }
 
 static int argmax(const std::vector<double>& v) { return (int)(std::max_element(v.begin(), v.end()) - v.begin()); }
@@ -201,26 +224,16 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             for (int r = 0; r < R; r++) as[r]->refs_finish();
         }
         par_for((int)need.size(), [&](int q) { need[q].states = states_of((*seeds[need[q].r])[need[q].k]); });
-        const double cap = max_batch_bytes();
+        const double cap = fwd_chunk_cap();
+        std::vector<FwdUnit> units(need.size());
+        for (size_t q = 0; q < need.size(); q++) units[q] = {as[need[q].r], (int)need[q].states.size()};
         size_t q0 = 0;
         int p_seen = 0;   // widest anti-diagonal footprint (in slots) a chunk of this call turned out to need
         size_t limit = (size_t)-1;   // (region, seed) pairs per chunk after a chunk had to be cut again
         while (q0 < need.size()) {
-            // chunk: as many (region, seed) pairs as the matrix budget holds (typical anti-diagonal footprint ~ half the band)
-            size_t q1 = q0;
-            double bytes = 0;
+            // chunk: as many (region, seed) pairs as the matrix budget holds
             size_t nref = 0;
-            while (q1 < need.size()) {
-                const Align* a = as[need[q1].r];
-                // slots per anti-diagonal as realign will probably size them (the first chunk finds out and is cut again if not)
-                const int P = std::max(p_seen, guess_slots(a));
-                double add = 0;
-                for (int e = 0; e < a->E; e++)
-                    add += sweep_enabled() && sweep_guess_k(a->par.realign_width) ? fwd_job_bytes(a, a->n[e], (int)need[q1].states.size())
-                                                                                  : matrix_bytes((int64_t)a->n[e] + (int64_t)need[q1].states.size() + 1, P, 1);
-                if (q1 > q0 && (bytes + add > cap || q1 - q0 >= limit)) break;
-                bytes += add; nref += (size_t)a->ntot; q1++;
-            }
+            const size_t q1 = fwd_chunk_end(units, q0, cap, p_seen, limit, &nref);
             const size_t stage_mark = rt->stage.mark();
             double* h_ra = (double*)rt->stage.alloc(std::max<size_t>(nref, 1) * sizeof(double));   // pinned: plain enqueue below
             if (!h_ra) return fail(PS_ERR_NOMEM, "hipHostMalloc (staging arena)");

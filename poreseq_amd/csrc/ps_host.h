@@ -132,6 +132,14 @@ void par_for(int n, const std::function<void(int)>& fn);
 int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes);
 int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seeds,
                          const std::vector<std::vector<Mut>*>& outs);
+// chunks of forward-only (AlignData, candidate sequence) units under this runtime's share (ps_find.cpp): FindMutations' seeds, ps_score_sequences
+struct FwdUnit { const Align* a; int C; };   // the AlignData whose events are aligned, the states of the sequence they are aligned to
+double fwd_chunk_cap();                      // bytes one chunk may take
+size_t fwd_chunk_end(const std::vector<FwdUnit>& units, size_t q0, double cap, int p_seen, size_t limit, size_t* nref);
+// Variant.py:48-61 (`variant -v`) for several AlignData: scores[r][s * E + e] = ScoreEvents()[e] of a copy of as[r] realigned to seqs[r][s],
+// accuracy[r][s] = swalign's identity in % (may be nullptr); no AlignData is modified (ps_variant.hip)
+int score_sequences_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seqs,
+                          const std::vector<double*>& scores, const std::vector<double*>& accuracy);
 int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
                          double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs);
 std::string info_string();   // process-wide state in one line (ps_info)

@@ -517,7 +517,11 @@ __device__ __forceinline__ void sw_tile(const SwPair& p, const char* s1, const c
 // SUMMARY: the same walk, counted instead of stored (SwForm, ps_sw.h): nothing goes to `out` (no buffer exists), and the record gets the
 // walk's ends and its gap steps next to the pair and match counts — what a caller would read off the reversed index lists.  In walk
 // order the first entry is the lists' last, the last entry their first; every value below is wave-uniform.
-template <int K, bool SUMMARY>
+// SW_MAP: the same walk writes part[i1] = i2 for every non-zero seq1 index of the lists (0 where the base faces a gap) into the pair's
+// table of n1 + 2 ints (`out`, which stays on the device) — i1 runs down from hi to lo, every index once, all of them inside 1 .. n1 —
+// and the record gets lo, hi, whether an entry with i1 == 0 exists and the i2 of the first such entry in list order (the last one the
+// walk meets: overwritten as it goes): RemapRec, ps_remap.h.  Entries with i1 == 0 write nothing to the table.
+template <int K, int FORM>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 : 4, 8))) void k_sw_trace(const SwPair* pairs, const char* chars, const int* rowsave, const int* colsave,
                                                  const int* blkmax, int* out, int* res) {
     __shared__ unsigned char codes[64][64];
@@ -563,10 +567,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
         }
         if (fc != 0x7fffffff) { bj = fc; bi = fr; }
     }
-    int* oi = SUMMARY ? nullptr : out + p.out_off;
-    int* oj = SUMMARY ? nullptr : oi + (p.n1 + p.n2 + 2);
+    constexpr bool SUMMARY = FORM == SW_SUMMARY, LISTS = FORM == SW_LISTS, MAP = FORM == SW_MAP;
+    int* oi = LISTS || MAP ? out + p.out_off : nullptr;   // (map form: the partner table)
+    int* oj = LISTS ? oi + (p.n1 + p.n2 + 2) : nullptr;
     int i = bi, j = bj, np = 0, nm = 0;
     int w1 = 0, w2 = 0, e1 = 0, e2 = 0, g1 = 0, g2 = 0;   // summary: first and latest entry of the walk, entries with a 0 on either side
+    int mlo = 0, mhi = 0, m0 = 0, my0 = 0;                // map: RemapRec
     bool done = false, inexact = false;
     while (!done && i > 0 && j > 0) {
         const int q = (i - 1) >> 6, cb = (j - 1) >> 6;   // 64 x 64 tile holding (i, j), one column per lane
@@ -585,7 +591,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             const unsigned long long dm = __ballot((code & 7u) == 7u);   // diagonal step from a cell with score > 0
             const int run = __builtin_amdgcn_readfirstlane(dm == ~0ull ? 64 : (int)__builtin_ctzll(~dm));
             if (__ballot(l < run && !(code & 16u))) { inexact = true; done = true; break; }   // band certificate
-            if (!SUMMARY) { if (l < run) { oi[np + l] = ii; oj[np + l] = jj; } }
+            if (LISTS) { if (l < run) { oi[np + l] = ii; oj[np + l] = jj; } }
+            else if (MAP) { if (l < run) oi[ii] = jj; if (run) { if (!mhi) mhi = i; mlo = i - run + 1; } }
             else if (run) { if (!np) { w1 = i; w2 = j; } e1 = i - run + 1; e2 = j - run + 1; }
             nm += (int)__popcll(__ballot((code & 8u) && l < run));
             np += run; i -= run; j -= run;
@@ -597,11 +604,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
             if (!(cr & 4u)) { done = true; break; }   // score <= 0
             const unsigned stp = cr & 3u;
             if (stp == 1u) {
-                if (!SUMMARY) { if (l == 0) { oi[np] = 0; oj[np] = j; } }
+                if (LISTS) { if (l == 0) { oi[np] = 0; oj[np] = j; } }
+                else if (MAP) { m0 = 1; my0 = j; }
                 else { if (!np) { w1 = 0; w2 = j; } e1 = 0; e2 = j; g1++; }
                 np++; j--;
             } else if (stp == 2u) {
-                if (!SUMMARY) { if (l == 0) { oi[np] = i; oj[np] = 0; } }
+                if (LISTS) { if (l == 0) { oi[np] = i; oj[np] = 0; } }
+                else if (MAP) { if (l == 0) oi[i] = 0; if (!mhi) mhi = i; mlo = i; }
                 else { if (!np) { w1 = i; w2 = 0; } e1 = i; e2 = 0; g2++; }
                 np++; i--;
             } else { done = true; break; }
@@ -609,6 +618,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 8 :
     }
     if (l == 0) { o[0] = best; o[1] = bi; o[2] = bj; o[3] = np; o[4] = nm; o[6] = inexact ? 1 : 0; }
     if (SUMMARY && l == 0) { o[8] = e1; o[9] = e2; o[10] = w1; o[11] = w2; o[12] = g1; o[13] = g2; }
+    if (MAP && l == 0) { o[8] = mlo; o[9] = mhi; o[10] = m0; o[11] = my0; }
 }
 
 // the device pointers of an enqueued batch
@@ -619,8 +629,7 @@ struct SwDev { const SwPair* pairs; const char* chars; int *row, *col, *blk, *pr
 // band: the packed fill, one workgroup of SWBW waves per pair over its 512-column strips, the same traceback (band-aware through
 // SwPair::wb).
 static int sw_run(hipStream_t st, const SwDev& d, int np, int nss, int K, int waves, bool packed, bool band, SwForm form) {
-    const bool sum = form == SW_SUMMARY;
-#define PS_SW_TRACE(K_) (sum ? k_sw_trace<K_, true> : k_sw_trace<K_, false>)
+#define PS_SW_TRACE(K_) (form == SW_SUMMARY ? k_sw_trace<K_, SW_SUMMARY> : (form == SW_MAP ? k_sw_trace<K_, SW_MAP> : k_sw_trace<K_, SW_LISTS>))
     auto run = [&](auto fill, dim3 grid, int wv, int* prog, int* ticket, auto trace) -> int {
         hipLaunchKernelGGL(fill, grid, dim3(64 * wv), 0, st, d.pairs, d.chars, d.row, d.col, d.blk, prog, ticket, d.res);
         PS_LAUNCH_CHECK();
@@ -718,7 +727,8 @@ int sw_band_choice(const std::string& s1, const std::string& s2) {
 }
 
 double sw_pair_bytes(int n1, int n2, int wb, SwForm form) {
-    const double out = form == SW_SUMMARY ? 0.0 : 8.0 * ((double)n1 + n2 + 2);
+    // (map form: the pair's table lives in the caller's buffer, allocated for all pairs outside any chunking: nothing in a launch's pools)
+    const double out = form == SW_LISTS ? 8.0 * ((double)n1 + n2 + 2) : 0.0;
     if (!wb) return 4.0 * (((double)n1 / 64 + 1) * (n2 + 8) + ((double)n2 / 64 + 1) * (n1 + 1)) + out;
     const double nbb = SWBS / 64 + 2 * wb / 64, ns = (n2 + SWBS - 1) / SWBS;
     return 4.0 * (ns * nbb * (SWBS + 1) + ((double)n2 / 64 + 1) * (64 * nbb + 1)) + out;
@@ -732,7 +742,8 @@ void sw_band_counters(int64_t out[5]) { for (int k = 0; k < 5; k++) out[k] = g_b
 // enqueue a batch of pairwise alignments on the runtime's second stream (asynchronous)
 int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, SwJob* job, const int* wbs, SwForm form) {
     const int np = (int)in.size();
-    const bool lists = form == SW_LISTS;
+    const bool lists = form == SW_LISTS, map = form == SW_MAP;
+    if (map && np && !job->d_map) return fail(PS_ERR_BAD_ARG, "Smith-Waterman (map form): no table buffer");
     job->np = np;
     job->form = form;
     if (!np) return PS_OK;
@@ -791,7 +802,9 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
             job->band_cells += band_cells(p.n1, p.n2, p.wb);
         }
         p.col_off = col_tot; col_tot += ((int64_t)p.n2 / 64 + 1) * p.cpitch;
-        p.out_off = out_tot; if (lists) out_tot += 2 * ((int64_t)p.n1 + p.n2 + 2);   // (summary form: no index lists anywhere)
+        p.out_off = out_tot;   // (summary form: no index lists anywhere; map form: the pair's table in the caller's buffer)
+        if (lists) out_tot += 2 * ((int64_t)p.n1 + p.n2 + 2);
+        if (map) out_tot += (int64_t)p.n1 + 2;
         p.res_off = (int64_t)k * SW_RES;
         job->cells += (double)p.n1 * p.n2;
     }
@@ -812,7 +825,7 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
     char* d_chars = rt->buf("sw_chars").as<char>();
     int* d_blk = rt->buf("sw_blk").as<int>();
     int* d_prog = rt->buf("sw_prog").as<int>();
-    int* d_out = lists ? rt->buf("sw_out").as<int>() : nullptr;
+    int* d_out = lists ? rt->buf("sw_out").as<int>() : (map ? job->d_map : nullptr);
     int* d_res = rt->buf("sw_res").as<int>();
     SwDev dv = {d_pairs, d_chars, rt->buf("sw_row").as<int>(), rt->buf("sw_col").as<int>(), d_blk, d_prog, d_prog + (size_t)nf * nss, d_out, d_res};
     hipStream_t st = nullptr;
@@ -838,6 +851,7 @@ int sw_launch(Runtime* rt, const std::vector<std::pair<const std::string*, const
         if (rt->prof_on) rt->prof["sw_band"].launches++;
     }
     if (rt->prof_on && packed_all) rt->prof["sw_pk8"].launches++;   // (which fill ran: a host-side count per batch, no event pair)
+    if (rt->prof_on) rt->prof[lists ? "sw_lists" : (map ? "sw_map" : "sw_summary")].launches++;   // (and which traceback form)
     if (rt->prof_on) PS_HIP(hipEventRecord(rt->sw1, st));
     PS_TRY(rt->hbuf("sw_res").ensure((size_t)np * SW_RES * sizeof(int)));
     job->res = rt->hbuf("sw_res").as<int>();
@@ -881,6 +895,8 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
         r.n_pairs = n; r.n_match = nm;
         if (job->form == SW_SUMMARY) {
             r.first1 = rec[8]; r.first2 = rec[9]; r.last1 = rec[10]; r.last2 = rec[11]; r.gap1 = rec[12]; r.gap2 = rec[13];
+        } else if (job->form == SW_MAP) {
+            r.map_lo = rec[8]; r.map_hi = rec[9]; r.map_has0 = rec[10]; r.map_y0 = rec[11]; r.map_off = p.out_off;
         } else {
             const int* oi = job->outbuf + p.out_off;
             const int* oj = oi + (p.n1 + p.n2 + 2);
@@ -906,13 +922,34 @@ int sw_finish(Runtime* rt, SwJob* job, std::vector<SwResult>* out) {
     for (size_t k = 0; k < redo.size(); k++) in2.push_back({&s[2 * k], &s[2 * k + 1]});
     const std::vector<int> full(redo.size(), 0);
     std::vector<SwResult> part;
-    PS_TRY(sw_batch(rt, in2, &part, full.data(), job->form));   // (in the form the batch was asked for)
-    for (size_t k = 0; k < redo.size(); k++) (*out)[redo[k]] = std::move(part[k]);
+    // (in the form the batch was asked for; map form: the tables go to a buffer of their own and from there to the pairs' places)
+    int* d_redo = nullptr;
+    if (job->form == SW_MAP) {
+        PS_TRY(rt->buf("sw_map_redo").ensure((size_t)sw_map_ints(in2, 0, in2.size()) * sizeof(int)));
+        d_redo = rt->buf("sw_map_redo").as<int>();
+    }
+    PS_TRY(sw_batch(rt, in2, &part, full.data(), job->form, d_redo));
+    for (size_t k = 0; k < redo.size(); k++) {
+        const SwPair& p = job->pairs[redo[k]];
+        if (job->form == SW_MAP) {
+            PS_HIP(hipMemcpyAsync(job->d_map + p.out_off, d_redo + part[k].map_off, ((size_t)p.n1 + 2) * sizeof(int), hipMemcpyDeviceToDevice, job->stream));
+            part[k].map_off = p.out_off;
+        }
+        (*out)[redo[k]] = std::move(part[k]);
+    }
+    if (job->form == SW_MAP) PS_HIP(hipStreamSynchronize(job->stream));
     return PS_OK;
 }
 
-int sw_batch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, std::vector<SwResult>* out, const int* wb, SwForm form) {
+int64_t sw_map_ints(const SwInput& in, size_t k0, size_t k1) {
+    int64_t t = 0;
+    for (size_t k = k0; k < k1; k++) t += (int64_t)in[k].first->size() + 2;
+    return t;
+}
+
+int sw_batch(Runtime* rt, const std::vector<std::pair<const std::string*, const std::string*>>& in, std::vector<SwResult>* out, const int* wb, SwForm form, int* d_map) {
     SwJob job;
+    job.d_map = d_map;
     PS_TRY(sw_launch(rt, in, &job, wb, form));
     return sw_finish(rt, &job, out);
 }
@@ -934,15 +971,16 @@ size_t sw_chunk_end(const SwInput& in, const int* wbs, SwForm form, size_t k0, d
 double sw_chunk_cap() { return device_share_bytes() / PLAN_SW_PART; }
 
 // pairs k0 .. end, chunk after chunk, appended to `out`; a chunk the device has no memory for is cut in two
-int sw_chunks(Runtime* rt, const SwInput& in, const int* wbs, SwForm form, size_t k0, std::vector<SwResult>* out, int* nchunks) {
+int sw_chunks(Runtime* rt, const SwInput& in, const int* wbs, SwForm form, size_t k0, std::vector<SwResult>* out, int* nchunks, int* d_map) {
     double cap = sw_chunk_cap();
     while (k0 < in.size()) {
         const size_t k1 = sw_chunk_end(in, wbs, form, k0, cap);
         std::vector<SwResult> part;
-        const int rc = sw_batch(rt, SwInput(in.begin() + k0, in.begin() + k1), &part, wbs + k0, form);
+        const int64_t map0 = form == SW_MAP ? sw_map_ints(in, 0, k0) : 0;   // the chunk's tables inside d_map
+        const int rc = sw_batch(rt, SwInput(in.begin() + k0, in.begin() + k1), &part, wbs + k0, form, d_map ? d_map + map0 : nullptr);
         if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { cap *= 0.5; continue; }
         PS_TRY(rc);
-        for (SwResult& r : part) out->push_back(std::move(r));
+        for (SwResult& r : part) { r.map_off += map0; out->push_back(std::move(r)); }
         if (nchunks) ++*nchunks;
         k0 = k1;
     }

@@ -45,6 +45,11 @@ def seqtostates(seq, _api=_api):
     return _api().seq_to_states(seq).tolist()
 
 
+def _check_realign_accuracy(acc):
+    if np.any(np.asarray(acc) < 0.6):  # sic: compares a percentage, as the reference does (pyx:256)
+        raise Exception('Error rate too large for realignment!')
+
+
 class PSAlign:
     """All data of reads aligned to a reference (pyx:189-472).
 
@@ -119,6 +124,26 @@ class PSAlign:
         """Total likelihood score of each event (pyx:263-276).  Does not write ref_align back."""
         with PSAlign._Data(self) as d:
             return d.api.score_alignments(d.h, len(self.events)).tolist()
+
+    def ScoreSequences(self, seqs):
+        """ndarray [len(seqs)][len(events)]: row s is what `pav = self.Copy(); pav.RealignTo(seqs[s]); pav.ScoreEvents()` returns,
+        the loop of the reference's `variant -v` (Variant.py:52-59) — as ONE native call (ps_score_sequences: batched Smith-Waterman,
+        the re-mapping of RealignTo on the device, all (sequence, event) alignments in one chain).  `self` is not modified.  Raises
+        RealignTo's exception for a sequence whose identity is below its (sic) 0.6 %.  A library without the entry point (the
+        test-suite's checkers) runs the literal loop, which is the definition of the result."""
+        seqs = [str(s) for s in seqs]
+        api = self._native()
+        if "ps_score_sequences" in api.missing:
+            rows = []
+            for s in seqs:
+                pav = self.Copy()
+                pav.RealignTo(s)
+                rows.append(pav.ScoreEvents())
+            return np.array(rows, dtype=np.float64).reshape(len(seqs), len(self.events))
+        with PSAlign._Data(self) as d:
+            scores, acc = d.api.score_sequences(d.h, seqs, len(self.events))
+        _check_realign_accuracy(acc)
+        return scores
 
     def ScorePoints(self):
         """Score every single-base deletion / substitution / insertion (pyx:278-308)."""
