@@ -215,6 +215,26 @@ int ps_seq_to_states(const char* seq, int64_t n, int32_t* states, int64_t* n_sta
  * (backtrace, cpp/Alignment.cpp:516-624); for direction 1 they are zero. */
 int ps_debug_fill(ps_align* a, int32_t ev, int32_t direction, double* main, double* stay,
                   uint8_t* step_main, uint8_t* step_stay);
+/* The tables of ViterbiMutate (cpp/Viterbi.cpp:239-426) for n AlignData, run as ps_batch_viterbi_mutate runs them (same launches,
+ * deviates from the calling thread's generator).  obs_build selects the emission kernel: 0 = the library's choice, 1 = k_vit_obs_lds
+ * (at most 72 events), 2 = k_vit_obs<64> (at most 64), 3 = k_vit_obs<256>; PS_ERR_BAD_ARG for a build that cannot take the batch's
+ * event count (the checkers have one emission loop and ignore it).  Outputs, region r at a row pitch of cap_T (PS_ERR_BAD_ARG when a
+ * region keeps more positions; T is written first): T[n] positions kept; obs[n][cap_T][1024] trimmed-mean emissions;
+ * bp[n][cap_T][1024] back-pointers; lik_final[n][1024]; fwd[n][cap_T][1024] forward vectors as the recursion left them, each row up
+ * to its own scale (nkeep > 0 only); paths[n][max(nkeep, 1)][cap_T] the STATE paths (nkeep = 0: the one deterministic back-trace).
+ * Any output but T may be NULL.  The reference shim has no such view: PS_ERR_UNSUPPORTED. */
+int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t obs_build, int32_t nkeep, double skip_prob, double stay_prob,
+                     double mut_min, double mut_max, int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final,
+                     double* fwd, int16_t* paths);
+/* The recursion and the back-traces alone, on emission rows and deviates from the caller (no AlignData): n_regions regions of T[r]
+ * rows, concatenated.  obs[sum T][1024]; deviates (nkeep > 0): per region a [nkeep][T[r]] block in the order the traces consume
+ * them (trace k, last position first), region r's block at nkeep * (T[0] + .. + T[r-1]); trace k runs at the attenuation
+ * mut_min + (mut_max - mut_min) k / nkeep.  Outputs bp[sum T][1024], lik_final[n_regions][1024], fwd[sum T][1024] (nkeep > 0),
+ * paths laid out like the deviates with max(nkeep, 1) traces; any may be NULL.  The HIP library skips only its emission kernel
+ * (exp(obs) is formed on the host) and launches k_vit_steps / k_vit_log / k_vit_trace as a production call does. */
+int ps_debug_viterbi_steps(int32_t n_regions, const int32_t* T, const double* obs, const double* deviates, int32_t nkeep,
+                           double skip_prob, double stay_prob, double mut_min, double mut_max, int16_t* bp, double* lik_final,
+                           double* fwd, int16_t* paths);
 
 /* Tuning knob (process-wide): forward-only alignment batches — ScoreAlignments, FindMutations' candidate sequences — of at
  * least `min_alignments` jobs run as strip sweeps (ps_sweep.hip / ps_sweepw.hip: one to four wavefronts per alignment, ps_set_sweep_form);

@@ -615,8 +615,7 @@ std::vector<double> build_T(double skip, double stay) {
 }
 
 // ref: cpp/Viterbi.cpp:105-131
-int rand_pred(const VStep& v, int cur, double atten, const std::vector<double>& T) {
-    const double r = rand() / (double(RAND_MAX) + 1);
+int rand_pred(const VStep& v, int cur, double atten, const std::vector<double>& T, double r) {
     double pr[NS];
     for (int i = 0; i < NS; i++) pr[i] = T[i + (size_t)cur * NS] * std::pow(v.fwd[i], atten);
     normalise(pr);
@@ -645,12 +644,18 @@ std::string path_to_bases(const std::vector<int>& st) {
     return s;
 }
 
-// ref: cpp/Viterbi.cpp:239-426
-std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, double skip, double stay,
-                                        double mmin, double mmax) {
-    std::vector<std::unique_ptr<VStep>> S;
+// The tables of one ViterbiMutate call: S[0] the start vectors, S[t + 1] the step at kept position t; obs_rows (optional) the
+// trimmed-mean emission rows.  viterbi_mutate and the test hooks ps_debug_viterbi / ps_debug_viterbi_steps share it.
+typedef std::vector<std::unique_ptr<VStep>> VTable;
+void vit_start(VTable& S) {
+    S.clear();
     S.emplace_back(new VStep());
     for (int i = 0; i < NS; i++) { S[0]->lik[i] = 0; S[0]->bp[i] = -1; S[0]->fwd[i] = 1.0 / NS; }
+}
+
+// the walk over the reference positions, ref: cpp/Viterbi.cpp:239-356
+void vit_walk(std::vector<Event>& ev, double skip, double stay, VTable& S, std::vector<std::vector<double>>* obs_rows) {
+    vit_start(S);
     const int E = (int)ev.size();
     int refind = ev[0].refstart;
     for (auto& e : ev) refind = std::min(refind, e.refstart);
@@ -683,11 +688,18 @@ std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, doubl
         } else {
             for (int j = 0; j < NS; j++) obs[j] = obs[(size_t)j * E];
         }
+        if (obs_rows) obs_rows->emplace_back(obs.begin(), obs.begin() + NS);
         S.emplace_back(new VStep());
         vstep(*S[S.size() - 2], obs, skip, stay, *S.back());
         refind++;
     }
-    std::vector<std::string> out;
+}
+
+// the back-traces, ref: cpp/Viterbi.cpp:358-426: state paths [max(nkeep, 1)][T]; deviate() is called in the reference's order
+// (per kept path, one per back-step)
+template <class Dev>
+std::vector<std::vector<int>> vit_paths(const VTable& S, int nkeep, double skip, double stay, double mmin, double mmax, Dev deviate) {
+    std::vector<std::vector<int>> out;
     const int start = argmax(S.back()->lik);
     const int n = (int)S.size() - 1;
     std::vector<int> path;
@@ -695,7 +707,7 @@ std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, doubl
         int c = start;
         for (int i = n - 1; i >= 0; i--) { path.push_back(c); c = S[i + 1]->bp[c]; }
         std::reverse(path.begin(), path.end());
-        if (!path.empty()) out.push_back(path_to_bases(path));
+        out.push_back(path);
         return out;
     }
     std::vector<double> T = build_T(skip, stay);
@@ -704,11 +716,23 @@ std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, doubl
         int c = start;
         for (int i = n - 1; i >= 0; i--) {
             path.push_back(c);
-            c = rand_pred(*S[i + 1], c, mmin + (mmax - mmin) * k / (double)nkeep, T);
+            c = rand_pred(*S[i + 1], c, mmin + (mmax - mmin) * k / (double)nkeep, T, deviate());
         }
         std::reverse(path.begin(), path.end());
-        if (!path.empty()) out.push_back(path_to_bases(path));
+        out.push_back(path);
     }
+    return out;
+}
+inline double libc_deviate() { return rand() / (double(RAND_MAX) + 1); }
+
+// ref: cpp/Viterbi.cpp:239-426
+std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, double skip, double stay,
+                                        double mmin, double mmax) {
+    VTable S;
+    vit_walk(ev, skip, stay, S, nullptr);
+    std::vector<std::string> out;
+    for (const std::vector<int>& path : vit_paths(S, nkeep, skip, stay, mmin, mmax, libc_deviate))
+        if (!path.empty()) out.push_back(path_to_bases(path));
     return out;
 }
 
@@ -926,6 +950,63 @@ int ps_debug_fill(ps_align* a, int32_t e, int32_t dir, double* main, double* sta
         }
     }
     al.backtrace();
+    return PS_OK;
+}
+// the tables of a walked region into the hooks' arrays (any may be NULL); pitch = rows between two paths of the region
+static void vit_export(const VTable& S, const std::vector<std::vector<int>>& pt, int16_t* bp, double* lik_final, double* fwd, int16_t* paths,
+                       size_t pitch) {
+    const int T = (int)S.size() - 1;
+    for (int t = 0; t < T; t++)
+        for (int c = 0; c < NS; c++) {
+            if (bp) bp[(size_t)t * NS + c] = (int16_t)S[t + 1]->bp[c];
+            if (fwd) fwd[(size_t)t * NS + c] = S[t + 1]->fwd[c];
+        }
+    if (lik_final) for (int c = 0; c < NS; c++) lik_final[c] = T ? S[T]->lik[c] : 0.0;
+    if (paths)
+        for (size_t k = 0; k < pt.size(); k++)
+            for (int i = 0; i < T; i++) paths[k * pitch + i] = (int16_t)pt[k][i];
+}
+int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t, int32_t nkeep, double skip, double stay, double mmin, double mmax,
+                     int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
+    if (n < 0 || (n && (!a || !T)) || nkeep < 0 || cap_T < 0) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi");
+    const int np = std::max(nkeep, 1);
+    for (int r = 0; r < n; r++) {
+        if (!a[r] || a[r]->d.ev.empty()) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: no events");
+        VTable S;
+        std::vector<std::vector<double>> rows;
+        vit_walk(a[r]->d.ev, skip, stay, S, &rows);
+        T[r] = (int)rows.size();
+        if (T[r] > cap_T) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: a region has more positions than cap_T");
+        std::vector<std::vector<int>> pt;
+        if (T[r]) pt = vit_paths(S, nkeep, skip, stay, mmin, mmax, libc_deviate);
+        const size_t to = (size_t)r * cap_T * NS;
+        if (obs) for (int t = 0; t < T[r]; t++) std::copy(rows[t].begin(), rows[t].end(), obs + to + (size_t)t * NS);
+        vit_export(S, pt, bp ? bp + to : nullptr, lik_final ? lik_final + (size_t)r * NS : nullptr, fwd && nkeep ? fwd + to : nullptr,
+                   paths ? paths + (size_t)r * np * cap_T : nullptr, (size_t)cap_T);
+    }
+    return PS_OK;
+}
+int ps_debug_viterbi_steps(int32_t R, const int32_t* T, const double* obs, const double* rnd, int32_t nkeep, double skip, double stay,
+                           double mmin, double mmax, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
+    if (R < 0 || nkeep < 0 || (R && !T)) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi_steps");
+    const int np = std::max(nkeep, 1);
+    size_t t_off = 0;
+    for (int r = 0; r < R; r++) {
+        if (T[r] < 0 || (T[r] && (!obs || (nkeep && !rnd)))) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi_steps: bad region");
+        VTable S;
+        vit_start(S);
+        for (int t = 0; t < T[r]; t++) {
+            const double* row = obs + (t_off + t) * NS;
+            S.emplace_back(new VStep());
+            vstep(*S[S.size() - 2], std::vector<double>(row, row + NS), skip, stay, *S.back());
+        }
+        std::vector<std::vector<int>> pt;
+        const double* next = rnd ? rnd + (size_t)nkeep * t_off : nullptr;
+        if (T[r]) pt = vit_paths(S, nkeep, skip, stay, mmin, mmax, [&]() { return *next++; });
+        vit_export(S, pt, bp ? bp + t_off * NS : nullptr, lik_final ? lik_final + (size_t)r * NS : nullptr,
+                   fwd && nkeep ? fwd + t_off * NS : nullptr, paths ? paths + (size_t)np * t_off : nullptr, (size_t)T[r]);
+        t_off += T[r];
+    }
     return PS_OK;
 }
 int ps_srand(uint32_t seed) { srand(seed); return PS_OK; }

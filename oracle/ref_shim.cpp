@@ -221,6 +221,11 @@ int ps_debug_fill(ps_align* a, int32_t e, int32_t dir, double* main, double* sta
     al.backtrace();
     return PS_OK;
 }
+// (the reference keeps its Viterbi tables in locals of ViterbiMutate: no view of them)
+int ps_debug_viterbi(int32_t, ps_align* const*, int32_t, int32_t, double, double, double, double, int64_t, int32_t*, double*, int16_t*, double*,
+                     double*, int16_t*) { return PS_ERR_UNSUPPORTED; }
+int ps_debug_viterbi_steps(int32_t, const int32_t*, const double*, const double*, int32_t, double, double, double, double, int16_t*, double*,
+                           double*, int16_t*) { return PS_ERR_UNSUPPORTED; }
 int ps_srand(uint32_t seed) { srand(seed); return PS_OK; }
 int ps_rand_draw(int64_t n, double* out) { for (int64_t k = 0; k < n; k++) out[k] = rand() / (double(RAND_MAX) + 1); return PS_OK; }
 int ps_set_sweep_min(int32_t) { return PS_OK; }

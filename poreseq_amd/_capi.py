@@ -18,6 +18,7 @@ c_dp = C.POINTER(C.c_double)
 c_i32p = C.POINTER(C.c_int32)
 c_i64p = C.POINTER(C.c_int64)
 c_u8p = C.POINTER(C.c_uint8)
+c_i16p = C.POINTER(C.c_int16)
 
 
 class PsParams(C.Structure):
@@ -90,6 +91,10 @@ SYMBOLS = {
                                       C.POINTER(PsSwSummary)]),
     "ps_seq_to_states": (C.c_int, [C.c_char_p, C.c_int64, c_i32p, c_i64p]),
     "ps_debug_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_dp, c_dp, c_u8p, c_u8p]),
+    "ps_debug_viterbi": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_int64, c_i32p, c_dp, c_i16p, c_dp, c_dp, c_i16p]),
+    "ps_debug_viterbi_steps": (C.c_int, [C.c_int32, c_i32p, c_dp, c_dp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         c_i16p, c_dp, c_dp, c_i16p]),
     "ps_set_sweep_min": (C.c_int, [C.c_int32]),
     "ps_set_sweep2_min": (C.c_int, [C.c_int32]),
     "ps_set_sparse_min": (C.c_int, [C.c_int32]),
@@ -103,8 +108,9 @@ SYMBOLS = {
 
 
 # entry points of the header that a checker library (the oracle, the reference shim) may lack: CApi serves them from what the
-# library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents)
-OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences"])
+# library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents).
+# The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
+OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
 # entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
@@ -160,6 +166,10 @@ class CApi:
             msg = self.lib.ps_last_error()
             raise PoreseqError("%s failed (%d): %s" % (os.path.basename(self.path), rc,
                                                       msg.decode() if msg else "?"))
+
+    def _need(self, name):
+        if name in self.missing:
+            raise PoreseqError("%s does not export %s" % (os.path.basename(self.path), name))
 
     def backend_name(self):
         return self.lib.ps_backend_name().decode()
@@ -477,6 +487,48 @@ class CApi:
         self.check(self.lib.ps_debug_fill(h, ev, direction, _dp(main), _dp(stay),
                                           sm.ctypes.data_as(c_u8p), ss.ctypes.data_as(c_u8p)))
         return main, stay, sm, ss
+
+    def debug_viterbi(self, handles, cap_T, nkeep, skip, stay, mmin, mmax, obs_build=0):
+        """the tables of ViterbiMutate for a batch of AlignData (ps_debug_viterbi) -> per region a dict: T, obs [T][1024],
+        bp int16 [T][1024], lik_final [1024], fwd [T][1024] (None when nkeep == 0; rows up to their own scale), paths int16
+        [max(nkeep, 1)][T] (states)"""
+        self._need("ps_debug_viterbi")
+        n, cap, np_ = len(handles), int(cap_T), max(int(nkeep), 1)
+        T = np.zeros(max(n, 1), dtype=np.int32)
+        obs = np.zeros((n, cap, 1024))
+        bp = np.zeros((n, cap, 1024), dtype=np.int16)
+        lik = np.zeros((n, 1024))
+        fwd = np.zeros((n, cap, 1024)) if nkeep else None
+        paths = np.zeros((n, np_, cap), dtype=np.int16)
+        self.check(self.lib.ps_debug_viterbi(n, self._harr(handles), int(obs_build), int(nkeep), skip, stay, mmin, mmax, cap,
+                                             T.ctypes.data_as(c_i32p), _dp(obs), bp.ctypes.data_as(c_i16p), _dp(lik),
+                                             _dp(fwd) if nkeep else None, paths.ctypes.data_as(c_i16p)))
+        return [dict(T=int(T[r]), obs=obs[r, :T[r]].copy(), bp=bp[r, :T[r]].copy(), lik_final=lik[r].copy(),
+                     fwd=fwd[r, :T[r]].copy() if nkeep else None, paths=paths[r, :, :T[r]].copy()) for r in range(n)]
+
+    def debug_viterbi_steps(self, obs_rows, deviates, nkeep, skip, stay, mmin, mmax):
+        """the recursion and back-traces on given emission rows (ps_debug_viterbi_steps): obs_rows[r] is [T_r][1024], deviates[r]
+        [nkeep][T_r] (ignored when nkeep == 0) -> per region a dict as debug_viterbi's, without obs"""
+        self._need("ps_debug_viterbi_steps")
+        R, np_ = len(obs_rows), max(int(nkeep), 1)
+        rows = [_f64(o).reshape(-1, 1024) for o in obs_rows]
+        T = np.array([o.shape[0] for o in rows] + [0], dtype=np.int32)
+        off = np.concatenate([[0], np.cumsum(T[:R])]).astype(np.int64)
+        tt = int(off[R])
+        obs = _f64(np.concatenate(rows)) if R else np.zeros((0, 1024))
+        rnd = None
+        if nkeep:
+            rnd = _f64(np.concatenate([_f64(deviates[r]).reshape(nkeep, int(T[r])).ravel() for r in range(R)] + [np.zeros(1)]))
+        bp = np.zeros((max(tt, 1), 1024), dtype=np.int16)
+        lik = np.zeros((max(R, 1), 1024))
+        fwd = np.zeros((max(tt, 1), 1024)) if nkeep else None
+        paths = np.zeros(max(np_ * tt, 1), dtype=np.int16)
+        self.check(self.lib.ps_debug_viterbi_steps(R, T.ctypes.data_as(c_i32p), _dp(obs), _dp(rnd) if nkeep else None, int(nkeep),
+                                                   skip, stay, mmin, mmax, bp.ctypes.data_as(c_i16p), _dp(lik),
+                                                   _dp(fwd) if nkeep else None, paths.ctypes.data_as(c_i16p)))
+        return [dict(T=int(T[r]), bp=bp[off[r]:off[r + 1]].copy(), lik_final=lik[r].copy(),
+                     fwd=fwd[off[r]:off[r + 1]].copy() if nkeep else None,
+                     paths=paths[np_ * off[r]:np_ * off[r + 1]].reshape(np_, int(T[r])).copy()) for r in range(R)]
 
     def set_sweep_min(self, n):
         """forward-only batches of at least n alignments run one wavefront per alignment (negative: the default)"""

@@ -365,6 +365,24 @@ int ps_debug_fill(ps_align* a, int32_t e, int32_t dir, double* main, double* sta
     NEED_RT();
     return debug_fill(rt, &a->a, e, dir, main, stay, sm, ss);
 }
+int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t build, int32_t nkeep, double skip, double stay, double mmin, double mmax,
+                     int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (nkeep < 0 || build < 0 || build > 3 || cap_T < 0 || (n && !T)) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi");
+    for (Align* x : as) if (x->E == 0) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: no events");
+    NEED_RT();
+    return debug_viterbi(rt, as, build, nkeep, skip, stay, mmin, mmax, cap_T, T, obs, bp, lik_final, fwd, paths);
+}
+int ps_debug_viterbi_steps(int32_t R, const int32_t* T, const double* obs, const double* rnd, int32_t nkeep, double skip, double stay,
+                           double mmin, double mmax, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
+    if (R < 0 || nkeep < 0 || (R && !T)) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi_steps");
+    int64_t ttot = 0;
+    for (int r = 0; r < R; r++) { if (T[r] < 0) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi_steps: negative T"); ttot += T[r]; }
+    if (ttot && (!obs || (nkeep && !rnd))) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi_steps: null rows or deviates");
+    NEED_RT();
+    return debug_viterbi_steps(rt, R, T, obs, rnd, nkeep, skip, stay, mmin, mmax, bp, lik_final, fwd, paths);
+}
 
 int ps_srand(uint32_t seed) { rand_seed(seed); return PS_OK; }
 int ps_rand_draw(int64_t n, double* out) {

@@ -1,5 +1,7 @@
-// ps_debug.cpp — ps_debug_fill: dump one event's dense DP matrices (test hook).
+// ps_debug.cpp — the test hooks: ps_debug_fill dumps one event's dense DP matrices, ps_debug_viterbi /
+// ps_debug_viterbi_steps the tables of a ViterbiMutate call (VitTap, ps_internal.h).
 #include <cmath>
+#include <cstring>
 
 #include "ps_host.h"
 #include "ps_sweep_body.h"   // layout and predicate bits of the strip sweeps' code bytes
@@ -74,6 +76,77 @@ int debug_fill(Runtime* rt, Align* a, int ev, int dir, double* main, double* sta
             // back-pointer codes exist for the forward matrix only (nothing reads the backward ones)
             if (sm && dir == 0) sm[to] = (uint8_t)(flg[at] & 255);
             if (ss && dir == 0) ss[to] = (uint8_t)((flg[at] >> 8) & 7);   // bits 14/15 are the backtrace's sign flags
+        }
+    }
+    return PS_OK;
+}
+
+// ViterbiMutate of a batch of AlignData as ps_batch_viterbi_mutate runs it (vit_gather, emission kernel, steps, log, trace; deviates from
+// the calling thread's generator), with the device tables tapped.  Outputs per region at a row pitch of cap_T.
+int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
+                  int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
+    const int R = (int)as.size();
+    VitTap tap;
+    tap.obs_build = build;
+    std::vector<std::vector<std::string>> seqs(R);
+    std::vector<std::vector<std::string>*> outs(R);
+    for (int r = 0; r < R; r++) outs[r] = &seqs[r];
+    PS_TRY(viterbi_mutate_multi(rt, as, std::vector<RandState*>(R, nullptr), nkeep, skip, stay, mmin, mmax, outs, &tap));
+    for (int r = 0; r < R; r++) T[r] = tap.T[r];
+    for (int r = 0; r < R; r++) if (tap.T[r] > cap_T) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: a region has more positions than cap_T");
+    const int np = std::max(nkeep, 1);
+    size_t t_off = 0;
+    for (int r = 0; r < R; r++) {
+        const size_t n = (size_t)tap.T[r] * NS, to = (size_t)r * cap_T * NS;
+        if (obs && n) memcpy(obs + to, tap.obs.data() + t_off * NS, n * sizeof(double));
+        if (bp && n) memcpy(bp + to, tap.bp.data() + t_off * NS, n * sizeof(short));
+        if (fwd && n && !tap.fwd.empty()) memcpy(fwd + to, tap.fwd.data() + t_off * NS, n * sizeof(double));
+        if (lik_final) memcpy(lik_final + (size_t)r * NS, tap.lik_final.data() + (size_t)r * NS, NS * sizeof(double));
+        if (paths)
+            for (size_t k = 0; k < tap.paths[r].size(); k++)
+                for (int i = 0; i < tap.T[r]; i++) paths[((size_t)r * np + k) * cap_T + i] = (int16_t)tap.paths[r][k][i];
+        t_off += tap.T[r];
+    }
+    return PS_OK;
+}
+
+namespace {
+struct GivenDeviates { const double* next; };
+void draw_given(void* g, double* out, size_t n) {
+    GivenDeviates* d = (GivenDeviates*)g;
+    memcpy(out, d->next, n * sizeof(double));
+    d->next += n;
+}
+}  // namespace
+
+// k_vit_steps / k_vit_log / k_vit_trace as a production call launches them, on emission rows and deviates from the caller: only the
+// emission kernel is skipped.  Regions concatenated: obs / bp / fwd rows at t_off[r] = T[0] + .. + T[r - 1], deviates and paths as
+// [max(nkeep, 1)][T[r]] blocks at max(nkeep, 1) * t_off[r].
+int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs, const double* rnd, int nkeep, double skip, double stay,
+                        double mmin, double mmax, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
+    std::vector<VitRegionH> regs(R);
+    std::vector<GivenDeviates> giv(R);
+    size_t t_off = 0;
+    for (int r = 0; r < R; r++) {
+        regs[r].T = T[r];
+        giv[r].next = rnd ? rnd + (size_t)nkeep * t_off : nullptr;
+        regs[r].rng = &giv[r]; regs[r].draw = draw_given;
+        t_off += T[r];
+    }
+    VitTap tap;
+    tap.obs_rows = obs;
+    std::vector<std::vector<std::vector<int>>> pt;
+    PS_TRY(viterbi_device_multi(rt, regs, nkeep, skip, stay, mmin, mmax, &pt, &tap));
+    if (bp && !tap.bp.empty()) memcpy(bp, tap.bp.data(), tap.bp.size() * sizeof(short));
+    if (fwd && !tap.fwd.empty()) memcpy(fwd, tap.fwd.data(), tap.fwd.size() * sizeof(double));
+    if (lik_final) memcpy(lik_final, tap.lik_final.data(), (size_t)R * NS * sizeof(double));
+    if (paths) {
+        const int np = std::max(nkeep, 1);
+        t_off = 0;
+        for (int r = 0; r < R; r++) {
+            for (size_t k = 0; k < tap.paths[r].size(); k++)
+                for (int i = 0; i < T[r]; i++) paths[(size_t)np * t_off + k * T[r] + i] = (int16_t)tap.paths[r][k][i];
+            t_off += T[r];
         }
     }
     return PS_OK;

@@ -493,9 +493,9 @@ static void vit_draw(void* rng, double* rnd, size_t n) {
 }
 
 // ViterbiMutate (cpp/Viterbi.cpp:239-426) for several AlignData in lock-step; rngs[r] = the region's generator (nullptr: the
-// calling thread's)
+// calling thread's); tap: the device tables for ps_debug_viterbi (ps_internal.h), a null pointer otherwise
 int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
-                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs) {
+                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap) {
     Tick tk("viterbi_mutate");
     const int R = (int)as.size();
     for (int r = 0; r < R; r++) outs[r]->clear();
@@ -532,7 +532,7 @@ int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             double acc = 0;
             for (; k1 < regs.size(); k1++) { const double add = need(k1); if (k1 > k0 && acc + add > cap) break; acc += add; }
             std::vector<std::vector<std::vector<int>>> part;
-            const int rc = viterbi_device_multi(rt, std::vector<VitRegionH>(regs.begin() + k0, regs.begin() + k1), nkeep, skip, stay, mmin, mmax, &part);
+            const int rc = viterbi_device_multi(rt, std::vector<VitRegionH>(regs.begin() + k0, regs.begin() + k1), nkeep, skip, stay, mmin, mmax, &part, tap);
             if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { cap *= 0.5; continue; }   // (nothing of this sub-batch has been drawn yet: allocation comes first)
             PS_TRY(rc);
             for (auto& pr : part) paths.push_back(std::move(pr));

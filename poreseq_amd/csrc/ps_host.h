@@ -141,7 +141,7 @@ size_t fwd_chunk_end(const std::vector<FwdUnit>& units, size_t q0, double cap, i
 int score_sequences_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seqs,
                           const std::vector<double*>& scores, const std::vector<double*>& accuracy);
 int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
-                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs);
+                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap = nullptr);
 std::string info_string();   // process-wide state in one line (ps_info)
 struct MemInfo { size_t slabs = 0, slab_bytes = 0; int slabs_planned = 0; long long pool_bytes = 0; };
 MemInfo mem_info();          // ps_mem.cpp's part of it: slabs allocated (and their bytes) of how many, bytes in the pools of this process
@@ -173,6 +173,11 @@ int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds,
 int viterbi_mutate(Runtime* rt, Align* a, int nkeep, double skip, double stay, double mmin, double mmax,
                    std::vector<std::string>* out, bool verbose = false);
 int debug_fill(Runtime* rt, Align* a, int ev, int dir, double* main, double* stay, uint8_t* sm, uint8_t* ss);
+// ps_debug_viterbi / ps_debug_viterbi_steps (include/poreseq_hip.h): the tables of a ViterbiMutate call
+int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
+                  int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths);
+int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs, const double* rnd, int nkeep, double skip, double stay,
+                        double mmin, double mmax, int16_t* bp, double* lik_final, double* fwd, int16_t* paths);
 
 }  // namespace ps
 #endif

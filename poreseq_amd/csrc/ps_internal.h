@@ -271,8 +271,21 @@ struct VitRegionH {
     void* rng = nullptr;                 // the region's generator state, handed to draw()
     void (*draw)(void* rng, double* out /*[nkeep][T]*/, size_t n) = nullptr;
 };
+// Table tap of viterbi_device_multi for the test hooks ps_debug_viterbi / ps_debug_viterbi_steps (ps_debug.cpp): a null pointer in
+// production.  The same launches, grids and buffers run whether it is set or not; with a tap the tables are also copied to the
+// host.  Results are appended (viterbi_mutate_multi may cut a batch into several device calls), regions in batch order.
+struct VitTap {
+    int obs_build = 0;                  // in: emission build: 0 the library's choice, 1 k_vit_obs_lds, 2 k_vit_obs<64>, 3 k_vit_obs<256>
+    const double* obs_rows = nullptr;   // in: [sum T][1024] emission rows from the caller; the emission kernel is skipped, exp(obs) is formed on the host
+    std::vector<int> T;                 // per region
+    std::vector<double> obs;            // [sum T][1024]
+    std::vector<short> bp;              // [sum T][1024]
+    std::vector<double> lik_final;      // [regions][1024]
+    std::vector<double> fwd;            // [sum T][1024] as k_vit_steps wrote it, before k_vit_log (nkeep > 0 only: no forward table otherwise)
+    std::vector<std::vector<std::vector<int>>> paths;   // per region [nkeep or 1][T] states
+};
 int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, int nkeep, double skip, double stay, double mmin, double mmax,
-                         std::vector<std::vector<std::vector<int>>>* paths);
+                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap = nullptr);
 
 void prof_flush(Runtime* rt);   // deferred mode: read the queued event pairs (drains the stream)
 void prof_begin(Runtime* rt);

@@ -14,8 +14,9 @@
 //                the uniform deviates are drawn on the host from libc rand() in the reference's
 //                call order.
 // Max-plus values (liks, back-pointers) are bit-exact; forward probabilities use device exp / log
-// (fwd^atten as exp(atten * log fwd)) and tree sums, i.e. agree to a few ulp; they only weight the
-// random back-traces.
+// (fwd^atten as exp(atten * log fwd)) and tree sums: measured against a long-double recursion they stay within
+// 4x the error of the reference's own serial float64 sums (tests/test_hip_viterbi_tables.py has the figures);
+// they only weight the random back-traces.
 #include <atomic>
 
 #include "ps_internal.h"
@@ -188,8 +189,12 @@ __device__ __forceinline__ double below(double x) {
 //
 // Forward probabilities: the reference renormalises the 1024-vector after every step
 // (normvec, cpp/Viterbi.cpp:101).  Only ratios within one step's vector are ever used (randbp
-// renormalises its own products), so here the vector is rescaled every 8 steps by an exact power of
-// two: it stays in range, no rounding is added, and no reduce -> divide chain sits on the step path.
+// renormalises its own products), so here every step's vector is scaled by an exact power of two
+// taken from the PREVIOUS step's total: no rounding is added and no reduce -> divide chain sits on the
+// step path.  The stored vector therefore carries one step's growth (its total is the step's mean
+// emission weight times a factor in [1/2, 1)), and the scale is applied to the sum before the emission
+// weight, so a row survives whenever exp(obs) itself does: like the reference, whose fs * exp(obs)
+// dies only where exp(obs) underflows.
 __global__ __launch_bounds__(1024) void k_vit_steps(const VitReg* __restrict__ regs, const double* __restrict__ obs_all, const double* __restrict__ eobs_all,
                                                     double skip, double stay, double lskip, double lstay, double l25,
                                                     short* __restrict__ bp_all, double* __restrict__ lfwd_all,
@@ -211,6 +216,7 @@ __global__ __launch_bounds__(1024) void k_vit_steps(const VitReg* __restrict__ r
     s_lik[0][VPAD(c)] = 0.0;
     s_fwd[0][VPAD(c)] = 1.0 / NS;
     if (c == 0) s_scale = 1.0;
+    if (c < 16) s_red[c] = 1.0 / 16;   // the start vector's total
     __syncthreads();
     const double sp1 = 0.25, sp2 = sp1 * 0.25 * skip, sp3 = sp2 * 0.25 * skip;
     const double lsp1 = l25, lsp2 = lsp1 + l25 + lskip, lsp3 = lsp2 + l25 + lskip;
@@ -235,7 +241,6 @@ __global__ __launch_bounds__(1024) void k_vit_steps(const VitReg* __restrict__ r
     auto vit_one = [&](const int t, const double o, const double eo) {
         const double* pl = s_lik[cur];
         const double* pf = s_fwd[cur];
-        const bool rescale = (t & 7) == 7;
         if (fj) {
             Fam m[4];
 #pragma unroll
@@ -248,13 +253,14 @@ __global__ __launch_bounds__(1024) void k_vit_steps(const VitReg* __restrict__ r
             if (fj == 3) { f = fam_join(f, fam_shl<4>(f)); f = fam_join(f, fam_shl<8>(f)); }
             const bool writer = fj == 1 || (fj == 2 && (c & 3) == 0) || (fj == 3 && (c & 15) == 0);
             if (writer) s_fam[(fj == 1 ? 0 : fj == 2 ? 256 : 320) + fg] = f;
-        } else if (c == 1023 && rescale) {
-            // the vector written at the end of this step is divided by 2^e, e from the previous total
+        } else if (c == 1023) {
+            // the vector written at the end of this step is divided by 2^e, e from the previous step's total (a total of 0 has
+            // e = 0; the clamp keeps the factor finite for a subnormal one)
             double ptot = 0.0;
             for (int w = 0; w < 16; w++) ptot += s_red[w];
             int ex;
             frexp(ptot, &ex);
-            s_scale = ldexp(1.0, -ex);
+            s_scale = ldexp(1.0, min(-ex, 1000));
         }
         PS_LDS_BARRIER();
         double best = -BIG; int bq = -1; double fsum = 0.0;
@@ -280,9 +286,8 @@ __global__ __launch_bounds__(1024) void k_vit_steps(const VitReg* __restrict__ r
             if (l > best) { best = l; bq = c; }
             fsum += stay * pf[VPAD(c)];
         }
-        double nf = fsum * eo;
-        if (rescale) nf *= s_scale;
-        if ((t & 7) == 6) {   // totals for the next rescale, one step ahead of their use
+        const double nf = (fsum * s_scale) * eo;
+        {   // totals for the next step's scale
             const double wsum = wave_sum(nf);
             if (lane == 0) s_red[wave] = wsum;
         }
@@ -410,7 +415,7 @@ __global__ __launch_bounds__(VT_THREADS) void k_vit_trace(const VitReg* __restri
 }
 
 int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, int nkeep, double skip, double stay, double mmin, double mmax,
-                         std::vector<std::vector<std::vector<int>>>* paths) {
+                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap) {
     const int R = (int)regions.size();
     paths->assign(R, {});
     std::vector<VitReg> regs(R);
@@ -422,6 +427,8 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
         intot += (int64_t)regions[r].T * regions[r].E * 4; ttot += regions[r].T;
         maxE = std::max(maxE, regions[r].E);
     }
+    if (tap)
+        for (int r = 0; r < R; r++) { tap->T.push_back(regions[r].T); tap->paths.emplace_back(); tap->lik_final.insert(tap->lik_final.end(), NS, 0.0); }
     if (ttot <= 0) return PS_OK;
     if (maxE > 256) return fail(PS_ERR_UNSUPPORTED, "ViterbiMutate: more than 256 events");
     std::vector<int> pos_reg((size_t)ttot);
@@ -456,8 +463,7 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
     PS_TRY(rt->up(d_regs, regs.data(), R * sizeof(VitReg)));
     PS_TRY(rt->up(d_posreg, pos_reg.data(), (size_t)ttot * sizeof(int)));
     for (int r = 0; r < R; r++)
-        if (regions[r].T) PS_TRY(rt->up(d_in + regs[r].in_off, regions[r].obsin, (size_t)regions[r].T * regions[r].E * 4 * sizeof(double)));
-    prof_begin(rt);
+        if (regions[r].T && regions[r].E) PS_TRY(rt->up(d_in + regs[r].in_off, regions[r].obsin, (size_t)regions[r].T * regions[r].E * 4 * sizeof(double)));
     bool lds_ok = false;
     if (maxE <= 72) {   // the LDS column sort needs 144 KB of dynamic LDS at 72 events: when the attribute cannot be had, the register / scratch kernels below serve
         static std::atomic<int> attr(0);   // 0: untried, 1: granted, -1: refused
@@ -468,16 +474,36 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
         }
         lds_ok = attr.load(std::memory_order_acquire) == 1;
     }
-    if (lds_ok)
+    // emission build: 1 k_vit_obs_lds, 2 k_vit_obs<64>, 3 k_vit_obs<256>; a tap may ask for one that admits the batch's events
+    int build = lds_ok ? 1 : maxE <= 64 ? 2 : 3;
+    if (tap && tap->obs_build) {
+        build = tap->obs_build;
+        if (build < 1 || build > 3 || (build == 1 && !lds_ok) || (build == 2 && maxE > 64))
+            return fail(PS_ERR_BAD_ARG, "ViterbiMutate: the emission build asked for does not take this many events");
+    }
+    prof_begin(rt);
+    if (tap && tap->obs_rows) {   // rows from the caller instead of the emission kernel (ps_debug_viterbi_steps)
+        std::vector<double> eo((size_t)ttot * NS);
+        for (size_t k = 0; k < eo.size(); k++) eo[k] = std::exp(tap->obs_rows[k]);
+        PS_TRY(rt->up(d_obs, tap->obs_rows, eo.size() * sizeof(double)));
+        PS_TRY(rt->up(d_eobs, eo.data(), eo.size() * sizeof(double)));
+    } else if (build == 1)
         hipLaunchKernelGGL(k_vit_obs_lds, dim3((unsigned)ttot), dim3(256), (size_t)256 * std::max(maxE, 1) * sizeof(double), rt->stream, d_regs, d_posreg, d_in,
                            std::log(2 * M_PI), d_obs, d_eobs);
-    else if (maxE <= 64) hipLaunchKernelGGL(k_vit_obs<64>, dim3((unsigned)ttot), dim3(256), 0, rt->stream, d_regs, d_posreg, d_in, std::log(2 * M_PI), d_obs, d_eobs);
+    else if (build == 2) hipLaunchKernelGGL(k_vit_obs<64>, dim3((unsigned)ttot), dim3(256), 0, rt->stream, d_regs, d_posreg, d_in, std::log(2 * M_PI), d_obs, d_eobs);
     else hipLaunchKernelGGL(k_vit_obs<256>, dim3((unsigned)ttot), dim3(256), 0, rt->stream, d_regs, d_posreg, d_in, std::log(2 * M_PI), d_obs, d_eobs);
     hipLaunchKernelGGL(k_vit_steps, dim3(R), dim3(1024), 0, rt->stream, d_regs, d_obs, d_eobs, skip, stay, std::log(skip), std::log(stay),
                        std::log(0.25), d_bp, d_fwd, d_lik, nkeep ? 1 : 0);
     PS_LAUNCH_CHECK();
     double* lik = nullptr;
     PS_TRY(rt->down(&lik, d_lik, (size_t)R * NS));
+    double *tap_obs = nullptr, *tap_fwd = nullptr;
+    short* tap_bp = nullptr;
+    if (tap) {   // the tables as the kernels left them: the forward vectors before k_vit_log overwrites them
+        PS_TRY(rt->down(&tap_obs, d_obs, (size_t)ttot * NS));
+        PS_TRY(rt->down(&tap_bp, d_bp, (size_t)ttot * NS));
+        if (nkeep > 0) PS_TRY(rt->down(&tap_fwd, d_fwd, (size_t)ttot * NS));
+    }
     // the uniform deviates of the stochastic back-traces are drawn on the host while the recursion runs: per region in the
     // reference's call order (for each kept path, one per back-step, cpp/Viterbi.cpp:108) from the region's own generator
     double* h_rand = nullptr;
@@ -487,6 +513,13 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
         for (int r = 0; r < R; r++) regions[r].draw(regions[r].rng, h_rand + (size_t)nkeep * regs[r].t_off, (size_t)nkeep * regions[r].T);
     }
     PS_HIP(hipStreamSynchronize(rt->stream));
+    if (tap) {
+        tap->obs.insert(tap->obs.end(), tap_obs, tap_obs + (size_t)ttot * NS);
+        tap->bp.insert(tap->bp.end(), tap_bp, tap_bp + (size_t)ttot * NS);
+        if (tap_fwd) tap->fwd.insert(tap->fwd.end(), tap_fwd, tap_fwd + (size_t)ttot * NS);
+        for (int r = 0; r < R; r++)   // (a region without positions keeps its zeros: k_vit_steps writes nothing for it)
+            if (regions[r].T) std::copy(lik + (size_t)r * NS, lik + (size_t)(r + 1) * NS, tap->lik_final.end() - (size_t)(R - r) * NS);
+    }
     std::vector<int> starts(R, 0);
     for (int r = 0; r < R; r++) starts[r] = (int)(std::max_element(lik + (size_t)r * NS, lik + (size_t)(r + 1) * NS) - (lik + (size_t)r * NS));
     if (nkeep == 0) {
@@ -501,6 +534,7 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
             for (int i = regions[r].T - 1; i >= 0; i--) { p[i] = c; c = bp[((size_t)regs[r].t_off + i) * NS + c]; }
             (*paths)[r].push_back(p);
         }
+        if (tap) std::copy(paths->begin(), paths->end(), tap->paths.end() - R);
         return PS_OK;
     }
     std::vector<double> att(nkeep);
@@ -526,6 +560,7 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
             (*paths)[r].push_back(p);
         }
     }
+    if (tap) std::copy(paths->begin(), paths->end(), tap->paths.end() - R);
     return PS_OK;
 }
 
