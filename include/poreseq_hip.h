@@ -145,6 +145,26 @@ int ps_make_mutations(ps_align* a, const ps_muts* scored, int32_t* n_bases);
  * accuracy may be NULL.  Sequences as a CSR string pool, as ps_find_mutations takes its seeds. */
 int ps_score_sequences(ps_align* a, int32_t n_seqs, const int64_t* seq_off, const char* seq_pool, double* scores, double* accuracy);
 
+/* The scores of ScorePoints (_poreseqcpp.pyx:278-308, `poreseq variant -a`, Variant.py:77-78) as a table per position instead of a
+ * scored list: FindPointMutations' list (cpp/FindMutations.cpp:200-228) is scored as by ps_score_mutations — at the scoring width the
+ * AlignData carries, events re-aligned as a side effect — and reduced on the device.  A sequence of L bases has n = max(L - 4, 0)
+ * positions (the states of cpp/Sequence.h:64-100): FindPointMutations walks those, the last four bases have no row.
+ *   table[p * 9 + slot]   slot 0: deletion of base p; 1-4: substitution by A / C / G / T; 5-8: insertion of A / C / G / T in front of
+ *                         it.  Each entry is the score ScoreMutations gives that edit: -1e-6 plus the events' terms added in event
+ *                         order (cpp/AlignUtil.h:86, cpp/MakeMutations.cpp:51), bit for bit.  The substitution by the base itself
+ *                         is not in the list (cpp/FindMutations.cpp:208-216): its slot holds a quiet NaN.  A base that is none of
+ *                         A / C / G / T has all four substitutions.
+ *   best[p]               margin: the largest non-NaN entry of the row (the support of the best single-base alternative against the
+ *                         called base); slot: the FIRST slot, in slot order, that holds it; n_positive: the row's entries > 0.
+ * n must be the AlignData's position count (PS_ERR_BAD_ARG otherwise).  Either output may be NULL: it is then neither produced nor
+ * copied back.  One call returns all its results in one device-to-host copy. */
+typedef struct ps_point_best {
+    double margin;
+    int32_t slot;
+    int32_t n_positive;
+} ps_point_best;
+int ps_point_table(ps_align* a, double* table /* [n][9] or NULL */, ps_point_best* best /* [n] or NULL */, int64_t n);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -184,6 +204,9 @@ int ps_batch_make_mutations(int32_t n, ps_align* const* a, const ps_muts* const*
 /* `poreseq variant -v` for every AlignData: seqs[i] are the candidate sequences of AlignData i (ps_seqs_create), scores[i] has
  * count(seqs[i]) * n_events(i) doubles and accuracy[i] (or the whole array) may be NULL: ps_score_sequences for all of them in one chain. */
 int ps_batch_score_sequences(int32_t n, ps_align* const* a, const ps_seqs* const* seqs, double* const* scores, double* const* accuracy);
+/* ps_point_table for every AlignData in one launch chain (the dense ScoreMutations path of Refine) and ONE copy back: table[i] is NULL
+ * or [n[i]][9], best[i] NULL or [n[i]] (either array itself may be NULL), n[i] the position count of AlignData i. */
+int ps_batch_point_table(int32_t n_regions, ps_align* const* a, double* const* table, ps_point_best* const* best, const int64_t* n);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -265,7 +288,7 @@ int ps_set_device_fraction(double fraction);
 
 /* Hot-kernel instrumentation for bench.py: accumulated HIP-event time (ms), launches and
  * algorithmic bytes of the named kernel class ("fill" = k_fill, "sweep" = the strip sweeps k_sweep / k_sweeps / k_sweep2 and their _w builds,
- * "score", "viterbi", "sw") since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab";
+ * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab";
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =
  * alignment chunks (launches) over distinct sequences (units) of ps_score_sequences. */
 /* ps_prof_enable(1) makes every hot-kernel launch be bracketed by HIP events on the library's stream

@@ -33,6 +33,16 @@ class PsSwSummary(C.Structure):
                [("accuracy", C.c_double)]
 
 
+class PsPointBest(C.Structure):
+    # ps_point_best, include/poreseq_hip.h
+    _fields_ = [("margin", C.c_double), ("slot", C.c_int32), ("n_positive", C.c_int32)]
+
+
+# the same record as a numpy dtype (16 bytes, no padding): what point_table / batch_point_table hand out
+POINT_BEST = np.dtype([("margin", np.float64), ("slot", np.int32), ("n_positive", np.int32)])
+POINT_SLOTS = 9   # deletion, substitution by A / C / G / T, insertion of A / C / G / T
+
+
 class PoreseqError(Exception):
     pass
 
@@ -72,6 +82,8 @@ SYMBOLS = {
     "ps_batch_score_sequences": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_dp), C.POINTER(c_dp)]),
     "ps_score_mutation_deltas": (C.c_int, [C.c_void_p, C.c_void_p, c_dp]),
     "ps_make_mutations": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p]),
+    "ps_point_table": (C.c_int, [C.c_void_p, c_dp, C.POINTER(PsPointBest), C.c_int64]),
+    "ps_batch_point_table": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_dp), C.POINTER(C.POINTER(PsPointBest)), c_i64p]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -108,9 +120,11 @@ SYMBOLS = {
 
 
 # entry points of the header that a checker library (the oracle, the reference shim) may lack: CApi serves them from what the
-# library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents).
+# library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents;
+# PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps"])
+OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
+                      "ps_point_table", "ps_batch_point_table"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
 # entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
@@ -331,6 +345,25 @@ class CApi:
         if out.size:
             self.check(self.lib.ps_score_mutation_deltas(h, hm, _dp(out)))
         return out
+
+    def point_table(self, h, n, want_table=True):
+        """-> (table float64 [n, 9] or None, best POINT_BEST [n]): ps_point_table of one AlignData with n positions"""
+        return self.batch_point_table([h], [n], want_table)[0]
+
+    def batch_point_table(self, hs, ns, want_table=True):
+        """ps_batch_point_table over the AlignData `hs` with ns[i] positions each, one launch chain and one copy back ->
+        [(table float64 [n, 9] or None, best POINT_BEST [n])]: slot 0 the deletion, 1-4 substitution by A / C / G / T (NaN for the
+        base itself), 5-8 insertion; best['margin'] the row's largest entry, ['slot'] the first slot holding it, ['n_positive']
+        the entries > 0."""
+        self._need("ps_batch_point_table")
+        R = len(hs)
+        ns = np.array([int(n) for n in ns] + [0], dtype=np.int64)
+        tables = [np.empty((int(n), POINT_SLOTS), dtype=np.float64) if want_table else None for n in ns[:R]]
+        bests = [np.empty(int(n), dtype=POINT_BEST) for n in ns[:R]]
+        tp = (c_dp * max(R, 1))(*[_dp(t) for t in tables]) if want_table else None
+        bp = (C.POINTER(PsPointBest) * max(R, 1))(*[b.ctypes.data_as(C.POINTER(PsPointBest)) for b in bests])
+        self.check(self.lib.ps_batch_point_table(R, self._harr(hs), tp, bp, ns.ctypes.data_as(c_i64p)))
+        return list(zip(tables, bests))
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

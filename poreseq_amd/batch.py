@@ -159,6 +159,24 @@ class RegionBatch:
             poreseqcpp._check_realign_accuracy(acc)
         return [sc for sc, _ in res]
 
+    def PointTable(self, idx=None, table=True):
+        """PSAlign.PointTable for the regions `idx` on their resident AlignData: ONE ps_batch_point_table call — the dense scoring
+        chain of Refine over all regions, reduced on the device, one copy back.  Returns one (table or None, margin, slot,
+        n_positive) per region; sequences and the Python events are not modified (the resident events are re-aligned, as by
+        every ScoreMutations call)."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        if "ps_batch_point_table" in self.api.missing:
+            return [self.pas[i].PointTable(table) for i in idx]
+        hs = self._open(idx, point_width=True)
+        try:
+            ns = [max(int(self.api.lib.ps_align_sequence_length(h)) - 4, 0) for h in hs]
+            res = self.api.batch_point_table(hs, ns, want_table=table)
+        finally:
+            self._close(idx, hs, write_back=False)
+        return [(tb, b["margin"].copy(), b["slot"].copy(), b["n_positive"].copy()) for tb, b in res]
+
     def Mutate(self, idx=None, seqs='self', reps=4):
         """PSAlign.Mutate (pyx:378-435) for the regions `idx`; returns {region index: total mutated bases}."""
         idx = list(range(len(self.pas))) if idx is None else list(idx)

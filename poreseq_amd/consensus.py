@@ -4,6 +4,7 @@
   consensus_region  <- poreseq/Mutate.py:8-101   (Mutate('self') then {Mutate('viterbi'), Refine()})
   test_start        <- poreseq/Mutate.py:59-65   (`test`: start from the read that spans the most of the draft)
   variant_region    <- poreseq/Variant.py:66-95  (ScoreMutations / ScorePoints with start offsetting)
+  variant_points    <- poreseq/Variant.py:77-93  (`variant -a`: every point edit of one or many regions, as tables from one lock-step call)
   variant_sequences <- poreseq/Variant.py:48-63  (`variant -v`: whole candidate sequences, one batched ScoreSequences call)
   split_regions     <- poreseq/split_fasta.py:94-101 (max_length pieces with 1 kb overlap)
 
@@ -15,6 +16,7 @@ import sys
 import numpy as np
 
 from . import poreseqcpp
+from .util import phred_from_margin
 
 
 def _report(verbose, text):
@@ -40,7 +42,7 @@ def test_start(events, refseq, summaries):
     return seq, chosen
 
 
-def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False):
+def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None):
     """Run the consensus schedule in place on `pa`; returns (sequence, accuracy_vs_refseq).
 
     The call sequence is the reference's (Mutate.py:39-101) and has to be: a region with fewer than 5 events is handed
@@ -51,6 +53,10 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     `test` (Mutate.py:45-46, 59-68; `poreseq consensus -T`, and `poreseq train` unless --descend): the loaded sequence is thrown
     away and the schedule starts from `test_start`'s pick among the reads' own sequences, WITHOUT realignment — the events keep
     the ref_align they were loaded with; the accuracy is still taken against the loaded sequence.  It turns `verbose` 0 into 1.
+    `qualities`, when given, is a list to which one entry is appended: the uint8 per-base qualities of the RETURNED sequence
+    (util.phred_from_margin of one PointTable pass after the schedule's last call, cut by the same `end_trim` slice; uncalibrated),
+    or None for a region handed back untouched.  The pass changes nothing else: sequence, accuracy, log and the events' ref_align /
+    ref_like are what they are without it, and it draws no random numbers.
     """
     params = pa.params if params is None else params
     pa.params.setdefault('verbose', 0)
@@ -60,6 +66,8 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
         verbose = 1
     if len(pa.events) < 5:
         _report(verbose, "fewer than 5 events: region returned as loaded")
+        if qualities is not None:
+            qualities.append(None)
         return (refseq, 100)
     _report(verbose, "refining %d bases with %d events" % (len(refseq), len(pa.events)))
     if test:
@@ -84,9 +92,16 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
             _report(verbose, "identity: %.1f%%" % identity(pa.sequence, refseq)[0])
         if changed == 0:
             break
+    qual = None
+    if qualities is not None:
+        qual = phred_from_margin(pa.PointTable(table=False)[1], len(pa.sequence))
     trim = int(params['end_trim']) if 'end_trim' in params else 0
     if 'end_trim' in params and len(pa.sequence) > 2 * params['end_trim']:
         pa.sequence = pa.sequence[trim:-trim]
+        if qual is not None:
+            qual = qual[trim:-trim]
+    if qualities is not None:
+        qualities.append(qual)
     acc, pairs = identity(pa.sequence, refseq)
     if verbose > 0:
         gaps = np.sum(np.array(pairs) == 0, 0)
@@ -95,7 +110,8 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     return (pa.sequence, acc)
 
 
-def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True, test=False, accuracies=None):
+def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True, test=False, accuracies=None,
+                      qualities=None):
     """The consensus schedule of `consensus_region` for several independent regions in lock-step (poreseq_amd.batch):
     every PSAlign call of the schedule is issued once for all regions that still take part in it, so each phase is one
     launch chain on the GPU.  Returns [(sequence, accuracy)] in the order of `pas`; each entry equals what
@@ -108,11 +124,16 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
     `accuracies`, when given, is a list of lists receiving per region the identity against its refseq after Mutate('self') and
     after every Refine (the "Accuracy:" lines of Mutate.py:72-83), each round's values from one batched call over the live regions.
     The final accuracies likewise come from one batched call.
+    `qualities`, when given, is a list that is set to one entry per region, in the order of `pas`: the uint8 per-base qualities of the
+    returned sequence (see consensus_region), None for a region with fewer than 5 events.  They come from ONE lock-step
+    RegionBatch.PointTable(table=False) over all refined regions after the schedule's last call; everything else the function returns
+    or writes is bit for bit what it is without `qualities`.
     """
     from .batch import RegionBatch
     n = len(pas)
     refseqs = [pa.sequence for pa in pas] if refseqs is None else list(refseqs)
     out = [None] * n
+    quals = [None] * n
     todo = []
     for i, pa in enumerate(pas):
         if 'verbose' not in pa.params:
@@ -166,14 +187,25 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
                     note(i, "Refine", nb[i])
                 identities(live)
                 live = [i for i in live if nb[i] != 0]
+            if qualities is not None:
+                # the pass re-aligns the resident events like every ScoreMutations call: what the schedule left is written back
+                # first, and the handles are forgotten afterwards, so that closing the batch writes nothing of it
+                rb.sync(todo)
+                for i, (_, margin, _, _) in zip(todo, rb.PointTable(todo, table=False)):
+                    quals[i] = phred_from_margin(margin, len(pas[i].sequence))
+                rb.drop(todo)
         for i in todo:
             pa = pas[i]
             p = pa.params if params is None else params
             if 'end_trim' in p and len(pa.sequence) > 2 * p['end_trim']:
                 pa.sequence = pa.sequence[int(p['end_trim']):-int(p['end_trim'])]
+                if quals[i] is not None:
+                    quals[i] = quals[i][int(p['end_trim']):-int(p['end_trim'])]
         final = poreseqcpp.swalign_summaries([(pas[i].sequence, refseqs[i]) for i in todo], api)
         for i, s in zip(todo, final):
             out[i] = (pas[i].sequence, s.accuracy)
+    if qualities is not None:
+        qualities[:] = quals
     return out
 
 
@@ -188,6 +220,42 @@ def variant_region(pa, muts, region_start=0, params=None, out=None):
         if out is not None:
             out.write(str(ms) + '\n')
     return mutscores
+
+
+def variant_points(pas, region_starts=None, params=None, out=None):
+    """`poreseq variant -a` (Variant.py:77-93: every single-base deletion, substitution and insertion at every position) for one
+    PSAlign or a list of them, all regions through ONE lock-step RegionBatch.PointTable call.  Returns (tables, percent): tables[r] =
+    (table, margin, slot, n_positive) of region r as PSAlign.PointTable returns them, percent[r] the reference's '% positive
+    variants' figure (Variant.py:80-93): the edits with a score > 0 among those with end_trim < start < len(sequence) - end_trim,
+    in % (NaN when there are none).  With `out`, the lines that `variant_region(pa, [], region_starts[r], out=out)` writes are
+    written region by region, in the reference's order — per position the deletion, the substitutions, the insertions, as
+    str(MutationScore) with absolute starts — straight from the table.  No PSAlign is modified."""
+    from .batch import RegionBatch
+    single = isinstance(pas, poreseqcpp.PSAlign)
+    pas = [pas] if single else list(pas)
+    starts = [0] * len(pas) if region_starts is None else ([region_starts] if single else list(region_starts))
+    if not pas:
+        return [], []
+    with RegionBatch(pas, resident=False) as rb:   # (not resident: nothing of the pass is written back to the PSAlign objects)
+        tables = rb.PointTable(table=True)
+    percent = []
+    for pa, start0, (table, _margin, _slot, npos) in zip(pas, starts, tables):
+        p = pa.params if params is None else params
+        trim = p.get('end_trim', 0)
+        pos = np.arange(table.shape[0])
+        inside = (pos > trim) & (pos < len(pa.sequence) - trim)
+        ntot = int(np.count_nonzero(~np.isnan(table[inside])))
+        percent.append(100 * float(np.sum(npos[inside])) / ntot if ntot else float('nan'))
+        if out is not None:
+            dot = lambda c: c if len(c) else '.'
+            lines = []
+            for i, row in enumerate(table.tolist()):
+                base, at = dot(pa.sequence[i]), i + start0
+                lines.append('{}\t{}\t.\t{}\n'.format(at, base, row[0]))
+                lines.extend('{}\t{}\t{}\t{}\n'.format(at, base, 'ACGT'[k], row[1 + k]) for k in range(4) if 'ACGT'[k] != pa.sequence[i])
+                lines.extend('{}\t.\t{}\t{}\n'.format(at, 'ACGT'[k], row[5 + k]) for k in range(4))
+            out.write(''.join(lines))
+    return tables, percent
 
 
 def variant_sequences(pa, variants, out=None):

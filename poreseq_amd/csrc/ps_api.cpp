@@ -274,6 +274,27 @@ int ps_batch_score_mutations(int32_t n, ps_align* const* a, const ps_muts* const
     for (int i = 0; i < n; i++) out[i] = m[i].release();
     return PS_OK;
 }
+int ps_batch_point_table(int32_t n_regions, ps_align* const* a, double* const* table, ps_point_best* const* best, const int64_t* n) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n_regions, a, &as));
+    if (n_regions && !n) return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: null position counts");
+    std::vector<double*> tb(n_regions);
+    std::vector<ps_point_best*> bs(n_regions);
+    for (int i = 0; i < n_regions; i++) {
+        const int64_t have = (int64_t)as[i]->states.size();
+        if (n[i] != have)
+            return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: region " + std::to_string(i) + " was given n = " + std::to_string(n[i]) + ", its sequence has " +
+                                        std::to_string(have) + " positions (length - 4)");
+        tb[i] = table ? table[i] : nullptr; bs[i] = best ? best[i] : nullptr;
+    }
+    if (!n_regions) return PS_OK;
+    NEED_RT();
+    return point_table_multi(rt, as, tb, bs);
+}
+int ps_point_table(ps_align* a, double* table, ps_point_best* best, int64_t n) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_point_table: null handle");
+    return ps_batch_point_table(1, &a, &table, &best, &n);
+}
 int ps_batch_make_mutations(int32_t n, ps_align* const* a, const ps_muts* const* scored, int32_t* n_bases) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

@@ -596,6 +596,32 @@ static void edited_window(const std::string& b, const Mut& m, int sidx, int ncol
     }
 }
 
+// Where FindPointMutations' list (cpp/FindMutations.cpp:200-228) keeps each position's edits: first[p] is the index of position p's
+// deletion, followed by its substitutions in ACGT order without the one by the base itself, then the four insertions — 8 edits for an
+// A / C / G / T base, 9 for any other character; first[n] = the length of the list.  triv[p]: table slot 1 .. 4 of the substitution
+// that is not in the list, 0 when all four are.
+static void point_layout(const Align* a, std::vector<int>* first, std::vector<int>* triv) {
+    const size_t n = a->states.size();
+    first->resize(n + 1); triv->resize(n);
+    int m = 0;
+    for (size_t i = 0; i < n; i++) {
+        const char c = a->bases[i];
+        const int t = c == 'A' ? 1 : c == 'C' ? 2 : c == 'G' ? 3 : c == 'T' ? 4 : 0;
+        (*first)[i] = m; (*triv)[i] = t;
+        m += t ? 8 : 9;
+    }
+    (*first)[n] = m;
+}
+
+// the rows of an AlignData without events: every edit keeps the seed of its sum, -1e-6 (cpp/AlignUtil.h:86)
+static void point_rows_seed(const std::vector<int>& triv, double* table, ps_point_best* best) {
+    for (size_t p = 0; p < triv.size(); p++) {
+        if (table)
+            for (int q = 0; q < PT_SLOTS; q++) table[p * PT_SLOTS + q] = (triv[p] && q == triv[p]) ? std::nan("") : -1e-6;
+        if (best) { best[p].margin = -1e-6; best[p].slot = 0; best[p].n_positive = 0; }
+    }
+}
+
 namespace {
 // host-side description of one AlignData's edit list for k_old / k_score
 struct EditPlan {
@@ -695,8 +721,14 @@ static void plan_tables(const Align* a, const std::vector<Mut>& muts, EditPlan* 
 
 // ScoreMutations, cpp/MakeMutations.cpp:23-69, for several AlignData at once: one realign launch chain over all their
 // events (forward + backward of one event share a workgroup), then the edit scoring of each
+// a point-table call (point_table_multi): per AlignData the host arrays that receive its rows and its per-position records (either may
+// be null); the lists are FindPointMutations' and no scored copy is made (`outs` is empty)
+namespace {
+struct PointOut { std::vector<double*> table; std::vector<ps_point_best*> best; };
+}  // namespace
 static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                   const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan);
+                                   const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
+                                   const PointOut* pt = nullptr);
 
 int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                           const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out) {
@@ -719,8 +751,9 @@ int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std:
 // runtime's share, and the halves of one whose bands came out wider than guessed, take their regions' plans with them (moved: the
 // caller returns right behind them) instead of copying and sizing 80 000 edits per region again
 static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                   const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan) {
-    Tick tk("score_mutations");
+                                   const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
+                                   const PointOut* pt) {
+    Tick tk(pt ? "point_table" : "score_mutations");
     const int R = (int)as.size();
     // the reference's progress line under `verbose` (cpp/MakeMutations.cpp:28-32, 55-66: "Scoring (<width>)", a dot per event, a newline);
     // a lock-step call over several AlignData has no single line to write: only the single-handle call speaks
@@ -760,9 +793,12 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         std::vector<double*> dsub;
         if (delta_out) dsub.assign(delta_out->begin() + k0, delta_out->begin() + k1);
         std::vector<EditPlan> psub(std::make_move_iterator(plan.begin() + k0), std::make_move_iterator(plan.begin() + k1));
+        PointOut ptsub;
+        if (pt) { ptsub.table.assign(pt->table.begin() + k0, pt->table.begin() + k1); ptsub.best.assign(pt->best.begin() + k0, pt->best.begin() + k1); }
         return score_mutations_planned(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1),
                                        std::vector<const std::vector<Mut>*>(muts.begin() + k0, muts.begin() + k1),
-                                       std::vector<std::vector<Mut>*>(outs.begin() + k0, outs.begin() + k1), delta_out ? &dsub : nullptr, psub);
+                                       pt ? std::vector<std::vector<Mut>*>() : std::vector<std::vector<Mut>*>(outs.begin() + k0, outs.begin() + k1),
+                                       delta_out ? &dsub : nullptr, psub, pt ? &ptsub : nullptr);
     };
     if (sparse && R > 1 && sparse_bytes > device_share_bytes()) return in_halves(as.size(), sub);
     if (!sparse && fit_share(as, 0, 2) < as.size()) return in_share_chunks(as, 2, sub);   // sub-batches that fit a slab
@@ -793,6 +829,14 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             specs.push_back(s);
         }
     }
+    // the per-position layout of FindPointMutations' list (point_layout); an AlignData without events has every score at its seed,
+    // -1e-6 (score_mutations): its rows are written here
+    std::vector<std::vector<int>> pfirst(pt ? R : 0), ptriv(pt ? R : 0);
+    if (pt)
+        for (int k = 0; k < R; k++) {
+            point_layout(as[k], &pfirst[k], &ptriv[k]);
+            if (!as[k]->E) point_rows_seed(ptriv[k], pt->table[k], pt->best[k]);
+        }
     if (specs.empty()) return PS_OK;
     Batch b;
     SlabHold slab;   // full matrices: one of the process's slabs for the duration of this call (released at every return)
@@ -826,10 +870,11 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
     for (int k = 0; k < R; k++) {
         const EditPlan& p = plan[k];
         ints += (size_t)p.M * 7 + (size_t)p.M * p.ncolmax + p.nr0 + 16;
+        if (pt) ints += pfirst[k].size() + ptriv[k].size();
         dbls += (size_t)as[k]->E * std::max(p.nr0, 1) + (size_t)as[k]->E * std::max(p.M, 1) + std::max(p.M, 1) + (size_t)as[k]->E * (as[k]->states.size() + 8);
     }
     DBuf& mb = rt->buf("mutint");
-    PS_TRY(mb.ensure(ints * sizeof(int) + 64 + (size_t)R * sizeof(ScoreArgs)));
+    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + sizeof(PointArgs))));
     DBuf& db = rt->buf("mutdbl");
     PS_TRY(db.ensure(dbls * sizeof(double)));
     int* dp = mb.as<int>();
@@ -844,7 +889,19 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
     std::vector<int> stage;
     stage.reserve(ints);
     auto push = [&](const std::vector<int>& v) { int* r = dp + stage.size(); stage.insert(stage.end(), v.begin(), v.end()); return r; };
+    // a point-table call: the records, then the rows, of all AlignData back to back in one buffer — ONE device-to-host copy
+    std::vector<size_t> best_at(R, 0), table_at(R, 0);
+    size_t pt_bytes = 0;
+    char* d_pt = nullptr;
+    if (pt) {
+        for (int k = 0; k < R; k++) if (pt->best[k] && as[k]->E) { best_at[k] = pt_bytes; pt_bytes += ptriv[k].size() * sizeof(ps_point_best); }
+        for (int k = 0; k < R; k++) if (pt->table[k] && as[k]->E) { table_at[k] = pt_bytes; pt_bytes += ptriv[k].size() * PT_SLOTS * sizeof(double); }
+        DBuf& pb = rt->buf("ptable");
+        PS_TRY(pb.ensure(std::max<size_t>(pt_bytes, 16)));
+        d_pt = pb.as<char>();
+    }
     std::vector<ScoreArgs> sas(R);
+    std::vector<PointArgs> pts(pt ? R : 0);
     for (int k = 0; k < R; k++) {
         const EditPlan& p = plan[k];
         ScoreArgs& sa = sas[k];
@@ -863,15 +920,26 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         sa.oldall = !b.sparse && (size_t)p.nr0 * 4 > as[k]->states.size() && p.nr0 >= 256 ? dd : nullptr;   // (k_oldall walks full matrices)
         if (sa.oldall) PS_HIP(hipMemsetAsync(sa.oldall, 0, (size_t)as[k]->E * sa.oldall_pitch * sizeof(double), rt->stream));
         dd += (size_t)as[k]->E * sa.oldall_pitch;
+        if (pt) {
+            PointArgs& q = pts[k];
+            memset(&q, 0, sizeof(q));
+            q.pos_first = push(pfirst[k]); q.pos_triv = push(ptriv[k]); q.npos = (int)ptriv[k].size();
+            if (pt->table[k] && as[k]->E) q.table = (double*)(d_pt + table_at[k]);
+            if (pt->best[k] && as[k]->E) q.best = (ps_point_best*)(d_pt + best_at[k]);
+            if (!q.table && !q.best) q.npos = 0;
+        }
         if (!p.M || !as[k]->E) { sa.njobs = 0; sa.nitems_per_job = 0; }   // nothing to score for this AlignData: its blocks leave at once
     }
     // the edit tables and their descriptors (ScoreArgs, behind the tables in the same buffer) in one copy
     const size_t sa_at = (stage.size() * sizeof(int) + 63) / 64 * 64;
-    std::vector<char> blob(sa_at + (size_t)R * sizeof(ScoreArgs));
+    const size_t pt_at = (sa_at + (size_t)R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them)
+    std::vector<char> blob(pt_at + pts.size() * sizeof(PointArgs));
     memcpy(blob.data(), stage.data(), stage.size() * sizeof(int));
     memcpy(blob.data() + sa_at, sas.data(), (size_t)R * sizeof(ScoreArgs));
+    if (pt) memcpy(blob.data() + pt_at, pts.data(), pts.size() * sizeof(PointArgs));
     PS_TRY(rt->up(dp, blob.data(), blob.size()));
     const ScoreArgs* d_sas = (const ScoreArgs*)((const char*)dp + sa_at);
+    const PointArgs* d_pts = pt ? (const PointArgs*)((const char*)dp + pt_at) : nullptr;
     tk.lap("upload");
     if (tk.on) { PS_HIP(hipStreamSynchronize(rt->stream)); }
     tk.lap("realign fwd+back (rest)");
@@ -890,7 +958,19 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             rt->prof["score"].units += (double)p.M * as[k]->E;
         }
     }
-    PS_TRY(launch_score(rt, b.d, d_sas, sas));
+    PS_TRY(launch_score(rt, b.d, d_sas, sas, d_pts, pt ? &pts : nullptr));
+    if (pt) {
+        char* h_pt = nullptr;
+        if (pt_bytes) PS_TRY(rt->down((void**)&h_pt, d_pt, pt_bytes));
+        PS_HIP(hipStreamSynchronize(rt->stream));
+        for (int k = 0; k < R; k++) {
+            if (!as[k]->E || ptriv[k].empty()) continue;
+            if (pt->best[k]) memcpy(pt->best[k], h_pt + best_at[k], ptriv[k].size() * sizeof(ps_point_best));
+            if (pt->table[k]) memcpy(pt->table[k], h_pt + table_at[k], ptriv[k].size() * PT_SLOTS * sizeof(double));
+        }
+        tk.lap("score edits");
+        return PS_OK;
+    }
     std::vector<double*> dl(R, nullptr);
     double* all_scores = nullptr;
     PS_TRY(rt->down(&all_scores, score0, score_tot));
@@ -906,6 +986,28 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
     }
     tk.lap("score edits");
     return PS_OK;
+}
+
+// ScorePoints (ScoreMutations on FindPointMutations' list, at the scoring width the AlignData carries) for several AlignData, reduced on
+// the device to a row per position (k_point_table) instead of a scored list: the same chain as score_mutations_multi up to k_score,
+// then one copy back of all rows and records.  tables[k]: null or [states][9]; bests[k]: null or [states].
+int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& tables, const std::vector<ps_point_best*>& bests) {
+    const int R = (int)as.size();
+    std::vector<std::vector<Mut>> lists(R);
+    std::vector<EditPlan> plan(R);
+    std::vector<const std::vector<Mut>*> muts(R);
+    par_for(R, [&](int k) {
+        find_point_mutations(as[k], &lists[k]);
+        plan_edits(as[k], lists[k], &plan[k]);
+        muts[k] = &lists[k];
+    });
+    for (int k = 0; k < R; k++) {
+        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
+        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
+    }
+    PointOut pt;
+    pt.table = tables; pt.best = bests;
+    return score_mutations_planned(rt, as, muts, {}, nullptr, plan, &pt);
 }
 
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out) {

@@ -167,6 +167,9 @@ int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector
 int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                           const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out = nullptr);
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out);
+// ps_point_table / ps_batch_point_table (include/poreseq_hip.h): ScorePoints reduced on the device to rows per position; tables[k]
+// (null or [states][9]) and bests[k] (null or [states]) are host arrays
+int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& tables, const std::vector<ps_point_best*>& bests);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases);
 int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds, std::vector<Mut>* out);

@@ -253,8 +253,22 @@ struct ScoreArgs {
     const int* cls_items[5];
     int cls_count[5];
 };
+// A point-edit table call (k_point_table instead of k_reduce) has one of these per AlignData beside its ScoreArgs — a record of its
+// own, so that ScoreArgs and with it the device code of every other scoring kernel stay what they were.  The list is
+// FindPointMutations' and position p's edits are pos_first[p] .. pos_first[p + 1] - 1 (8 of them for an A / C / G / T base, 9 for
+// any other character).
+struct PointArgs {
+    const int* pos_first;      // [npos + 1]
+    const int* pos_triv;       // [npos] slot 1 .. 4 of the trivial substitution (the position's own base), 0: none
+    int npos;                  // positions with a row: states of the sequence (0: nothing to write for this AlignData)
+    double* table;             // NULL, or [npos][9]
+    ps_point_best* best;       // NULL, or [npos]
+};
+constexpr int PT_SLOTS = 9;    // deletion, substitution by A / C / G / T, insertion of A / C / G / T
 constexpr int SCORE_CLASSES = 5;
-int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas);
+// (d_pts / h_pts: the PointArgs of a point-edit table call on the device and on the host, parallel to the ScoreArgs; null otherwise)
+int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
+                 const PointArgs* d_pts = nullptr, const std::vector<PointArgs>* h_pts = nullptr);
 int launch_begin(Runtime* rt, const BatchD& b);
 int launch_gather_best(Runtime* rt, const BatchD& b, double* out);   // out[job] = the job's forward maxScore (JobOut.best)
 

@@ -1266,6 +1266,52 @@ __global__ void k_reduce(const ScoreArgs* __restrict__ A) {
     a.score[m] = s;
 }
 
+// k_reduce for FindPointMutations' list (cpp/FindMutations.cpp:200-228), laid out per position: table[p][9] = {deletion, substitution
+// by A / C / G / T (a quiet NaN for the base itself, which the list does not hold), insertion of A / C / G / T}, and per position the
+// largest entry, the first slot that holds it and the number of entries > 0 (ps_point_best, include/poreseq_hip.h).  A block owns
+// PT_POS consecutive positions, i.e. one contiguous run of at most 9 PT_POS edits: a thread per edit adds the events' terms in event
+// order (k_reduce's loop: plain FP64 adds, coalesced reads of delta[e][m]), then a thread per position lays its row out in LDS and
+// the block writes the rows back to back.
+constexpr int PT_POS = 28;   // 9 x 28 = 252 edits: one per thread of a 256-thread block
+__global__ __launch_bounds__(256) void k_point_table(const ScoreArgs* __restrict__ A, const PointArgs* __restrict__ Q) {
+    const ScoreArgs& a = A[blockIdx.y];
+    const PointArgs& q = Q[blockIdx.y];
+    const int p0 = blockIdx.x * PT_POS;
+    if (p0 >= q.npos || !a.njobs) return;
+    __shared__ double s_sum[PT_POS * PT_SLOTS], s_row[PT_POS * PT_SLOTS];
+    const int np = min(PT_POS, q.npos - p0);
+    const int m0 = q.pos_first[p0];
+    const int nm = min(q.pos_first[p0 + np] - m0, PT_POS * PT_SLOTS);
+    const int t = threadIdx.x;
+    if (t < nm) {
+        const int njobs = a.njobs;
+        const int m = m0 + t;
+        double s = -1e-6;
+        for (int e = 0; e < njobs; e++) s += a.delta[(size_t)e * a.nitems_per_job + m];
+        s_sum[t] = s;
+    }
+    __syncthreads();
+    if (t < np) {
+        const int p = p0 + t;
+        const int at = q.pos_first[p] - m0, triv = q.pos_triv[p];
+        double* row = s_row + PT_SLOTS * t;
+        // (a list that is not FindPointMutations' would point past the block's run: such a row is all NaN instead of an LDS read out of bounds)
+        const bool ok = at >= 0 && at + (triv ? 8 : 9) <= nm;
+        int k = at;
+        ps_point_best b;
+        b.margin = -INFINITY; b.slot = 0; b.n_positive = 0;
+        for (int sl = 0; sl < PT_SLOTS; sl++) {
+            const double v = (!ok || (triv && sl == triv)) ? __builtin_nan("") : s_sum[k++];   // (triv == 0: every slot holds an edit)
+            row[sl] = v;
+            if (v > b.margin) { b.margin = v; b.slot = sl; }
+            if (v > 0) b.n_positive++;
+        }
+        if (q.best) q.best[p] = b;
+    }
+    __syncthreads();
+    if (q.table && t < PT_SLOTS * np) q.table[(size_t)PT_SLOTS * p0 + t] = s_row[t];
+}
+
 // latch the reference's "stripe_width == 0" decision (cpp/Alignment.cpp:51-59) for this API call
 __global__ void k_begin(BatchD b) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1440,7 +1486,8 @@ int launch_begin(Runtime* rt, const BatchD& b) {
 
 // edit scoring of several AlignData of one batch (d_sas: their ScoreArgs on the device, h_sas the same on the host): one launch
 // per kernel over all of them — grid.z (k_reduce: grid.y) is the AlignData, blocks past an AlignData's own sizes leave at once
-int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas) {
+int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
+                 const PointArgs* d_pts, const std::vector<PointArgs>* h_pts) {
     const int R = (int)h_sas.size();
     int maxE = 0, maxnr0 = 0, maxnr0_all = 0, maxM = 0, cls_max[SCORE_CLASSES] = {0, 0, 0, 0, 0};
     int64_t maxS = 0;
@@ -1477,6 +1524,23 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
         PS_LAUNCH_CHECK();
     }
     prof_end(rt, "score", 0.0);
+    if (h_pts) {   // a point-table call (every AlignData of it): rows per position instead of a score per edit
+        int maxnpos = 0;
+        double bytes = 0;
+        for (int k = 0; k < R; k++) {
+            const ScoreArgs& a = h_sas[k];
+            const int npos = (*h_pts)[k].npos;
+            if (!a.njobs || !npos) continue;
+            maxnpos = std::max(maxnpos, npos);
+            bytes += 8.0 * a.njobs * a.nitems_per_job + 88.0 * npos;
+        }
+        if (!maxnpos) return PS_OK;
+        prof_begin(rt);
+        hipLaunchKernelGGL(k_point_table, dim3((maxnpos + PT_POS - 1) / PT_POS, R), dim3(256), 0, rt->stream, d_sas, d_pts);
+        PS_LAUNCH_CHECK();
+        prof_end(rt, "point_table", bytes);
+        return PS_OK;
+    }
     hipLaunchKernelGGL(k_reduce, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, d_sas);
     PS_LAUNCH_CHECK();
     return PS_OK;

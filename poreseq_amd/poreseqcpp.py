@@ -50,6 +50,20 @@ def _check_realign_accuracy(acc):
         raise Exception('Error rate too large for realignment!')
 
 
+def point_table_from_list(n, start, orig, mut, score):
+    """The point-edit table of a scored FindPointMutations list, built literally — the definition of what ps_point_table returns:
+    every edit goes to row `start`, slot 0 for a deletion (mut == ''), 1 + 'ACGT'.index(mut) for a substitution, 5 + that for an
+    insertion (orig == ''); slots without an edit (the substitution by the base itself) stay NaN.  margin / slot come from numpy's
+    argmax (the first maximum) over the row with NaN masked, n_positive counts the entries > 0.
+    Returns (table float64 [n, 9], margin float64 [n], slot int32 [n], n_positive int32 [n])."""
+    table = np.full((int(n), _capi.POINT_SLOTS), np.nan, dtype=np.float64)
+    for p, o, m, sc in zip(start, orig, mut, score):
+        table[int(p), 0 if m == '' else ('ACGT'.index(m) + (5 if o == '' else 1))] = sc
+    slot = np.argmax(np.where(np.isnan(table), -np.inf, table), axis=1).astype(np.int32)
+    margin = table[np.arange(int(n)), slot]
+    return table, margin, slot, np.sum(table > 0, axis=1).astype(np.int32)
+
+
 class PSAlign:
     """All data of reads aligned to a reference (pyx:189-472).
 
@@ -157,6 +171,31 @@ class PSAlign:
                 return self._scores_to_py(d.api, hs)
             finally:
                 d.api.muts_destroy(hs)
+
+    def PointTable(self, table=True):
+        """ScorePoints as arrays (ps_point_table): (table, margin, slot, n_positive) over the len(sequence) - 4 positions that
+        FindPointMutations walks (the last four bases have no row), at `point_width` like ScorePoints.  table is float64 [n, 9] —
+        slot 0 the deletion of the base, 1-4 its substitution by A / C / G / T (NaN for the base itself), 5-8 the insertion of
+        A / C / G / T in front of it, each entry the score ScorePoints gives that edit — or None with table=False (it is then
+        not copied back); margin [n] is the row's largest entry, slot [n] the first slot that holds it, n_positive [n] the
+        entries > 0.  The reduction runs on the device (k_point_table); `self` is not modified.  A library without the entry
+        point (the test-suite's checkers) builds the arrays from its scored list: `point_table_from_list`."""
+        api = self._native()
+        n = max(len(self.sequence) - 4, 0)
+        with PSAlign._Data(self, point_width=True) as d:
+            if "ps_point_table" in api.missing:
+                hm = d.api.find_point_mutations(d.h)
+                try:
+                    hs = d.api.score_mutations(d.h, hm)
+                finally:
+                    d.api.muts_destroy(hm)
+                try:
+                    tb, margin, slot, npos = point_table_from_list(n, *d.api.muts_export(hs))
+                finally:
+                    d.api.muts_destroy(hs)
+                return (tb if table else None), margin, slot, npos
+            tb, best = d.api.point_table(d.h, n, want_table=table)
+        return tb, best["margin"].copy(), best["slot"].copy(), best["n_positive"].copy()
 
     def ScoreMutations(self, muts):
         """Score the given MutationInfo list, same order (pyx:310-345)."""

@@ -109,3 +109,27 @@ def SaveParams(filename, params):
     with open(filename, 'w') as f:
         for p in params:
             f.write('{} = {}\n'.format(p, params[p]))
+
+
+def phred_from_margin(margin, length):
+    """Per-base qualities uint8 [length] of a consensus from PointTable's `margin` (the largest point-edit score per position):
+    Q = clip(floor(-margin * 10 / ln 10 + 0.5), 0, 93).  The scores are natural-log likelihood ratios, so this is the Phred scale
+    of the ratio between the called base and its best single-base alternative (deletion, substitution or insertion in front of
+    it); 93 is the top of FASTQ's printable range.  Positions without a row — the last four bases, which FindPointMutations does
+    not walk — get 0, and so does a position whose best alternative scores >= 0.
+    UNCALIBRATED: a likelihood ratio of this model, not a measured error rate; it orders bases by confidence and no more."""
+    import numpy as np
+    m = np.asarray(margin, dtype=np.float64)
+    q = np.zeros(int(length), dtype=np.uint8)
+    k = min(m.size, int(length))
+    with np.errstate(invalid='ignore', over='ignore'):
+        v = np.clip(np.floor(-m[:k] * 10.0 / np.log(10.0) + 0.5), 0, 93)
+    q[:k] = np.where(np.isnan(v), 0, v).astype(np.uint8)
+    return q
+
+
+def write_fastq(out, name, seq, qual):
+    """One FASTQ record: '@name', the sequence, '+', chr(33 + q) per base."""
+    if len(qual) != len(seq):
+        raise ValueError("write_fastq: %d qualities for %d bases" % (len(qual), len(seq)))
+    out.write('@{}\n{}\n+\n{}\n'.format(name, seq, ''.join(chr(33 + int(q)) for q in qual)))
