@@ -6,6 +6,10 @@
  * (poreseq/_poreseqcpp.pyx) calls in the reference C++ core; the reference
  * interface each one stands in for is cited as file:line relative to the
  * reference tree.  Only plain pointers and sizes cross this boundary.
+ * A few entry points go beyond the reference's surface and reduce its scores on the device: ps_point_table (a row per position)
+ * and ps_score_mutation_support (per edit and event group: the summed terms, the reads that span the edit and how many of
+ * them favour or oppose it).  `cover` there is a span test on the re-aligned reads, not a likelihood test, and anything
+ * Phred-scaled that drivers derive from these scores is uncalibrated.
  *
  * All functions return PS_OK (0) or a negative ps_status; ps_last_error()
  * gives the message of the last failure on the calling thread.  The library
@@ -165,6 +169,31 @@ typedef struct ps_point_best {
 } ps_point_best;
 int ps_point_table(ps_align* a, double* table /* [n][9] or NULL */, ps_point_best* best /* [n] or NULL */, int64_t n);
 
+/* Per-edit read support by event group.  The list is scored as by ps_score_mutations — at the scoring width the AlignData carries,
+ * events re-aligned once as a side effect — and the per-event terms delta[e][m] (what ps_score_mutation_deltas returns) are reduced
+ * on the device; the events x edits matrix never goes to the host.  group[e] in 0 .. n_groups - 1 assigns every event to one of
+ * 1 <= n_groups <= 8 groups; the library does not know what a group means (strand, sample, haplotype ...).
+ *   scores[m]              the bits of ps_score_mutations: -1e-6 plus all events' terms in event order.  May be NULL.
+ *   support[m * n_groups + g]
+ *       sum                0.0, then += delta[e][m] for e ascending with group[e] == g: plain FP64 adds over ALL events of the
+ *                          group, covering or not (a read's term is not zero outside its aligned span).
+ *       cover              the events e of g that SPAN the edit: the event has a positive ref_align entry after the call's
+ *                          re-alignment and refstart <= start + 1 <= refend, refstart / refend being the int of its first / last
+ *                          positive ref_align entry (cpp/EventData.h:110-169) and start + 1 the column of the 5-mer that begins at
+ *                          the edit's first base.  This is a span test, not a likelihood test: a covering read's term can be zero.
+ *       pos / neg          those of the covering events with delta > 0 / delta < 0.
+ *       reserved           0.
+ * An edit that ScoreMutations skips (start > sequence length, cpp/MakeMutations.cpp:46-47) has all-zero records and score -1e-6.
+ * n_groups outside 1 .. 8, a group id outside 0 .. n_groups - 1 or a NULL group / support is PS_ERR_BAD_ARG.  An empty list is PS_OK
+ * and launches nothing (the events are then not re-aligned either).  One call, or one chunk of a batch that was cut to fit device
+ * memory, returns all its results in one device-to-host copy. */
+typedef struct ps_edit_support {
+    double sum;
+    int32_t cover, pos, neg, reserved /* 0 */;
+} ps_edit_support;   /* 24 bytes */
+int ps_score_mutation_support(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group /* [n_events] */,
+                              double* scores /* [M] or NULL */, ps_edit_support* support /* [M][n_groups] */);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -207,6 +236,10 @@ int ps_batch_score_sequences(int32_t n, ps_align* const* a, const ps_seqs* const
 /* ps_point_table for every AlignData in one launch chain (the dense ScoreMutations path of Refine) and ONE copy back: table[i] is NULL
  * or [n[i]][9], best[i] NULL or [n[i]] (either array itself may be NULL), n[i] the position count of AlignData i. */
 int ps_batch_point_table(int32_t n_regions, ps_align* const* a, double* const* table, ps_point_best* const* best, const int64_t* n);
+/* ps_score_mutation_support for every AlignData in one launch chain: muts[i], n_groups[i], group[i] ([n_events(i)]) and support[i] ([count(muts[i])][n_groups[i]]) per AlignData; scores[i], or the whole array, may be NULL. */
+int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* n_groups /* [n] */,
+                                    const int32_t* const* group, double* const* scores /* entries or array may be NULL */,
+                                    ps_edit_support* const* support);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -288,7 +321,7 @@ int ps_set_device_fraction(double fraction);
 
 /* Hot-kernel instrumentation for bench.py: accumulated HIP-event time (ms), launches and
  * algorithmic bytes of the named kernel class ("fill" = k_fill, "sweep" = the strip sweeps k_sweep / k_sweeps / k_sweep2 and their _w builds,
- * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab";
+ * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab";
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =
  * alignment chunks (launches) over distinct sequences (units) of ps_score_sequences. */
 /* ps_prof_enable(1) makes every hot-kernel launch be bracketed by HIP events on the library's stream

@@ -43,6 +43,16 @@ POINT_BEST = np.dtype([("margin", np.float64), ("slot", np.int32), ("n_positive"
 POINT_SLOTS = 9   # deletion, substitution by A / C / G / T, insertion of A / C / G / T
 
 
+class PsEditSupport(C.Structure):
+    # ps_edit_support, include/poreseq_hip.h
+    _fields_ = [("sum", C.c_double), ("cover", C.c_int32), ("pos", C.c_int32), ("neg", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same record as a numpy dtype (24 bytes, no padding): what score_mutation_support / batch_score_mutation_support hand out
+EDIT_SUPPORT = np.dtype([("sum", np.float64), ("cover", np.int32), ("pos", np.int32), ("neg", np.int32), ("reserved", np.int32)])
+SUPPORT_MAX_GROUPS = 8
+
+
 class PoreseqError(Exception):
     pass
 
@@ -84,6 +94,9 @@ SYMBOLS = {
     "ps_make_mutations": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p]),
     "ps_point_table": (C.c_int, [C.c_void_p, c_dp, C.POINTER(PsPointBest), C.c_int64]),
     "ps_batch_point_table": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_dp), C.POINTER(C.POINTER(PsPointBest)), c_i64p]),
+    "ps_score_mutation_support": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, c_dp, C.POINTER(PsEditSupport)]),
+    "ps_batch_score_mutation_support": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32p, C.POINTER(c_i32p), C.POINTER(c_dp),
+                                                  C.POINTER(C.POINTER(PsEditSupport))]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -121,10 +134,11 @@ SYMBOLS = {
 
 # entry points of the header that a checker library (the oracle, the reference shim) may lack: CApi serves them from what the
 # library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents;
-# PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations).
+# PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations; PSAlign.ScoreMutationSupport reduces
+# score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
 OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
-                      "ps_point_table", "ps_batch_point_table"])
+                      "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
 # entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
@@ -255,6 +269,17 @@ class CApi:
             ev.ref_align[:] = ra
             ev.ref_like[:] = rl
 
+    def align_event_refs(self, h, n_events):
+        """[ref_align float64 [n]] of every event of the AlignData, as they are now (after a scoring call: re-aligned)"""
+        out = []
+        for e in range(int(n_events)):
+            n = int(self.lib.ps_align_n_levels(h, e))
+            ra = np.empty(n, dtype=np.float64)
+            rl = np.empty(n, dtype=np.float64)
+            self.check(self.lib.ps_align_get_event_refs(h, e, _dp(ra), _dp(rl)))
+            out.append(ra)
+        return out
+
     # ------------------------------------------------------------------ mutation lists
     def muts_create(self, muts, with_scores=False):
         n = len(muts)
@@ -364,6 +389,28 @@ class CApi:
         bp = (C.POINTER(PsPointBest) * max(R, 1))(*[b.ctypes.data_as(C.POINTER(PsPointBest)) for b in bests])
         self.check(self.lib.ps_batch_point_table(R, self._harr(hs), tp, bp, ns.ctypes.data_as(c_i64p)))
         return list(zip(tables, bests))
+
+    def score_mutation_support(self, h, hm, n_muts, groups, n_groups):
+        """-> (scores float64 [M], support EDIT_SUPPORT [M, n_groups]): ps_score_mutation_support of one AlignData"""
+        return self.batch_score_mutation_support([h], [hm], [n_muts], [groups], [n_groups])[0]
+
+    def batch_score_mutation_support(self, hs, hms, n_muts, groups, n_groups):
+        """ps_batch_score_mutation_support over the AlignData `hs` with the edit lists `hms` of n_muts[i] edits, groups[i] the group
+        id of every event of AlignData i (0 .. n_groups[i] - 1): one launch chain, reduced on the device, one copy back ->
+        [(scores float64 [M], support EDIT_SUPPORT [M, n_groups[i]])].  support['sum'] is the group's events' terms added in event
+        order, ['cover'] the events of the group whose re-aligned span holds the edit, ['pos'] / ['neg'] those of them with a
+        positive / negative term."""
+        self._need("ps_batch_score_mutation_support")
+        R = len(hs)
+        ng = np.array([int(g) for g in n_groups] + [0], dtype=np.int32)
+        grp = [np.ascontiguousarray(list(g) + [0], dtype=np.int32) for g in groups]   # (one spare entry: never a null pointer)
+        scores = [np.empty(int(m), dtype=np.float64) for m in n_muts]
+        recs = [np.empty((int(m), max(int(g), 0)), dtype=EDIT_SUPPORT) for m, g in zip(n_muts, ng[:R])]
+        gp = (c_i32p * max(R, 1))(*[g.ctypes.data_as(c_i32p) for g in grp])
+        sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores])
+        rp = (C.POINTER(PsEditSupport) * max(R, 1))(*[r.ctypes.data_as(C.POINTER(PsEditSupport)) for r in recs])
+        self.check(self.lib.ps_batch_score_mutation_support(R, self._harr(hs), self._harr(hms), ng.ctypes.data_as(c_i32p), gp, sp, rp))
+        return list(zip(scores, recs))
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

@@ -177,6 +177,66 @@ class RegionBatch:
             self._close(idx, hs, write_back=False)
         return [(tb, b["margin"].copy(), b["slot"].copy(), b["n_positive"].copy()) for tb, b in res]
 
+    def _lists(self, muts_per_region, idx):
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        lists = [None] * len(idx) if muts_per_region is None else [None if m is None else list(m) for m in muts_per_region]
+        if len(lists) != len(idx):
+            raise ValueError("one list of edits per region")
+        return idx, lists
+
+    def ScoreMutations(self, muts_per_region, idx=None):
+        """PSAlign.ScoreMutations (`poreseq variant -m`) for the regions `idx` in lock-step: muts_per_region[k] is the MutationInfo
+        list of region idx[k] (may be empty), all regions' lists scored by ONE ps_batch_score_mutations call.  Returns one
+        MutationScore list per region, same order; sequences and the Python events are not modified (the resident events are
+        re-aligned, as by every ScoreMutations call)."""
+        idx, lists = self._lists(muts_per_region, idx)
+        if not idx:
+            return []
+        if any(m is None for m in lists):
+            raise ValueError("one list of edits per region")
+        hs = self._open(idx)
+        hm, scored = [], []
+        try:
+            hm = [self.api.muts_create(m) for m in lists]
+            scored = self.api.batch_score_mutations(hs, hm)
+            return [poreseqcpp._scored_list(*self.api.muts_export(s)) for s in scored]
+        finally:
+            for m in hm + scored:
+                self.api.muts_destroy(m)
+            self._close(idx, hs, write_back=False)
+
+    def ScoreMutationSupport(self, muts_per_region, idx=None, groups=None, n_groups=None):
+        """PSAlign.ScoreMutationSupport for the regions `idx` in lock-step: ONE ps_batch_score_mutation_support call — one scoring
+        chain over all regions, reduced per event group on the device, one copy back.  muts_per_region[k] is the MutationInfo list
+        of region idx[k]; None instead of the lists means every region's point edits at `point_width`.  groups[k] / n_groups[k]
+        (or one n_groups for all) as PSAlign.ScoreMutationSupport takes them, None for the strand default.  Returns one
+        (scores, support, scored list) per region; sequences and the Python events are not modified."""
+        points = muts_per_region is None
+        idx, lists = self._lists(muts_per_region, idx)
+        if not idx:
+            return []
+        if not points and any(m is None for m in lists):
+            raise ValueError("one list of edits per region")
+        groups = [None] * len(idx) if groups is None else list(groups)
+        n_groups = list(n_groups) if isinstance(n_groups, (list, tuple)) else [n_groups] * len(idx)
+        if len(groups) != len(idx) or len(n_groups) != len(idx):
+            raise ValueError("one list of group ids per region")
+        gG = [poreseqcpp.support_groups(self.pas[i].events, g, n) for i, g, n in zip(idx, groups, n_groups)]
+        hs = self._open(idx, point_width=points)
+        hm = []
+        try:
+            hm = [self.api.find_point_mutations(h) if points else self.api.muts_create(m) for h, m in zip(hs, lists)]
+            if "ps_batch_score_mutation_support" in self.api.missing:
+                return [poreseqcpp._support_on(self.api, h, m, len(self.pas[i].events), len(self.pas[i].sequence), g, G)
+                        for i, h, m, (g, G) in zip(idx, hs, hm, gG)]
+            lists_x = [self.api.muts_export(m) for m in hm]
+            res = self.api.batch_score_mutation_support(hs, hm, [len(x[0]) for x in lists_x], [g for g, _ in gG], [G for _, G in gG])
+            return [(sc, sup, poreseqcpp._scored_list(x[0], x[1], x[2], sc)) for (sc, sup), x in zip(res, lists_x)]
+        finally:
+            for m in hm:
+                self.api.muts_destroy(m)
+            self._close(idx, hs, write_back=False)
+
     def Mutate(self, idx=None, seqs='self', reps=4):
         """PSAlign.Mutate (pyx:378-435) for the regions `idx`; returns {region index: total mutated bases}."""
         idx = list(range(len(self.pas))) if idx is None else list(idx)

@@ -6,6 +6,7 @@
   variant_region    <- poreseq/Variant.py:66-95  (ScoreMutations / ScorePoints with start offsetting)
   variant_points    <- poreseq/Variant.py:77-93  (`variant -a`: every point edit of one or many regions, as tables from one lock-step call)
   variant_sequences <- poreseq/Variant.py:48-63  (`variant -v`: whole candidate sequences, one batched ScoreSequences call)
+  variant_support   <- poreseq/Variant.py:66-95  (`variant -m` over many regions in lock-step, with per-group read support; TSV or VCF)
   split_regions     <- poreseq/split_fasta.py:94-101 (max_length pieces with 1 kb overlap)
 
 fast5 / BAM loading is out of scope: callers hand over a PSAlign whose events are already
@@ -256,6 +257,101 @@ def variant_points(pas, region_starts=None, params=None, out=None):
                 lines.extend('{}\t.\t{}\t{}\n'.format(at, 'ACGT'[k], row[5 + k]) for k in range(4))
             out.write(''.join(lines))
     return tables, percent
+
+
+VCF_INFO = (("LLR", "1", "Float", "Log-likelihood change of the edit summed over all reads (natural log)"),
+            ("DP", "1", "Integer", "Reads whose re-aligned span holds the edit (a span test, not a likelihood test)"),
+            ("GDP", ".", "Integer", "Spanning reads per group"),
+            ("GSUP", ".", "Integer", "Spanning reads per group that favour the edit (term > 0)"),
+            ("GOPP", ".", "Integer", "Spanning reads per group that oppose the edit (term < 0)"),
+            ("GLLR", ".", "Float", "Log-likelihood change per group, over all reads of the group"))
+
+
+def vcf_fields(seq, start, orig, mut, offset=0):
+    """(POS, REF, ALT) of the edit `start` (0-based in `seq`) orig -> mut; `offset` is added to POS (the region's start).  A
+    replacement of equal length stands as it is (POS = start + 1); everything else is anchored on the base before it (POS =
+    start), and at start 0, where there is none, on the base after `orig`, which is appended to both alleles (POS = 1)."""
+    if len(orig) == len(mut) and len(orig) > 0:
+        return start + 1 + offset, orig, mut
+    if start > 0:
+        a = seq[start - 1:start]
+        return start + offset, a + orig, a + mut
+    a = seq[len(orig):len(orig) + 1]
+    return 1 + offset, orig + a, mut + a
+
+
+def vcf_qual(score):
+    """QUAL of a record: clip(floor(score * 10 / ln 10 + 0.5), 0, 9999), the Phred scale of the likelihood ratio.  UNCALIBRATED, as
+    the FASTQ qualities are (util.phred_from_margin): a ratio of this model, not a measured error rate."""
+    q = np.floor(float(score) * 10.0 / np.log(10.0) + 0.5)
+    return int(min(max(q, 0.0), 9999.0)) if q == q else 0
+
+
+def variant_support(pas, muts_per_region, region_starts=None, groups=None, group_names=("t", "c"), out=None, fmt="tsv", chrom="region",
+                    min_score=0.0):
+    """`poreseq variant -m` for one PSAlign or a list of them with the read evidence behind every score: all regions go through ONE
+    lock-step RegionBatch.ScoreMutationSupport call.  muts_per_region[r] is the MutationInfo list of region r with ABSOLUTE starts
+    (region_starts[r] is subtracted inside the call and added again outside, as variant_region does — on copies: the lists handed
+    in are not changed); None means every point edit of every region.  groups[r] gives every event of region r a group id below
+    len(group_names); None is the strand default, template 0 / complement 1, which the default names ("t", "c") fit.
+    Returns one (scores, support, scored list) per region, as PSAlign.ScoreMutationSupport does, the scored starts absolute.
+    fmt="tsv": one '#' header line (MutationInfo reads it as a comment), then per edit str(MutationScore) — the reference's four
+      columns, byte for byte what variant_region writes — followed per group by tab-separated cover, pos, neg, sum.
+    fmt="vcf": a VCF 4.2 header and one record per edit with score > min_score, in list order (`vcf_fields`, `vcf_qual`); `chrom`
+      is one name or one per region.  INFO = LLR=<score>;DP=<sum of cover>;GDP=..;GSUP=..;GOPP=..;GLLR=.., the G-tags
+      comma-separated per group in group order.
+    `cover` is a span test, not a likelihood test, and QUAL is uncalibrated.  No PSAlign is modified."""
+    from .batch import RegionBatch
+    from .util import MutationInfo
+    if fmt not in ("tsv", "vcf"):
+        raise ValueError("variant_support: fmt is 'tsv' or 'vcf'")
+    single = isinstance(pas, poreseqcpp.PSAlign)
+    pas = [pas] if single else list(pas)
+    if single:
+        muts_per_region = None if muts_per_region is None else [muts_per_region]
+        groups = None if groups is None else [groups]
+    starts = [0] * len(pas) if region_starts is None else ([region_starts] if single else list(region_starts))
+    chroms = [chrom] * len(pas) if isinstance(chrom, str) else list(chrom)
+    names = [str(n) for n in group_names]
+    rel = None
+    if muts_per_region is not None:
+        rel = []
+        for ml, s0 in zip(muts_per_region, starts):
+            row = []
+            for m in ml:
+                mi = MutationInfo()
+                mi.start, mi.orig, mi.mut = int(m.start) - int(s0), m.orig, m.mut
+                row.append(mi)
+            rel.append(row)
+    res = []
+    if pas:
+        with RegionBatch(pas, resident=False) as rb:   # (not resident: nothing of the pass is written back to the PSAlign objects)
+            res = rb.ScoreMutationSupport(rel, groups=groups, n_groups=len(names))
+    if out is not None:
+        if fmt == "tsv":
+            out.write('#start\torig\tmut\tscore' + ''.join('\tcover_{0}\tpos_{0}\tneg_{0}\tsum_{0}'.format(n) for n in names) + '\n')
+        else:
+            out.write('##fileformat=VCFv4.2\n##source=poreseq_amd.variant_support\n')
+            for tag, num, typ, desc in VCF_INFO:
+                per = '' if num == '1' else ' (groups: {})'.format(','.join(names))
+                out.write('##INFO=<ID={},Number={},Type={},Description="{}{}">\n'.format(tag, num, typ, desc, per))
+            out.write('#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n')
+    for pa, s0, ch, (scores, sup, scored) in zip(pas, starts, chroms, res):
+        lines = []
+        for ms, rec in zip(scored, sup.tolist()):
+            if fmt == "tsv":
+                ms.start += int(s0)
+                lines.append(str(ms) + ''.join('\t{}\t{}\t{}\t{}'.format(r[1], r[2], r[3], r[0]) for r in rec) + '\n')
+                continue
+            if ms.score > min_score:
+                pos, ref, alt = vcf_fields(pa.sequence, ms.start, ms.orig, ms.mut, int(s0))
+                col = lambda k: ','.join(str(r[k]) for r in rec)
+                info = 'LLR={};DP={};GDP={};GSUP={};GOPP={};GLLR={}'.format(ms.score, sum(r[1] for r in rec), col(1), col(2), col(3), col(0))
+                lines.append('{}\t{}\t.\t{}\t{}\t{}\t.\t{}\n'.format(ch, pos, ref, alt, vcf_qual(ms.score), info))
+            ms.start += int(s0)
+        if out is not None:
+            out.write(''.join(lines))
+    return res[0] if single and res else res
 
 
 def variant_sequences(pa, variants, out=None):

@@ -295,6 +295,38 @@ int ps_point_table(ps_align* a, double* table, ps_point_best* best, int64_t n) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_point_table: null handle");
     return ps_batch_point_table(1, &a, &table, &best, &n);
 }
+int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* n_groups,
+                                    const int32_t* const* group, double* const* scores, ps_edit_support* const* support) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n && (!muts || !n_groups || !group || !support)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_support: null array");
+    std::vector<const std::vector<Mut>*> in(n);
+    std::vector<const int32_t*> gr(n);
+    std::vector<int> ng(n);
+    std::vector<double*> sc(n);
+    std::vector<ps_edit_support*> rec(n);
+    size_t edits = 0;
+    for (int i = 0; i < n; i++) {
+        const std::string who = "ps_score_mutation_support: region " + std::to_string(i);
+        if (!muts[i]) return fail(PS_ERR_BAD_ARG, who + ": null list");
+        if (n_groups[i] < 1 || n_groups[i] > SUPPORT_MAX_GROUPS)
+            return fail(PS_ERR_BAD_ARG, who + ": n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(SUPPORT_MAX_GROUPS));
+        if (!group[i]) return fail(PS_ERR_BAD_ARG, who + ": null group array");
+        if (!support[i]) return fail(PS_ERR_BAD_ARG, who + ": null support array");
+        for (int e = 0; e < as[i]->E; e++)
+            if (group[i][e] < 0 || group[i][e] >= n_groups[i])
+                return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(group[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
+        in[i] = &muts[i]->v; gr[i] = group[i]; ng[i] = n_groups[i]; sc[i] = scores ? scores[i] : nullptr; rec[i] = support[i];
+        edits += in[i]->size();
+    }
+    if (!edits) return PS_OK;   // nothing to score anywhere: no launch
+    NEED_RT();
+    return score_mutation_support_multi(rt, as, in, gr, ng, sc, rec);
+}
+int ps_score_mutation_support(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group, double* scores, ps_edit_support* support) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_support: null handle");
+    return ps_batch_score_mutation_support(1, &a, &muts, &n_groups, &group, &scores, &support);
+}
 int ps_batch_make_mutations(int32_t n, ps_align* const* a, const ps_muts* const* scored, int32_t* n_bases) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

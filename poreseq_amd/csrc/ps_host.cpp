@@ -725,10 +725,13 @@ static void plan_tables(const Align* a, const std::vector<Mut>& muts, EditPlan* 
 // be null); the lists are FindPointMutations' and no scored copy is made (`outs` is empty)
 namespace {
 struct PointOut { std::vector<double*> table; std::vector<ps_point_best*> best; };
+// a support call (score_mutation_support_multi): per AlignData the events' group ids, the number of groups and the host arrays that
+// receive the scores (may be null) and the [M][ngroups] records; no scored copy of the lists is made either
+struct SupportOut { std::vector<const int32_t*> group; std::vector<int> ngroups; std::vector<double*> score; std::vector<ps_edit_support*> rec; };
 }  // namespace
 static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                                    const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
-                                   const PointOut* pt = nullptr);
+                                   const PointOut* pt = nullptr, const SupportOut* sp = nullptr);
 
 int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                           const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out) {
@@ -752,8 +755,8 @@ int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std:
 // caller returns right behind them) instead of copying and sizing 80 000 edits per region again
 static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                                    const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
-                                   const PointOut* pt) {
-    Tick tk(pt ? "point_table" : "score_mutations");
+                                   const PointOut* pt, const SupportOut* sp) {
+    Tick tk(pt ? "point_table" : sp ? "score_mutation_support" : "score_mutations");
     const int R = (int)as.size();
     // the reference's progress line under `verbose` (cpp/MakeMutations.cpp:28-32, 55-66: "Scoring (<width>)", a dot per event, a newline);
     // a lock-step call over several AlignData has no single line to write: only the single-handle call speaks
@@ -795,10 +798,15 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         std::vector<EditPlan> psub(std::make_move_iterator(plan.begin() + k0), std::make_move_iterator(plan.begin() + k1));
         PointOut ptsub;
         if (pt) { ptsub.table.assign(pt->table.begin() + k0, pt->table.begin() + k1); ptsub.best.assign(pt->best.begin() + k0, pt->best.begin() + k1); }
+        SupportOut spsub;
+        if (sp) {
+            spsub.group.assign(sp->group.begin() + k0, sp->group.begin() + k1); spsub.ngroups.assign(sp->ngroups.begin() + k0, sp->ngroups.begin() + k1);
+            spsub.score.assign(sp->score.begin() + k0, sp->score.begin() + k1); spsub.rec.assign(sp->rec.begin() + k0, sp->rec.begin() + k1);
+        }
         return score_mutations_planned(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1),
                                        std::vector<const std::vector<Mut>*>(muts.begin() + k0, muts.begin() + k1),
-                                       pt ? std::vector<std::vector<Mut>*>() : std::vector<std::vector<Mut>*>(outs.begin() + k0, outs.begin() + k1),
-                                       delta_out ? &dsub : nullptr, psub, pt ? &ptsub : nullptr);
+                                       pt || sp ? std::vector<std::vector<Mut>*>() : std::vector<std::vector<Mut>*>(outs.begin() + k0, outs.begin() + k1),
+                                       delta_out ? &dsub : nullptr, psub, pt ? &ptsub : nullptr, sp ? &spsub : nullptr);
     };
     if (sparse && R > 1 && sparse_bytes > device_share_bytes()) return in_halves(as.size(), sub);
     if (!sparse && fit_share(as, 0, 2) < as.size()) return in_share_chunks(as, 2, sub);   // sub-batches that fit a slab
@@ -837,6 +845,13 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             point_layout(as[k], &pfirst[k], &ptriv[k]);
             if (!as[k]->E) point_rows_seed(ptriv[k], pt->table[k], pt->best[k]);
         }
+    // a support call: an AlignData without events has every score at its seed and all-zero records
+    if (sp)
+        for (int k = 0; k < R; k++)
+            if (!as[k]->E) {
+                if (sp->score[k]) std::fill(sp->score[k], sp->score[k] + plan[k].M, -1e-6);
+                memset(sp->rec[k], 0, (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
+            }
     if (specs.empty()) return PS_OK;
     Batch b;
     SlabHold slab;   // full matrices: one of the process's slabs for the duration of this call (released at every return)
@@ -871,10 +886,11 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         const EditPlan& p = plan[k];
         ints += (size_t)p.M * 7 + (size_t)p.M * p.ncolmax + p.nr0 + 16;
         if (pt) ints += pfirst[k].size() + ptriv[k].size();
+        if (sp) ints += (size_t)as[k]->E;
         dbls += (size_t)as[k]->E * std::max(p.nr0, 1) + (size_t)as[k]->E * std::max(p.M, 1) + std::max(p.M, 1) + (size_t)as[k]->E * (as[k]->states.size() + 8);
     }
     DBuf& mb = rt->buf("mutint");
-    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + sizeof(PointArgs))));
+    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max(sizeof(PointArgs), sizeof(SupportArgs)))));
     DBuf& db = rt->buf("mutdbl");
     PS_TRY(db.ensure(dbls * sizeof(double)));
     int* dp = mb.as<int>();
@@ -900,8 +916,21 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         PS_TRY(pb.ensure(std::max<size_t>(pt_bytes, 16)));
         d_pt = pb.as<char>();
     }
+    // a support call: the scores, then the records, of all AlignData back to back in one buffer — ONE device-to-host copy
+    std::vector<size_t> sscore_at(R, 0), srec_at(R, 0);
+    size_t sp_bytes = 0;
+    char* d_sp = nullptr;
+    auto sp_live = [&](int k) { return plan[k].M > 0 && as[k]->E > 0; };
+    if (sp) {
+        for (int k = 0; k < R; k++) if (sp_live(k)) { sscore_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sizeof(double); }
+        for (int k = 0; k < R; k++) if (sp_live(k)) { srec_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support); }
+        DBuf& sb = rt->buf("support");
+        PS_TRY(sb.ensure(std::max<size_t>(sp_bytes, 16)));
+        d_sp = sb.as<char>();
+    }
     std::vector<ScoreArgs> sas(R);
     std::vector<PointArgs> pts(pt ? R : 0);
+    std::vector<SupportArgs> sps(sp ? R : 0);
     for (int k = 0; k < R; k++) {
         const EditPlan& p = plan[k];
         ScoreArgs& sa = sas[k];
@@ -928,18 +957,26 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             if (pt->best[k] && as[k]->E) q.best = (ps_point_best*)(d_pt + best_at[k]);
             if (!q.table && !q.best) q.npos = 0;
         }
+        if (sp) {
+            SupportArgs& q = sps[k];
+            memset(&q, 0, sizeof(q));
+            q.group = push(std::vector<int>(sp->group[k], sp->group[k] + as[k]->E));
+            if (sp_live(k)) { q.ngroups = sp->ngroups[k]; q.score = (double*)(d_sp + sscore_at[k]); q.out = (ps_edit_support*)(d_sp + srec_at[k]); }
+        }
         if (!p.M || !as[k]->E) { sa.njobs = 0; sa.nitems_per_job = 0; }   // nothing to score for this AlignData: its blocks leave at once
     }
     // the edit tables and their descriptors (ScoreArgs, behind the tables in the same buffer) in one copy
     const size_t sa_at = (stage.size() * sizeof(int) + 63) / 64 * 64;
     const size_t pt_at = (sa_at + (size_t)R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them)
-    std::vector<char> blob(pt_at + pts.size() * sizeof(PointArgs));
+    std::vector<char> blob(pt_at + pts.size() * sizeof(PointArgs) + sps.size() * sizeof(SupportArgs));   // (PointArgs or SupportArgs, never both)
     memcpy(blob.data(), stage.data(), stage.size() * sizeof(int));
     memcpy(blob.data() + sa_at, sas.data(), (size_t)R * sizeof(ScoreArgs));
     if (pt) memcpy(blob.data() + pt_at, pts.data(), pts.size() * sizeof(PointArgs));
+    if (sp) memcpy(blob.data() + pt_at, sps.data(), sps.size() * sizeof(SupportArgs));
     PS_TRY(rt->up(dp, blob.data(), blob.size()));
     const ScoreArgs* d_sas = (const ScoreArgs*)((const char*)dp + sa_at);
     const PointArgs* d_pts = pt ? (const PointArgs*)((const char*)dp + pt_at) : nullptr;
+    const SupportArgs* d_sps = sp ? (const SupportArgs*)((const char*)dp + pt_at) : nullptr;
     tk.lap("upload");
     if (tk.on) { PS_HIP(hipStreamSynchronize(rt->stream)); }
     tk.lap("realign fwd+back (rest)");
@@ -958,7 +995,19 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             rt->prof["score"].units += (double)p.M * as[k]->E;
         }
     }
-    PS_TRY(launch_score(rt, b.d, d_sas, sas, d_pts, pt ? &pts : nullptr));
+    PS_TRY(launch_score(rt, b.d, d_sas, sas, d_pts, pt ? &pts : nullptr, d_sps, sp ? &sps : nullptr));
+    if (sp) {
+        char* h_sp = nullptr;
+        if (sp_bytes) PS_TRY(rt->down((void**)&h_sp, d_sp, sp_bytes));
+        PS_HIP(hipStreamSynchronize(rt->stream));
+        for (int k = 0; k < R; k++) {
+            if (!sp_live(k)) continue;
+            if (sp->score[k]) memcpy(sp->score[k], h_sp + sscore_at[k], (size_t)plan[k].M * sizeof(double));
+            memcpy(sp->rec[k], h_sp + srec_at[k], (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
+        }
+        tk.lap("score edits");
+        return PS_OK;
+    }
     if (pt) {
         char* h_pt = nullptr;
         if (pt_bytes) PS_TRY(rt->down((void**)&h_pt, d_pt, pt_bytes));
@@ -1008,6 +1057,25 @@ int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vec
     PointOut pt;
     pt.table = tables; pt.best = bests;
     return score_mutations_planned(rt, as, muts, {}, nullptr, plan, &pt);
+}
+
+// ps_score_mutation_support / ps_batch_score_mutation_support: the chain of score_mutations_multi up to k_score, then k_support instead
+// of k_reduce and one copy back of all scores and records.  group[k]: [E] ids in 0 .. ngroups[k] - 1 (checked by the caller);
+// scores[k]: null or [M]; recs[k]: [M][ngroups[k]].
+int score_mutation_support_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
+                                 const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
+                                 const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs) {
+    const int R = (int)as.size();
+    std::vector<EditPlan> plan(R);
+    par_for(R, [&](int k) { plan_edits(as[k], *muts[k], &plan[k]); });
+    for (int k = 0; k < R; k++) {
+        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
+        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
+        if (plan[k].ncolmax > 64 && as[k]->par.scoring_width > 511) return fail(PS_ERR_UNSUPPORTED, "edit longer than 58 bases with scoring_width > 511");
+    }
+    SupportOut sp;
+    sp.group = group; sp.ngroups = ngroups; sp.score = scores; sp.rec = recs;
+    return score_mutations_planned(rt, as, muts, {}, nullptr, plan, nullptr, &sp);
 }
 
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out) {

@@ -170,6 +170,11 @@ int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::ve
 // ps_point_table / ps_batch_point_table (include/poreseq_hip.h): ScorePoints reduced on the device to rows per position; tables[k]
 // (null or [states][9]) and bests[k] (null or [states]) are host arrays
 int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& tables, const std::vector<ps_point_best*>& bests);
+// ps_score_mutation_support / ps_batch_score_mutation_support (include/poreseq_hip.h): the edit lists scored and reduced on the device per
+// event group; group[k] [E] ids below ngroups[k], scores[k] (null or [M]) and recs[k] ([M][ngroups[k]]) are host arrays
+int score_mutation_support_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
+                                 const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
+                                 const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases);
 int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds, std::vector<Mut>* out);

@@ -265,10 +265,21 @@ struct PointArgs {
     ps_point_best* best;       // NULL, or [npos]
 };
 constexpr int PT_SLOTS = 9;    // deletion, substitution by A / C / G / T, insertion of A / C / G / T
+// A support call (k_support instead of k_reduce, ps_score_mutation_support) likewise has one of these per AlignData beside its
+// ScoreArgs: the events' group ids and where the scores and the per-(edit, group) records go.
+struct SupportArgs {
+    const int* group;          // [njobs] group id of every event, 0 .. ngroups - 1
+    int ngroups;               // 1 .. SUPPORT_MAX_GROUPS (0: nothing to write for this AlignData)
+    double* score;             // [M]
+    ps_edit_support* out;      // [M][ngroups]
+};
+constexpr int SUPPORT_MAX_GROUPS = 8;
 constexpr int SCORE_CLASSES = 5;
-// (d_pts / h_pts: the PointArgs of a point-edit table call on the device and on the host, parallel to the ScoreArgs; null otherwise)
+// (d_pts / h_pts: the PointArgs of a point-edit table call on the device and on the host, parallel to the ScoreArgs; null otherwise.
+//  d_sps / h_sps: the same for the SupportArgs of a support call.  At most one of the two is given.)
 int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
-                 const PointArgs* d_pts = nullptr, const std::vector<PointArgs>* h_pts = nullptr);
+                 const PointArgs* d_pts = nullptr, const std::vector<PointArgs>* h_pts = nullptr,
+                 const SupportArgs* d_sps = nullptr, const std::vector<SupportArgs>* h_sps = nullptr);
 int launch_begin(Runtime* rt, const BatchD& b);
 int launch_gather_best(Runtime* rt, const BatchD& b, double* out);   // out[job] = the job's forward maxScore (JobOut.best)
 

@@ -1312,6 +1312,68 @@ __global__ __launch_bounds__(256) void k_point_table(const ScoreArgs* __restrict
     if (q.table && t < PT_SLOTS * np) q.table[(size_t)PT_SLOTS * p0 + t] = s_row[t];
 }
 
+// k_reduce with the events' terms also added up per event group, and per (edit, group) the events that span the edit and how many
+// of those have a positive / negative term (ps_edit_support, include/poreseq_hip.h).  A thread per edit walks the events in order
+// (k_reduce's coalesced reads of delta[e][m], plain FP64 adds).  An event's group id and its re-aligned span (JobOut.has_index /
+// refstart / refend as k_updaterefs left them behind the backtrace) are the same for every thread of a step: the block stages them
+// in LDS, SUP_EV events at a time.  The accumulators are never indexed by a runtime value (they would go to scratch): the loop over
+// g is unrolled over all SUPPORT_MAX_GROUPS and `acc[g] += (grp == g) ? d : 0.0` leaves the other groups' sums as they are — an
+// accumulator starts at +0.0 and can therefore never be -0.0, the one value that adding +0.0 would change.
+constexpr int SUP_EV = 256;
+__global__ __launch_bounds__(256) void k_support(BatchD b, const ScoreArgs* __restrict__ A, const SupportArgs* __restrict__ Q) {
+    const ScoreArgs& a = A[blockIdx.y];
+    const SupportArgs& q = Q[blockIdx.y];
+    const int M = a.nitems_per_job, njobs = a.njobs, G = q.ngroups;
+    if ((int)(blockIdx.x * blockDim.x) >= M || !njobs || !G) return;   // (the same for every thread of the block)
+    __shared__ int s_grp[SUP_EV], s_lo[SUP_EV], s_hi[SUP_EV];
+    const int t = threadIdx.x;
+    const int m = blockIdx.x * blockDim.x + t;
+    const bool have = m < M;
+    // column of the 5-mer that begins at the edit's first base; a skipped edit (start > length) is spanned by no event
+    const int col = (have && !a.m_skip[m]) ? a.m_start[m] + 1 : -0x7fffffff;
+    double s = -1e-6;
+    double acc[SUPPORT_MAX_GROUPS];
+    int cov[SUPPORT_MAX_GROUPS], pos[SUPPORT_MAX_GROUPS], neg[SUPPORT_MAX_GROUPS];
+#pragma unroll
+    for (int g = 0; g < SUPPORT_MAX_GROUPS; g++) { acc[g] = 0.0; cov[g] = 0; pos[g] = 0; neg[g] = 0; }
+    for (int e0 = 0; e0 < njobs; e0 += SUP_EV) {
+        if (e0) __syncthreads();   // (everyone is done with the previous events)
+        if (e0 + t < njobs) {
+            const JobOut* O = b.jobs[a.job0 + e0 + t].out;
+            const bool span = O->has_index != 0;     // a positive ref_align entry: refstart / refend are the int of the first / last
+            s_grp[t] = q.group[e0 + t];
+            s_lo[t] = span ? O->refstart : 1;
+            s_hi[t] = span ? O->refend : 0;
+        }
+        __syncthreads();
+        const int ne = min(SUP_EV, njobs - e0);
+        if (have)
+            for (int k = 0; k < ne; k++) {
+                const double d = a.delta[(size_t)(e0 + k) * M + m];
+                s += d;
+                const int grp = s_grp[k];
+                const bool cv = s_lo[k] <= col && col <= s_hi[k];
+#pragma unroll
+                for (int g = 0; g < SUPPORT_MAX_GROUPS; g++) {
+                    const bool in = grp == g;
+                    acc[g] += in ? d : 0.0;
+                    cov[g] += (in && cv) ? 1 : 0;
+                    pos[g] += (in && cv && d > 0) ? 1 : 0;
+                    neg[g] += (in && cv && d < 0) ? 1 : 0;
+                }
+            }
+    }
+    if (!have) return;
+    q.score[m] = s;
+#pragma unroll
+    for (int g = 0; g < SUPPORT_MAX_GROUPS; g++)
+        if (g < G) {
+            ps_edit_support r;
+            r.sum = acc[g]; r.cover = cov[g]; r.pos = pos[g]; r.neg = neg[g]; r.reserved = 0;
+            q.out[(size_t)m * G + g] = r;
+        }
+}
+
 // latch the reference's "stripe_width == 0" decision (cpp/Alignment.cpp:51-59) for this API call
 __global__ void k_begin(BatchD b) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1487,7 +1549,8 @@ int launch_begin(Runtime* rt, const BatchD& b) {
 // edit scoring of several AlignData of one batch (d_sas: their ScoreArgs on the device, h_sas the same on the host): one launch
 // per kernel over all of them — grid.z (k_reduce: grid.y) is the AlignData, blocks past an AlignData's own sizes leave at once
 int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
-                 const PointArgs* d_pts, const std::vector<PointArgs>* h_pts) {
+                 const PointArgs* d_pts, const std::vector<PointArgs>* h_pts,
+                 const SupportArgs* d_sps, const std::vector<SupportArgs>* h_sps) {
     const int R = (int)h_sas.size();
     int maxE = 0, maxnr0 = 0, maxnr0_all = 0, maxM = 0, cls_max[SCORE_CLASSES] = {0, 0, 0, 0, 0};
     int64_t maxS = 0;
@@ -1539,6 +1602,19 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
         hipLaunchKernelGGL(k_point_table, dim3((maxnpos + PT_POS - 1) / PT_POS, R), dim3(256), 0, rt->stream, d_sas, d_pts);
         PS_LAUNCH_CHECK();
         prof_end(rt, "point_table", bytes);
+        return PS_OK;
+    }
+    if (h_sps) {   // a support call (every AlignData of it): the score per edit and a record per (edit, group)
+        double bytes = 0;
+        for (int k = 0; k < R; k++) {
+            const ScoreArgs& a = h_sas[k];
+            if (!a.njobs || !a.nitems_per_job) continue;
+            bytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 + 24.0 * (*h_sps)[k].ngroups) * a.nitems_per_job;
+        }
+        prof_begin(rt);
+        hipLaunchKernelGGL(k_support, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, d_sas, d_sps);
+        PS_LAUNCH_CHECK();
+        prof_end(rt, "support", bytes);
         return PS_OK;
     }
     hipLaunchKernelGGL(k_reduce, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, d_sas);

@@ -11,7 +11,7 @@ import copy
 import numpy as np
 
 from . import _capi
-from .util import MutationInfo, MutationScore
+from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas
 
 
 def _api():
@@ -62,6 +62,31 @@ def point_table_from_list(n, start, orig, mut, score):
     slot = np.argmax(np.where(np.isnan(table), -np.inf, table), axis=1).astype(np.int32)
     margin = table[np.arange(int(n)), slot]
     return table, margin, slot, np.sum(table > 0, axis=1).astype(np.int32)
+
+
+def _scored_list(start, orig, mut, score):
+    out = []
+    for i in range(len(start)):
+        s = MutationScore()
+        s.start = int(start[i])
+        s.orig = orig[i]
+        s.mut = mut[i]
+        s.score = float(score[i])
+        out.append(s)
+    return out
+
+
+def _support_on(api, h, hm, n_events, seq_len, grp, G):
+    """(scores, support, scored list) of the edit list `hm` on the AlignData `h`: ps_score_mutation_support, or — a library without
+    the entry point — the literal reduction of its score_mutation_deltas and of the refs it leaves (util.support_from_deltas)"""
+    start, orig, mut, _ = api.muts_export(hm)
+    if "ps_score_mutation_support" in api.missing:
+        deltas = api.score_mutation_deltas(h, hm, n_events, len(start))
+        spans = spans_from_refs(api.align_event_refs(h, n_events))
+        scores, sup = support_from_deltas(deltas, grp, G, spans, start, seq_len)
+    else:
+        scores, sup = api.score_mutation_support(h, hm, len(start), grp, G)
+    return scores, sup, _scored_list(start, orig, mut, scores)
 
 
 class PSAlign:
@@ -209,6 +234,25 @@ class PSAlign:
                 return self._scores_to_py(d.api, hs)
             finally:
                 d.api.muts_destroy(hs)
+
+    def ScoreMutationSupport(self, muts=None, groups=None, n_groups=None):
+        """Per-edit read support by event group (ps_score_mutation_support): (scores [M], support [M, G], scored list).
+        `muts` is a MutationInfo list, scored as by ScoreMutations; None means every point edit (FindPointMutations' list) at
+        `point_width`, as ScorePoints.  `groups` gives every event a group id 0 .. G - 1 — by default its strand, 0 template and
+        1 complement (ev.model.complement) — and `n_groups` = G (1 .. 8; default 2 for strands, else the largest id + 1).
+        scores are ScoreMutations' bit for bit and the scored list is what it returns.  support is a structured array
+        (_capi.EDIT_SUPPORT): per edit and group `sum`, the group's events' terms added in event order (ALL its events: a read's
+        term is not zero outside its aligned span), `cover`, the events of the group whose re-aligned span holds the edit
+        (refstart <= start + 1 <= refend — a span test, not a likelihood test: a covering read's term can be zero), and `pos` /
+        `neg`, the covering events with a positive / negative term.  The events x edits matrix stays on the device (k_support);
+        `self` is not modified.  ValueError for groups that do not fit."""
+        grp, G = support_groups(self.events, groups, n_groups)
+        with PSAlign._Data(self, point_width=muts is None) as d:
+            hm = d.api.find_point_mutations(d.h) if muts is None else d.api.muts_create(muts)
+            try:
+                return _support_on(d.api, d.h, hm, len(self.events), len(self.sequence), grp, G)
+            finally:
+                d.api.muts_destroy(hm)
 
     def ScoreMutationDeltas(self, muts):
         """ndarray [events][edits]: what each event adds to each edit's score (MakeMutations.cpp:51); `ScoreMutations` returns

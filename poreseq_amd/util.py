@@ -133,3 +133,74 @@ def write_fastq(out, name, seq, qual):
     if len(qual) != len(seq):
         raise ValueError("write_fastq: %d qualities for %d bases" % (len(qual), len(seq)))
     out.write('@{}\n{}\n+\n{}\n'.format(name, seq, ''.join(chr(33 + int(q)) for q in qual)))
+
+
+def support_groups(events, groups=None, n_groups=None):
+    """(group ids int32 [E], G) of a support call (PSAlign.ScoreMutationSupport): `groups` defaults to the strand of every event
+    (0 template, 1 complement, from ev.model.complement) and `n_groups` to 2 for that default, otherwise to the largest id + 1.
+    ValueError for a list that is not one id per event, G outside 1 .. 8 or an id outside 0 .. G - 1."""
+    import numpy as np
+    E = len(events)
+    if groups is None:
+        groups = [1 if getattr(ev.model, 'complement', False) else 0 for ev in events]
+        if n_groups is None:
+            n_groups = 2
+    grp = np.asarray(list(groups), dtype=np.int64).reshape(-1)
+    if grp.size != E:
+        raise ValueError("support: %d group ids for %d events" % (grp.size, E))
+    G = int(n_groups) if n_groups is not None else (int(grp.max()) + 1 if E else 1)
+    if not 1 <= G <= 8:
+        raise ValueError("support: n_groups = %d, allowed are 1 .. 8" % G)
+    bad = np.flatnonzero((grp < 0) | (grp >= G))
+    if bad.size:
+        raise ValueError("support: event %d has group %d, n_groups = %d" % (int(bad[0]), int(grp[bad[0]]), G))
+    return grp.astype(np.int32), G
+
+
+def spans_from_refs(ref_aligns):
+    """int64 [E, 2]: (refstart, refend) of every event — the int of the first and of the last positive entry of its ref_align
+    (cpp/EventData.h:110-169) — and (1, 0), an empty span, for an event without a positive entry."""
+    import numpy as np
+    out = np.empty((len(ref_aligns), 2), dtype=np.int64)
+    for e, ra in enumerate(ref_aligns):
+        on = np.asarray(ra)[np.asarray(ra) > 0]
+        out[e] = (int(on[0]), int(on[-1])) if on.size else (1, 0)
+    return out
+
+
+def support_from_deltas(deltas, groups, n_groups, spans, starts, seq_len):
+    """The definition of what ps_score_mutation_support returns, in numpy — and the path of a library without the entry point.
+    deltas [E, M]: every event's term of every edit's score (ScoreMutationDeltas); groups [E] ids in 0 .. n_groups - 1;
+    spans [E, 2]: (refstart, refend) of the events as re-aligned by that call, empty (refstart > refend) for an event without
+    alignment (`spans_from_refs`); starts [M] the edits' starts; seq_len the length of the sequence they edit.
+    Returns (scores float64 [M], support [M, n_groups] of _capi.EDIT_SUPPORT):
+      scores   -1e-6 plus all events' terms in event order (the bits of ScoreMutations)
+      sum      0.0 plus the terms of the group's events in event order, covering or not
+      cover    events of the group with refstart <= start + 1 <= refend; an edit with start > seq_len (skipped by ScoreMutations) has none
+      pos/neg  those of them with a term > 0 / < 0
+    `cover` is a span test, not a likelihood test: a covering read's term can be zero and a read's term is not zero outside its span."""
+    import numpy as np
+    from ._capi import EDIT_SUPPORT
+    deltas = np.asarray(deltas, dtype=np.float64)
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    E, M = (deltas.shape[0], starts.size) if deltas.ndim == 2 else (0, starts.size)
+    deltas = deltas.reshape(E, M)
+    grp = np.asarray(groups, dtype=np.int64).reshape(-1)
+    G = int(n_groups)
+    if grp.size != E or not 1 <= G <= 8 or np.any((grp < 0) | (grp >= G)):
+        raise ValueError("support_from_deltas: groups / n_groups")
+    spans = np.asarray(spans, dtype=np.int64).reshape(E, 2)
+    col = starts + 1
+    live = starts <= int(seq_len)
+    scores = np.full(M, -1e-6, dtype=np.float64)
+    sup = np.zeros((M, G), dtype=EDIT_SUPPORT)
+    for e in range(E):
+        d = deltas[e]
+        scores = scores + d
+        g = int(grp[e])
+        sup['sum'][:, g] = sup['sum'][:, g] + d
+        cv = live & (spans[e, 0] <= col) & (col <= spans[e, 1])
+        sup['cover'][:, g] += cv
+        sup['pos'][:, g] += cv & (d > 0)
+        sup['neg'][:, g] += cv & (d < 0)
+    return scores, sup
