@@ -74,7 +74,11 @@ typedef struct ps_align ps_align;
  *   model[E][4][1024]   level_mean, level_stdv, sd_mean, sd_stdv
  *   trans[E][4]         prob_skip, prob_stay, prob_extend, prob_insert
  *   evseq/evseq_off     each event's own 2D base-called sequence (may be NULL)
- * Everything is copied; the caller keeps ownership of its buffers. */
+ * Everything is copied; the caller keeps ownership of its buffers.
+ * Tables that make an emission +infinity — a level with stdv == 0, a model row with level_stdv == 0 or an infinite lambda =
+ * sd_mean^3 / sd_stdv^2, a lik_offset that is not finite — are PS_ERR_BAD_ARG, the message naming the first of them.  Other values
+ * outside the reference's domain (NaN or infinite means, negative or infinite deviations) are taken; ps_viterbi_mutate and
+ * ps_batch_viterbi_mutate alone answer PS_ERR_BAD_ARG for such an AlignData. */
 int ps_align_create(ps_align** out, const char* seq, int64_t seq_len, int32_t n_events,
                     const int64_t* level_off, const double* mean, const double* stdv,
                     const double* ref_align, const double* ref_like, const double* model,
@@ -321,7 +325,9 @@ int ps_set_device_fraction(double fraction);
 
 /* Hot-kernel instrumentation for bench.py: accumulated HIP-event time (ms), launches and
  * algorithmic bytes of the named kernel class ("fill" = k_fill, "sweep" = the strip sweeps k_sweep / k_sweeps / k_sweep2 and their _w builds,
- * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab";
+ * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
+ * "fill_pair" / "fill_pair_fwd" / "fill_cmp" / "fill_512" / "fill_1024" / "fill_wide" (which form a k_fill launch took), "score_g7" .. "score_g64"
+ * (k_score's size classes) and "fill_ieee" / "sweep_ieee" / "score_ieee" (launches that took the IEEE-division build);
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =
  * alignment chunks (launches) over distinct sequences (units) of ps_score_sequences. */
 /* ps_prof_enable(1) makes every hot-kernel launch be bracketed by HIP events on the library's stream

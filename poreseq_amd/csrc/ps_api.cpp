@@ -173,9 +173,16 @@ int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
     *nb = n;
     return PS_OK;
 }
+// ViterbiMutate on emissions that are -infinity or NaN: a position whose candidates are all NaN leaves the back-pointer -1 behind
+// (k_vit_steps), which the back-trace would index with — refused
+static int viterbi_refuses(const Align& a, const char* call) {
+    if (a.nonfinite.empty()) return PS_OK;
+    return fail(PS_ERR_BAD_ARG, std::string(call) + ": " + a.nonfinite + " (ViterbiMutate needs finite levels with stdv > 0 and a model with positive deviations)");
+}
 int ps_viterbi_mutate(ps_align* a, int32_t nkeep, double skip, double stay, double mmin, double mmax,
                       int32_t verbose, ps_seqs** out) {
     if (!a || !out || a->a.E == 0 || nkeep < 0) return fail(PS_ERR_BAD_ARG, "ps_viterbi_mutate");
+    PS_TRY(viterbi_refuses(a->a, "ps_viterbi_mutate"));
     NEED_RT();
     std::unique_ptr<ps_seqs> s(new ps_seqs());
     PS_TRY(viterbi_mutate(rt, &a->a, nkeep, skip, stay, mmin, mmax, &s->v, verbose != 0));
@@ -347,6 +354,7 @@ int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, i
     if (n && !out) return fail(PS_ERR_BAD_ARG, "ps_batch_viterbi_mutate");
     if (nkeep < 0) return fail(PS_ERR_BAD_ARG, "ps_batch_viterbi_mutate: nkeep");
     for (Align* x : as) if (x->E == 0) return fail(PS_ERR_BAD_ARG, "ps_batch_viterbi_mutate: no events");
+    for (Align* x : as) PS_TRY(viterbi_refuses(*x, "ps_batch_viterbi_mutate"));
     NEED_RT();
     std::vector<std::unique_ptr<ps_seqs>> s(n);
     std::vector<RandState*> rs(n, nullptr);
@@ -424,6 +432,7 @@ int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t build, int32_t nkeep
     PS_TRY(batch_handles(n, a, &as));
     if (nkeep < 0 || build < 0 || build > 3 || cap_T < 0 || (n && !T)) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi");
     for (Align* x : as) if (x->E == 0) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: no events");
+    for (Align* x : as) PS_TRY(viterbi_refuses(*x, "ps_debug_viterbi"));
     NEED_RT();
     return debug_viterbi(rt, as, build, nkeep, skip, stay, mmin, mmax, cap_T, T, obs, bp, lik_final, fwd, paths);
 }

@@ -6,6 +6,7 @@
 // All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_sw.hip,
 // ps_viterbi.hip); there is no CPU implementation of it in this library.
 #include "ps_host.h"
+#include "ps_sane.h"
 
 #include <algorithm>
 #include <atomic>
@@ -171,6 +172,25 @@ int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_event
     const int64_t base = E ? level_off[0] : 0;
     evseqs.resize(E);
     if (evseq && evseq_off) for (int e = 0; e < E; e++) evseqs[e].assign(evseq + evseq_off[e], evseq + evseq_off[e + 1]);
+    // +infinity emissions are refused, the other values outside the reference's domain marked (ps_sane.h)
+    nonfinite.clear();
+    {
+        char msg[200];
+        if (offset_refused(par.lik_offset)) { snprintf(msg, sizeof msg, "lik_offset %g is not finite", par.lik_offset); return fail(PS_ERR_BAD_ARG, msg); }
+        for (int e = 0; e < E; e++) {
+            for (int64_t t = off[e]; t < off[e + 1]; t++) {
+                const double m = mean[base + t], sd = stdv[base + t];
+                if (level_plus_inf(sd)) {
+                    snprintf(msg, sizeof msg, "event %d, level %lld: stdv %g (the emission of the mirrored row is +infinity)", e, (long long)(t - off[e]), sd);
+                    return fail(PS_ERR_BAD_ARG, msg);
+                }
+                if (nonfinite.empty() && level_nonfinite(m, sd)) {
+                    snprintf(msg, sizeof msg, "event %d, level %lld: mean %g, stdv %g", e, (long long)(t - off[e]), m, sd);
+                    nonfinite = msg;
+                }
+            }
+        }
+    }
     h_mean.assign(mean + base, mean + base + ntot);
     h_stdv.assign(stdv + base, stdv + base + ntot);
     h_ra.assign(ref_align + base, ref_align + base + ntot);
@@ -184,7 +204,13 @@ int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_event
         double* dst = mdl.data() + (size_t)e * 6 * NS;
         for (int k = 0; k < NS; k++) {
             const double lm = src[k], ls = src[NS + k], sm = src[2 * NS + k], ss = src[3 * NS + k];
-            const double lam = std::pow(sm, 3) / std::pow(ss, 2);
+            const double lam = model_lambda(sm, ss);
+            if (model_row_plus_inf(ls, lam) || (nonfinite.empty() && model_row_nonfinite(lm, ls, sm, lam))) {   // (rare: the message is built only then)
+                char msg[200];
+                snprintf(msg, sizeof msg, "event %d, model row %d: level_mean %g, level_stdv %g, sd_mean %g, sd_stdv %g", e, k, lm, ls, sm, ss);
+                if (model_row_plus_inf(ls, lam)) return fail(PS_ERR_BAD_ARG, std::string(msg) + " (its emissions are +infinity)");
+                nonfinite = msg;
+            }
             dst[k] = lm; dst[NS + k] = ls; dst[2 * NS + k] = std::log(ls);
             dst[3 * NS + k] = sm; dst[4 * NS + k] = lam; dst[5 * NS + k] = std::log(lam);
         }
@@ -195,7 +221,6 @@ int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_event
     // k_fill's tables: model rows with the reciprocals of the two model divisors, level records per direction with the
     // reciprocal of the level stdv (correctly rounded: host IEEE division)
     std::vector<double> mdl8((size_t)E * (MODEL_ROW_BYTES / 8) * NS), lev((size_t)2 * 4 * std::max<int64_t>(ntot, 1));
-    auto sane = [](double v) { return std::isfinite(v) && v > 1e-100 && v < 1e100; };
     fastdiv = true;
     for (int e = 0; e < E; e++) {
         const double* d6 = mdl.data() + (size_t)e * 6 * NS;
@@ -205,7 +230,7 @@ int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_event
             double* r8 = d8 + (size_t)k * (MODEL_ROW_BYTES / 8);
             r8[0] = lm; r8[1] = 1.0 / ls; r8[2] = ls; r8[3] = d6[2 * NS + k];
             r8[4] = sm; r8[5] = 1.0 / sm; r8[6] = lam; r8[7] = d6[5 * NS + k];
-            if (!sane(ls) || !sane(sm) || !std::isfinite(lm) || !std::isfinite(lam) || std::fabs(lm) > 1e100 || std::fabs(lam) > 1e100) fastdiv = false;
+            if (!sane_model_row(lm, ls, sm, lam)) fastdiv = false;   // (ps_sane.h: the range, and why)
         }
         const int64_t o = off[e];
         const int ne = n[e];
@@ -218,8 +243,8 @@ int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_event
         }
     }
     for (int64_t t = 0; t < ntot; t++)
-        if (!sane(h_stdv[t]) || !std::isfinite(h_mean[t]) || std::fabs(h_mean[t]) > 1e100) fastdiv = false;
-    if (getenv("PORESEQ_EXACT_DIV")) fastdiv = false;   // tests: run the IEEE-division build of k_fill
+        if (!sane_level(h_mean[t], h_stdv[t])) fastdiv = false;
+    if (getenv("PORESEQ_EXACT_DIV")) fastdiv = false;   // tests: the IEEE-division build of every kernel that computes emissions
     // one slab: mean, stdv, lsd, ra, rl, ri [ntot each] | model | trans | out
     const size_t nlev = (size_t)std::max<int64_t>(ntot, 1);
     const size_t bytes = (6 + 8) * nlev * sizeof(double) + (mdl.size() + mdl8.size() + tr.size() + 2) * sizeof(double) + 256 +

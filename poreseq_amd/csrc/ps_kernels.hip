@@ -177,9 +177,10 @@ __global__ __launch_bounds__(256) void k_lo(BatchD b, int ndir) {
 // a/b is formed as  q0 = a*y; r = fma(-b,q0,a); q1 = fma(r,y,q0); r = fma(-b,q1,a); q = fma(r,y,q1)  — Markstein's
 // sequence, whose last step is provably the correctly rounded quotient given y = RN(1/b) and a faithful q1 (Markstein 1990;
 // Muller et al., Handbook of Floating-Point Arithmetic, section 4.7): bit-identical to the reference's IEEE division at 5
-// instructions instead of ~13 (no v_rcp_f64 / v_div_*).  The host enables it per AlignData only when every divisor is a
-// finite, normal, positive number of moderate magnitude; otherwise the kernel divides.  tests/test_fastdiv.py checks the
-// sequence against IEEE division on 10^8 operand pairs, including all-ones and power-of-two significands.
+// instructions instead of ~13 (no v_rcp_f64 / v_div_*).  The host enables it per AlignData only when every table value lies in
+// the range of ps_sane.h, which bounds the numerators as well (an infinite or subnormal numerator breaks the sequence); otherwise
+// the kernel divides.  tests/test_fastdiv.py checks the sequence against IEEE division on 10^8 operand pairs, including all-ones
+// and power-of-two significands; tests/native/emission_check.cpp the whole emission over the corners of the accepted range.
 //
 // Software pipeline (everything that does not depend on a neighbour runs ahead of the recurrence):
 //   windows, 4-step groups  5-mer states of the lane's next four columns (one 16-byte load) and the level record of its
@@ -1460,6 +1461,7 @@ int launch_fill(Runtime* rt, const BatchD& b, const std::vector<JobD>& jobs, int
         with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL(k_fill_wide<fd.value>, dim3(b.njobs * ndir), dim3(P / 2), lds, rt->stream, b, ndir, rc); });
         PS_LAUNCH_CHECK();
         prof_end(rt, "fill", 0.0);
+        if (rt->prof_on) { rt->prof["fill_wide"].launches++; if (!b.fastdiv) rt->prof["fill_ieee"].launches++; }   // (which form ran: host-side counts, no event pair)
         hipLaunchKernelGGL(k_prefix, dim3(b.njobs * ndir), dim3(64), 0, rt->stream, b, ndir);
         PS_LAUNCH_CHECK();
         return PS_OK;
@@ -1509,6 +1511,10 @@ int launch_fill(Runtime* rt, const BatchD& b, const std::vector<JobD>& jobs, int
     else fill_launch<1024, false, false>(rt, b, d_pairs, nwg, ndir, P, maxS, lds);
     PS_LAUNCH_CHECK();
     prof_end(rt, "fill", 0.0);
+    if (rt->prof_on) {   // (which form ran: host-side counts, no event pair; fill_ieee beside the form: the launch divided)
+        rt->prof[pair ? (ndir == 2 ? "fill_pair" : "fill_pair_fwd") : compact ? "fill_cmp" : P <= 512 ? "fill_512" : "fill_1024"].launches++;
+        if (!b.fastdiv) rt->prof["fill_ieee"].launches++;
+    }
     hipLaunchKernelGGL(k_prefix, dim3(b.njobs * ndir), dim3(64), 0, rt->stream, b, ndir);
     PS_LAUNCH_CHECK();
     return PS_OK;
@@ -1585,6 +1591,11 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
         if (k == 4) PS_SCORE(7); else if (k == 0) PS_SCORE(8); else if (k == 1) PS_SCORE(16); else if (k == 2) PS_SCORE(32); else PS_SCORE(64);
 #undef PS_SCORE
         PS_LAUNCH_CHECK();
+        if (rt->prof_on) {   // (which size class ran, and whether it divided: host-side counts)
+            static const char* const cls_name[SCORE_CLASSES] = {"score_g8", "score_g16", "score_g32", "score_g64", "score_g7"};
+            rt->prof[cls_name[k]].launches++;
+            if (!b.fastdiv) rt->prof["score_ieee"].launches++;
+        }
     }
     prof_end(rt, "score", 0.0);
     if (h_pts) {   // a point-table call (every AlignData of it): rows per position instead of a score per edit

@@ -465,6 +465,7 @@ int sweep_run(Runtime* rt, Batch& bt) {
     if (rt->prof_on) {   // (which form ran: host-side counts, no event pair)
         if (NW > 1) rt->prof[NW == 2 ? "sweep_w2" : "sweep_w4"].launches++;
         if (bt.ndir == 2 && bt.sparse) rt->prof["sweep_kept"].launches++;
+        if (!b.fastdiv) rt->prof["sweep_ieee"].launches++;
     }
     hipLaunchKernelGGL(k_best, dim3(b.njobs), dim3(64), 0, rt->stream, b, sw);
     if (bt.ndir == 2) PS_TRY(launch_prefix(rt, b, 2));   // running MaxInfo per column of both directions (the strip jobs' best cell is k_best's)
