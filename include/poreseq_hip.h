@@ -329,7 +329,9 @@ int ps_set_device_fraction(double fraction);
  * "fill_pair" / "fill_pair_fwd" / "fill_cmp" / "fill_512" / "fill_1024" / "fill_wide" (which form a k_fill launch took), "score_g7" .. "score_g64"
  * (k_score's size classes) and "fill_ieee" / "sweep_ieee" / "score_ieee" (launches that took the IEEE-division build);
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =
- * alignment chunks (launches) over distinct sequences (units) of ps_score_sequences. */
+ * alignment chunks (launches) over distinct sequences (units) of ps_score_sequences; "likes_dev" / "likes_host" = chunks of FindMutations'
+ * candidate sequences whose per-base likelihood vectors came from k_likes / from the host loop (a sequence of more than 12 284 states in
+ * the chunk, or PORESEQ_DEBUG_LIKES_HOST=1). */
 /* ps_prof_enable(1) makes every hot-kernel launch be bracketed by HIP events on the library's stream
  * (one extra synchronisation per launch: use it in a separate, untimed pass); ps_prof_enable(2) queues the
  * event pairs instead and reads them when the profile is asked for (no synchronisation per launch: usable

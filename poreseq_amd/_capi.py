@@ -328,9 +328,17 @@ class CApi:
         return [s[off[i]:off[i + 1]] for i in range(n)]
 
     # ------------------------------------------------------------------ free functions
-    def score_alignments(self, h, n_events, likes_len=None):
+    def score_alignments(self, h, n_events, likes_len=None, likes=None):
+        """-> scores float64 [n_events]; with likes_len, or a caller's `likes` (contiguous float64 of at least len(sequence) entries,
+        accumulated into in place), -> (scores, likes): the per-base cumulative likelihoods of cpp/MakeMutations.cpp:168-189"""
         scores = np.zeros(n_events, dtype=np.float64)
-        likes = np.zeros(likes_len, dtype=np.float64) if likes_len is not None else None
+        if likes is not None:
+            if not (isinstance(likes, np.ndarray) and likes.dtype == np.float64 and likes.flags.c_contiguous and likes.flags.writeable):
+                raise PoreseqError("score_alignments: likes must be a writeable contiguous float64 array")
+        elif likes_len is not None:
+            likes = np.zeros(likes_len, dtype=np.float64)
+        if likes is not None and likes.size < int(self.lib.ps_align_sequence_length(h)):      # (the library writes len(sequence) entries)
+            raise PoreseqError("score_alignments: likes has %d entries, the sequence %d bases" % (likes.size, int(self.lib.ps_align_sequence_length(h))))
         self.check(self.lib.ps_score_alignments(h, _dp(scores), _dp(likes) if likes is not None else None))
         return (scores, likes) if likes is not None else scores
 

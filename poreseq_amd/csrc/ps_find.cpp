@@ -9,6 +9,7 @@
 #include <map>
 #include <thread>
 
+#include "ps_extract.h"   // the tail of FindMutations on plain host data (no HIP)
 #include "ps_host.h"
 #include "ps_sw.h"
 
@@ -17,6 +18,9 @@ namespace ps {
 // cap on the DP-matrix bytes of one chunk of candidate-sequence alignments (FindMutations' seeds, ps_score_sequences): this runtime's
 // share of the device (ps_mem.cpp)
 double fwd_chunk_cap() { return device_share_bytes(); }
+
+// PORESEQ_DEBUG_LIKES_HOST=1 (tests; read per call): every chunk's per-base likelihood vectors come from the host loop
+static bool likes_on_host() { const char* e = getenv("PORESEQ_DEBUG_LIKES_HOST"); return e && atoi(e) != 0; }
 
 static void fillinds(SwResult& al) {  // cpp/swlib.cpp:342-365
     if (al.a.empty()) return;
@@ -47,101 +51,6 @@ size_t fwd_chunk_end(const std::vector<FwdUnit>& units, size_t q0, double cap, i
         bytes += add; *nref += (size_t)a->ntot; q1++;
     }
     return q1;
-}
-
-static int argmax(const std::vector<double>& v) { return (int)(std::max_element(v.begin(), v.end()) - v.begin()); }
-
-// the tail of FindMutations for one AlignData (host only): likelihood differences along the pairwise alignments ->
-// clamped CUSUM -> greedy extraction of candidate edits (cpp/FindMutations.cpp:51-183)
-static int extract_edits(Align* a, const std::vector<std::string>& seeds, std::vector<SwResult>& als, const std::vector<double>& base,
-                         std::vector<Mut>* out) {
-    const size_t L = a->bases.size();
-    const int S = (int)seeds.size();
-    std::vector<std::vector<double>> dl(S);
-    for (int k = 0; k < S; k++) {
-        SwResult& al = als[k];
-        const std::vector<double>& rl = a->seqlikes[seeds[k]];
-        for (size_t q = 0; q < al.a.size(); q++) { al.a[q] -= 2; al.b[q] -= 2; }
-        while (!al.a.empty() && (al.a[0] < 0 || al.b[0] < 0)) { al.a.erase(al.a.begin()); al.b.erase(al.b.begin()); }
-        const size_t n = al.a.size();
-        std::vector<double> x(n), y(n);
-        for (size_t q = 0; q < n; q++) {
-            x[q] = (size_t)al.a[q] < base.size() ? base[al.a[q]] : 0.0;
-            y[q] = (size_t)al.b[q] < rl.size() ? rl[al.b[q]] : 0.0;
-        }
-        for (size_t q = n; q-- > 1;) { x[q] -= x[q - 1]; y[q] -= y[q - 1]; }
-        if (n) { x[0] = 0; y[0] = 0; }
-        std::vector<double>& cs = dl[k];
-        cs.resize(n);
-        double run = 0;
-        for (size_t q = 0; q < n; q++) {
-            run += y[q] - x[q];
-            if (run < 0) run = 0;
-            cs[q] = run;
-            if (std::fabs(x[q] - y[q]) < 1e-5) cs[q] = 0;
-        }
-    }
-    // greedy extraction (cpp/FindMutations.cpp:111-183).  The reference rescans every seed's vector for its maximum on
-    // each round; here per-seed block maxima (128 entries per block) are kept current instead — same first-maximum
-    // semantics (std::max_element), same output.
-    const size_t BLK = 128;
-    std::vector<std::vector<double>> bmax(S);
-    auto block_refresh = [&](int k, size_t blk) {
-        const std::vector<double>& v = dl[k];
-        const size_t lo = blk * BLK, hi = std::min(v.size(), lo + BLK);
-        double m = v[lo];
-        for (size_t q = lo + 1; q < hi; q++) if (v[q] > m) m = v[q];
-        bmax[k][blk] = m;
-    };
-    auto seed_argmax = [&](int k) -> int {   // index of the first maximum of dl[k]
-        const std::vector<double>& bm = bmax[k];
-        size_t bb = 0;
-        for (size_t q = 1; q < bm.size(); q++) if (bm[q] > bm[bb]) bb = q;
-        const std::vector<double>& v = dl[k];
-        const size_t lo = bb * BLK, hi = std::min(v.size(), lo + BLK);
-        size_t at = lo;
-        for (size_t q = lo + 1; q < hi; q++) if (v[q] > v[at]) at = q;
-        return (int)at;
-    };
-    std::vector<double> top(S, 0.0);
-    std::vector<int> topi(S, 0);
-    for (int k = 0; k < S; k++) {
-        if (dl[k].empty()) continue;
-        bmax[k].resize((dl[k].size() + BLK - 1) / BLK);
-        for (size_t blk = 0; blk < bmax[k].size(); blk++) block_refresh(k, blk);
-        topi[k] = seed_argmax(k);
-        top[k] = dl[k][topi[k]];
-    }
-    while (out->size() < L / 3) {
-        const int w = argmax(top);
-        std::vector<double>& v = dl[w];
-        if (v.empty()) break;
-        const int ind = topi[w];
-        if (v[ind] < 0.25) break;
-        int i1 = (int)(std::find(v.begin() + ind, v.end(), 0.0) - v.begin());
-        int i0 = -1;
-        for (int q = ind; q >= 0; q--) if (v[q] == 0) { i0 = q; break; }
-        if (i0 < 0) i0 = 0;
-        if (i1 < 0) i1 = 0;
-        if ((size_t)i0 >= v.size()) i0 = (int)v.size() - 1;
-        if ((size_t)i1 >= v.size()) i1 = (int)v.size() - 1;
-        const int s1 = als[w].a[i0], s2 = als[w].b[i0], e1 = als[w].a[ind], e2 = als[w].b[ind];
-        Mut m;
-        m.start = s1;
-        if ((size_t)s1 > a->bases.size() || (size_t)s2 > seeds[w].size()) return PS_ERR_BAD_ARG;
-        m.orig = a->bases.substr(s1, (size_t)(e1 - s1));
-        m.mut = seeds[w].substr(s2, (size_t)(e2 - s2));
-        while (!m.orig.empty() && !m.mut.empty() && m.orig.front() == m.mut.front()) {
-            m.orig.erase(m.orig.begin()); m.mut.erase(m.mut.begin()); m.start++;
-        }
-        while (!m.orig.empty() && !m.mut.empty() && m.orig.back() == m.mut.back()) { m.orig.pop_back(); m.mut.pop_back(); }
-        if (!m.orig.empty() || !m.mut.empty()) out->push_back(m);
-        std::fill(v.begin() + i0, v.begin() + i1 + 1, 0.0);
-        for (size_t blk = (size_t)i0 / BLK; blk <= (size_t)i1 / BLK; blk++) block_refresh(w, blk);
-        topi[w] = seed_argmax(w);
-        top[w] = v[topi[w]];
-    }
-    return PS_OK;
 }
 
 // FindMutations (cpp/FindMutations.cpp:24-186) for several AlignData in lock-step: one Smith-Waterman batch for all
@@ -302,6 +211,8 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             std::vector<std::vector<double>> lks(q1 - q0);
             bool on_device = true;
             for (size_t q = q0; q < q1; q++) if ((int)need[q].states.size() > likes_max_states()) on_device = false;
+            if (likes_on_host()) on_device = false;
+            if (rt->prof_on) rt->prof[on_device ? "likes_dev" : "likes_host"].launches++;   // (chunks that took each path: host-side counts)
             if (on_device) {
                 std::vector<LikeGroup> groups(q1 - q0);
                 int64_t out_tot = 0;
@@ -350,9 +261,15 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     }
     tk.lap("seed likes");
     std::vector<int> rcs(R, PS_OK);
-    par_for(R, [&](int r) {
-        std::vector<SwResult> als(als_all.begin() + pair0[r], als_all.begin() + pair0[r + 1]);
-        rcs[r] = extract_edits(as[r], *seeds[r], als, base[r], outs[r]);
+    par_for(R, [&](int r) {   // likelihood differences -> clamped CUSUM -> greedy extraction (ps_extract.h), per AlignData
+        const std::vector<std::string>& sd = *seeds[r];
+        std::vector<std::vector<int>> ia(sd.size()), ib(sd.size());
+        std::vector<const std::vector<double>*> lk(sd.size());
+        for (size_t k = 0; k < sd.size(); k++) {
+            ia[k] = std::move(als_all[pair0[r] + k].a); ib[k] = std::move(als_all[pair0[r] + k].b);
+            lk[k] = &as[r]->seqlikes[sd[k]];
+        }
+        if (extract_edits(as[r]->bases, sd, ia, ib, base[r], lk, outs[r])) rcs[r] = PS_ERR_BAD_ARG;
     });
     for (int r = 0; r < R; r++) if (rcs[r] != PS_OK) return fail(rcs[r], "FindMutations: alignment index outside the sequence");
     tk.lap("extract");

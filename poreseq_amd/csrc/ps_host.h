@@ -96,7 +96,6 @@ struct Align {
 };
 
 std::vector<int> states_of(const std::string& bases);
-std::string apply_edit(const std::string& b, const Mut& m);
 void accumulate_likes(const double* ra, const double* rl, int n, int C, double* likes);
 
 // strip sweeps (ps_sweep.hip, ps_sweepw.hip): K rows per lane on NW wavefronts per sweep

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/poreseq_hip.h"
+#include "ps_greedy.h" // struct Mut, apply_edit, greedy_apply (host-only, no HIP)
 #include "ps_plan.h"   // MAT_FRONT, MAT_BACK and the memory plan's arithmetic (host-only, no HIP)
 
 namespace ps {
@@ -111,12 +112,7 @@ int runtime(Runtime** out);  // PS_ERR_NO_DEVICE when no usable GPU; never falls
 int second_stream(Runtime* rt, hipStream_t* out);
 int live_runtimes();   // host threads that currently own a runtime (ps_runtime.cpp)
 
-// ---- mutation list (vector<MutInfo>/vector<MutScore>, cpp/AlignUtil.h:69-91) ----------------
-struct Mut {
-    int start = 0;
-    std::string orig, mut;
-    double score = -1e-6;
-};
+// ---- mutation list: struct Mut, with Sequence(original, mut) and the greedy pass of MakeMutations, in ps_greedy.h (no HIP) ----
 
 // ---- device-side job descriptor: one (event, sequence) alignment ---------------------------
 // Everything a kernel needs about a job hangs off the descriptor itself (device pointers into the owning
