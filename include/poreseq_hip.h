@@ -90,9 +90,19 @@ int ps_align_set_scoring_width(ps_align* a, int32_t width);
 /* A driver that keeps one AlignData alive across several PSAlign calls (events resident in device memory instead of
  * re-marshalled per call) announces each new call with this: it resets what PythonToAlignData would have rebuilt —
  * params.scoring_width and the seed-likelihood cache (cpp/AlignData.h:34), which the reference drops between PSAlign
- * calls (_poreseqcpp.pyx:139-153).  Sequence and events' ref_align / ref_like carry over, exactly as the Python
- * attributes do in the reference. */
+ * calls (_poreseqcpp.pyx:139-153).  The sequence carries over.  The events' ref_align / ref_like carry over as the Python
+ * attributes do in the reference, and those are written only by the calls that end in MakeMutations (ApplyMuts, Mutate,
+ * Refine: UpdatePythonEvents, _poreseqcpp.pyx:375, 434, 471).  ScoreEvents, ScorePoints and ScoreMutations realign a scratch
+ * AlignData and drop it, so a driver announces such a call with ps_align_new_call + ps_align_keep_refs, and the next
+ * ps_align_new_call puts ref_align / ref_like (and what follows from them: ref_index, refstart, refend) back to where that
+ * call found them.  Without ps_align_keep_refs the realignment of a scoring call stays in the handle, and with any
+ * realign_width that does not bring an event back to the same path the next call starts somewhere a PSAlign never is. */
 int ps_align_new_call(ps_align* a, int32_t scoring_width);
+/* The call just announced will not write ref_align / ref_like back (no ps_make_mutations follows): remember them as they are
+ * now — the last write-back point — for the next ps_align_new_call to restore.  One device copy of the refs the first time
+ * after a write-back, nothing while scoring calls follow each other; ps_make_mutations / ps_batch_make_mutations forget the
+ * kept refs, and calls that write back (never announced this way) cost nothing extra. */
+int ps_align_keep_refs(ps_align* a);
 int32_t ps_align_n_events(const ps_align* a);
 int64_t ps_align_n_levels(const ps_align* a, int32_t ev);
 int64_t ps_align_sequence_length(const ps_align* a);

@@ -742,7 +742,7 @@ std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, doubl
 // lik_offset term, ref: cpp/Viterbi.cpp:300-306) is unchanged because x + 0.0 == x for finite x.
 
 // ================================================================= C ABI
-struct ps_align { Data d; };
+struct ps_align { Data d; std::vector<std::pair<std::vector<double>, std::vector<double>>> kept; };
 struct ps_muts { std::vector<Mut> v; };
 struct ps_seqs { std::vector<std::string> v; };
 
@@ -793,7 +793,25 @@ int ps_align_create(ps_align** out, const char* seq, int64_t seq_len, int32_t n_
 }
 void ps_align_destroy(ps_align* a) { delete a; }
 int ps_align_set_scoring_width(ps_align* a, int32_t w) { if (!a) return fail(PS_ERR_BAD_ARG, "null"); a->d.par.scoring_width = w; return PS_OK; }
-int ps_align_new_call(ps_align* a, int32_t w) { if (!a) return fail(PS_ERR_BAD_ARG, "null"); a->d.par.scoring_width = w; a->d.seqlikes.clear(); return PS_OK; }
+// refs of the last write-back point (ps_align_keep_refs): kept[e] = {ref_align, ref_like}; MakeMutations drops them
+static void restore_refs(ps_align* a) {
+    for (size_t e = 0; e < a->kept.size(); e++) {
+        Event& ev = a->d.ev[e];
+        ev.ref_align = a->kept[e].first; ev.ref_like = a->kept[e].second;
+        ev.updaterefs();
+    }
+}
+int ps_align_new_call(ps_align* a, int32_t w) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "null");
+    a->d.par.scoring_width = w; a->d.seqlikes.clear();
+    restore_refs(a);
+    return PS_OK;
+}
+int ps_align_keep_refs(ps_align* a) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "null");
+    if (a->kept.empty()) for (Event& ev : a->d.ev) a->kept.push_back({ev.ref_align, ev.ref_like});
+    return PS_OK;
+}
 int32_t ps_align_n_events(const ps_align* a) { return a ? (int32_t)a->d.ev.size() : 0; }
 int64_t ps_align_n_levels(const ps_align* a, int32_t e) { return (a && e >= 0 && e < (int)a->d.ev.size()) ? a->d.ev[e].n : -1; }
 int64_t ps_align_sequence_length(const ps_align* a) { return a ? (int64_t)a->d.seq.bases.size() : -1; }
@@ -900,6 +918,7 @@ int ps_score_mutation_deltas(ps_align* a, const ps_muts* in, double* deltas) {
 }
 int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
     if (!a || !in || !nb) return fail(PS_ERR_BAD_ARG, "ps_make_mutations");
+    a->kept.clear();   // a call that writes its refs back
     *nb = make_mutations(a->d, in->v);
     return PS_OK;
 }

@@ -31,7 +31,7 @@
 #include <string>
 #include <vector>
 
-struct ps_align { AlignData d; };
+struct ps_align { AlignData d; std::vector<std::pair<std::vector<double>, std::vector<double>>> kept; };   // kept: ps_align_keep_refs
 struct ps_muts { std::vector<MutScore> v; };
 struct ps_seqs { std::vector<std::string> v; };
 
@@ -75,7 +75,19 @@ int ps_align_create(ps_align** out, const char* seq, int64_t seq_len, int32_t n_
 }
 void ps_align_destroy(ps_align* a) { delete a; }
 int ps_align_set_scoring_width(ps_align* a, int32_t w) { a->d.params.scoring_width = w; return PS_OK; }
-int ps_align_new_call(ps_align* a, int32_t w) { a->d.params.scoring_width = w; a->d.seqlikes.clear(); return PS_OK; }
+int ps_align_new_call(ps_align* a, int32_t w) {
+    a->d.params.scoring_width = w; a->d.seqlikes.clear();
+    for (size_t e = 0; e < a->kept.size(); e++) {   // back to the refs of the last write-back point
+        EventData& ev = a->d.events[e];
+        ev.ref_align = a->kept[e].first; ev.ref_like = a->kept[e].second;
+        ev.updaterefs();
+    }
+    return PS_OK;
+}
+int ps_align_keep_refs(ps_align* a) {
+    if (a->kept.empty()) for (EventData& ev : a->d.events) a->kept.push_back({ev.ref_align, ev.ref_like});
+    return PS_OK;
+}
 int32_t ps_align_n_events(const ps_align* a) { return (int32_t)a->d.events.size(); }
 int64_t ps_align_n_levels(const ps_align* a, int32_t e) { return a->d.events[e].length; }
 int64_t ps_align_sequence_length(const ps_align* a) { return (int64_t)a->d.sequence.bases.size(); }
@@ -170,6 +182,7 @@ int ps_score_mutations(ps_align* a, const ps_muts* in, ps_muts** out) {
 // (the reference only returns the sums: not available from its public functions)
 int ps_score_mutation_deltas(ps_align*, const ps_muts*, double*) { return PS_ERR_UNSUPPORTED; }
 int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
+    a->kept.clear();   // a call that writes its refs back
     *nb = MakeMutations(a->d, in->v);
     return PS_OK;
 }

@@ -68,6 +68,7 @@ SYMBOLS = {
     "ps_align_destroy": (None, [C.c_void_p]),
     "ps_align_set_scoring_width": (C.c_int, [C.c_void_p, C.c_int32]),
     "ps_align_new_call": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ps_align_keep_refs": (C.c_int, [C.c_void_p]),
     "ps_align_n_events": (C.c_int32, [C.c_void_p]),
     "ps_align_n_levels": (C.c_int64, [C.c_void_p, C.c_int32]),
     "ps_align_sequence_length": (C.c_int64, [C.c_void_p]),
@@ -137,7 +138,7 @@ SYMBOLS = {
 # PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations; PSAlign.ScoreMutationSupport reduces
 # score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
+OPTIONAL = frozenset(["ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the

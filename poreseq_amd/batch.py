@@ -20,14 +20,19 @@ class RegionBatch:
     def __init__(self, pas, api=None, resident=True):
         """resident=True keeps one native AlignData per region for the life of the batch: the events are marshalled and
         copied to the GPU once, every later call only announces itself (`ps_align_new_call` resets the scoring width and
-        the seed-likelihood cache, the two things a fresh AlignData would differ in), and sequence / ref_align / ref_like
-        are written back to the Python objects when the batch is closed (or by `sync()`).  resident=False rebuilds the
-        AlignData for every call, as PythonToAlignData does (pyx:139-153); results are identical."""
+        the seed-likelihood cache), and sequence / ref_align / ref_like are written back to the Python objects when the
+        batch is closed (or by `sync()`).  The calls that only score (ScoreEvents, ScoreMutations, PointTable,
+        ScoreMutationSupport) realign the events as a side effect, which the reference drops with its scratch AlignData
+        (only ApplyMuts / Mutate / Refine write ref_align / ref_like back, pyx:375, 434, 471): the handle's refs are kept
+        before such a call (`ps_align_keep_refs`) and put back after it, so the next call starts where a PSAlign would.
+        resident=False rebuilds the AlignData for every call, as PythonToAlignData does (pyx:139-153); results are
+        identical, whatever the order of the calls (tests/test_call_order.py)."""
         self.pas = list(pas)
         self.api = api if api is not None else (self.pas[0]._native() if self.pas else poreseqcpp._api())
         self.rngs = [self.api.rng_create(1) for _ in self.pas]   # rand() of a fresh process per region (Viterbi.cpp:108)
         self.resident = bool(resident)
         self._h = {}
+        self._scratch = set()   # handles built for one scoring call by a library without ps_align_keep_refs (_open)
 
     def load(self, idx=None):
         """Create the resident AlignData of the regions `idx` now (e.g. before a timed section)."""
@@ -71,16 +76,29 @@ class RegionBatch:
         return False
 
     # -- plumbing ---------------------------------------------------------------------------------------------
-    def _open(self, idx, point_width=False):
-        """Native AlignData for the regions `idx`, as PythonToAlignData builds one per PSAlign call (pyx:139-153)."""
+    def _width(self, pa, point_width):
+        return pa.params['point_width'] if (point_width and 'point_width' in pa.params) else pa.params.get('scoring_width', 150)
+
+    def _open(self, idx, point_width=False, keep=False):
+        """Native AlignData for the regions `idx`, as PythonToAlignData builds one per PSAlign call (pyx:139-153).  keep: the call
+        only scores; a resident handle's refs are to come out of it as they went in (`_close` with write_back=False).  A library
+        without ps_align_keep_refs (an older build of the test-suite's checkers) gets a scratch AlignData for such a call, built
+        from the resident one's written-back state, as the reference does."""
         hs = []
+        scratch = keep and self.resident and "ps_align_keep_refs" in self.api.missing
         for i in idx:
             pa = self.pas[i]
-            if self.resident:
+            if scratch:
+                self.sync([i])
+                h = self.api.align_create(pa.sequence, pa.events, pa.params)
+                self.api.check(self.api.lib.ps_align_set_scoring_width(h, int(self._width(pa, point_width))))
+                self._scratch.add(h.value)
+            elif self.resident:
                 self.load([i])
                 h = self._h[i]
-                w = pa.params['point_width'] if (point_width and 'point_width' in pa.params) else pa.params.get('scoring_width', 150)
-                self.api.check(self.api.lib.ps_align_new_call(h, int(w)))
+                self.api.check(self.api.lib.ps_align_new_call(h, int(self._width(pa, point_width))))
+                if keep:
+                    self.api.check(self.api.lib.ps_align_keep_refs(h))
             else:
                 h = self.api.align_create(pa.sequence, pa.events, pa.params)
                 if point_width and 'point_width' in pa.params:
@@ -90,9 +108,15 @@ class RegionBatch:
 
     def _close(self, idx, hs, write_back=True):
         for i, h in zip(idx, hs):
+            if h.value in self._scratch:
+                self._scratch.discard(h.value)
+                self.api.align_destroy(h)
+                continue
             if self.resident:
                 if write_back:
                     self.pas[i].sequence = self.api.align_sequence(h)   # cheap; refs follow at sync() / close()
+                else:   # the end of a call that does not write back: kept refs return now, so that sync() reads them
+                    self.api.check(self.api.lib.ps_align_new_call(h, int(self._width(self.pas[i], False))))
                 continue
             if write_back:
                 pa = self.pas[i]
@@ -131,7 +155,7 @@ class RegionBatch:
     # -- the PSAlign calls of the consensus schedule, for the regions `idx` (default: all) ---------------------------
     def ScoreEvents(self, idx=None):
         idx = list(range(len(self.pas))) if idx is None else list(idx)
-        hs = self._open(idx)
+        hs = self._open(idx, keep=True)
         try:
             sc = self.api.batch_score_alignments(hs, [len(self.pas[i].events) for i in idx])
         finally:
@@ -162,14 +186,13 @@ class RegionBatch:
     def PointTable(self, idx=None, table=True):
         """PSAlign.PointTable for the regions `idx` on their resident AlignData: ONE ps_batch_point_table call — the dense scoring
         chain of Refine over all regions, reduced on the device, one copy back.  Returns one (table or None, margin, slot,
-        n_positive) per region; sequences and the Python events are not modified (the resident events are re-aligned, as by
-        every ScoreMutations call)."""
+        n_positive) per region; sequences and events are not modified (a resident handle's refs come out as they went in)."""
         idx = list(range(len(self.pas))) if idx is None else list(idx)
         if not idx:
             return []
         if "ps_batch_point_table" in self.api.missing:
             return [self.pas[i].PointTable(table) for i in idx]
-        hs = self._open(idx, point_width=True)
+        hs = self._open(idx, point_width=True, keep=True)
         try:
             ns = [max(int(self.api.lib.ps_align_sequence_length(h)) - 4, 0) for h in hs]
             res = self.api.batch_point_table(hs, ns, want_table=table)
@@ -187,17 +210,34 @@ class RegionBatch:
     def ScoreMutations(self, muts_per_region, idx=None):
         """PSAlign.ScoreMutations (`poreseq variant -m`) for the regions `idx` in lock-step: muts_per_region[k] is the MutationInfo
         list of region idx[k] (may be empty), all regions' lists scored by ONE ps_batch_score_mutations call.  Returns one
-        MutationScore list per region, same order; sequences and the Python events are not modified (the resident events are
-        re-aligned, as by every ScoreMutations call)."""
+        MutationScore list per region, same order; sequences and events are not modified (a resident handle's refs come out as
+        they went in)."""
         idx, lists = self._lists(muts_per_region, idx)
         if not idx:
             return []
         if any(m is None for m in lists):
             raise ValueError("one list of edits per region")
-        hs = self._open(idx)
+        hs = self._open(idx, keep=True)
         hm, scored = [], []
         try:
             hm = [self.api.muts_create(m) for m in lists]
+            scored = self.api.batch_score_mutations(hs, hm)
+            return [poreseqcpp._scored_list(*self.api.muts_export(s)) for s in scored]
+        finally:
+            for m in hm + scored:
+                self.api.muts_destroy(m)
+            self._close(idx, hs, write_back=False)
+
+    def ScorePoints(self, idx=None):
+        """PSAlign.ScorePoints for the regions `idx` in lock-step: every region's point edits at its `point_width`, scored by ONE
+        ps_batch_score_mutations call.  Returns one MutationScore list per region; sequences and events are not modified."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        hs = self._open(idx, point_width=True, keep=True)
+        hm, scored = [], []
+        try:
+            hm = [self.api.find_point_mutations(h) for h in hs]
             scored = self.api.batch_score_mutations(hs, hm)
             return [poreseqcpp._scored_list(*self.api.muts_export(s)) for s in scored]
         finally:
@@ -222,7 +262,7 @@ class RegionBatch:
         if len(groups) != len(idx) or len(n_groups) != len(idx):
             raise ValueError("one list of group ids per region")
         gG = [poreseqcpp.support_groups(self.pas[i].events, g, n) for i, g, n in zip(idx, groups, n_groups)]
-        hs = self._open(idx, point_width=points)
+        hs = self._open(idx, point_width=points, keep=True)
         hm = []
         try:
             hm = [self.api.find_point_mutations(h) if points else self.api.muts_create(m) for h, m in zip(hs, lists)]

@@ -56,7 +56,14 @@ int ps_align_new_call(ps_align* a, int32_t w) {
     if (!a) return fail(PS_ERR_BAD_ARG, "null handle");
     a->a.par.scoring_width = w;
     a->a.seqlikes.clear();
-    return PS_OK;
+    if (!a->a.keep_valid || !a->a.restore_due) return PS_OK;   // (no device work unless a scoring call asked for its refs to be kept)
+    NEED_RT();
+    return a->a.restore_refs(rt);
+}
+int ps_align_keep_refs(ps_align* a) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "null handle");
+    NEED_RT();
+    return a->a.keep_refs(rt);
 }
 int32_t ps_align_n_events(const ps_align* a) { return a ? a->a.E : 0; }
 int64_t ps_align_n_levels(const ps_align* a, int32_t e) { return (a && e >= 0 && e < a->a.E) ? a->a.n[e] : -1; }

@@ -145,7 +145,10 @@ double Batch::fill_alg_bytes() const {
 }
 
 // ------------------------------------------------------------------------------------------ AlignData
-Align::~Align() { align_slab_give(slab, slab_cap, last_stream); }   // (back to the cache of ps_mem.cpp, or freed)
+Align::~Align() {
+    if (d_keep) (void)hipFree(d_keep);
+    align_slab_give(slab, slab_cap, last_stream);   // (back to the cache of ps_mem.cpp, or freed)
+}
 
 int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_events, const int64_t* level_off,
                   const double* mean, const double* stdv, const double* ref_align, const double* ref_like,
@@ -304,6 +307,34 @@ int Align::refs_to_host(Runtime* rt) {
     PS_TRY(refs_to_host_async(rt));
     if (pend_ra) PS_HIP(hipStreamSynchronize(rt->stream));
     refs_finish();
+    return PS_OK;
+}
+
+// ps_align_keep_refs / ps_align_new_call (include/poreseq_hip.h): d_ra and d_rl lie next to each other in the slab
+// (Align::create carves them in this order), one copy each way
+int Align::keep_refs(Runtime* rt) {
+    if (!ntot) return PS_OK;
+    if (keep_valid) { restore_due = true; return PS_OK; }   // (kept before and restored by the last new_call: the refs are the kept ones)
+    const size_t span = (size_t)(d_rl - d_ra) + (size_t)ntot;
+    if (!d_keep) PS_HIP(hipMalloc((void**)&d_keep, span * sizeof(double)));
+    last_stream = (void*)rt->stream;
+    PS_HIP(hipMemcpyAsync(d_keep, d_ra, span * sizeof(double), hipMemcpyDeviceToDevice, rt->stream));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    keep_valid = true;
+    restore_due = true;
+    return PS_OK;
+}
+int Align::restore_refs(Runtime* rt) {
+    if (!keep_valid || !restore_due || !ntot) return PS_OK;
+    restore_due = false;
+    const size_t span = (size_t)(d_rl - d_ra) + (size_t)ntot;
+    last_stream = (void*)rt->stream;
+    PS_HIP(hipMemcpyAsync(d_ra, d_keep, span * sizeof(double), hipMemcpyDeviceToDevice, rt->stream));
+    host_refs_valid = false;
+    Batch b;   // ref_index, refstart and refend follow ref_align (k_updaterefs), as after EventData::setData
+    PS_TRY(base_batch(rt, &b, 1, 0));
+    PS_TRY(launch_updaterefs(rt, b.d));
+    PS_HIP(hipStreamSynchronize(rt->stream));
     return PS_OK;
 }
 
@@ -1138,6 +1169,7 @@ int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector
     Tick tk("make_mutations");
     const int R = (int)as.size();
     nbases->assign(R, 0);
+    for (Align* a : as) a->keep_valid = a->restore_due = false;   // MakeMutations belongs to the calls that write their refs back: nothing to go back to
     std::vector<int> active(R);
     std::iota(active.begin(), active.end(), 0);
     std::vector<std::vector<Mut>> later(R);

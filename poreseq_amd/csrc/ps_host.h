@@ -93,6 +93,13 @@ struct Align {
     int refs_to_host_async(Runtime* rt);   // enqueue; refs_finish() after the stream has been synchronised
     void refs_finish();
     double *pend_ra = nullptr, *pend_rl = nullptr;
+    // ref_align / ref_like as the last call that writes back left them (ps_align_keep_refs): a call that only scores realigns the
+    // events as a side effect, and the reference drops that realignment with its scratch AlignData
+    double* d_keep = nullptr;      // [2][ntot], allocated by the first keep_refs()
+    bool keep_valid = false;       // d_keep holds the refs of the last write-back point; make_mutations (a call that writes back) clears it
+    bool restore_due = false;      // a scoring call was announced since: the refs may have left d_keep
+    int keep_refs(Runtime* rt);    // remember the current refs, unless d_keep already holds them
+    int restore_refs(Runtime* rt); // back to the kept refs (ref_index and the spans with them), if a scoring call may have moved them
 };
 
 std::vector<int> states_of(const std::string& bases);

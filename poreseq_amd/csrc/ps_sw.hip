@@ -157,6 +157,9 @@ __device__ __forceinline__ unsigned sw_row(int (&G)[K], const int (&c2)[K], cons
 // review's item 5, parity-tested, and slower than the chained strips where it was meant to win (see sw_launch): selected only by
 // PORESEQ_SW_FORM=one.
 constexpr int SW_SPIN_LIMIT = 1 << 22;
+// byte code of the columns past n2 that fill out a lane's span: above every byte, so that no byte of seq1 — a NUL least of all — matches
+// the padding (its shifted form, SW_PAD << 4, still fits the packed fill's 16-bit halves)
+constexpr int SW_PAD = 256;
 template <int K, int WW>
 __global__ __launch_bounds__(64 * WW) void k_sw_fill(const SwPair* pairs, const char* chars, int* rowsave, int* colsave,
                                                   int* blkmax, int* prog, int* ticket, int* res) {
@@ -178,7 +181,7 @@ __global__ __launch_bounds__(64 * WW) void k_sw_fill(const SwPair* pairs, const 
     const char* s2 = chars + p.s2_off;
     int c2[K], G[K], bmk[K];
 #pragma unroll
-    for (int k = 0; k < K; k++) { c2[k] = jbase + k < p.n2 ? (int)(unsigned char)s2[jbase + k] << 4 : 0; G[k] = 8 * k; bmk[k] = 0; }
+    for (int k = 0; k < K; k++) { c2[k] = (jbase + k < p.n2 ? (int)(unsigned char)s2[jbase + k] : SW_PAD) << 4; G[k] = 8 * k; bmk[k] = 0; }
     const int lane0 = l ? -(1 << 29) : 0;
     __shared__ int hand[WW][2][SWB];
     // this lane's last column is column jbase + K (1-based); every 64th column is kept as a tile boundary
@@ -357,7 +360,7 @@ __global__ __launch_bounds__(64 * WW) __attribute__((amdgpu_waves_per_eu(8, 8)))
         unsigned tb[4][4];
 #pragma unroll
         for (int m = 0; m < 4; m++) {
-            const unsigned a = jbase + 2 * m < p.n2 ? (unsigned)(unsigned char)s2[jbase + 2 * m] : 0u, b = jbase + 2 * m + 1 < p.n2 ? (unsigned)(unsigned char)s2[jbase + 2 * m + 1] : 0u;
+            const unsigned a = jbase + 2 * m < p.n2 ? (unsigned)(unsigned char)s2[jbase + 2 * m] : (unsigned)SW_PAD, b = jbase + 2 * m + 1 < p.n2 ? (unsigned)(unsigned char)s2[jbase + 2 * m + 1] : (unsigned)SW_PAD;
             c2p[m] = (a << 4) | (b << 20);
             auto tab = [&](unsigned ch) { return (a == ch ? 13u : 4u) | ((b == ch ? 13u : 4u) << 16); };
             tb[0][m] = tab('A'); tb[1][m] = tab('C'); tb[2][m] = tab('G'); tb[3][m] = tab('T');
@@ -496,7 +499,7 @@ __device__ __forceinline__ void sw_tile(const SwPair& p, const char* s1, const c
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const bool ok = jbase + k < p.n2;
-        c2[k] = ok ? (int)(unsigned char)s2[jbase + k] << 4 : 0;
+        c2[k] = (ok ? (int)(unsigned char)s2[jbase + k] : SW_PAD) << 4;
         G[k] = ((ok && top) ? rs[k] : 0) + 8 * k;
     }
     const int* cprev = colsave + col_base(p, c0 >> 6);   // H(*, c0): rows up to chi, 0 below

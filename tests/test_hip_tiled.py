@@ -263,7 +263,7 @@ def test_lock_step_batch_equals_regions_alone_and_the_oracle(fwd_kernel):
         nv = rb.Mutate(seqs="viterbi")
         s2 = [pa.sequence for pa in pas]
         rb.sync()
-        rf = [refs(pa) for pa in pas]            # (PointTable re-aligns the resident events, as every scoring call does)
+        rf = [refs(pa) for pa in pas]            # (PointTable leaves a resident handle's refs as it found them: tests/test_call_order.py)
         tables = rb.PointTable()
     for r, pa in enumerate(pas):
         got = [se[r], nb[r], s1[r], nv[r], s2[r]]
