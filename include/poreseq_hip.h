@@ -8,7 +8,8 @@
  * reference tree.  Only plain pointers and sizes cross this boundary.
  * A few entry points go beyond the reference's surface and reduce its scores on the device: ps_point_table (a row per position)
  * and ps_score_mutation_support (per edit and event group: the summed terms, the reads that span the edit and how many of
- * them favour or oppose it).  `cover` there is a span test on the re-aligned reads, not a likelihood test, and anything
+ * them favour or oppose it) with ps_score_mutation_genotypes (per edit: the likelihood of every alt-allele fraction asked for,
+ * over the reads that span the edit).  `cover` there is a span test on the re-aligned reads, not a likelihood test, and anything
  * Phred-scaled that drivers derive from these scores is uncalibrated.
  *
  * All functions return PS_OK (0) or a negative ps_status; ps_last_error()
@@ -208,6 +209,37 @@ typedef struct ps_edit_support {
 int ps_score_mutation_support(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group /* [n_events] */,
                               double* scores /* [M] or NULL */, ps_edit_support* support /* [M][n_groups] */);
 
+/* Genotype likelihoods per edit.  ps_score_mutation_support's call — same list, same scoring, same re-alignment, same group
+ * arguments and checks — with a second reduction of the same events x edits matrix on the device (k_genotype).  ps_score_mutations
+ * adds an edit's terms over all reads: the log-likelihood of "every read carries the edit".  A genotype whose alt-allele fraction
+ * is f has  sum over reads of log((1 - f) + f * exp(delta))  instead.
+ *   alt_frac[k]            0 <= n_frac <= 8 alt fractions, each 1e-6 <= f <= 1 - 1e-6;  g_k = 1.0 - f_k is formed once on the host.
+ *   cover(e, m)            exactly the test behind ps_edit_support.cover: the edit is not skipped (start <= sequence length), event e
+ *                          has a positive ref_align entry after the call's re-alignment and refstart <= start + 1 <= refend.
+ *                          ONLY covering events enter the likelihoods: a read's term is not zero outside its span, and such terms
+ *                          are noise here.
+ *   n_cover[m]             the number of covering events.  May be NULL.
+ *   lik[m * (n_frac + 1) + k], k < n_frac
+ *                          acc = 0.0; for e ascending with cover(e, m):  d = delta[e][m];  u = exp(-|d|);
+ *                          x = (d > 0) ? g_k * u + f_k : g_k + f_k * u;  acc += (d > 0 ? d : 0.0) + log(x).
+ *                          One exp per (event, edit), one log per fraction, no argument of exp is positive and x lies in
+ *                          [min(f, 1 - f), 1]: nothing overflows.  d = -inf contributes log(g_k), d = +inf gives +inf, NaN gives NaN.
+ *                          exp / log are the device library's FP64 functions: these columns agree with a host evaluation to a few
+ *                          units in the last place per term, not bit for bit.
+ *   lik[m * (n_frac + 1) + n_frac]
+ *                          0.0, then += d over the covering events in event order, plain FP64 adds: the hom-alt likelihood, bit-exact.
+ *                          (The hom-ref likelihood is 0 by construction and is not stored.)
+ *   scores[m]              the bits of ps_score_mutations.  May be NULL.
+ *   support                as ps_score_mutation_support; may be NULL here and is then neither produced nor copied.
+ * A skipped edit, and every edit of an AlignData without events, has n_cover = 0 and all-zero lik.  PS_ERR_BAD_ARG: n_frac outside
+ * 0 .. 8, a fraction outside 1e-6 .. 1 - 1e-6 (NaN included), NULL alt_frac with n_frac > 0, NULL lik, and what the support call
+ * rejects.  An empty list is PS_OK and launches nothing.  Scores, records, lik and n_cover of one call (or chunk) come back in the
+ * one device-to-host copy of the support call.  Uncalibrated, like everything derived from these scores. */
+int ps_score_mutation_genotypes(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group /* [n_events] */,
+                                int32_t n_frac, const double* alt_frac /* [n_frac]; NULL allowed when n_frac == 0 */,
+                                double* scores /* [M] or NULL */, ps_edit_support* support /* [M][n_groups] or NULL */,
+                                double* lik /* [M][n_frac + 1] */, int32_t* n_cover /* [M] or NULL */);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -254,6 +286,10 @@ int ps_batch_point_table(int32_t n_regions, ps_align* const* a, double* const* t
 int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* n_groups /* [n] */,
                                     const int32_t* const* group, double* const* scores /* entries or array may be NULL */,
                                     ps_edit_support* const* support);
+/* ps_score_mutation_genotypes for every AlignData in one launch chain: n_frac[i], alt_frac[i] ([n_frac[i]]; may be NULL where n_frac[i] == 0) and lik[i] ([count(muts[i])][n_frac[i] + 1]) per AlignData; scores, support and n_cover — entries or whole arrays — may be NULL. */
+int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* n_groups /* [n] */,
+                                      const int32_t* const* group, const int32_t* n_frac /* [n] */, const double* const* alt_frac,
+                                      double* const* scores, ps_edit_support* const* support, double* const* lik, int32_t* const* n_cover);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);

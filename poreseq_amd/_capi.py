@@ -51,6 +51,7 @@ class PsEditSupport(C.Structure):
 # the same record as a numpy dtype (24 bytes, no padding): what score_mutation_support / batch_score_mutation_support hand out
 EDIT_SUPPORT = np.dtype([("sum", np.float64), ("cover", np.int32), ("pos", np.int32), ("neg", np.int32), ("reserved", np.int32)])
 SUPPORT_MAX_GROUPS = 8
+GENO_MAX_FRAC = 8   # alt fractions per ps_score_mutation_genotypes call
 
 
 class PoreseqError(Exception):
@@ -98,6 +99,9 @@ SYMBOLS = {
     "ps_score_mutation_support": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, c_dp, C.POINTER(PsEditSupport)]),
     "ps_batch_score_mutation_support": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32p, C.POINTER(c_i32p), C.POINTER(c_dp),
                                                   C.POINTER(C.POINTER(PsEditSupport))]),
+    "ps_score_mutation_genotypes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, C.c_int32, c_dp, c_dp, C.POINTER(PsEditSupport), c_dp, c_i32p]),
+    "ps_batch_score_mutation_genotypes": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32p, C.POINTER(c_i32p), c_i32p, C.POINTER(c_dp),
+                                                    C.POINTER(c_dp), C.POINTER(C.POINTER(PsEditSupport)), C.POINTER(c_dp), C.POINTER(c_i32p)]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -136,10 +140,12 @@ SYMBOLS = {
 # entry points of the header that a checker library (the oracle, the reference shim) may lack: CApi serves them from what the
 # library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents;
 # PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations; PSAlign.ScoreMutationSupport reduces
-# score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas).
+# score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas, and PSAlign.ScoreMutationGenotypes does the
+# same with util.genotypes_from_deltas on top).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
 OPTIONAL = frozenset(["ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
-                      "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support"])
+                      "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
+                      "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
 # entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
@@ -420,6 +426,38 @@ class CApi:
         rp = (C.POINTER(PsEditSupport) * max(R, 1))(*[r.ctypes.data_as(C.POINTER(PsEditSupport)) for r in recs])
         self.check(self.lib.ps_batch_score_mutation_support(R, self._harr(hs), self._harr(hms), ng.ctypes.data_as(c_i32p), gp, sp, rp))
         return list(zip(scores, recs))
+
+    def score_mutation_genotypes(self, h, hm, n_muts, groups, n_groups, alt_frac, want_support=True):
+        """-> (scores [M], support [M, n_groups] or None, lik float64 [M, K + 1], n_cover int32 [M]): ps_score_mutation_genotypes
+        of one AlignData"""
+        return self.batch_score_mutation_genotypes([h], [hm], [n_muts], [groups], [n_groups], [alt_frac], want_support)[0]
+
+    def batch_score_mutation_genotypes(self, hs, hms, n_muts, groups, n_groups, alt_frac, want_support=True):
+        """ps_batch_score_mutation_genotypes over the AlignData `hs`: batch_score_mutation_support's arguments plus alt_frac[i], the
+        K_i alt-allele fractions of AlignData i (0 .. 8 of them, each 1e-6 .. 1 - 1e-6).  One launch chain, reduced on the device,
+        one copy back -> [(scores float64 [M], support EDIT_SUPPORT [M, n_groups[i]] — None with want_support=False, the records
+        are then neither produced nor copied —, lik float64 [M, K_i + 1], n_cover int32 [M])].  lik[:, k] is the log-likelihood of
+        alt fraction alt_frac[i][k] over the events that span the edit, relative to hom-ref (0); lik[:, K_i] is hom-alt, the
+        covering events' terms added in event order; n_cover counts those events."""
+        self._need("ps_batch_score_mutation_genotypes")
+        R = len(hs)
+        ng = np.array([int(g) for g in n_groups] + [0], dtype=np.int32)
+        grp = [np.ascontiguousarray(list(g) + [0], dtype=np.int32) for g in groups]   # (one spare entry: never a null pointer)
+        frs = [np.ascontiguousarray(list(f) + [0.0], dtype=np.float64) for f in alt_frac]
+        nf = np.array([len(f) - 1 for f in frs] + [0], dtype=np.int32)
+        scores = [np.empty(int(m), dtype=np.float64) for m in n_muts]
+        recs = [np.empty((int(m), max(int(g), 0)), dtype=EDIT_SUPPORT) if want_support else None for m, g in zip(n_muts, ng[:R])]
+        liks = [np.empty((int(m), max(int(k), 0) + 1), dtype=np.float64) for m, k in zip(n_muts, nf[:R])]
+        ncov = [np.empty(int(m), dtype=np.int32) for m in n_muts]
+        gp = (c_i32p * max(R, 1))(*[g.ctypes.data_as(c_i32p) for g in grp])
+        fp = (c_dp * max(R, 1))(*[_dp(f) for f in frs])
+        sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores])
+        rp = (C.POINTER(PsEditSupport) * max(R, 1))(*[r.ctypes.data_as(C.POINTER(PsEditSupport)) for r in recs]) if want_support else None
+        lp = (c_dp * max(R, 1))(*[_dp(a) for a in liks])
+        cp = (c_i32p * max(R, 1))(*[a.ctypes.data_as(c_i32p) for a in ncov])
+        self.check(self.lib.ps_batch_score_mutation_genotypes(R, self._harr(hs), self._harr(hms), ng.ctypes.data_as(c_i32p), gp,
+                                                              nf.ctypes.data_as(c_i32p), fp, sp, rp, lp, cp))
+        return list(zip(scores, recs, liks, ncov))
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

@@ -11,6 +11,8 @@ Results are those of running the same `PSAlign` calls region by region, bit for 
 (`ps_rng`, seeded like a fresh process) for ViterbiMutate's stochastic back-traces, and regions that have converged
 simply drop out of the later rounds of a call, as their own `break` would.
 """
+import numpy as np
+
 from . import poreseqcpp
 
 
@@ -245,12 +247,9 @@ class RegionBatch:
                 self.api.muts_destroy(m)
             self._close(idx, hs, write_back=False)
 
-    def ScoreMutationSupport(self, muts_per_region, idx=None, groups=None, n_groups=None):
-        """PSAlign.ScoreMutationSupport for the regions `idx` in lock-step: ONE ps_batch_score_mutation_support call — one scoring
-        chain over all regions, reduced per event group on the device, one copy back.  muts_per_region[k] is the MutationInfo list
-        of region idx[k]; None instead of the lists means every region's point edits at `point_width`.  groups[k] / n_groups[k]
-        (or one n_groups for all) as PSAlign.ScoreMutationSupport takes them, None for the strand default.  Returns one
-        (scores, support, scored list) per region; sequences and the Python events are not modified."""
+    def _support(self, muts_per_region, idx, groups, n_groups, alt_frac=None):
+        """ScoreMutationSupport (alt_frac None) and ScoreMutationGenotypes (one tuple of alt fractions for all regions, or a list of
+        one per region) share everything but the native call: lists, groups, open / close and the path of a checker library"""
         points = muts_per_region is None
         idx, lists = self._lists(muts_per_region, idx)
         if not idx:
@@ -261,21 +260,54 @@ class RegionBatch:
         n_groups = list(n_groups) if isinstance(n_groups, (list, tuple)) else [n_groups] * len(idx)
         if len(groups) != len(idx) or len(n_groups) != len(idx):
             raise ValueError("one list of group ids per region")
+        geno = alt_frac is not None
+        fracs = [None] * len(idx)
+        if geno:
+            alt_frac = list(alt_frac)
+            per_region = bool(alt_frac) and all(isinstance(f, (list, tuple, np.ndarray)) and np.ndim(f) == 1 for f in alt_frac)
+            fracs = alt_frac if per_region else [alt_frac] * len(idx)
+            if len(fracs) != len(idx):
+                raise ValueError("one tuple of alt fractions for all regions or one per region")
+            fracs = [poreseqcpp.check_alt_frac(f) for f in fracs]
         gG = [poreseqcpp.support_groups(self.pas[i].events, g, n) for i, g, n in zip(idx, groups, n_groups)]
+        name = "ps_batch_score_mutation_genotypes" if geno else "ps_batch_score_mutation_support"
         hs = self._open(idx, point_width=points, keep=True)
         hm = []
         try:
             hm = [self.api.find_point_mutations(h) if points else self.api.muts_create(m) for h, m in zip(hs, lists)]
-            if "ps_batch_score_mutation_support" in self.api.missing:
+            if name in self.api.missing:
+                if geno:
+                    return [poreseqcpp._genotypes_on(self.api, h, m, len(self.pas[i].events), len(self.pas[i].sequence), g, G, f)
+                            for i, h, m, (g, G), f in zip(idx, hs, hm, gG, fracs)]
                 return [poreseqcpp._support_on(self.api, h, m, len(self.pas[i].events), len(self.pas[i].sequence), g, G)
                         for i, h, m, (g, G) in zip(idx, hs, hm, gG)]
             lists_x = [self.api.muts_export(m) for m in hm]
-            res = self.api.batch_score_mutation_support(hs, hm, [len(x[0]) for x in lists_x], [g for g, _ in gG], [G for _, G in gG])
+            n_muts, grps, Gs = [len(x[0]) for x in lists_x], [g for g, _ in gG], [G for _, G in gG]
+            if geno:
+                res = self.api.batch_score_mutation_genotypes(hs, hm, n_muts, grps, Gs, fracs)
+                return [(sc, sup, poreseqcpp._scored_list(x[0], x[1], x[2], sc), lik, nc) for (sc, sup, lik, nc), x in zip(res, lists_x)]
+            res = self.api.batch_score_mutation_support(hs, hm, n_muts, grps, Gs)
             return [(sc, sup, poreseqcpp._scored_list(x[0], x[1], x[2], sc)) for (sc, sup), x in zip(res, lists_x)]
         finally:
             for m in hm:
                 self.api.muts_destroy(m)
             self._close(idx, hs, write_back=False)
+
+    def ScoreMutationSupport(self, muts_per_region, idx=None, groups=None, n_groups=None):
+        """PSAlign.ScoreMutationSupport for the regions `idx` in lock-step: ONE ps_batch_score_mutation_support call — one scoring
+        chain over all regions, reduced per event group on the device, one copy back.  muts_per_region[k] is the MutationInfo list
+        of region idx[k]; None instead of the lists means every region's point edits at `point_width`.  groups[k] / n_groups[k]
+        (or one n_groups for all) as PSAlign.ScoreMutationSupport takes them, None for the strand default.  Returns one
+        (scores, support, scored list) per region; sequences and the Python events are not modified."""
+        return self._support(muts_per_region, idx, groups, n_groups)
+
+    def ScoreMutationGenotypes(self, muts_per_region, idx=None, alt_frac=(0.5,), groups=None, n_groups=None):
+        """PSAlign.ScoreMutationGenotypes for the regions `idx` in lock-step: ONE ps_batch_score_mutation_genotypes call — the
+        scoring chain of ScoreMutationSupport over all regions, both reductions on the device, one copy back.  muts_per_region,
+        groups and n_groups as ScoreMutationSupport takes them; alt_frac is one tuple of fractions for all regions or a list of
+        one tuple (list, array) per region.  Returns one (scores, support, scored list, lik, n_cover) per region; sequences and
+        the Python events are not modified."""
+        return self._support(muts_per_region, idx, groups, n_groups, alt_frac=alt_frac)
 
     def Mutate(self, idx=None, seqs='self', reps=4):
         """PSAlign.Mutate (pyx:378-435) for the regions `idx`; returns {region index: total mutated bases}."""

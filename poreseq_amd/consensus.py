@@ -265,6 +265,10 @@ VCF_INFO = (("LLR", "1", "Float", "Log-likelihood change of the edit summed over
             ("GSUP", ".", "Integer", "Spanning reads per group that favour the edit (term > 0)"),
             ("GOPP", ".", "Integer", "Spanning reads per group that oppose the edit (term < 0)"),
             ("GLLR", ".", "Float", "Log-likelihood change per group, over all reads of the group"))
+# (with a ploidy: the sample column.  GQ and PL are Phred-scaled ratios of this model's likelihoods: uncalibrated, like QUAL)
+VCF_FORMAT = (("GT", "1", "String", "Genotype: the alt-copy count with the largest likelihood over the spanning reads (uncalibrated)"),
+              ("GQ", "1", "Integer", "Genotype quality: the second smallest PL, at most 99 (uncalibrated)"),
+              ("PL", "G", "Integer", "Phred-scaled genotype likelihoods over the spanning reads, 0 .. ploidy alt copies (uncalibrated)"))
 
 
 def vcf_fields(seq, start, orig, mut, offset=0):
@@ -288,7 +292,7 @@ def vcf_qual(score):
 
 
 def variant_support(pas, muts_per_region, region_starts=None, groups=None, group_names=("t", "c"), out=None, fmt="tsv", chrom="region",
-                    min_score=0.0):
+                    min_score=0.0, ploidy=None, sample="sample"):
     """`poreseq variant -m` for one PSAlign or a list of them with the read evidence behind every score: all regions go through ONE
     lock-step RegionBatch.ScoreMutationSupport call.  muts_per_region[r] is the MutationInfo list of region r with ABSOLUTE starts
     (region_starts[r] is subtracted inside the call and added again outside, as variant_region does — on copies: the lists handed
@@ -300,11 +304,17 @@ def variant_support(pas, muts_per_region, region_starts=None, groups=None, group
     fmt="vcf": a VCF 4.2 header and one record per edit with score > min_score, in list order (`vcf_fields`, `vcf_qual`); `chrom`
       is one name or one per region.  INFO = LLR=<score>;DP=<sum of cover>;GDP=..;GSUP=..;GOPP=..;GLLR=.., the G-tags
       comma-separated per group in group order.
-    `cover` is a span test, not a likelihood test, and QUAL is uncalibrated.  No PSAlign is modified."""
+    ploidy=P (1 .. 9) adds a genotype per edit: the regions go through ONE RegionBatch.ScoreMutationGenotypes call with
+      util.alt_fractions(P) instead, every returned tuple gains (lik, n_cover), and util.call_genotypes writes them out — the VCF
+      gets FORMAT lines for GT, GQ and PL, the column `sample` and GT:GQ:PL per record (which records appear is unchanged); the TSV
+      gets the columns n_cover, gt, gq and gl_0 .. gl_P, the natural-log likelihood of 0 .. P alt copies relative to hom-ref.
+      ploidy=None is the output without them, byte for byte.
+    `cover` is a span test, not a likelihood test, and QUAL, GQ and PL are uncalibrated.  No PSAlign is modified."""
     from .batch import RegionBatch
-    from .util import MutationInfo
+    from .util import MutationInfo, alt_fractions, call_genotypes
     if fmt not in ("tsv", "vcf"):
         raise ValueError("variant_support: fmt is 'tsv' or 'vcf'")
+    fracs = None if ploidy is None else alt_fractions(ploidy)
     single = isinstance(pas, poreseqcpp.PSAlign)
     pas = [pas] if single else list(pas)
     if single:
@@ -326,28 +336,44 @@ def variant_support(pas, muts_per_region, region_starts=None, groups=None, group
     res = []
     if pas:
         with RegionBatch(pas, resident=False) as rb:   # (not resident: nothing of the pass is written back to the PSAlign objects)
-            res = rb.ScoreMutationSupport(rel, groups=groups, n_groups=len(names))
+            if ploidy is None:
+                res = rb.ScoreMutationSupport(rel, groups=groups, n_groups=len(names))
+            else:
+                res = rb.ScoreMutationGenotypes(rel, alt_frac=fracs, groups=groups, n_groups=len(names))
     if out is not None:
         if fmt == "tsv":
-            out.write('#start\torig\tmut\tscore' + ''.join('\tcover_{0}\tpos_{0}\tneg_{0}\tsum_{0}'.format(n) for n in names) + '\n')
+            out.write('#start\torig\tmut\tscore' + ''.join('\tcover_{0}\tpos_{0}\tneg_{0}\tsum_{0}'.format(n) for n in names) +
+                      ('' if ploidy is None else '\tn_cover\tgt\tgq' + ''.join('\tgl_{}'.format(k) for k in range(int(ploidy) + 1))) + '\n')
         else:
             out.write('##fileformat=VCFv4.2\n##source=poreseq_amd.variant_support\n')
             for tag, num, typ, desc in VCF_INFO:
                 per = '' if num == '1' else ' (groups: {})'.format(','.join(names))
                 out.write('##INFO=<ID={},Number={},Type={},Description="{}{}">\n'.format(tag, num, typ, desc, per))
-            out.write('#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n')
-    for pa, s0, ch, (scores, sup, scored) in zip(pas, starts, chroms, res):
+            if ploidy is not None:
+                for tag, num, typ, desc in VCF_FORMAT:
+                    out.write('##FORMAT=<ID={},Number={},Type={},Description="{}">\n'.format(tag, num, typ, desc))
+            out.write('#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO' + ('' if ploidy is None else '\tFORMAT\t{}'.format(sample)) + '\n')
+    for pa, s0, ch, one in zip(pas, starts, chroms, res):
+        scores, sup, scored = one[:3]
         lines = []
-        for ms, rec in zip(scored, sup.tolist()):
+        gcol = [''] * len(scored)      # what a genotype adds behind every line
+        if ploidy is not None:
+            gts, gqs, pls = call_genotypes(one[3], one[4], ploidy)
+            if fmt == "tsv":
+                gcol = ['\t{}\t{}\t{}\t0.0'.format(nc, gt, gq) + ''.join('\t' + repr(v) for v in row)
+                        for nc, gt, gq, row in zip(np.asarray(one[4]).tolist(), gts, gqs, np.asarray(one[3], dtype=np.float64).tolist())]
+            else:
+                gcol = ['\tGT:GQ:PL\t{}:{}:{}'.format(gt, gq, ','.join(str(p) for p in pl)) for gt, gq, pl in zip(gts, gqs, pls)]
+        for ms, rec, gc in zip(scored, sup.tolist(), gcol):
             if fmt == "tsv":
                 ms.start += int(s0)
-                lines.append(str(ms) + ''.join('\t{}\t{}\t{}\t{}'.format(r[1], r[2], r[3], r[0]) for r in rec) + '\n')
+                lines.append(str(ms) + ''.join('\t{}\t{}\t{}\t{}'.format(r[1], r[2], r[3], r[0]) for r in rec) + gc + '\n')
                 continue
             if ms.score > min_score:
                 pos, ref, alt = vcf_fields(pa.sequence, ms.start, ms.orig, ms.mut, int(s0))
                 col = lambda k: ','.join(str(r[k]) for r in rec)
                 info = 'LLR={};DP={};GDP={};GSUP={};GOPP={};GLLR={}'.format(ms.score, sum(r[1] for r in rec), col(1), col(2), col(3), col(0))
-                lines.append('{}\t{}\t.\t{}\t{}\t{}\t.\t{}\n'.format(ch, pos, ref, alt, vcf_qual(ms.score), info))
+                lines.append('{}\t{}\t.\t{}\t{}\t{}\t.\t{}{}\n'.format(ch, pos, ref, alt, vcf_qual(ms.score), info, gc))
             ms.start += int(s0)
         if out is not None:
             out.write(''.join(lines))

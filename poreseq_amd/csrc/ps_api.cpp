@@ -341,6 +341,53 @@ int ps_score_mutation_support(ps_align* a, const ps_muts* muts, int32_t n_groups
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_support: null handle");
     return ps_batch_score_mutation_support(1, &a, &muts, &n_groups, &group, &scores, &support);
 }
+int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* n_groups,
+                                      const int32_t* const* group, const int32_t* n_frac, const double* const* alt_frac,
+                                      double* const* scores, ps_edit_support* const* support, double* const* lik, int32_t* const* n_cover) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n && (!muts || !n_groups || !group || !n_frac || !lik)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_genotypes: null array");
+    std::vector<const std::vector<Mut>*> in(n);
+    std::vector<const int32_t*> gr(n);
+    std::vector<int> ng(n), nf(n);
+    std::vector<const double*> fr(n);
+    std::vector<double*> sc(n), lk(n);
+    std::vector<ps_edit_support*> rec(n);
+    std::vector<int32_t*> nc(n);
+    size_t edits = 0;
+    for (int i = 0; i < n; i++) {
+        const std::string who = "ps_score_mutation_genotypes: region " + std::to_string(i);
+        if (!muts[i]) return fail(PS_ERR_BAD_ARG, who + ": null list");
+        if (n_groups[i] < 1 || n_groups[i] > SUPPORT_MAX_GROUPS)
+            return fail(PS_ERR_BAD_ARG, who + ": n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(SUPPORT_MAX_GROUPS));
+        if (!group[i]) return fail(PS_ERR_BAD_ARG, who + ": null group array");
+        for (int e = 0; e < as[i]->E; e++)
+            if (group[i][e] < 0 || group[i][e] >= n_groups[i])
+                return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(group[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
+        if (n_frac[i] < 0 || n_frac[i] > GENO_MAX_FRAC)
+            return fail(PS_ERR_BAD_ARG, who + ": n_frac = " + std::to_string(n_frac[i]) + ", allowed are 0 .. " + std::to_string(GENO_MAX_FRAC));
+        const double* f = alt_frac ? alt_frac[i] : nullptr;
+        if (n_frac[i] > 0 && !f) return fail(PS_ERR_BAD_ARG, who + ": null alt_frac with n_frac = " + std::to_string(n_frac[i]));
+        for (int k = 0; k < n_frac[i]; k++)
+            if (!(f[k] >= 1e-6 && f[k] <= 1.0 - 1e-6)) {   // (NaN fails both comparisons)
+                char msg[96];
+                snprintf(msg, sizeof msg, ": alt_frac[%d] = %g, allowed is 1e-06 .. 1 - 1e-06", k, f[k]);
+                return fail(PS_ERR_BAD_ARG, who + msg);
+            }
+        if (!lik[i]) return fail(PS_ERR_BAD_ARG, who + ": null lik");
+        in[i] = &muts[i]->v; gr[i] = group[i]; ng[i] = n_groups[i]; nf[i] = n_frac[i]; fr[i] = f;
+        sc[i] = scores ? scores[i] : nullptr; rec[i] = support ? support[i] : nullptr; lk[i] = lik[i]; nc[i] = n_cover ? n_cover[i] : nullptr;
+        edits += in[i]->size();
+    }
+    if (!edits) return PS_OK;   // nothing to score anywhere: no launch
+    NEED_RT();
+    return score_mutation_genotypes_multi(rt, as, in, gr, ng, nf, fr, sc, rec, lk, nc);
+}
+int ps_score_mutation_genotypes(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group, int32_t n_frac, const double* alt_frac,
+                                double* scores, ps_edit_support* support, double* lik, int32_t* n_cover) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_genotypes: null handle");
+    return ps_batch_score_mutation_genotypes(1, &a, &muts, &n_groups, &group, &n_frac, &alt_frac, &scores, &support, &lik, &n_cover);
+}
 int ps_batch_make_mutations(int32_t n, ps_align* const* a, const ps_muts* const* scored, int32_t* n_bases) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

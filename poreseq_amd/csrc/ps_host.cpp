@@ -773,7 +773,13 @@ namespace {
 struct PointOut { std::vector<double*> table; std::vector<ps_point_best*> best; };
 // a support call (score_mutation_support_multi): per AlignData the events' group ids, the number of groups and the host arrays that
 // receive the scores (may be null) and the [M][ngroups] records; no scored copy of the lists is made either
-struct SupportOut { std::vector<const int32_t*> group; std::vector<int> ngroups; std::vector<double*> score; std::vector<ps_edit_support*> rec; };
+struct SupportOut {
+    std::vector<const int32_t*> group; std::vector<int> ngroups; std::vector<double*> score; std::vector<ps_edit_support*> rec;
+    // a genotype call (score_mutation_genotypes_multi) on top: per AlignData the alt fractions and the host arrays that receive the
+    // [M][nfrac + 1] likelihoods and the covering-event counts (may be null); `rec` entries may then be null (no records wanted)
+    bool geno = false;
+    std::vector<int> nfrac; std::vector<const double*> frac; std::vector<double*> lik; std::vector<int32_t*> ncover;
+};
 }  // namespace
 static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                                    const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
@@ -802,7 +808,7 @@ int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std:
 static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                                    const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
                                    const PointOut* pt, const SupportOut* sp) {
-    Tick tk(pt ? "point_table" : sp ? "score_mutation_support" : "score_mutations");
+    Tick tk(pt ? "point_table" : sp ? (sp->geno ? "score_mutation_genotypes" : "score_mutation_support") : "score_mutations");
     const int R = (int)as.size();
     // the reference's progress line under `verbose` (cpp/MakeMutations.cpp:28-32, 55-66: "Scoring (<width>)", a dot per event, a newline);
     // a lock-step call over several AlignData has no single line to write: only the single-handle call speaks
@@ -848,6 +854,11 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         if (sp) {
             spsub.group.assign(sp->group.begin() + k0, sp->group.begin() + k1); spsub.ngroups.assign(sp->ngroups.begin() + k0, sp->ngroups.begin() + k1);
             spsub.score.assign(sp->score.begin() + k0, sp->score.begin() + k1); spsub.rec.assign(sp->rec.begin() + k0, sp->rec.begin() + k1);
+            spsub.geno = sp->geno;
+            if (sp->geno) {
+                spsub.nfrac.assign(sp->nfrac.begin() + k0, sp->nfrac.begin() + k1); spsub.frac.assign(sp->frac.begin() + k0, sp->frac.begin() + k1);
+                spsub.lik.assign(sp->lik.begin() + k0, sp->lik.begin() + k1); spsub.ncover.assign(sp->ncover.begin() + k0, sp->ncover.begin() + k1);
+            }
         }
         return score_mutations_planned(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1),
                                        std::vector<const std::vector<Mut>*>(muts.begin() + k0, muts.begin() + k1),
@@ -896,7 +907,11 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         for (int k = 0; k < R; k++)
             if (!as[k]->E) {
                 if (sp->score[k]) std::fill(sp->score[k], sp->score[k] + plan[k].M, -1e-6);
-                memset(sp->rec[k], 0, (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
+                if (sp->rec[k]) memset(sp->rec[k], 0, (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
+                if (sp->geno) {   // (and no covering event: all-zero likelihoods)
+                    std::fill(sp->lik[k], sp->lik[k] + (size_t)plan[k].M * (sp->nfrac[k] + 1), 0.0);
+                    if (sp->ncover[k]) std::fill(sp->ncover[k], sp->ncover[k] + plan[k].M, 0);
+                }
             }
     if (specs.empty()) return PS_OK;
     Batch b;
@@ -936,7 +951,7 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         dbls += (size_t)as[k]->E * std::max(p.nr0, 1) + (size_t)as[k]->E * std::max(p.M, 1) + std::max(p.M, 1) + (size_t)as[k]->E * (as[k]->states.size() + 8);
     }
     DBuf& mb = rt->buf("mutint");
-    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max(sizeof(PointArgs), sizeof(SupportArgs)))));
+    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max(sizeof(PointArgs), sizeof(SupportArgs)) + sizeof(GenoArgs)) + 64));
     DBuf& db = rt->buf("mutdbl");
     PS_TRY(db.ensure(dbls * sizeof(double)));
     int* dp = mb.as<int>();
@@ -962,14 +977,19 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         PS_TRY(pb.ensure(std::max<size_t>(pt_bytes, 16)));
         d_pt = pb.as<char>();
     }
-    // a support call: the scores, then the records, of all AlignData back to back in one buffer — ONE device-to-host copy
-    std::vector<size_t> sscore_at(R, 0), srec_at(R, 0);
+    // a support call: the scores, then the records, of all AlignData back to back in one buffer — ONE device-to-host copy; a genotype
+    // call's likelihoods and covering-event counts follow them in the same buffer and come back in the same copy
+    std::vector<size_t> sscore_at(R, 0), srec_at(R, 0), glik_at(R, 0), gcov_at(R, 0);
     size_t sp_bytes = 0;
     char* d_sp = nullptr;
     auto sp_live = [&](int k) { return plan[k].M > 0 && as[k]->E > 0; };
     if (sp) {
         for (int k = 0; k < R; k++) if (sp_live(k)) { sscore_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sizeof(double); }
-        for (int k = 0; k < R; k++) if (sp_live(k)) { srec_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support); }
+        for (int k = 0; k < R; k++) if (sp_live(k) && sp->rec[k]) { srec_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support); }
+        if (sp->geno) {
+            for (int k = 0; k < R; k++) if (sp_live(k)) { glik_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * (sp->nfrac[k] + 1) * sizeof(double); }
+            for (int k = 0; k < R; k++) if (sp_live(k)) { gcov_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sizeof(int32_t); }
+        }
         DBuf& sb = rt->buf("support");
         PS_TRY(sb.ensure(std::max<size_t>(sp_bytes, 16)));
         d_sp = sb.as<char>();
@@ -977,6 +997,7 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
     std::vector<ScoreArgs> sas(R);
     std::vector<PointArgs> pts(pt ? R : 0);
     std::vector<SupportArgs> sps(sp ? R : 0);
+    std::vector<GenoArgs> gts(sp && sp->geno ? R : 0);
     for (int k = 0; k < R; k++) {
         const EditPlan& p = plan[k];
         ScoreArgs& sa = sas[k];
@@ -1007,22 +1028,36 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             SupportArgs& q = sps[k];
             memset(&q, 0, sizeof(q));
             q.group = push(std::vector<int>(sp->group[k], sp->group[k] + as[k]->E));
-            if (sp_live(k)) { q.ngroups = sp->ngroups[k]; q.score = (double*)(d_sp + sscore_at[k]); q.out = (ps_edit_support*)(d_sp + srec_at[k]); }
+            if (sp_live(k) && sp->rec[k]) { q.ngroups = sp->ngroups[k]; q.score = (double*)(d_sp + sscore_at[k]); q.out = (ps_edit_support*)(d_sp + srec_at[k]); }
+        }
+        if (sp && sp->geno) {
+            GenoArgs& q = gts[k];
+            memset(&q, 0, sizeof(q));
+            q.nfrac = -1;
+            if (sp_live(k)) {
+                q.nfrac = sp->nfrac[k];
+                for (int i = 0; i < q.nfrac; i++) { q.f[i] = sp->frac[k][i]; q.g[i] = 1.0 - q.f[i]; }
+                if (!sp->rec[k]) q.score = (double*)(d_sp + sscore_at[k]);   // (k_support writes nothing for this AlignData)
+                q.lik = (double*)(d_sp + glik_at[k]); q.ncover = (int*)(d_sp + gcov_at[k]);
+            }
         }
         if (!p.M || !as[k]->E) { sa.njobs = 0; sa.nitems_per_job = 0; }   // nothing to score for this AlignData: its blocks leave at once
     }
     // the edit tables and their descriptors (ScoreArgs, behind the tables in the same buffer) in one copy
     const size_t sa_at = (stage.size() * sizeof(int) + 63) / 64 * 64;
     const size_t pt_at = (sa_at + (size_t)R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them)
-    std::vector<char> blob(pt_at + pts.size() * sizeof(PointArgs) + sps.size() * sizeof(SupportArgs));   // (PointArgs or SupportArgs, never both)
+    const size_t gt_at = (pt_at + sps.size() * sizeof(SupportArgs) + 63) / 64 * 64;                       // (a genotype call: its GenoArgs behind the SupportArgs)
+    std::vector<char> blob(std::max(pt_at + pts.size() * sizeof(PointArgs), gt_at + gts.size() * sizeof(GenoArgs)));   // (PointArgs or SupportArgs, never both)
     memcpy(blob.data(), stage.data(), stage.size() * sizeof(int));
     memcpy(blob.data() + sa_at, sas.data(), (size_t)R * sizeof(ScoreArgs));
     if (pt) memcpy(blob.data() + pt_at, pts.data(), pts.size() * sizeof(PointArgs));
     if (sp) memcpy(blob.data() + pt_at, sps.data(), sps.size() * sizeof(SupportArgs));
+    if (!gts.empty()) memcpy(blob.data() + gt_at, gts.data(), gts.size() * sizeof(GenoArgs));
     PS_TRY(rt->up(dp, blob.data(), blob.size()));
     const ScoreArgs* d_sas = (const ScoreArgs*)((const char*)dp + sa_at);
     const PointArgs* d_pts = pt ? (const PointArgs*)((const char*)dp + pt_at) : nullptr;
     const SupportArgs* d_sps = sp ? (const SupportArgs*)((const char*)dp + pt_at) : nullptr;
+    const GenoArgs* d_gts = !gts.empty() ? (const GenoArgs*)((const char*)dp + gt_at) : nullptr;
     tk.lap("upload");
     if (tk.on) { PS_HIP(hipStreamSynchronize(rt->stream)); }
     tk.lap("realign fwd+back (rest)");
@@ -1041,7 +1076,7 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
             rt->prof["score"].units += (double)p.M * as[k]->E;
         }
     }
-    PS_TRY(launch_score(rt, b.d, d_sas, sas, d_pts, pt ? &pts : nullptr, d_sps, sp ? &sps : nullptr));
+    PS_TRY(launch_score(rt, b.d, d_sas, sas, d_pts, pt ? &pts : nullptr, d_sps, sp ? &sps : nullptr, d_gts, d_gts ? &gts : nullptr));
     if (sp) {
         char* h_sp = nullptr;
         if (sp_bytes) PS_TRY(rt->down((void**)&h_sp, d_sp, sp_bytes));
@@ -1049,7 +1084,11 @@ static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, c
         for (int k = 0; k < R; k++) {
             if (!sp_live(k)) continue;
             if (sp->score[k]) memcpy(sp->score[k], h_sp + sscore_at[k], (size_t)plan[k].M * sizeof(double));
-            memcpy(sp->rec[k], h_sp + srec_at[k], (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
+            if (sp->rec[k]) memcpy(sp->rec[k], h_sp + srec_at[k], (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
+            if (sp->geno) {
+                memcpy(sp->lik[k], h_sp + glik_at[k], (size_t)plan[k].M * (sp->nfrac[k] + 1) * sizeof(double));
+                if (sp->ncover[k]) memcpy(sp->ncover[k], h_sp + gcov_at[k], (size_t)plan[k].M * sizeof(int32_t));
+            }
         }
         tk.lap("score edits");
         return PS_OK;
@@ -1121,6 +1160,28 @@ int score_mutation_support_multi(Runtime* rt, const std::vector<Align*>& as, con
     }
     SupportOut sp;
     sp.group = group; sp.ngroups = ngroups; sp.score = scores; sp.rec = recs;
+    return score_mutations_planned(rt, as, muts, {}, nullptr, plan, nullptr, &sp);
+}
+
+// ps_score_mutation_genotypes / ps_batch_score_mutation_genotypes: score_mutation_support_multi with k_genotype behind k_support, and the
+// likelihoods and covering-event counts in the same copy back.  recs[k] and ncover[k] may be null; frac[k]: [nfrac[k]] alt fractions
+// (checked by the caller); lik[k]: [M][nfrac[k] + 1].
+int score_mutation_genotypes_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
+                                   const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
+                                   const std::vector<int>& nfrac, const std::vector<const double*>& frac,
+                                   const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs,
+                                   const std::vector<double*>& lik, const std::vector<int32_t*>& ncover) {
+    const int R = (int)as.size();
+    std::vector<EditPlan> plan(R);
+    par_for(R, [&](int k) { plan_edits(as[k], *muts[k], &plan[k]); });
+    for (int k = 0; k < R; k++) {
+        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
+        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
+        if (plan[k].ncolmax > 64 && as[k]->par.scoring_width > 511) return fail(PS_ERR_UNSUPPORTED, "edit longer than 58 bases with scoring_width > 511");
+    }
+    SupportOut sp;
+    sp.group = group; sp.ngroups = ngroups; sp.score = scores; sp.rec = recs;
+    sp.geno = true; sp.nfrac = nfrac; sp.frac = frac; sp.lik = lik; sp.ncover = ncover;
     return score_mutations_planned(rt, as, muts, {}, nullptr, plan, nullptr, &sp);
 }
 

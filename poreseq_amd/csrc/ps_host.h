@@ -182,6 +182,13 @@ int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vec
 int score_mutation_support_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
                                  const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
                                  const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs);
+// ps_score_mutation_genotypes / ps_batch_score_mutation_genotypes: the support call with the genotype likelihoods of every edit reduced
+// on the device behind it (k_genotype); recs[k] and ncover[k] may be null
+int score_mutation_genotypes_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
+                                   const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
+                                   const std::vector<int>& nfrac, const std::vector<const double*>& frac,
+                                   const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs,
+                                   const std::vector<double*>& lik, const std::vector<int32_t*>& ncover);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases);
 int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds, std::vector<Mut>* out);

@@ -270,12 +270,26 @@ struct SupportArgs {
     ps_edit_support* out;      // [M][ngroups]
 };
 constexpr int SUPPORT_MAX_GROUPS = 8;
+// A genotype call (ps_score_mutation_genotypes: k_genotype behind k_support) has one of these per AlignData beside its ScoreArgs and
+// SupportArgs: the alt fractions f and g = 1 - f, and where the likelihoods and the covering-event counts go.  `score` is set for
+// an AlignData whose caller wants no support records (its SupportArgs.ngroups is 0 and k_support leaves at once): k_genotype then
+// writes the score, k_reduce's sum, itself.
+constexpr int GENO_MAX_FRAC = 8;
+struct GenoArgs {
+    int nfrac;                 // 0 .. GENO_MAX_FRAC (-1: nothing to write for this AlignData)
+    double f[GENO_MAX_FRAC], g[GENO_MAX_FRAC];
+    double* score;             // NULL, or [M]
+    double* lik;               // [M][nfrac + 1]
+    int* ncover;               // [M]
+};
 constexpr int SCORE_CLASSES = 5;
 // (d_pts / h_pts: the PointArgs of a point-edit table call on the device and on the host, parallel to the ScoreArgs; null otherwise.
-//  d_sps / h_sps: the same for the SupportArgs of a support call.  At most one of the two is given.)
+//  d_sps / h_sps: the same for the SupportArgs of a support call.  At most one of the two is given.  d_gts / h_gts: the GenoArgs of
+//  a genotype call, which is a support call with k_genotype behind k_support.)
 int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
                  const PointArgs* d_pts = nullptr, const std::vector<PointArgs>* h_pts = nullptr,
-                 const SupportArgs* d_sps = nullptr, const std::vector<SupportArgs>* h_sps = nullptr);
+                 const SupportArgs* d_sps = nullptr, const std::vector<SupportArgs>* h_sps = nullptr,
+                 const GenoArgs* d_gts = nullptr, const std::vector<GenoArgs>* h_gts = nullptr);
 int launch_begin(Runtime* rt, const BatchD& b);
 int launch_gather_best(Runtime* rt, const BatchD& b, double* out);   // out[job] = the job's forward maxScore (JobOut.best)
 

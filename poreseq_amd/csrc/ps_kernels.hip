@@ -1375,6 +1375,67 @@ __global__ __launch_bounds__(256) void k_support(BatchD b, const ScoreArgs* __re
         }
 }
 
+// Genotype likelihoods per edit (ps_score_mutation_genotypes, include/poreseq_hip.h): a second reduction of the delta matrix that
+// k_support has just read, over the events that SPAN the edit only (k_support's `cv`).  For an alt fraction f with g = 1 - f a
+// covering event adds log(g + f e^d), evaluated as max(d, 0) + log(x) with u = exp(-|d|) and x = g u + f (d > 0) or g + f u: one
+// exp per (event, edit) and one log per fraction, no positive exponent, x in [min(f, g), 1].  The hom-alt column is the covering
+// events' terms in plain FP64 adds.  k_support's shape: a thread per edit, events in order, coalesced reads of delta[e][m], the
+// events' spans staged in LDS SUP_EV at a time behind the same two barriers.  The accumulators are never indexed by a runtime
+// value: the loop over k is unrolled over all GENO_MAX_FRAC and `k < K` (the same for the whole block) guards each.
+__global__ __launch_bounds__(256) void k_genotype(BatchD b, const ScoreArgs* __restrict__ A, const GenoArgs* __restrict__ Q) {
+    const ScoreArgs& a = A[blockIdx.y];
+    const GenoArgs& q = Q[blockIdx.y];
+    const int M = a.nitems_per_job, njobs = a.njobs, K = q.nfrac;
+    if ((int)(blockIdx.x * blockDim.x) >= M || !njobs || K < 0) return;   // (the same for every thread of the block)
+    __shared__ int s_lo[SUP_EV], s_hi[SUP_EV];
+    const int t = threadIdx.x;
+    const int m = blockIdx.x * blockDim.x + t;
+    const bool have = m < M;
+    // column of the 5-mer that begins at the edit's first base; a skipped edit (start > length) is spanned by no event
+    const int col = (have && !a.m_skip[m]) ? a.m_start[m] + 1 : -0x7fffffff;
+    double s = -1e-6, hom = 0.0;
+    int nc = 0;
+    double acc[GENO_MAX_FRAC];
+#pragma unroll
+    for (int k = 0; k < GENO_MAX_FRAC; k++) acc[k] = 0.0;
+    for (int e0 = 0; e0 < njobs; e0 += SUP_EV) {
+        if (e0) __syncthreads();   // (everyone is done with the previous events)
+        if (e0 + t < njobs) {
+            const JobOut* O = b.jobs[a.job0 + e0 + t].out;
+            const bool span = O->has_index != 0;
+            s_lo[t] = span ? O->refstart : 1;
+            s_hi[t] = span ? O->refend : 0;
+        }
+        __syncthreads();
+        const int ne = min(SUP_EV, njobs - e0);
+        if (have)
+            for (int i = 0; i < ne; i++) {
+                const double d = a.delta[(size_t)(e0 + i) * M + m];
+                s += d;
+                if (s_lo[i] <= col && col <= s_hi[i]) {
+                    nc++;
+                    hom += d;
+                    const bool up = d > 0;
+                    const double u = exp(-fabs(d)), top = up ? d : 0.0;
+#pragma unroll
+                    for (int k = 0; k < GENO_MAX_FRAC; k++)
+                        if (k < K) {
+                            const double x = up ? q.g[k] * u + q.f[k] : q.g[k] + q.f[k] * u;
+                            acc[k] += top + log(x);
+                        }
+                }
+            }
+    }
+    if (!have) return;
+    if (q.score) q.score[m] = s;
+    q.ncover[m] = nc;
+    double* out = q.lik + (size_t)m * (K + 1);
+#pragma unroll
+    for (int k = 0; k < GENO_MAX_FRAC; k++)
+        if (k < K) out[k] = acc[k];
+    out[K] = hom;
+}
+
 // latch the reference's "stripe_width == 0" decision (cpp/Alignment.cpp:51-59) for this API call
 __global__ void k_begin(BatchD b) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1556,7 +1617,8 @@ int launch_begin(Runtime* rt, const BatchD& b) {
 // per kernel over all of them — grid.z (k_reduce: grid.y) is the AlignData, blocks past an AlignData's own sizes leave at once
 int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
                  const PointArgs* d_pts, const std::vector<PointArgs>* h_pts,
-                 const SupportArgs* d_sps, const std::vector<SupportArgs>* h_sps) {
+                 const SupportArgs* d_sps, const std::vector<SupportArgs>* h_sps,
+                 const GenoArgs* d_gts, const std::vector<GenoArgs>* h_gts) {
     const int R = (int)h_sas.size();
     int maxE = 0, maxnr0 = 0, maxnr0_all = 0, maxM = 0, cls_max[SCORE_CLASSES] = {0, 0, 0, 0, 0};
     int64_t maxS = 0;
@@ -1619,13 +1681,30 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
         double bytes = 0;
         for (int k = 0; k < R; k++) {
             const ScoreArgs& a = h_sas[k];
-            if (!a.njobs || !a.nitems_per_job) continue;
+            if (!a.njobs || !a.nitems_per_job || !(*h_sps)[k].ngroups) continue;
             bytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 + 24.0 * (*h_sps)[k].ngroups) * a.nitems_per_job;
         }
-        prof_begin(rt);
-        hipLaunchKernelGGL(k_support, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, d_sas, d_sps);
-        PS_LAUNCH_CHECK();
-        prof_end(rt, "support", bytes);
+        // (a genotype call may want no support records anywhere: k_support then has nothing to write; a support call always launches it)
+        bool any_records = !h_gts;
+        for (int k = 0; k < R; k++) any_records |= h_sas[k].njobs && h_sas[k].nitems_per_job && (*h_sps)[k].ngroups;
+        if (any_records) {
+            prof_begin(rt);
+            hipLaunchKernelGGL(k_support, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, d_sas, d_sps);
+            PS_LAUNCH_CHECK();
+            prof_end(rt, "support", bytes);
+        }
+        if (h_gts) {   // a genotype call: the same matrix reduced once more, over the covering events
+            double gbytes = 0;
+            for (int k = 0; k < R; k++) {
+                const ScoreArgs& a = h_sas[k];
+                if (!a.njobs || !a.nitems_per_job || (*h_gts)[k].nfrac < 0) continue;
+                gbytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 * ((*h_gts)[k].nfrac + 1) + 4.0) * a.nitems_per_job;
+            }
+            prof_begin(rt);
+            hipLaunchKernelGGL(k_genotype, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, d_sas, d_gts);
+            PS_LAUNCH_CHECK();
+            prof_end(rt, "genotype", gbytes);
+        }
         return PS_OK;
     }
     hipLaunchKernelGGL(k_reduce, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, d_sas);

@@ -11,7 +11,7 @@ import copy
 import numpy as np
 
 from . import _capi
-from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas
+from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas, genotypes_from_deltas, check_alt_frac
 
 
 def _api():
@@ -87,6 +87,21 @@ def _support_on(api, h, hm, n_events, seq_len, grp, G):
     else:
         scores, sup = api.score_mutation_support(h, hm, len(start), grp, G)
     return scores, sup, _scored_list(start, orig, mut, scores)
+
+
+def _genotypes_on(api, h, hm, n_events, seq_len, grp, G, frac):
+    """(scores, support, scored list, lik, n_cover) of the edit list `hm` on the AlignData `h`: ps_score_mutation_genotypes, or — a
+    library without the entry point — the literal reductions of its score_mutation_deltas and of the refs it leaves
+    (util.support_from_deltas, util.genotypes_from_deltas)"""
+    start, orig, mut, _ = api.muts_export(hm)
+    if "ps_score_mutation_genotypes" in api.missing:
+        deltas = api.score_mutation_deltas(h, hm, n_events, len(start))
+        spans = spans_from_refs(api.align_event_refs(h, n_events))
+        scores, sup = support_from_deltas(deltas, grp, G, spans, start, seq_len)
+        lik, n_cover = genotypes_from_deltas(deltas, spans, start, seq_len, frac)
+    else:
+        scores, sup, lik, n_cover = api.score_mutation_genotypes(h, hm, len(start), grp, G, frac)
+    return scores, sup, _scored_list(start, orig, mut, scores), lik, n_cover
 
 
 class PSAlign:
@@ -251,6 +266,25 @@ class PSAlign:
             hm = d.api.find_point_mutations(d.h) if muts is None else d.api.muts_create(muts)
             try:
                 return _support_on(d.api, d.h, hm, len(self.events), len(self.sequence), grp, G)
+            finally:
+                d.api.muts_destroy(hm)
+
+    def ScoreMutationGenotypes(self, muts=None, alt_frac=(0.5,), groups=None, n_groups=None):
+        """Genotype likelihoods per edit (ps_score_mutation_genotypes): (scores [M], support [M, G], scored list, lik [M, K + 1],
+        n_cover [M]).  The first three are ScoreMutationSupport's, from the same call; `muts`, `groups` and `n_groups` as there.
+        alt_frac gives K alt-allele fractions (0 .. 8, each 1e-6 .. 1 - 1e-6; util.alt_fractions(ploidy) for a ploidy):
+        lik[:, k] is the sum over the events that SPAN the edit of log((1 - f_k) + f_k e^delta), the log-likelihood of a sample
+        that carries the edit at fraction f_k relative to one that does not carry it (hom-ref, 0); lik[:, K] is hom-alt, the
+        spanning events' terms added in event order; n_cover counts those events (the sum of support['cover'] over the groups).
+        Only spanning events enter: a read's term is not zero outside its aligned span.  Reduced on the device (k_genotype), exp /
+        log by the device library; `self` is not modified.  util.call_genotypes turns lik into GT / GQ / PL, uncalibrated.
+        ValueError for groups or fractions that do not fit."""
+        grp, G = support_groups(self.events, groups, n_groups)
+        frac = check_alt_frac(alt_frac)
+        with PSAlign._Data(self, point_width=muts is None) as d:
+            hm = d.api.find_point_mutations(d.h) if muts is None else d.api.muts_create(muts)
+            try:
+                return _genotypes_on(d.api, d.h, hm, len(self.events), len(self.sequence), grp, G, frac)
             finally:
                 d.api.muts_destroy(hm)
 

@@ -204,3 +204,99 @@ def support_from_deltas(deltas, groups, n_groups, spans, starts, seq_len):
         sup['pos'][:, g] += cv & (d > 0)
         sup['neg'][:, g] += cv & (d < 0)
     return scores, sup
+
+
+def alt_fractions(ploidy):
+    """The alt-allele fractions of the heterozygous genotypes of a sample with `ploidy` copies: [k / ploidy for k in 1 .. ploidy - 1]
+    (empty for ploidy 1: hom-ref and hom-alt need none).  ValueError outside 1 .. 9 — a genotype call takes at most 8 fractions."""
+    P = int(ploidy)
+    if P != ploidy or not 1 <= P <= 9:
+        raise ValueError("alt_fractions: ploidy = %r, allowed are 1 .. 9" % (ploidy,))
+    return [k / P for k in range(1, P)]
+
+
+def check_alt_frac(alt_frac):
+    """float64 [K] of the alt fractions of a genotype call; ValueError for more than 8 or one outside 1e-6 .. 1 - 1e-6 (NaN included)"""
+    import numpy as np
+    f = np.asarray(list(alt_frac), dtype=np.float64).reshape(-1)
+    if f.size > 8:
+        raise ValueError("genotypes: n_frac = %d, allowed are 0 .. 8" % f.size)
+    bad = np.flatnonzero(~((f >= 1e-6) & (f <= 1.0 - 1e-6)))
+    if bad.size:
+        raise ValueError("genotypes: alt_frac[%d] = %g, allowed is 1e-06 .. 1 - 1e-06" % (int(bad[0]), float(f[bad[0]])))
+    return f
+
+
+def genotypes_from_deltas(deltas, spans, starts, seq_len, alt_frac):
+    """The definition of what ps_score_mutation_genotypes adds to the support call, in numpy float64 — and the path of a library
+    without the entry point.  deltas [E, M], spans [E, 2], starts [M], seq_len as `support_from_deltas` takes them; alt_frac the K
+    alt-allele fractions f_k (0 .. 8 of them, each 1e-6 .. 1 - 1e-6), g_k = 1.0 - f_k.
+    Returns (lik float64 [M, K + 1], n_cover int32 [M]).  Only the events that COVER an edit (support_from_deltas' test) enter:
+      n_cover     the number of covering events
+      lik[:, k]   0.0, then for e ascending with cover:  d = delta[e][m], u = exp(-|d|), x = g_k u + f_k if d > 0 else g_k + f_k u,
+                  += (d if d > 0 else 0.0) + log(x) — log((1 - f) + f e^d) without a positive exponent.  d = -inf adds log(g_k),
+                  d = +inf gives +inf, NaN gives NaN.
+      lik[:, K]   0.0, then += d over the covering events in event order: hom-alt, every covering read carries the edit.
+    Hom-ref is 0 by construction.  An edit with start > seq_len and every edit without covering events has n_cover 0 and lik 0."""
+    import numpy as np
+    deltas = np.asarray(deltas, dtype=np.float64)
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    E, M = (deltas.shape[0], starts.size) if deltas.ndim == 2 else (0, starts.size)
+    deltas = deltas.reshape(E, M)
+    f = check_alt_frac(alt_frac)
+    g = 1.0 - f
+    K = f.size
+    spans = np.asarray(spans, dtype=np.int64).reshape(E, 2)
+    col = starts + 1
+    live = starts <= int(seq_len)
+    lik = np.zeros((M, K + 1), dtype=np.float64)
+    n_cover = np.zeros(M, dtype=np.int32)
+    with np.errstate(all='ignore'):
+        for e in range(E):
+            cv = live & (spans[e, 0] <= col) & (col <= spans[e, 1])
+            if not cv.any():
+                continue
+            d = deltas[e][cv]
+            up = d > 0
+            u = np.exp(-np.abs(d))
+            top = np.where(up, d, 0.0)
+            for k in range(K):
+                x = np.where(up, g[k] * u + f[k], g[k] + f[k] * u)
+                lik[cv, k] = lik[cv, k] + (top + np.log(x))
+            lik[cv, K] = lik[cv, K] + d
+            n_cover[cv] += 1
+    return lik, n_cover
+
+
+def call_genotypes(lik, n_cover, ploidy):
+    """(GT strings [M], GQ ints [M], PL lists [M][ploidy + 1]) from the likelihoods of a genotype call made with
+    alt_fractions(ploidy).  Host only.  Genotype k is the number of alt copies, 0 .. P: L_0 = 0 (hom-ref), L_k = lik[:, k - 1],
+    L_P = lik[:, -1] (hom-alt).  PL_k = min(int(floor(-10 (L_k - max L) / ln 10 + 0.5)), 9999); GT is the first k that holds the
+    maximum, written as (P - k) zeros then k ones joined by '/' ('0/0', '0/1', '1/1' for P = 2; '0' or '1' for P = 1);
+    GQ = min(99, second smallest PL).  An edit with n_cover == 0 or a NaN among its L is a no-call: '.' repeated P times, GQ 0,
+    all PL 0.  UNCALIBRATED, like QUAL and the FASTQ qualities: ratios of this model's likelihoods, not measured error rates."""
+    import math
+    import numpy as np
+    P = len(alt_fractions(ploidy)) + 1
+    lik = np.asarray(lik, dtype=np.float64)
+    n_cover = np.asarray(n_cover).reshape(-1)
+    if lik.size != n_cover.size * P or (lik.ndim == 2 and lik.shape[1] != P):     # (an empty list has no rows to call: three empty lists)
+        raise ValueError("call_genotypes: ploidy %d needs %d likelihood columns per edit" % (P, P))
+    gts, gqs, pls = [], [], []
+    for row, nc in zip(lik.reshape(n_cover.size, P).tolist(), n_cover.tolist()):
+        L = [0.0] + row
+        if nc == 0 or any(v != v for v in L):
+            gts.append('/'.join(['.'] * P))
+            gqs.append(0)
+            pls.append([0] * (P + 1))
+            continue
+        top = max(L)
+        k = L.index(top)
+        pl = []
+        for v in L:
+            q = 0.0 if v == top else -10.0 * (v - top) / math.log(10.0)     # (an infinite maximum: 0 for itself, the cap for the rest)
+            pl.append(9999 if not q < 9999.0 else min(int(math.floor(q + 0.5)), 9999))
+        gts.append('/'.join(['0'] * (P - k) + ['1'] * k))
+        gqs.append(min(99, sorted(pl)[1]))
+        pls.append(pl)
+    return gts, gqs, pls
