@@ -169,8 +169,9 @@ int ps_score_mutation_deltas(ps_align* a, const ps_muts* in, double* deltas) {
     if (!a || !in || !deltas) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_deltas");
     NEED_RT();
     std::vector<Mut> scored;
-    std::vector<double*> dout(1, deltas);
-    return score_mutations_multi(rt, {&a->a}, {&in->v}, {&scored}, &dout);
+    EditReq q;
+    q.a = &a->a; q.muts = &in->v; q.out = &scored; q.delta = deltas;
+    return score_edits(rt, EditKind::List, &q, 1);
 }
 int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
     if (!a || !in || !nb) return fail(PS_ERR_BAD_ARG, "ps_make_mutations");
@@ -278,13 +279,12 @@ int ps_batch_score_mutations(int32_t n, ps_align* const* a, const ps_muts* const
     if (n && (!muts || !out)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutations");
     NEED_RT();
     std::vector<std::unique_ptr<ps_muts>> m(n);
-    std::vector<const std::vector<Mut>*> in(n);
-    std::vector<std::vector<Mut>*> o(n);
+    std::vector<EditReq> rq(n);
     for (int i = 0; i < n; i++) {
         if (!muts[i]) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutations: null list");
-        m[i].reset(new ps_muts()); in[i] = &muts[i]->v; o[i] = &m[i]->v;
+        m[i].reset(new ps_muts()); rq[i].a = as[i]; rq[i].muts = &muts[i]->v; rq[i].out = &m[i]->v;
     }
-    PS_TRY(score_mutations_multi(rt, as, in, o));
+    PS_TRY(score_edits(rt, EditKind::List, rq.data(), rq.size()));
     for (int i = 0; i < n; i++) out[i] = m[i].release();
     return PS_OK;
 }
@@ -292,18 +292,19 @@ int ps_batch_point_table(int32_t n_regions, ps_align* const* a, double* const* t
     std::vector<Align*> as;
     PS_TRY(batch_handles(n_regions, a, &as));
     if (n_regions && !n) return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: null position counts");
-    std::vector<double*> tb(n_regions);
-    std::vector<ps_point_best*> bs(n_regions);
+    std::vector<EditReq> rq(n_regions);
     for (int i = 0; i < n_regions; i++) {
         const int64_t have = (int64_t)as[i]->states.size();
         if (n[i] != have)
             return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: region " + std::to_string(i) + " was given n = " + std::to_string(n[i]) + ", its sequence has " +
                                         std::to_string(have) + " positions (length - 4)");
-        tb[i] = table ? table[i] : nullptr; bs[i] = best ? best[i] : nullptr;
+        rq[i].a = as[i]; rq[i].table = table ? table[i] : nullptr; rq[i].best = best ? best[i] : nullptr;
     }
     if (!n_regions) return PS_OK;
     NEED_RT();
-    return point_table_multi(rt, as, tb, bs);
+    // ScorePoints (ScoreMutations on FindPointMutations' list, at the scoring width the AlignData carries), reduced on the device to a
+    // row per position (k_point_table) instead of a scored list
+    return score_edits(rt, EditKind::Points, rq.data(), rq.size());
 }
 int ps_point_table(ps_align* a, double* table, ps_point_best* best, int64_t n) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_point_table: null handle");
@@ -314,11 +315,7 @@ int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
     if (n && (!muts || !n_groups || !group || !support)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_support: null array");
-    std::vector<const std::vector<Mut>*> in(n);
-    std::vector<const int32_t*> gr(n);
-    std::vector<int> ng(n);
-    std::vector<double*> sc(n);
-    std::vector<ps_edit_support*> rec(n);
+    std::vector<EditReq> rq(n);
     size_t edits = 0;
     for (int i = 0; i < n; i++) {
         const std::string who = "ps_score_mutation_support: region " + std::to_string(i);
@@ -330,12 +327,13 @@ int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts
         for (int e = 0; e < as[i]->E; e++)
             if (group[i][e] < 0 || group[i][e] >= n_groups[i])
                 return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(group[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
-        in[i] = &muts[i]->v; gr[i] = group[i]; ng[i] = n_groups[i]; sc[i] = scores ? scores[i] : nullptr; rec[i] = support[i];
-        edits += in[i]->size();
+        EditReq& q = rq[i];
+        q.a = as[i]; q.muts = &muts[i]->v; q.group = group[i]; q.ngroups = n_groups[i]; q.score = scores ? scores[i] : nullptr; q.rec = support[i];
+        edits += q.muts->size();
     }
     if (!edits) return PS_OK;   // nothing to score anywhere: no launch
     NEED_RT();
-    return score_mutation_support_multi(rt, as, in, gr, ng, sc, rec);
+    return score_edits(rt, EditKind::Support, rq.data(), rq.size());   // k_support instead of k_reduce behind k_score
 }
 int ps_score_mutation_support(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group, double* scores, ps_edit_support* support) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_support: null handle");
@@ -347,13 +345,7 @@ int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_mu
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
     if (n && (!muts || !n_groups || !group || !n_frac || !lik)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_genotypes: null array");
-    std::vector<const std::vector<Mut>*> in(n);
-    std::vector<const int32_t*> gr(n);
-    std::vector<int> ng(n), nf(n);
-    std::vector<const double*> fr(n);
-    std::vector<double*> sc(n), lk(n);
-    std::vector<ps_edit_support*> rec(n);
-    std::vector<int32_t*> nc(n);
+    std::vector<EditReq> rq(n);
     size_t edits = 0;
     for (int i = 0; i < n; i++) {
         const std::string who = "ps_score_mutation_genotypes: region " + std::to_string(i);
@@ -375,13 +367,14 @@ int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_mu
                 return fail(PS_ERR_BAD_ARG, who + msg);
             }
         if (!lik[i]) return fail(PS_ERR_BAD_ARG, who + ": null lik");
-        in[i] = &muts[i]->v; gr[i] = group[i]; ng[i] = n_groups[i]; nf[i] = n_frac[i]; fr[i] = f;
-        sc[i] = scores ? scores[i] : nullptr; rec[i] = support ? support[i] : nullptr; lk[i] = lik[i]; nc[i] = n_cover ? n_cover[i] : nullptr;
-        edits += in[i]->size();
+        EditReq& q = rq[i];
+        q.a = as[i]; q.muts = &muts[i]->v; q.group = group[i]; q.ngroups = n_groups[i]; q.nfrac = n_frac[i]; q.frac = f;
+        q.score = scores ? scores[i] : nullptr; q.rec = support ? support[i] : nullptr; q.lik = lik[i]; q.ncover = n_cover ? n_cover[i] : nullptr;
+        edits += q.muts->size();
     }
     if (!edits) return PS_OK;   // nothing to score anywhere: no launch
     NEED_RT();
-    return score_mutation_genotypes_multi(rt, as, in, gr, ng, nf, fr, sc, rec, lk, nc);
+    return score_edits(rt, EditKind::Genotype, rq.data(), rq.size());   // k_genotype behind k_support
 }
 int ps_score_mutation_genotypes(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group, int32_t n_frac, const double* alt_frac,
                                 double* scores, ps_edit_support* support, double* lik, int32_t* n_cover) {

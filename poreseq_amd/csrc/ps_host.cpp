@@ -1,8 +1,8 @@
 // ps_host.cpp — host side of libporeseq_hip.so above the runtime: sequences, AlignData, alignment batches and realign() (which
 // fill runs for a batch, in which form), and the refinement-loop logic that the reference keeps in C++ above its Alignment class
-// (cpp/MakeMutations.cpp, cpp/FindMutations.cpp, cpp/EventUtil.cpp, cpp/Sequence.h): ScoreAlignments, ScoreMutations with its edit
-// plans, FindPointMutations, MakeMutations.  The runtime, its streams and par_for are in ps_runtime.cpp; device memory — pools,
-// shares, slabs, the AlignData slab cache — in ps_mem.cpp, its arithmetic in ps_plan.h.
+// (cpp/MakeMutations.cpp, cpp/EventUtil.cpp): ScoreAlignments and MakeMutations.  ScoreMutations and its reductions — the edit-scoring
+// chain — are in ps_score.cpp, the edit plans in ps_editplan.h, FindMutations in ps_find.cpp.  The runtime, its streams and par_for
+// are in ps_runtime.cpp; device memory — pools, shares, slabs, the AlignData slab cache — in ps_mem.cpp, its arithmetic in ps_plan.h.
 // All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_sw.hip,
 // ps_viterbi.hip); there is no CPU implementation of it in this library.
 #include "ps_host.h"
@@ -14,27 +14,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <iterator>
 #include <numeric>
-#include <thread>
 
 namespace ps {
-
-// ------------------------------------------------------------------------------------------ sequences
-// Sequence::populateStates, cpp/Sequence.h:64-100
-std::vector<int> states_of(const std::string& bases) {
-    std::vector<int> st;
-    if (bases.size() < 5) return st;
-    auto code = [](char c) -> int { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : (int)(signed char)c; };
-    int cur = 0;
-    for (int i = 0; i < 4; i++) cur = (cur << 2) + code(bases[i]);
-    st.resize(bases.size() - 4);
-    for (size_t i = 4; i < bases.size(); i++) {
-        if (code(bases[i - 4]) < 4) { cur = (NS - 1) & ((cur << 2) + code(bases[i])); st[i - 4] = cur; }
-        else { cur = 0; st[i - 4] = -1; }
-    }
-    return st;
-}
 
 // ------------------------------------------------------------------------------------------ batch
 int Batch::build(Runtime* rt, const std::vector<JobSpec>& specs, int ndir_, int lb_extra) {
@@ -354,7 +336,7 @@ static std::atomic<int> g_sweep_min(-1), g_sweep2_min(-1), g_sparse_min(-1);
 void sweep_min_set(int n) { g_sweep_min.store(n); }
 void sweep2_min_set(int n) { g_sweep2_min.store(n); }
 void sparse_min_set(int n) { g_sparse_min.store(n); }
-static int sparse_min() { return g_sparse_min.load() >= 0 ? g_sparse_min.load() : sparse_min_default(); }
+int sparse_min() { return g_sparse_min.load() >= 0 ? g_sparse_min.load() : sparse_min_default(); }
 bool sweep_enabled() { static const bool off = getenv("PORESEQ_NO_SWEEP") != nullptr; return !off; }
 
 // PORESEQ_DEBUG_SWEEP_K (tests: a given strip height, i.e. a wrong guess; read per call); < 0: not set
@@ -521,36 +503,16 @@ int guess_slots(const Align* a) {
     return dbg > 0 ? std::min(1024, std::max(64, dbg)) : guess_slots_w(a->par.realign_width);
 }
 
-// Where the sub-batch of AlignData that starts at as[k0] ends when each event takes `ndir` sweeps: everything if it fits this
-// runtime's device share; otherwise the fewest sub-batches that fit, of about equal size (share_cut, ps_plan.h)
-static size_t fit_share(const std::vector<Align*>& as, size_t k0, int ndir) {
-    const double cap = ndir == 2 ? dense_cap_bytes() : device_share_bytes();   // (full forward + backward matrices live in a slab)
-    auto need = [&](size_t k) {
-        const Align* a = as[k];
-        const int P = guess_slots(a);
-        double add = 0;
-        for (int e = 0; e < a->E; e++)
-            add += ndir == 1 ? fwd_job_bytes(a, a->n[e], (int)a->states.size()) : matrix_bytes((int64_t)a->n[e] + (int64_t)a->states.size() + 1, P, ndir);
-        return add;
-    };
-    return share_cut(k0, as.size(), cap, need);
+// What the events of one AlignData will probably take on the device when each takes `ndir` sweeps, and what a lock-step call may
+// take of it (in_share_chunks, ps_host.h)
+double share_need(const Align* a, int ndir) {
+    const int P = guess_slots(a);
+    double add = 0;
+    for (int e = 0; e < a->E; e++)
+        add += ndir == 1 ? fwd_job_bytes(a, a->n[e], (int)a->states.size()) : matrix_bytes((int64_t)a->n[e] + (int64_t)a->states.size() + 1, P, ndir);
+    return add;
 }
-
-// regions k0 .. k1 - 1 of a lock-step call as calls of their own, sub(k0, k1), one after the other: the sub-batches that fit this
-// runtime's share (fit_share), or two halves (a call whose bands came out wider than guessed)
-template <class Sub> static int in_share_chunks(const std::vector<Align*>& as, int ndir, Sub&& sub) {
-    for (size_t k0 = 0; k0 < as.size();) {
-        const size_t k1 = fit_share(as, k0, ndir);
-        PS_TRY(sub(k0, k1));
-        k0 = k1;
-    }
-    return PS_OK;
-}
-template <class Sub> static int in_halves(size_t n, Sub&& sub) {
-    const size_t h = n / 2;
-    PS_TRY(sub(0, h));
-    return sub(h, n);
-}
+double share_cap(int ndir) { return ndir == 2 ? dense_cap_bytes() : device_share_bytes(); }
 
 // ScoreAlignments, cpp/MakeMutations.cpp:148-195, for several AlignData in one launch chain (independent regions in lock-step)
 int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes) {
@@ -558,7 +520,8 @@ int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std
         return score_alignments_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
                                       std::vector<double*>(likes.begin() + k0, likes.begin() + k1));
     };
-    if (fit_share(as, 0, 1) < as.size()) return in_share_chunks(as, 1, sub);   // more matrices than this runtime's share of the device
+    auto need = [&](size_t k) { return share_need(as[k], 1); };
+    if (over_share(as.size(), 1, need)) return in_share_chunks(as.size(), 1, need, sub);   // more matrices than this runtime's share of the device
     std::vector<JobSpec> specs;
     for (Align* a : as)
         for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
@@ -567,7 +530,7 @@ int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std
     PS_TRY(b.build(rt, specs, 1, 0));
     {
         const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
-        if (rc == PS_SPLIT) return in_halves(as.size(), sub);   // bands wider than fit_share guessed: two halves, one after the other
+        if (rc == PS_SPLIT) return in_halves(as.size(), sub);   // bands wider than share_need guessed: two halves, one after the other
         PS_TRY(rc);
     }
     // the jobs' scores, gathered into one array on the device: one copy back instead of one per AlignData
@@ -602,620 +565,6 @@ int score_alignments(Runtime* rt, Align* a, double* scores, double* likes) {
     return score_alignments_multi(rt, {a}, {scores}, {likes});
 }
 
-// the `likes` loop of ScoreAlignments, cpp/MakeMutations.cpp:168-189 (one event)
-void accumulate_likes(const double* ra, const double* rl, int n, int C, double* likes) {
-    double last = 0;
-    int refind = 1;
-    for (int t = 0; t < n; t++) {
-        if (ra[t] > 0) {
-            for (int k = refind; k < ra[t]; k++) likes[k + 1] += last;
-            last = rl[t];
-            refind = (int)ra[t];
-        }
-    }
-    for (int64_t k = refind; k < (int64_t)C + 3; k++) likes[k + 1] += last;
-}
-
-// states of the edited sequence at columns sidx+1 .. sidx+ncol, without building the whole sequence;
-// equals Sequence(original, mut).states there (cpp/Sequence.h:37-100).  A 12-base look-back flushes
-// every effect of earlier non-ACGT characters (they reach at most 8 states ahead).
-static void edited_window(const std::string& b, const Mut& m, int sidx, int ncol, int* out) {
-    const bool copy = (size_t)m.start >= b.size();
-    const int64_t L = (int64_t)b.size();
-    const int64_t cut = copy ? L : std::min<int64_t>(L, (int64_t)m.start + (int64_t)m.orig.size());
-    const int64_t mlen = copy ? 0 : (int64_t)m.mut.size();
-    const int64_t Lm = copy ? L : (int64_t)m.start + mlen + (L - cut);
-    auto at = [&](int64_t p) -> char {
-        if (copy || p < m.start) return b[p];
-        if (p < m.start + mlen) return m.mut[p - m.start];
-        return b[cut + (p - m.start - mlen)];
-    };
-    const int64_t lo = std::max<int64_t>(0, (int64_t)sidx - 12);
-    const int64_t hi = std::min<int64_t>(Lm, (int64_t)sidx + ncol + 4);
-    std::string w;
-    w.reserve(hi - lo);
-    for (int64_t p = lo; p < hi; p++) w.push_back(at(p));
-    std::vector<int> st = states_of(w);
-    for (int c = 0; c < ncol; c++) {
-        const int64_t k = (int64_t)sidx + c - lo;
-        out[c] = (k >= 0 && k < (int64_t)st.size()) ? st[k] : -1;
-    }
-}
-
-// Where FindPointMutations' list (cpp/FindMutations.cpp:200-228) keeps each position's edits: first[p] is the index of position p's
-// deletion, followed by its substitutions in ACGT order without the one by the base itself, then the four insertions — 8 edits for an
-// A / C / G / T base, 9 for any other character; first[n] = the length of the list.  triv[p]: table slot 1 .. 4 of the substitution
-// that is not in the list, 0 when all four are.
-static void point_layout(const Align* a, std::vector<int>* first, std::vector<int>* triv) {
-    const size_t n = a->states.size();
-    first->resize(n + 1); triv->resize(n);
-    int m = 0;
-    for (size_t i = 0; i < n; i++) {
-        const char c = a->bases[i];
-        const int t = c == 'A' ? 1 : c == 'C' ? 2 : c == 'G' ? 3 : c == 'T' ? 4 : 0;
-        (*first)[i] = m; (*triv)[i] = t;
-        m += t ? 8 : 9;
-    }
-    (*first)[n] = m;
-}
-
-// the rows of an AlignData without events: every edit keeps the seed of its sum, -1e-6 (cpp/AlignUtil.h:86)
-static void point_rows_seed(const std::vector<int>& triv, double* table, ps_point_best* best) {
-    for (size_t p = 0; p < triv.size(); p++) {
-        if (table)
-            for (int q = 0; q < PT_SLOTS; q++) table[p * PT_SLOTS + q] = (triv[p] && q == triv[p]) ? std::nan("") : -1e-6;
-        if (best) { best[p].margin = -1e-6; best[p].slot = 0; best[p].n_positive = 0; }
-    }
-}
-
-namespace {
-// host-side description of one AlignData's edit list for k_old / k_score
-struct EditPlan {
-    int M = 0, ncolmax = 1, extra = 0, nr0 = 0;
-    std::vector<int> start, mlen, cm, ncol, skip, oldidx, states, r0s, cls[SCORE_CLASSES];
-    std::vector<int> keep[2];   // per direction: kept-column index of column 0 .. C + 1, or -1 (plan_keep)
-    int nkeep[2] = {0, 0};
-    int rc = PS_OK;
-};
-}  // namespace
-
-static void plan_edits(const Align* a, const std::vector<Mut>& muts, EditPlan* p) {
-    const int M = (int)muts.size();
-    p->M = M;
-    for (const Mut& m : muts) if (m.start < 0) { p->rc = PS_ERR_BAD_ARG; return; }
-    const int64_t L = (int64_t)a->bases.size();
-    const int C = (int)a->states.size();
-    const int WS = a->par.scoring_width;
-    p->start.resize(M); p->mlen.resize(M); p->cm.resize(M); p->ncol.resize(M); p->skip.resize(M); p->oldidx.resize(M);
-    int ncolmax = 1, extra = 0;
-    for (int i = 0; i < M; i++) {
-        const Mut& m = muts[i];
-        p->start[i] = m.start; p->mlen[i] = (int)m.mut.size();
-        p->skip[i] = (int64_t)m.start > L ? 1 : 0;  // "sanity check", cpp/MakeMutations.cpp:46-47
-        const bool copy = (int64_t)m.start >= L;
-        const int64_t cut = std::min<int64_t>(L, (int64_t)m.start + (int64_t)m.orig.size());
-        const int64_t Lm = copy ? L : (int64_t)m.start + (int64_t)m.mut.size() + (L - cut);
-        const int Cm = Lm >= 5 ? (int)(Lm - 4) : 0;
-        p->cm[i] = Cm;
-        const int sidx = std::max(m.start - 4, 0);
-        int ncol = std::min<int64_t>((int64_t)m.mut.size() + 6, std::max<int64_t>(0, (int64_t)Cm - sidx));
-        if (WS == 0 || p->skip[i]) ncol = 0;  // stripe_width 0 makes fillColumn a no-op, cpp/Alignment.cpp:118-119
-        p->ncol[i] = ncol;
-        ncolmax = std::max(ncolmax, ncol);
-        if (!p->skip[i]) extra = std::max(extra, sidx + ncol + 1 - (C + 1));
-    }
-    p->ncolmax = ncolmax;
-    p->extra = std::max(extra, 0) + 2;
-}
-
-// The matrix columns the scoring of this list will read (k_old / k_score, cpp/Alignment.cpp:447-512, cpp/Alignment.h:181-214):
-// per edit the forward column it is spliced behind, max(start - 4, 0), the column pair of its old score, max(start - 3, 1) forward
-// and C - that + 1 backward, and the backward column its target is combined with — with the kernels' own clamping.  Column 0 (the
-// blank column) is never read from the records.
-static void plan_keep(const Align* a, EditPlan* p) {
-    const int C = (int)a->states.size();
-    for (int d = 0; d < 2; d++) { p->keep[d].assign((size_t)C + 2, -1); p->nkeep[d] = 0; }
-    auto clampc = [&](int c) { return (unsigned)c >= (unsigned)(C + 1) ? C : c; };
-    for (int i = 0; i < p->M; i++) {
-        if (p->skip[i]) continue;
-        const int start = p->start[i];
-        const int sidx = std::max(start - 4, 0);
-        const int tcol = std::min(start + p->mlen[i] + 1, sidx + p->ncol[i]);
-        const int backind = clampc(p->cm[i] - tcol + 1);
-        const int r0 = std::max(start - 3, 1);
-        const int raf = clampc(r0), rab = clampc(C - r0 + 1);
-        const int sf = clampc(sidx);
-        if (sf > 0) p->keep[0][sf] = 0;
-        if (raf > 0) p->keep[0][raf] = 0;
-        if (backind > 0) p->keep[1][backind] = 0;
-        if (rab > 0) p->keep[1][rab] = 0;
-    }
-    for (int d = 0; d < 2; d++)
-        for (int c = 0; c <= C + 1; c++) if (p->keep[d][c] == 0) p->keep[d][c] = p->nkeep[d]++;
-}
-
-// second half of the plan (runs on host threads while the GPU realigns): edited states, distinct r0, size classes
-static void plan_tables(const Align* a, const std::vector<Mut>& muts, EditPlan* p, int nth) {
-    const int M = p->M, ncolmax = p->ncolmax;
-    const int64_t L = (int64_t)a->bases.size();
-    p->states.assign((size_t)M * ncolmax, -1);
-    {
-        auto work = [&](int lo, int hi) {
-            for (int i = lo; i < hi; i++)
-                if (p->ncol[i] > 0) edited_window(a->bases, muts[i], std::max(muts[i].start - 4, 0), p->ncol[i], p->states.data() + (size_t)i * ncolmax);
-        };
-        if (M < 4096) nth = 1;   // Refine-sized lists: split over a few host threads (disjoint outputs)
-        std::vector<std::thread> th;
-        for (int t = 1; t < nth; t++) th.emplace_back(work, (int)((int64_t)M * t / nth), (int)((int64_t)M * (t + 1) / nth));
-        work(0, (int)((int64_t)M / nth));
-        for (std::thread& x : th) x.join();
-    }
-    std::vector<int> idx((size_t)std::max<int64_t>(L, 4) + 2, -1);   // r0 <= L - 3 for every edit that is not skipped
-    for (int i = 0; i < M; i++) {
-        if (p->skip[i]) { p->oldidx[i] = 0; continue; }
-        const int r0 = std::max(muts[i].start - 3, 1);
-        int& at = idx[r0];
-        if (at < 0) { at = (int)p->r0s.size(); p->r0s.push_back(r0); }
-        p->oldidx[i] = at;
-    }
-    p->nr0 = (int)p->r0s.size();
-    for (int i = 0; i < M; i++) {
-        const int nc = p->ncol[i];
-        p->cls[nc <= 7 ? 4 : nc <= 8 ? 0 : nc <= 16 ? 1 : nc <= 32 ? 2 : 3].push_back(i);
-    }
-}
-
-// ScoreMutations, cpp/MakeMutations.cpp:23-69, for several AlignData at once: one realign launch chain over all their
-// events (forward + backward of one event share a workgroup), then the edit scoring of each
-// a point-table call (point_table_multi): per AlignData the host arrays that receive its rows and its per-position records (either may
-// be null); the lists are FindPointMutations' and no scored copy is made (`outs` is empty)
-namespace {
-struct PointOut { std::vector<double*> table; std::vector<ps_point_best*> best; };
-// a support call (score_mutation_support_multi): per AlignData the events' group ids, the number of groups and the host arrays that
-// receive the scores (may be null) and the [M][ngroups] records; no scored copy of the lists is made either
-struct SupportOut {
-    std::vector<const int32_t*> group; std::vector<int> ngroups; std::vector<double*> score; std::vector<ps_edit_support*> rec;
-    // a genotype call (score_mutation_genotypes_multi) on top: per AlignData the alt fractions and the host arrays that receive the
-    // [M][nfrac + 1] likelihoods and the covering-event counts (may be null); `rec` entries may then be null (no records wanted)
-    bool geno = false;
-    std::vector<int> nfrac; std::vector<const double*> frac; std::vector<double*> lik; std::vector<int32_t*> ncover;
-};
-}  // namespace
-static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                   const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
-                                   const PointOut* pt = nullptr, const SupportOut* sp = nullptr);
-
-int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                          const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out) {
-    const int R = (int)as.size();
-    std::vector<EditPlan> plan(R);
-    par_for(R, [&](int k) {   // (a Refine list is 80 000 edits per region: copied and sized side by side)
-        *outs[k] = *muts[k];
-        for (Mut& m : *outs[k]) m.score = -1e-6;
-        plan_edits(as[k], *muts[k], &plan[k]);
-    });
-    for (int k = 0; k < R; k++) {
-        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
-        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
-        if (plan[k].ncolmax > 64 && as[k]->par.scoring_width > 511) return fail(PS_ERR_UNSUPPORTED, "edit longer than 58 bases with scoring_width > 511");
-    }
-    return score_mutations_planned(rt, as, muts, outs, delta_out, plan);
-}
-
-// `plan`: every list sized (plan_edits) and `outs` initialised — once per call: the sub-batches of a call that does not fit a slab or the
-// runtime's share, and the halves of one whose bands came out wider than guessed, take their regions' plans with them (moved: the
-// caller returns right behind them) instead of copying and sizing 80 000 edits per region again
-static int score_mutations_planned(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                   const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out, std::vector<EditPlan>& plan,
-                                   const PointOut* pt, const SupportOut* sp) {
-    Tick tk(pt ? "point_table" : sp ? (sp->geno ? "score_mutation_genotypes" : "score_mutation_support") : "score_mutations");
-    const int R = (int)as.size();
-    // the reference's progress line under `verbose` (cpp/MakeMutations.cpp:28-32, 55-66: "Scoring (<width>)", a dot per event, a newline);
-    // a lock-step call over several AlignData has no single line to write: only the single-handle call speaks
-    if (R == 1 && as[0]->par.verbose) {
-        fprintf(stderr, "Scoring (%d)", (int)as[0]->par.scoring_width);
-        for (int e = 0; e < as[0]->E; e++) fputc('.', stderr);
-        fputc('\n', stderr);
-        fflush(stderr);
-    }
-    // Which columns of the score matrices will the edit lists read?  A short list (FindMutations' found edits, the rounds of
-    // MakeMutations' recursion: tens to hundreds of edits per region) reads a few percent of them: the fills then run as strip
-    // sweeps that keep those columns only (ps_sweep.hip, k_sweeps) — a few MB per alignment instead of 2 x 110 MB.  A list that
-    // touches more than a quarter of the columns (Refine's point edits at every position) takes full matrices.
-    static const double sparse_frac = getenv("PORESEQ_SPARSE_FRAC") ? atof(getenv("PORESEQ_SPARSE_FRAC")) : 0.25;
-    bool sparse = sweep_enabled();
-    int njobs_all = 0;
-    double sparse_bytes = 0;
-    for (int k = 0; k < R && sparse; k++) {
-        const Align* a = as[k];
-        const int C = (int)a->states.size();
-        if (plan[k].keep[0].empty()) plan_keep(a, &plan[k]);   // (C + 2 entries once computed)
-        if (std::max(plan[k].nkeep[0], plan[k].nkeep[1]) > sparse_frac * C) sparse = false;
-        const int K = sweep_guess_k(a->par.realign_width);
-        if (!K) sparse = false;
-        njobs_all += a->E;
-        for (int e = 0; e < a->E && sparse; e++)
-            sparse_bytes += 1.15 * sweep_job_bytes(a->n[e], C, sweep_guess_form(a->par.realign_width, 1)) + 16.0 * (plan[k].nkeep[0] + plan[k].nkeep[1]) * (std::min(2 * a->par.realign_width + 1, a->n[e]) + 24);
-    }
-    if (sparse && 2 * njobs_all < sparse_min()) sparse = false;
-    if (tk.on) {
-        double fr = 0; size_t M = 0;
-        for (int k = 0; k < R; k++) { M += plan[k].M; if (!plan[k].keep[0].empty()) fr = std::max(fr, (double)std::max(plan[k].nkeep[0], plan[k].nkeep[1]) / std::max<size_t>(as[k]->states.size(), 1)); }
-        fprintf(stderr, "[ps] score_mutations: %d regions, %d events, %zu edits, kept columns <= %.3f of a matrix: %s\n", R, njobs_all, M, fr, sparse ? "kept columns" : "full matrices");
-    }
-    tk.lap("edit sizes");
-    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own, with their plans
-        std::vector<double*> dsub;
-        if (delta_out) dsub.assign(delta_out->begin() + k0, delta_out->begin() + k1);
-        std::vector<EditPlan> psub(std::make_move_iterator(plan.begin() + k0), std::make_move_iterator(plan.begin() + k1));
-        PointOut ptsub;
-        if (pt) { ptsub.table.assign(pt->table.begin() + k0, pt->table.begin() + k1); ptsub.best.assign(pt->best.begin() + k0, pt->best.begin() + k1); }
-        SupportOut spsub;
-        if (sp) {
-            spsub.group.assign(sp->group.begin() + k0, sp->group.begin() + k1); spsub.ngroups.assign(sp->ngroups.begin() + k0, sp->ngroups.begin() + k1);
-            spsub.score.assign(sp->score.begin() + k0, sp->score.begin() + k1); spsub.rec.assign(sp->rec.begin() + k0, sp->rec.begin() + k1);
-            spsub.geno = sp->geno;
-            if (sp->geno) {
-                spsub.nfrac.assign(sp->nfrac.begin() + k0, sp->nfrac.begin() + k1); spsub.frac.assign(sp->frac.begin() + k0, sp->frac.begin() + k1);
-                spsub.lik.assign(sp->lik.begin() + k0, sp->lik.begin() + k1); spsub.ncover.assign(sp->ncover.begin() + k0, sp->ncover.begin() + k1);
-            }
-        }
-        return score_mutations_planned(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1),
-                                       std::vector<const std::vector<Mut>*>(muts.begin() + k0, muts.begin() + k1),
-                                       pt || sp ? std::vector<std::vector<Mut>*>() : std::vector<std::vector<Mut>*>(outs.begin() + k0, outs.begin() + k1),
-                                       delta_out ? &dsub : nullptr, psub, pt ? &ptsub : nullptr, sp ? &spsub : nullptr);
-    };
-    if (sparse && R > 1 && sparse_bytes > device_share_bytes()) return in_halves(as.size(), sub);
-    if (!sparse && fit_share(as, 0, 2) < as.size()) return in_share_chunks(as, 2, sub);   // sub-batches that fit a slab
-    // the kept-column tables of all AlignData in one block (before the jobs are built: their descriptors point into it)
-    std::vector<const int*> d_keep(2 * (size_t)R, nullptr);
-    if (sparse) {
-        size_t tot = 0;
-        for (int k = 0; k < R; k++) tot += plan[k].keep[0].size() + plan[k].keep[1].size();
-        DBuf& kb = rt->buf("keep");
-        PS_TRY(kb.ensure(std::max<size_t>(tot, 1) * sizeof(int)));
-        std::vector<int> hk;
-        hk.reserve(tot);
-        for (int k = 0; k < R; k++)
-            for (int d = 0; d < 2; d++) { d_keep[2 * k + d] = kb.as<int>() + hk.size(); hk.insert(hk.end(), plan[k].keep[d].begin(), plan[k].keep[d].end()); }
-        PS_TRY(rt->up(kb.p, hk.data(), hk.size() * sizeof(int)));
-    }
-    // Alignment::update for every event of every AlignData: enqueued now, so that the fills run while the host prepares the edit tables
-    std::vector<JobSpec> specs;
-    std::vector<int> job0(R, 0);
-    int extra = 0;
-    for (int k = 0; k < R; k++) {
-        Align* a = as[k];
-        job0[k] = (int)specs.size();
-        extra = std::max(extra, plan[k].extra);
-        for (int e = 0; e < a->E; e++) {
-            JobSpec s = a->job(e);
-            if (sparse) for (int d = 0; d < 2; d++) { s.keep[d] = d_keep[2 * k + d]; s.nkeep[d] = plan[k].nkeep[d]; }
-            specs.push_back(s);
-        }
-    }
-    // the per-position layout of FindPointMutations' list (point_layout); an AlignData without events has every score at its seed,
-    // -1e-6 (score_mutations): its rows are written here
-    std::vector<std::vector<int>> pfirst(pt ? R : 0), ptriv(pt ? R : 0);
-    if (pt)
-        for (int k = 0; k < R; k++) {
-            point_layout(as[k], &pfirst[k], &ptriv[k]);
-            if (!as[k]->E) point_rows_seed(ptriv[k], pt->table[k], pt->best[k]);
-        }
-    // a support call: an AlignData without events has every score at its seed and all-zero records
-    if (sp)
-        for (int k = 0; k < R; k++)
-            if (!as[k]->E) {
-                if (sp->score[k]) std::fill(sp->score[k], sp->score[k] + plan[k].M, -1e-6);
-                if (sp->rec[k]) memset(sp->rec[k], 0, (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
-                if (sp->geno) {   // (and no covering event: all-zero likelihoods)
-                    std::fill(sp->lik[k], sp->lik[k] + (size_t)plan[k].M * (sp->nfrac[k] + 1), 0.0);
-                    if (sp->ncover[k]) std::fill(sp->ncover[k], sp->ncover[k] + plan[k].M, 0);
-                }
-            }
-    if (specs.empty()) return PS_OK;
-    Batch b;
-    SlabHold slab;   // full matrices: one of the process's slabs for the duration of this call (released at every return)
-    double lone_need = 0;   // a single AlignData cannot be split: matrices beyond a slab go to the runtime's own pools
-    if (!sparse && R == 1) for (int e = 0; e < as[0]->E; e++) lone_need += matrix_bytes((int64_t)as[0]->n[e] + (int64_t)as[0]->states.size() + 1, most_slots_w(as[0]->par.realign_width), 2);
-    if (!sparse && lone_need <= (double)slab_bytes()) {
-        PS_TRY(slab_acquire(&slab));
-        if (R == 1 && lone_need > (double)slab.bytes) {
-            // the slab this call was handed is smaller than the plan (a device fuller than expected: slab_acquire's fallback sizes) and a
-            // single AlignData cannot be split: its matrices go to the runtime's own pools, as those beyond a planned slab do
-            slab.release();
-        } else {
-            if (rt->prof_on) rt->prof["slab"].launches++;   // (dense calls that took a slab: a host-side count)
-            slab.drain = rt->stream;
-            b.ext = slab.p; b.ext_bytes = R > 1 ? std::min(slab.bytes, (size_t)dense_cap_bytes()) : slab.bytes;
-        }
-        tk.lap("slab wait");
-    }
-    PS_TRY(b.build(rt, specs, 2, extra));
-    {
-        const int rc = realign(rt, b, R > 1 ? (sparse ? PLAN_OVER_GUESS * device_share_bytes() : (double)b.ext_bytes) : 0.0);
-        if (rc == PS_SPLIT) { slab.release(); return in_halves(as.size(), sub); }   // bands wider than guessed: two halves, one after the other
-        PS_TRY(rc);
-    }
-    for (Align* a : as) a->host_refs_valid = false;
-    tk.lap("realign enqueue");
-    par_for(R, [&](int k) { plan_tables(as[k], *muts[k], &plan[k], R == 1 ? 8 : (R <= 4 ? 4 : 1)); });
-    tk.lap("edit geometry");
-    // upload the edit tables of all AlignData in one block
-    size_t ints = 16, dbls = 1;
-    for (int k = 0; k < R; k++) {
-        const EditPlan& p = plan[k];
-        ints += (size_t)p.M * 7 + (size_t)p.M * p.ncolmax + p.nr0 + 16;
-        if (pt) ints += pfirst[k].size() + ptriv[k].size();
-        if (sp) ints += (size_t)as[k]->E;
-        dbls += (size_t)as[k]->E * std::max(p.nr0, 1) + (size_t)as[k]->E * std::max(p.M, 1) + std::max(p.M, 1) + (size_t)as[k]->E * (as[k]->states.size() + 8);
-    }
-    DBuf& mb = rt->buf("mutint");
-    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max(sizeof(PointArgs), sizeof(SupportArgs)) + sizeof(GenoArgs)) + 64));
-    DBuf& db = rt->buf("mutdbl");
-    PS_TRY(db.ensure(dbls * sizeof(double)));
-    int* dp = mb.as<int>();
-    double* dd = db.as<double>();
-    // every AlignData's score array first, back to back: ONE device-to-host copy returns them all (a copy per region before:
-    // 20 000 of a bench step's 25 000 copy commands, ~0.2 ms each on a loaded stream)
-    double* const score0 = dd;
-    size_t score_tot = 0;
-    std::vector<size_t> score_at(R, 0);
-    for (int k = 0; k < R; k++) { score_at[k] = score_tot; score_tot += (size_t)std::max(plan[k].M, 1); }
-    dd += score_tot;
-    std::vector<int> stage;
-    stage.reserve(ints);
-    auto push = [&](const std::vector<int>& v) { int* r = dp + stage.size(); stage.insert(stage.end(), v.begin(), v.end()); return r; };
-    // a point-table call: the records, then the rows, of all AlignData back to back in one buffer — ONE device-to-host copy
-    std::vector<size_t> best_at(R, 0), table_at(R, 0);
-    size_t pt_bytes = 0;
-    char* d_pt = nullptr;
-    if (pt) {
-        for (int k = 0; k < R; k++) if (pt->best[k] && as[k]->E) { best_at[k] = pt_bytes; pt_bytes += ptriv[k].size() * sizeof(ps_point_best); }
-        for (int k = 0; k < R; k++) if (pt->table[k] && as[k]->E) { table_at[k] = pt_bytes; pt_bytes += ptriv[k].size() * PT_SLOTS * sizeof(double); }
-        DBuf& pb = rt->buf("ptable");
-        PS_TRY(pb.ensure(std::max<size_t>(pt_bytes, 16)));
-        d_pt = pb.as<char>();
-    }
-    // a support call: the scores, then the records, of all AlignData back to back in one buffer — ONE device-to-host copy; a genotype
-    // call's likelihoods and covering-event counts follow them in the same buffer and come back in the same copy
-    std::vector<size_t> sscore_at(R, 0), srec_at(R, 0), glik_at(R, 0), gcov_at(R, 0);
-    size_t sp_bytes = 0;
-    char* d_sp = nullptr;
-    auto sp_live = [&](int k) { return plan[k].M > 0 && as[k]->E > 0; };
-    if (sp) {
-        for (int k = 0; k < R; k++) if (sp_live(k)) { sscore_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sizeof(double); }
-        for (int k = 0; k < R; k++) if (sp_live(k) && sp->rec[k]) { srec_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support); }
-        if (sp->geno) {
-            for (int k = 0; k < R; k++) if (sp_live(k)) { glik_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * (sp->nfrac[k] + 1) * sizeof(double); }
-            for (int k = 0; k < R; k++) if (sp_live(k)) { gcov_at[k] = sp_bytes; sp_bytes += (size_t)plan[k].M * sizeof(int32_t); }
-        }
-        DBuf& sb = rt->buf("support");
-        PS_TRY(sb.ensure(std::max<size_t>(sp_bytes, 16)));
-        d_sp = sb.as<char>();
-    }
-    std::vector<ScoreArgs> sas(R);
-    std::vector<PointArgs> pts(pt ? R : 0);
-    std::vector<SupportArgs> sps(sp ? R : 0);
-    std::vector<GenoArgs> gts(sp && sp->geno ? R : 0);
-    for (int k = 0; k < R; k++) {
-        const EditPlan& p = plan[k];
-        ScoreArgs& sa = sas[k];
-        memset(&sa, 0, sizeof(sa));
-        sa.job0 = job0[k]; sa.njobs = as[k]->E;
-        sa.nitems_per_job = p.M; sa.ncolmax = p.ncolmax; sa.ws = as[k]->par.scoring_width; sa.nr0 = p.nr0;
-        sa.m_start = push(p.start); sa.m_mlen = push(p.mlen); sa.m_cm = push(p.cm); sa.m_ncol = push(p.ncol);
-        sa.m_skip = push(p.skip); sa.m_oldidx = push(p.oldidx); sa.m_states = push(p.states); sa.r0 = push(p.r0s);
-        for (int q = 0; q < SCORE_CLASSES; q++) { sa.cls_items[q] = push(p.cls[q]); sa.cls_count[q] = (int)p.cls[q].size(); }
-        sa.old = dd; dd += (size_t)as[k]->E * std::max(p.nr0, 1);
-        sa.delta = dd; dd += (size_t)as[k]->E * std::max(p.M, 1);
-        sa.score = score0 + score_at[k];
-        // edit positions on more than a quarter of the columns: column-pair maxima of ALL columns in one coalesced pass (k_oldall)
-        sa.oldall_pitch = (int64_t)as[k]->states.size() + 8;
-        sa.maxS = b.maxS;
-        sa.oldall = !b.sparse && (size_t)p.nr0 * 4 > as[k]->states.size() && p.nr0 >= 256 ? dd : nullptr;   // (k_oldall walks full matrices)
-        if (sa.oldall) PS_HIP(hipMemsetAsync(sa.oldall, 0, (size_t)as[k]->E * sa.oldall_pitch * sizeof(double), rt->stream));
-        dd += (size_t)as[k]->E * sa.oldall_pitch;
-        if (pt) {
-            PointArgs& q = pts[k];
-            memset(&q, 0, sizeof(q));
-            q.pos_first = push(pfirst[k]); q.pos_triv = push(ptriv[k]); q.npos = (int)ptriv[k].size();
-            if (pt->table[k] && as[k]->E) q.table = (double*)(d_pt + table_at[k]);
-            if (pt->best[k] && as[k]->E) q.best = (ps_point_best*)(d_pt + best_at[k]);
-            if (!q.table && !q.best) q.npos = 0;
-        }
-        if (sp) {
-            SupportArgs& q = sps[k];
-            memset(&q, 0, sizeof(q));
-            q.group = push(std::vector<int>(sp->group[k], sp->group[k] + as[k]->E));
-            if (sp_live(k) && sp->rec[k]) { q.ngroups = sp->ngroups[k]; q.score = (double*)(d_sp + sscore_at[k]); q.out = (ps_edit_support*)(d_sp + srec_at[k]); }
-        }
-        if (sp && sp->geno) {
-            GenoArgs& q = gts[k];
-            memset(&q, 0, sizeof(q));
-            q.nfrac = -1;
-            if (sp_live(k)) {
-                q.nfrac = sp->nfrac[k];
-                for (int i = 0; i < q.nfrac; i++) { q.f[i] = sp->frac[k][i]; q.g[i] = 1.0 - q.f[i]; }
-                if (!sp->rec[k]) q.score = (double*)(d_sp + sscore_at[k]);   // (k_support writes nothing for this AlignData)
-                q.lik = (double*)(d_sp + glik_at[k]); q.ncover = (int*)(d_sp + gcov_at[k]);
-            }
-        }
-        if (!p.M || !as[k]->E) { sa.njobs = 0; sa.nitems_per_job = 0; }   // nothing to score for this AlignData: its blocks leave at once
-    }
-    // the edit tables and their descriptors (ScoreArgs, behind the tables in the same buffer) in one copy
-    const size_t sa_at = (stage.size() * sizeof(int) + 63) / 64 * 64;
-    const size_t pt_at = (sa_at + (size_t)R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them)
-    const size_t gt_at = (pt_at + sps.size() * sizeof(SupportArgs) + 63) / 64 * 64;                       // (a genotype call: its GenoArgs behind the SupportArgs)
-    std::vector<char> blob(std::max(pt_at + pts.size() * sizeof(PointArgs), gt_at + gts.size() * sizeof(GenoArgs)));   // (PointArgs or SupportArgs, never both)
-    memcpy(blob.data(), stage.data(), stage.size() * sizeof(int));
-    memcpy(blob.data() + sa_at, sas.data(), (size_t)R * sizeof(ScoreArgs));
-    if (pt) memcpy(blob.data() + pt_at, pts.data(), pts.size() * sizeof(PointArgs));
-    if (sp) memcpy(blob.data() + pt_at, sps.data(), sps.size() * sizeof(SupportArgs));
-    if (!gts.empty()) memcpy(blob.data() + gt_at, gts.data(), gts.size() * sizeof(GenoArgs));
-    PS_TRY(rt->up(dp, blob.data(), blob.size()));
-    const ScoreArgs* d_sas = (const ScoreArgs*)((const char*)dp + sa_at);
-    const PointArgs* d_pts = pt ? (const PointArgs*)((const char*)dp + pt_at) : nullptr;
-    const SupportArgs* d_sps = sp ? (const SupportArgs*)((const char*)dp + pt_at) : nullptr;
-    const GenoArgs* d_gts = !gts.empty() ? (const GenoArgs*)((const char*)dp + gt_at) : nullptr;
-    tk.lap("upload");
-    if (tk.on) { PS_HIP(hipStreamSynchronize(rt->stream)); }
-    tk.lap("realign fwd+back (rest)");
-    PS_TRY(launch_lb(rt, b.d, 1, b.maxlbn));
-    std::vector<double*> sc(R, nullptr);
-    for (int k = 0; k < R; k++) {
-        const EditPlan& p = plan[k];
-        if (!p.M || !as[k]->E) continue;
-        if (rt->prof_on) {
-            // per (event, edit) item  16(Bs+1) + 16 Br + 24(Bs+c) + 32 Br / k + 8
-            double t = 0;
-            const double Bs = 2.0 * sas[k].ws + 1, Br = 2.0 * as[k]->par.realign_width + 1;
-            const double kk = (double)p.M / std::max(p.nr0, 1);
-            for (int i = 0; i < p.M; i++) t += 16 * (Bs + 1) + 16 * Br + 24 * (Bs + p.mlen[i] + 6) + 32 * Br / kk + 8;
-            rt->prof["score"].bytes += t * as[k]->E;
-            rt->prof["score"].units += (double)p.M * as[k]->E;
-        }
-    }
-    PS_TRY(launch_score(rt, b.d, d_sas, sas, d_pts, pt ? &pts : nullptr, d_sps, sp ? &sps : nullptr, d_gts, d_gts ? &gts : nullptr));
-    if (sp) {
-        char* h_sp = nullptr;
-        if (sp_bytes) PS_TRY(rt->down((void**)&h_sp, d_sp, sp_bytes));
-        PS_HIP(hipStreamSynchronize(rt->stream));
-        for (int k = 0; k < R; k++) {
-            if (!sp_live(k)) continue;
-            if (sp->score[k]) memcpy(sp->score[k], h_sp + sscore_at[k], (size_t)plan[k].M * sizeof(double));
-            if (sp->rec[k]) memcpy(sp->rec[k], h_sp + srec_at[k], (size_t)plan[k].M * sp->ngroups[k] * sizeof(ps_edit_support));
-            if (sp->geno) {
-                memcpy(sp->lik[k], h_sp + glik_at[k], (size_t)plan[k].M * (sp->nfrac[k] + 1) * sizeof(double));
-                if (sp->ncover[k]) memcpy(sp->ncover[k], h_sp + gcov_at[k], (size_t)plan[k].M * sizeof(int32_t));
-            }
-        }
-        tk.lap("score edits");
-        return PS_OK;
-    }
-    if (pt) {
-        char* h_pt = nullptr;
-        if (pt_bytes) PS_TRY(rt->down((void**)&h_pt, d_pt, pt_bytes));
-        PS_HIP(hipStreamSynchronize(rt->stream));
-        for (int k = 0; k < R; k++) {
-            if (!as[k]->E || ptriv[k].empty()) continue;
-            if (pt->best[k]) memcpy(pt->best[k], h_pt + best_at[k], ptriv[k].size() * sizeof(ps_point_best));
-            if (pt->table[k]) memcpy(pt->table[k], h_pt + table_at[k], ptriv[k].size() * PT_SLOTS * sizeof(double));
-        }
-        tk.lap("score edits");
-        return PS_OK;
-    }
-    std::vector<double*> dl(R, nullptr);
-    double* all_scores = nullptr;
-    PS_TRY(rt->down(&all_scores, score0, score_tot));
-    for (int k = 0; k < R; k++)
-        if (plan[k].M && as[k]->E) {
-            sc[k] = all_scores + score_at[k];
-            if (delta_out && (*delta_out)[k]) PS_TRY(rt->down(&dl[k], sas[k].delta, (size_t)as[k]->E * plan[k].M));
-        }
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    for (int k = 0; k < R; k++) {
-        if (sc[k]) for (int i = 0; i < plan[k].M; i++) (*outs[k])[i].score = sc[k][i];
-        if (dl[k]) memcpy((*delta_out)[k], dl[k], (size_t)as[k]->E * plan[k].M * sizeof(double));
-    }
-    tk.lap("score edits");
-    return PS_OK;
-}
-
-// ScorePoints (ScoreMutations on FindPointMutations' list, at the scoring width the AlignData carries) for several AlignData, reduced on
-// the device to a row per position (k_point_table) instead of a scored list: the same chain as score_mutations_multi up to k_score,
-// then one copy back of all rows and records.  tables[k]: null or [states][9]; bests[k]: null or [states].
-int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& tables, const std::vector<ps_point_best*>& bests) {
-    const int R = (int)as.size();
-    std::vector<std::vector<Mut>> lists(R);
-    std::vector<EditPlan> plan(R);
-    std::vector<const std::vector<Mut>*> muts(R);
-    par_for(R, [&](int k) {
-        find_point_mutations(as[k], &lists[k]);
-        plan_edits(as[k], lists[k], &plan[k]);
-        muts[k] = &lists[k];
-    });
-    for (int k = 0; k < R; k++) {
-        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
-        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
-    }
-    PointOut pt;
-    pt.table = tables; pt.best = bests;
-    return score_mutations_planned(rt, as, muts, {}, nullptr, plan, &pt);
-}
-
-// ps_score_mutation_support / ps_batch_score_mutation_support: the chain of score_mutations_multi up to k_score, then k_support instead
-// of k_reduce and one copy back of all scores and records.  group[k]: [E] ids in 0 .. ngroups[k] - 1 (checked by the caller);
-// scores[k]: null or [M]; recs[k]: [M][ngroups[k]].
-int score_mutation_support_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                 const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
-                                 const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs) {
-    const int R = (int)as.size();
-    std::vector<EditPlan> plan(R);
-    par_for(R, [&](int k) { plan_edits(as[k], *muts[k], &plan[k]); });
-    for (int k = 0; k < R; k++) {
-        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
-        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
-        if (plan[k].ncolmax > 64 && as[k]->par.scoring_width > 511) return fail(PS_ERR_UNSUPPORTED, "edit longer than 58 bases with scoring_width > 511");
-    }
-    SupportOut sp;
-    sp.group = group; sp.ngroups = ngroups; sp.score = scores; sp.rec = recs;
-    return score_mutations_planned(rt, as, muts, {}, nullptr, plan, nullptr, &sp);
-}
-
-// ps_score_mutation_genotypes / ps_batch_score_mutation_genotypes: score_mutation_support_multi with k_genotype behind k_support, and the
-// likelihoods and covering-event counts in the same copy back.  recs[k] and ncover[k] may be null; frac[k]: [nfrac[k]] alt fractions
-// (checked by the caller); lik[k]: [M][nfrac[k] + 1].
-int score_mutation_genotypes_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                   const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
-                                   const std::vector<int>& nfrac, const std::vector<const double*>& frac,
-                                   const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs,
-                                   const std::vector<double*>& lik, const std::vector<int32_t*>& ncover) {
-    const int R = (int)as.size();
-    std::vector<EditPlan> plan(R);
-    par_for(R, [&](int k) { plan_edits(as[k], *muts[k], &plan[k]); });
-    for (int k = 0; k < R; k++) {
-        if (as[k]->par.scoring_width < 0) return fail(PS_ERR_BAD_ARG, "scoring_width < 0");
-        if (plan[k].rc != PS_OK) return fail(plan[k].rc, "negative mutation start");
-        if (plan[k].ncolmax > 64 && as[k]->par.scoring_width > 511) return fail(PS_ERR_UNSUPPORTED, "edit longer than 58 bases with scoring_width > 511");
-    }
-    SupportOut sp;
-    sp.group = group; sp.ngroups = ngroups; sp.score = scores; sp.rec = recs;
-    sp.geno = true; sp.nfrac = nfrac; sp.frac = frac; sp.lik = lik; sp.ncover = ncover;
-    return score_mutations_planned(rt, as, muts, {}, nullptr, plan, nullptr, &sp);
-}
-
-int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out) {
-    if (!a->E) {
-        *out = muts;
-        for (Mut& m : *out) m.score = -1e-6;
-        for (const Mut& m : muts) if (m.start < 0) return fail(PS_ERR_BAD_ARG, "negative mutation start");
-        return PS_OK;
-    }
-    return score_mutations_multi(rt, {a}, {&muts}, {out});
-}
-
-// FindPointMutations, cpp/FindMutations.cpp:191-234
-void find_point_mutations(const Align* a, std::vector<Mut>* out) {
-    static const char B4[] = "ACGT";
-    out->clear();
-    out->reserve(a->states.size() * 8);
-    for (size_t i = 0; i < a->states.size(); i++) {
-        Mut m;
-        m.start = (int)i;
-        m.orig.assign(1, a->bases[i]);
-        out->push_back(m);
-        for (int k = 0; k < 4; k++) {
-            if (a->bases[i] == B4[k]) continue;
-            m.mut.assign(1, B4[k]);
-            out->push_back(m);
-        }
-        m.orig.clear();
-        for (int k = 0; k < 4; k++) { m.mut.assign(1, B4[k]); out->push_back(m); }
-    }
-    if (a->par.verbose) { fputs("Point ", stderr); fflush(stderr); }   // cpp/FindMutations.cpp:230-231
-}
-
 // One greedy pass of MakeMutations (ps_greedy.h: sort, apply, defer, shift) on the AlignData's sequence
 static int greedy_apply(Align* a, std::vector<Mut>& muts, std::vector<Mut>* later, bool talk) {
     bool changed = false;
@@ -1243,11 +592,9 @@ int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector
         std::vector<int> next;
         for (int k : active) if (later[k].size() > 10) next.push_back(k);
         if (next.empty()) break;
-        std::vector<Align*> sa;
-        std::vector<const std::vector<Mut>*> in;
-        std::vector<std::vector<Mut>*> out;
-        for (int k : next) { sa.push_back(as[k]); in.push_back(&later[k]); out.push_back(&muts[k]); }
-        PS_TRY(score_mutations_multi(rt, sa, in, out));
+        std::vector<EditReq> rq(next.size());
+        for (size_t q = 0; q < next.size(); q++) { rq[q].a = as[next[q]]; rq[q].muts = &later[next[q]]; rq[q].out = &muts[next[q]]; }
+        PS_TRY(score_edits(rt, EditKind::List, rq.data(), rq.size()));
         active.swap(next);
     }
     return PS_OK;

@@ -102,7 +102,6 @@ struct Align {
     int restore_refs(Runtime* rt); // back to the kept refs (ref_index and the spans with them), if a scoring call may have moved them
 };
 
-std::vector<int> states_of(const std::string& bases);
 void accumulate_likes(const double* ra, const double* rl, int n, int C, double* likes);
 
 // strip sweeps (ps_sweep.hip, ps_sweepw.hip): K rows per lane on NW wavefronts per sweep
@@ -126,6 +125,7 @@ int sweep_run(Runtime* rt, Batch& b);             // sweeps, maxima, backtrace, 
 void sweep_min_set(int n);                        // forward-only batches of at least n alignments take the strip sweep (< 0: default)
 void sweep2_min_set(int n);                       // the same for Alignment::update batches (sweeps = 2 per alignment)
 void sparse_min_set(int n);                       // Alignment::update batches whose edit list reads few columns: strip sweeps with kept columns from n sweeps on
+int sparse_min();                                 // that threshold as it stands (the default when none was set)
 int launch_likes(Runtime* rt, const BatchD& b, const LikeGroup* d_groups, int ngroups, double* d_out);   // per-base likelihood vectors on the device
 int likes_max_states();                           // longest sequence (states) k_likes takes
 bool sweep_enabled();                             // PORESEQ_NO_SWEEP unset
@@ -157,6 +157,24 @@ int hwq_mode(std::string* why);   // 1: every stream on one priority level (a ha
 int peak_runtimes();   // most host threads that ever owned a runtime at the same time
 int live_runtimes();   // host threads that currently own a runtime
 int guess_slots(const Align* a);   // anti-diagonal footprint realign() will probably choose
+// A lock-step call over n AlignData that may not fit the device in one piece re-issues itself over sub-ranges, sub(k0, k1), one after
+// the other: the fewest sub-batches of about equal size that fit (share_cut, ps_plan.h), when AlignData k probably takes need(k) of
+// share_cap(ndir) bytes — or two halves, when the bands came out wider than guessed
+double share_need(const Align* a, int ndir);   // device bytes the events of `a` will probably take at `ndir` sweeps each
+double share_cap(int ndir);                    // this runtime's device share; for full forward + backward matrices (ndir == 2) what a slab holds
+template <class Need> bool over_share(size_t n, int ndir, Need&& need) { return share_cut(0, n, share_cap(ndir), need) < n; }
+template <class Need, class Sub> int in_share_chunks(size_t n, int ndir, Need&& need, Sub&& sub) {
+    for (size_t k0 = 0; k0 < n;) {
+        const size_t k1 = share_cut(k0, n, share_cap(ndir), need);
+        PS_TRY(sub(k0, k1));
+        k0 = k1;
+    }
+    return PS_OK;
+}
+template <class Sub> int in_halves(size_t n, Sub&& sub) {
+    PS_TRY(sub(0, n / 2));
+    return sub(n / 2, n);
+}
 void device_fraction_set(double f);   // the part of the device this process plans for (several ranks on one GPU); <= 0: PORESEQ_DEVICE_FRACTION, else 1
 double device_fraction();
 double device_share_bytes();   // this runtime's share of the device memory for its own pools (step codes, kept columns, small matrices)
@@ -170,25 +188,28 @@ int ensure_matrix_pools(Runtime* rt, const Batch& bt, size_t need_rec, size_t ne
 int align_slab_take(Runtime* rt, size_t bytes, void** out, size_t* cap);   // an AlignData's slab, from the process-wide cache when one fits
 void align_slab_give(void* slab, size_t cap, void* last_stream);           // and back to it (or freed)
 int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector<std::vector<Mut>> muts, std::vector<int>* nbases);
-// delta_out (optional): per AlignData a host array [E][M] receiving every event's term of every edit's score
-int score_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                          const std::vector<std::vector<Mut>*>& outs, const std::vector<double*>* delta_out = nullptr);
+// One AlignData of an edit-scoring call (ps_score.cpp): its handle, its edit list and, of the outputs below, those the call's EditKind
+// means — host arrays, null where the caller does not want one.  A lock-step call is an array of these; a sub-batch (a call cut to
+// fit the share, or halved because its bands came out wider than guessed) is a sub-range of the same array.
+struct EditReq {
+    Align* a = nullptr;
+    const std::vector<Mut>* muts = nullptr;   // the list to score (Points: FindPointMutations', made by score_edits into `own`)
+    // List: the scored copy of the list, and [E][M] every event's term of every edit's score (optional)
+    std::vector<Mut>* out = nullptr; double* delta = nullptr;
+    // Points: [states][9] rows and [states] per-position records (either may be null)
+    double* table = nullptr; ps_point_best* best = nullptr;
+    // Support, Genotype: [E] group ids below ngroups (checked by the caller), [M] scores (optional), [M][ngroups] records (Genotype: optional)
+    const int32_t* group = nullptr; int ngroups = 0; double* score = nullptr; ps_edit_support* rec = nullptr;
+    // Genotype: [nfrac] alt fractions (checked by the caller), [M][nfrac + 1] likelihoods, [M] covering-event counts (optional)
+    int nfrac = 0; const double* frac = nullptr; double* lik = nullptr; int32_t* ncover = nullptr;
+    // filled by score_edits: the plan, the list of a Points call and its point_layout
+    EditPlan plan;
+    std::vector<Mut> own;
+    std::vector<int> pos_first, pos_triv;
+};
+// ScoreMutations (cpp/MakeMutations.cpp:23-69) and its reductions for reqs[0 .. n - 1] in one launch chain
+int score_edits(Runtime* rt, EditKind kind, EditReq* reqs, size_t n);
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out);
-// ps_point_table / ps_batch_point_table (include/poreseq_hip.h): ScorePoints reduced on the device to rows per position; tables[k]
-// (null or [states][9]) and bests[k] (null or [states]) are host arrays
-int point_table_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& tables, const std::vector<ps_point_best*>& bests);
-// ps_score_mutation_support / ps_batch_score_mutation_support (include/poreseq_hip.h): the edit lists scored and reduced on the device per
-// event group; group[k] [E] ids below ngroups[k], scores[k] (null or [M]) and recs[k] ([M][ngroups[k]]) are host arrays
-int score_mutation_support_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                 const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
-                                 const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs);
-// ps_score_mutation_genotypes / ps_batch_score_mutation_genotypes: the support call with the genotype likelihoods of every edit reduced
-// on the device behind it (k_genotype); recs[k] and ncover[k] may be null
-int score_mutation_genotypes_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<Mut>*>& muts,
-                                   const std::vector<const int32_t*>& group, const std::vector<int>& ngroups,
-                                   const std::vector<int>& nfrac, const std::vector<const double*>& frac,
-                                   const std::vector<double*>& scores, const std::vector<ps_edit_support*>& recs,
-                                   const std::vector<double*>& lik, const std::vector<int32_t*>& ncover);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases);
 int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds, std::vector<Mut>* out);

@@ -21,11 +21,11 @@
 
 #include "../../include/poreseq_hip.h"
 #include "ps_greedy.h" // struct Mut, apply_edit, greedy_apply (host-only, no HIP)
+#include "ps_editplan.h" // NS, states_of, EditPlan, PT_SLOTS, SCORE_CLASSES and the size classes of k_score (host-only, no HIP)
 #include "ps_plan.h"   // MAT_FRONT, MAT_BACK and the memory plan's arithmetic (host-only, no HIP)
 
 namespace ps {
 
-constexpr int NS = PS_N_STATES;
 constexpr double BIG = 1e300;  // "inf" of the reference, cpp/AlignUtil.h:20
 
 // ---- error plumbing ------------------------------------------------------------------------
@@ -244,10 +244,9 @@ struct ScoreArgs {
     int64_t oldall_pitch, maxS;
     double* delta;             // [njobs][M]
     double* score;             // [M]
-    // device lists of edit indices by new-column count: class k < 4 fits 8 << k lanes (k = 3: chunked, any size), class 4 fits 7 (point
-    // edits, len(mut) <= 1: 6 or 7 new columns — nine edits to a wave instead of eight)
-    const int* cls_items[5];
-    int cls_count[5];
+    // device lists of edit indices by new-column count (score_class, ps_editplan.h)
+    const int* cls_items[SCORE_CLASSES];
+    int cls_count[SCORE_CLASSES];
 };
 // A point-edit table call (k_point_table instead of k_reduce) has one of these per AlignData beside its ScoreArgs — a record of its
 // own, so that ScoreArgs and with it the device code of every other scoring kernel stay what they were.  The list is
@@ -260,7 +259,6 @@ struct PointArgs {
     double* table;             // NULL, or [npos][9]
     ps_point_best* best;       // NULL, or [npos]
 };
-constexpr int PT_SLOTS = 9;    // deletion, substitution by A / C / G / T, insertion of A / C / G / T
 // A support call (k_support instead of k_reduce, ps_score_mutation_support) likewise has one of these per AlignData beside its
 // ScoreArgs: the events' group ids and where the scores and the per-(edit, group) records go.
 struct SupportArgs {
@@ -282,14 +280,17 @@ struct GenoArgs {
     double* lik;               // [M][nfrac + 1]
     int* ncover;               // [M]
 };
-constexpr int SCORE_CLASSES = 5;
-// (d_pts / h_pts: the PointArgs of a point-edit table call on the device and on the host, parallel to the ScoreArgs; null otherwise.
-//  d_sps / h_sps: the same for the SupportArgs of a support call.  At most one of the two is given.  d_gts / h_gts: the GenoArgs of
-//  a genotype call, which is a support call with k_genotype behind k_support.)
-int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
-                 const PointArgs* d_pts = nullptr, const std::vector<PointArgs>* h_pts = nullptr,
-                 const SupportArgs* d_sps = nullptr, const std::vector<SupportArgs>* h_sps = nullptr,
-                 const GenoArgs* d_gts = nullptr, const std::vector<GenoArgs>* h_gts = nullptr);
+// What an edit-scoring call makes of k_score's [event][edit] matrix: a scored list (ScoreMutations), rows per position (ps_point_table),
+// scores and per-group records (ps_score_mutation_support), or those with genotype likelihoods behind them
+enum class EditKind { List, Points, Support, Genotype };
+// One such call as launch_score runs it: the descriptors of its AlignData on the host (`pts` for Points, `sps` for Support and
+// Genotype, `gts` for Genotype; the others stay empty) and where their copies lie on the device (null where the vector is empty)
+struct ScoreLaunch {
+    EditKind kind = EditKind::List;
+    std::vector<ScoreArgs> sas; std::vector<PointArgs> pts; std::vector<SupportArgs> sps; std::vector<GenoArgs> gts;
+    const ScoreArgs* d_sas = nullptr; const PointArgs* d_pts = nullptr; const SupportArgs* d_sps = nullptr; const GenoArgs* d_gts = nullptr;
+};
+int launch_score(Runtime* rt, const BatchD& b, const ScoreLaunch& L);
 int launch_begin(Runtime* rt, const BatchD& b);
 int launch_gather_best(Runtime* rt, const BatchD& b, double* out);   // out[job] = the job's forward maxScore (JobOut.best)
 

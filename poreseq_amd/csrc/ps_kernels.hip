@@ -1613,17 +1613,72 @@ int launch_begin(Runtime* rt, const BatchD& b) {
     return PS_OK;
 }
 
-// edit scoring of several AlignData of one batch (d_sas: their ScoreArgs on the device, h_sas the same on the host): one launch
-// per kernel over all of them — grid.z (k_reduce: grid.y) is the AlignData, blocks past an AlignData's own sizes leave at once
-int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std::vector<ScoreArgs>& h_sas,
-                 const PointArgs* d_pts, const std::vector<PointArgs>* h_pts,
-                 const SupportArgs* d_sps, const std::vector<SupportArgs>* h_sps,
-                 const GenoArgs* d_gts, const std::vector<GenoArgs>* h_gts) {
-    const int R = (int)h_sas.size();
+// the tails of launch_score: what is made of the [event][edit] matrix k_score left behind
+// a point-table call (every AlignData of it): rows per position instead of a score per edit
+static int launch_point_table(Runtime* rt, const ScoreLaunch& L) {
+    const int R = (int)L.sas.size();
+    int maxnpos = 0;
+    double bytes = 0;
+    for (int k = 0; k < R; k++) {
+        const ScoreArgs& a = L.sas[k];
+        const int npos = L.pts[k].npos;
+        if (!a.njobs || !npos) continue;
+        maxnpos = std::max(maxnpos, npos);
+        bytes += 8.0 * a.njobs * a.nitems_per_job + 88.0 * npos;
+    }
+    if (!maxnpos) return PS_OK;
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_point_table, dim3((maxnpos + PT_POS - 1) / PT_POS, R), dim3(256), 0, rt->stream, L.d_sas, L.d_pts);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "point_table", bytes);
+    return PS_OK;
+}
+
+// a support call (every AlignData of it): the score per edit and a record per (edit, group)
+static int launch_support(Runtime* rt, const BatchD& b, const ScoreLaunch& L, int maxM) {
+    const int R = (int)L.sas.size();
+    double bytes = 0;
+    // (a genotype call may want no support records anywhere: k_support then has nothing to write; a support call always launches it)
+    bool any_records = L.kind != EditKind::Genotype;
+    for (int k = 0; k < R; k++) {
+        const ScoreArgs& a = L.sas[k];
+        if (!a.njobs || !a.nitems_per_job || !L.sps[k].ngroups) continue;
+        any_records = true;
+        bytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 + 24.0 * L.sps[k].ngroups) * a.nitems_per_job;
+    }
+    if (!any_records) return PS_OK;
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_support, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, L.d_sas, L.d_sps);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "support", bytes);
+    return PS_OK;
+}
+
+// a genotype call, behind launch_support: the same matrix reduced once more, over the covering events
+static int launch_genotype(Runtime* rt, const BatchD& b, const ScoreLaunch& L, int maxM) {
+    const int R = (int)L.sas.size();
+    double bytes = 0;
+    for (int k = 0; k < R; k++) {
+        const ScoreArgs& a = L.sas[k];
+        if (!a.njobs || !a.nitems_per_job || L.gts[k].nfrac < 0) continue;
+        bytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 * (L.gts[k].nfrac + 1) + 4.0) * a.nitems_per_job;
+    }
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_genotype, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, L.d_sas, L.d_gts);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "genotype", bytes);
+    return PS_OK;
+}
+
+// edit scoring of several AlignData of one batch (L: their descriptors on the host and on the device): one launch per kernel over
+// all of them — grid.z (k_reduce: grid.y) is the AlignData, blocks past an AlignData's own sizes leave at once
+int launch_score(Runtime* rt, const BatchD& b, const ScoreLaunch& L) {
+    const ScoreArgs* d_sas = L.d_sas;
+    const int R = (int)L.sas.size();
     int maxE = 0, maxnr0 = 0, maxnr0_all = 0, maxM = 0, cls_max[SCORE_CLASSES] = {0, 0, 0, 0, 0};
     int64_t maxS = 0;
     bool any_all = false, any_old = false;
-    for (const ScoreArgs& a : h_sas) {
+    for (const ScoreArgs& a : L.sas) {
         if (!a.njobs || !a.nitems_per_job) continue;
         maxE = std::max(maxE, a.njobs); maxM = std::max(maxM, a.nitems_per_job);
         if (a.nr0 > 0 && a.oldall) { any_all = true; maxS = std::max(maxS, a.maxS); maxnr0_all = std::max(maxnr0_all, a.nr0); }
@@ -1647,10 +1702,10 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
     for (int k = 0; k < SCORE_CLASSES; k++) {
         const int n = cls_max[k];
         if (!n) continue;
-        const int G = k == 4 ? 7 : 8 << k, ipb = 4 * (64 / G);
+        const int G = score_class_lanes(k), ipb = 4 * (64 / G);
         dim3 grid((n + ipb - 1) / ipb, maxE, R), block(256);
 #define PS_SCORE(GG) with_fastdiv(b.fastdiv, [&](auto fd) { hipLaunchKernelGGL((k_score<GG, fd.value>), grid, block, 0, rt->stream, b, d_sas); })
-        if (k == 4) PS_SCORE(7); else if (k == 0) PS_SCORE(8); else if (k == 1) PS_SCORE(16); else if (k == 2) PS_SCORE(32); else PS_SCORE(64);
+        if (G == 7) PS_SCORE(7); else if (G == 8) PS_SCORE(8); else if (G == 16) PS_SCORE(16); else if (G == 32) PS_SCORE(32); else PS_SCORE(64);
 #undef PS_SCORE
         PS_LAUNCH_CHECK();
         if (rt->prof_on) {   // (which size class ran, and whether it divided: host-side counts)
@@ -1660,52 +1715,11 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreArgs* d_sas, const std
         }
     }
     prof_end(rt, "score", 0.0);
-    if (h_pts) {   // a point-table call (every AlignData of it): rows per position instead of a score per edit
-        int maxnpos = 0;
-        double bytes = 0;
-        for (int k = 0; k < R; k++) {
-            const ScoreArgs& a = h_sas[k];
-            const int npos = (*h_pts)[k].npos;
-            if (!a.njobs || !npos) continue;
-            maxnpos = std::max(maxnpos, npos);
-            bytes += 8.0 * a.njobs * a.nitems_per_job + 88.0 * npos;
-        }
-        if (!maxnpos) return PS_OK;
-        prof_begin(rt);
-        hipLaunchKernelGGL(k_point_table, dim3((maxnpos + PT_POS - 1) / PT_POS, R), dim3(256), 0, rt->stream, d_sas, d_pts);
-        PS_LAUNCH_CHECK();
-        prof_end(rt, "point_table", bytes);
-        return PS_OK;
-    }
-    if (h_sps) {   // a support call (every AlignData of it): the score per edit and a record per (edit, group)
-        double bytes = 0;
-        for (int k = 0; k < R; k++) {
-            const ScoreArgs& a = h_sas[k];
-            if (!a.njobs || !a.nitems_per_job || !(*h_sps)[k].ngroups) continue;
-            bytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 + 24.0 * (*h_sps)[k].ngroups) * a.nitems_per_job;
-        }
-        // (a genotype call may want no support records anywhere: k_support then has nothing to write; a support call always launches it)
-        bool any_records = !h_gts;
-        for (int k = 0; k < R; k++) any_records |= h_sas[k].njobs && h_sas[k].nitems_per_job && (*h_sps)[k].ngroups;
-        if (any_records) {
-            prof_begin(rt);
-            hipLaunchKernelGGL(k_support, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, d_sas, d_sps);
-            PS_LAUNCH_CHECK();
-            prof_end(rt, "support", bytes);
-        }
-        if (h_gts) {   // a genotype call: the same matrix reduced once more, over the covering events
-            double gbytes = 0;
-            for (int k = 0; k < R; k++) {
-                const ScoreArgs& a = h_sas[k];
-                if (!a.njobs || !a.nitems_per_job || (*h_gts)[k].nfrac < 0) continue;
-                gbytes += 8.0 * a.njobs * a.nitems_per_job + (8.0 * ((*h_gts)[k].nfrac + 1) + 4.0) * a.nitems_per_job;
-            }
-            prof_begin(rt);
-            hipLaunchKernelGGL(k_genotype, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, d_sas, d_gts);
-            PS_LAUNCH_CHECK();
-            prof_end(rt, "genotype", gbytes);
-        }
-        return PS_OK;
+    switch (L.kind) {
+    case EditKind::Points: return launch_point_table(rt, L);
+    case EditKind::Genotype: PS_TRY(launch_support(rt, b, L, maxM)); return launch_genotype(rt, b, L, maxM);
+    case EditKind::Support: return launch_support(rt, b, L, maxM);
+    case EditKind::List: break;
     }
     hipLaunchKernelGGL(k_reduce, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, d_sas);
     PS_LAUNCH_CHECK();

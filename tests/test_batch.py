@@ -17,6 +17,10 @@ from poreseq_amd.poreseqcpp import PSAlign, swalign
 from poreseq_amd.util import DEFAULT_PARAMS
 
 P = dict(DEFAULT_PARAMS, verbose=0)
+# PORESEQ_MAX_BATCH_GB at which the three regions of _split_case are cut.  Full matrices at a guess of 64 slots: 0.008 is the smallest
+# budget that still leaves a sub-batch of two regions (2 + 1), which realign then finds over the share and halves; 0.004 sends every
+# region alone.  Kept columns: 0.002 is the largest at which the call is halved (1 + 2 regions); 0.004 fits.
+SPLIT_DENSE_GB, SPLIT_KEPT_GB = "0.008", "0.002"
 
 
 def _regions(sizes, seed0, sw):
@@ -140,6 +144,117 @@ def test_hip_seed_chunks_are_cut_again_when_the_bands_are_wider_than_guessed():
     got2, err2 = run({"PORESEQ_MAX_BATCH_GB": "0.002"})
     assert "the rest in chunks" in err2  # Smith-Waterman batches larger than an eighth of the share
     assert got2 == want
+
+
+def _split_case():
+    """three small regions for the split paths of the edit-scoring chain: (draft, events) each, the middle one without events; the
+    lists of the support / genotype calls (a short list that keeps few columns, a list on the region without events, an empty one),
+    the lists of ScoreMutations (none empty) and the events' group ids (3 groups)"""
+    import support_cases as S
+    regs = [synth.make_region(L, E, 7600 + k, B.oracle_swalign, P)[:2] for k, (L, E) in enumerate([(260, 4), (220, 3), (300, 5)])]
+    regs[1] = (regs[1][0], [])
+    def short(d):
+        n = len(d)
+        return [S.edit(0, d[0:3], "G"), S.edit(30, d[30], "A" if d[30] != "A" else "C"), S.edit(31, "", "T"), S.edit(90, d[90:92], ""),
+                S.edit(140, "", "GTTA"), S.edit(141, d[141:144], "AC"), S.edit(200, d[200], ""), S.edit(n - 6, d[n - 6:n - 2], ""),
+                S.edit(n, "", "AC"), S.edit(n + 3, "A", "C")]
+    sup_lists = [short(regs[0][0]), short(regs[1][0])[:4], []]
+    sm_lists = [short(regs[0][0]), short(regs[1][0])[:4], short(regs[2][0])]
+    groups = [[e % 3 for e in range(len(ev))] for _, ev in regs]
+    return regs, sup_lists, sm_lists, groups
+
+
+SPLIT_FRACS = (0.25, 0.5)
+_HERE = os.path.dirname(os.path.abspath(__file__))
+# the child process of the test below: every call of it on the three regions of _split_case, pickled to argv[2]
+_SPLIT_CHILD = (
+    "import copy, pickle, sys\n"
+    "sys.path[:0] = [%r, %r]\n"
+    "import numpy as np\n"
+    "import backends as B\n"
+    "import support_cases as S\n"
+    "from test_batch import _split_case, SPLIT_FRACS, P\n"
+    "from poreseq_amd import _capi\n"
+    "from poreseq_amd.batch import RegionBatch\n"
+    "from poreseq_amd.poreseqcpp import PSAlign\n"
+    "api = _capi.load_hip()\n"
+    "if sys.argv[1] == 'kept': api.set_sparse_min(0)\n"
+    "regs, sup_lists, sm_lists, groups = _split_case()\n"
+    "rb = RegionBatch([B.make_pa(PSAlign, d, copy.deepcopy(ev), P) for d, ev in regs])\n"
+    "out = {'pt': rb.PointTable(), 'pt_lean': rb.PointTable(table=False)}\n"
+    "out['sup'] = [r[:2] + (S.score_bytes(r[2]),) for r in rb.ScoreMutationSupport(sup_lists, groups=groups, n_groups=3)]\n"
+    "out['gen'] = [r[:2] + (S.score_bytes(r[2]),) + r[3:] for r in rb.ScoreMutationGenotypes(sup_lists, alt_frac=SPLIT_FRACS, groups=groups, n_groups=3)]\n"
+    "# the same call without the support records, which only the C ABI wrapper offers: on AlignData of its own\n"
+    "hs = [api.align_create(d, copy.deepcopy(ev), P) for d, ev in regs]\n"
+    "hm = [api.muts_create(m) for m in sup_lists]\n"
+    "try:\n"
+    "    out['gen_lean'] = api.batch_score_mutation_genotypes(hs, hm, [len(m) for m in sup_lists], groups, [3] * 3, [SPLIT_FRACS] * 3, want_support=False)\n"
+    "finally:\n"
+    "    for m in hm: api.muts_destroy(m)\n"
+    "    for h in hs: api.align_destroy(h)\n"
+    "out['sm'] = [S.score_bytes(s) for s in rb.ScoreMutations(sm_lists)]\n"
+    "rb.drop(); rb.close()\n"
+    "pickle.dump(out, open(sys.argv[2], 'wb'))\n"
+) % (os.path.dirname(_HERE), _HERE)
+
+
+@pytest.mark.gpu
+def test_hip_point_support_and_genotype_calls_survive_being_cut_into_sub_batches(tmp_path):
+    """The edit-scoring chain cuts a lock-step call that is over the share, and halves one whose bands came out wider than guessed
+    or whose kept columns do not fit; test_hip_seed_chunks_are_cut_again... pins that for ScoreMutations inside a consensus run.
+    Here the calls with per-region outputs of their own — PointTable with and without the table, ScoreMutationSupport,
+    ScoreMutationGenotypes with and without the support records — and ScoreMutations go through both cuts on three regions (an odd
+    count: unequal halves), the middle one without events, one with an empty list: byte for byte the outputs of the call that was not
+    cut, and those equal the oracle's loops.  The traces say that the cuts happened (and that the plain run had none).  Three child processes, as the
+    knobs are read once per process: 5 to 6 s in all on an MI355X."""
+    import pickle, subprocess, sys
+    import genotype_cases as GC
+    import support_cases as S
+    from point_cases import oracle_table, same as same_table
+    def run(mode, extra):
+        path = str(tmp_path / (mode + ".pkl"))
+        env = dict(os.environ, PORESEQ_TRACE="1", **extra)
+        r = subprocess.run([sys.executable, "-c", _SPLIT_CHILD, mode, path], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        with open(path, "rb") as f:
+            return pickle.load(f), r.stderr
+
+    def digest(out):
+        flat = []
+        for key in sorted(out):
+            for r in out[key]:
+                flat.append([None if a is None else a if isinstance(a, bytes) else np.ascontiguousarray(a).tobytes() for a in (r if isinstance(r, tuple) else (r,))])
+        return flat
+
+    cut = lambda err: [l for l in err.splitlines() if "over the share" in l or ("[ps] score_mutations: " in l and " 3 regions" not in l)]
+    plain, err0 = run("plain", {})
+    dense, err1 = run("dense", {"PORESEQ_DEBUG_GUESS_P": "64", "PORESEQ_NO_SWEEP": "1", "PORESEQ_MAX_BATCH_GB": SPLIT_DENSE_GB})
+    kept, err2 = run("kept", {"PORESEQ_MAX_BATCH_GB": SPLIT_KEPT_GB})
+    print("\n".join(["plain:"] + cut(err0) + ["dense:"] + cut(err1) + ["kept:"] + cut(err2)))
+    # the plain run: every call one chain over the three regions
+    assert not cut(err0) and "[ps] score_mutations: 3 regions" in err0
+    # full matrices: cut into sub-batches under the share, and a sub-batch of two halved when its bands turn out wider than the guess
+    assert "over the share: split" in err1 and "[ps] score_mutations: 1 regions" in err1 and "kept columns\n" not in err1
+    # kept columns that do not fit the share: halves, 1 + 2 regions
+    assert any("[ps] score_mutations: 1 regions" in l and l.endswith(": kept columns") for l in err2.splitlines())
+    assert any("[ps] score_mutations: 2 regions" in l and l.endswith(": kept columns") for l in err2.splitlines())
+    assert digest(dense) == digest(plain) and digest(kept) == digest(plain)
+    # the plain run against the oracle's loops
+    regs, sup_lists, sm_lists, groups = _split_case()
+    for k, (d, ev) in enumerate(regs):
+        want_pt = oracle_table(d, ev, P)
+        assert same_table(plain["pt"][k], want_pt) and same_table(plain["pt_lean"][k], (None,) + tuple(want_pt[1:]))
+        sup = S.loop(d, ev, P, sup_lists[k], groups[k], 3)
+        geno = GC.yardstick(S.oracle_terms(d, ev, P, sup_lists[k]), len(d), list(SPLIT_FRACS))
+        sc, rec, scored = plain["sup"][k]
+        assert S.same((sc, rec), sup) and scored == np.asarray(sc).tobytes()
+        sc, rec, scored, lik, nc = plain["gen"][k]
+        print("region %d: worst |lik - loopld| / bound = %.4f" % (k, GC.worst(lik, geno)))
+        assert S.same((sc, rec), sup) and scored == np.asarray(sc).tobytes() and GC.same(lik, nc, geno)
+        sc2, rec2, lik2, nc2 = plain["gen_lean"][k]
+        assert rec2 is None and sc2.tobytes() == sc.tobytes() and lik2.tobytes() == lik.tobytes() and np.array_equal(nc2, nc)
+        assert plain["sm"][k] == S.loop(d, ev, P, sm_lists[k], groups[k], 3)[0].tobytes()
+    assert len(plain["sup"][2][0]) == 0 and not plain["sup"][1][1]["cover"].any() and (plain["sup"][1][0] == -1e-6).all()
 
 
 def test_package_import_asks_hip_for_more_hardware_queues_unless_told_otherwise():

@@ -271,7 +271,7 @@ def test_exact_div_dense_sweeps(exact_div, fwd_kernel):
 @pytest.mark.parametrize("fwd_kernel", ["sweep"], indirect=True)
 def test_exact_div_sparse_column_sweep_and_score_groups(exact_div, fwd_kernel):
     """k_sweeps<K, false> and k_score<7 / 8 / 16 / 32 / 64, false> on kept columns: 24 edits on L = 400 read at most 2 columns each per
-    direction, under a quarter of the 396 (score_mutations_planned), sparse_min = 0; the insertions of 2, 5, 20 and 40 bases fill
+    direction, under a quarter of the 396 (choose_columns, ps_score.cpp), sparse_min = 0; the insertions of 2, 5, 20 and 40 bases fill
     the four wider size classes of k_score beside the point edits' seven columns"""
     draft, events, par = EC.shape("sparse")
     muts = EC.shape_edits(draft)
