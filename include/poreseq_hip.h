@@ -9,7 +9,8 @@
  * A few entry points go beyond the reference's surface and reduce its scores on the device: ps_point_table (a row per position)
  * and ps_score_mutation_support (per edit and event group: the summed terms, the reads that span the edit and how many of
  * them favour or oppose it) with ps_score_mutation_genotypes (per edit: the likelihood of every alt-allele fraction asked for,
- * over the reads that span the edit).  `cover` there is a span test on the re-aligned reads, not a likelihood test, and anything
+ * over the reads that span the edit) and ps_score_mutation_phase (pair links between candidate sites, phase sets and a haplotype per read).
+ * `cover` there is a span test on the re-aligned reads, not a likelihood test, and anything
  * Phred-scaled that drivers derive from these scores is uncalibrated.
  *
  * All functions return PS_OK (0) or a negative ps_status; ps_last_error()
@@ -240,6 +241,62 @@ int ps_score_mutation_genotypes(ps_align* a, const ps_muts* muts, int32_t n_grou
                                 double* scores /* [M] or NULL */, ps_edit_support* support /* [M][n_groups] or NULL */,
                                 double* lik /* [M][n_frac + 1] */, int32_t* n_cover /* [M] or NULL */);
 
+/* Phase of heterozygous edits.  The list of candidate sites (a driver passes its het calls sorted by position; the library takes
+ * any list, and "order" below is list order) is scored as by ps_score_mutations — same re-alignment side effect, same checks — and
+ * the events x edits matrix delta[e][m] is then reduced three times on the device (k_link, k_phase, k_haptag).  cover(e, m) is
+ * exactly the test of ps_edit_support.cover / ps_score_mutation_genotypes.  E events, M sites, window W, S = max_sets.
+ *
+ *   link[m * W + (w - 1)]  the pair (m, j = m + w), w = 1 .. W; all zero where j >= M.  For e ascending over the events with
+ *                          cover(e, m) && cover(e, j), da = delta[e][m], db = delta[e][j], s = da + db, r = da - db:
+ *       cis               += (s > 0 ? s : 0.0) + log(0.5 + 0.5 * exp(-fabs(s)))       sum log(1/2 e^(da + db) + 1/2): both alts on one copy
+ *       trans             += (da > db ? da : db) + log(0.5 + 0.5 * exp(-fabs(r)))     sum log(1/2 e^da + 1/2 e^db): one alt on each copy
+ *       n_both            ++
+ *       n_cis             += (da > 0 && db > 0) || (da < 0 && db < 0)
+ *       n_trans           += (da > 0 && db < 0) || (da < 0 && db > 0)
+ *                          No argument of exp is positive and every argument of log lies in [0.5, 1]; non-finite terms give what IEEE
+ *                          gives for these lines.  exp / log are the device library's FP64 functions: cis / trans agree with a
+ *                          host evaluation to a few units in the last place per term, not bit for bit.
+ *   phase[m]               a serial scan in list order, defined on the link records alone (a host can replay it bit for bit):
+ *                          site 0 has vote = 0.0, hap = +1, set = 0.  Site m > 0: vote = 0.0; for w = 1 .. min(W, m) ascending with
+ *                          i = m - w and L = link[i * W + (w - 1)]:  if phase[i].set == phase[m - 1].set && L.n_both > 0 then
+ *                          vote += phase[i].hap * (L.cis - L.trans), plain FP64 operations in that order.  If vote != 0.0 &&
+ *                          fabs(vote) >= min_link (a NaN fails both) site m joins: set = phase[m - 1].set, hap = vote > 0 ? +1 : -1.
+ *                          Otherwise it opens a new set: set = phase[m - 1].set + 1, hap = +1.  vote is stored either way.
+ *                          hap = +1: the site's alt is on the copy that carries the alt of the set's first site.
+ *   n_sets                 phase[M - 1].set + 1 (0 for an empty list).  May be NULL.
+ *   hap[e * S + k]         event e against the k-th phase set (sets with ordinal >= S are not tagged): lik1 / n1 the sum and the count
+ *                          over the sites m of set k with cover(e, m) and hap == +1, lik2 / n2 the same for hap == -1.  The order of
+ *                          the adds is fixed: partial l = 0.0, then += delta[e][m] for m = l, l + 64, l + 128, ... ascending (sites
+ *                          that do not qualify are passed over), and the 64 partials are added into 0.0 for l = 0 .. 63.  An event
+ *                          is from the first copy where lik1 > lik2.  May be NULL: then neither produced nor copied.
+ *   scores[m]              the bits of ps_score_mutations.  May be NULL.
+ * An AlignData without events gets the records the rules give for all-zero links, written on the host: every site its own set, hap
+ * +1, vote 0.0, n_sets = M, scores -1e-6; hap then has no rows.  A skipped edit is covered by no event.  An empty list is PS_OK and
+ * launches nothing; n_sets is then 0 and hap all zero.  PS_ERR_BAD_ARG: window outside 1 .. 8, max_sets outside 1 .. 8, min_link
+ * negative or not finite (NaN included), NULL link or phase, and what ps_score_mutations rejects.  All outputs of one call, or of one
+ * chunk of a batch that was cut to fit device memory, come back in one device-to-host copy; a batch is cut between AlignData, never
+ * inside a list.
+ * Model limit: an edit's terms are treated as independent of the other edit of the pair.  For two edits closer than the scoring band
+ * this is an approximation (a read's term for one edit is computed on the sequence without the other).  Votes, sets and haplotypes
+ * are uncalibrated, like everything derived from these scores. */
+#define PS_LINK_MAX_WINDOW 8
+#define PS_PHASE_MAX_SETS 8
+typedef struct ps_edit_link {
+    double cis, trans;
+    int32_t n_both, n_cis, n_trans, reserved /* 0 */;
+} ps_edit_link;    /* 32 bytes */
+typedef struct ps_edit_phase {
+    double vote;
+    int32_t hap /* +1 / -1 */, set;
+} ps_edit_phase;   /* 16 bytes */
+typedef struct ps_event_hap {
+    double lik1, lik2;
+    int32_t n1, n2;
+} ps_event_hap;    /* 24 bytes */
+int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, double min_link, int32_t max_sets,
+                            double* scores /* [M] or NULL */, ps_edit_link* link /* [M][window] */, ps_edit_phase* phase /* [M] */,
+                            ps_event_hap* hap /* [n_events][max_sets] or NULL */, int32_t* n_sets /* one, or NULL */);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -290,6 +347,10 @@ int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts
 int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* n_groups /* [n] */,
                                       const int32_t* const* group, const int32_t* n_frac /* [n] */, const double* const* alt_frac,
                                       double* const* scores, ps_edit_support* const* support, double* const* lik, int32_t* const* n_cover);
+/* ps_score_mutation_phase for every AlignData in one launch chain: window[i], min_link[i], max_sets[i], link[i] ([count(muts[i])][window[i]]) and phase[i] ([count(muts[i])]) per AlignData; scores, hap ([n_events(i)][max_sets[i]]) and n_sets (one int32 each) — entries or whole arrays — may be NULL. */
+int ps_batch_score_mutation_phase(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* window /* [n] */,
+                                  const double* min_link /* [n] */, const int32_t* max_sets /* [n] */, double* const* scores,
+                                  ps_edit_link* const* link, ps_edit_phase* const* phase, ps_event_hap* const* hap, int32_t* const* n_sets);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -371,7 +432,9 @@ int ps_set_device_fraction(double fraction);
 
 /* Hot-kernel instrumentation for bench.py: accumulated HIP-event time (ms), launches and
  * algorithmic bytes of the named kernel class ("fill" = k_fill, "sweep" = the strip sweeps k_sweep / k_sweeps / k_sweep2 and their _w builds,
- * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
+ * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written, "genotype" = k_genotype: 8 per (event, edit) read, 8 (n_frac + 1) + 4 per edit written,
+ * "link" = k_link: 8 per (event, edit) read, 32 window per edit written, "phase" = k_phase: 32 window per edit read, 16 per edit written,
+ * "haptag" = k_haptag: 8 per (event, edit) and 16 per edit read, 24 max_sets per event written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
  * "fill_pair" / "fill_pair_fwd" / "fill_cmp" / "fill_512" / "fill_1024" / "fill_wide" (which form a k_fill launch took), "score_g7" .. "score_g64"
  * (k_score's size classes) and "fill_ieee" / "sweep_ieee" / "score_ieee" (launches that took the IEEE-division build);
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =

@@ -52,6 +52,13 @@ class PsEditSupport(C.Structure):
 EDIT_SUPPORT = np.dtype([("sum", np.float64), ("cover", np.int32), ("pos", np.int32), ("neg", np.int32), ("reserved", np.int32)])
 SUPPORT_MAX_GROUPS = 8
 GENO_MAX_FRAC = 8   # alt fractions per ps_score_mutation_genotypes call
+# the records of ps_score_mutation_phase as numpy dtypes (32, 16 and 24 bytes, no padding): ps_edit_link per (site, w), ps_edit_phase
+# per site, ps_event_hap per (event, phase set)
+EDIT_LINK = np.dtype([("cis", np.float64), ("trans", np.float64), ("n_both", np.int32), ("n_cis", np.int32), ("n_trans", np.int32), ("reserved", np.int32)])
+EDIT_PHASE = np.dtype([("vote", np.float64), ("hap", np.int32), ("set", np.int32)])
+EVENT_HAP = np.dtype([("lik1", np.float64), ("lik2", np.float64), ("n1", np.int32), ("n2", np.int32)])
+LINK_MAX_WINDOW = 8
+PHASE_MAX_SETS = 8
 
 
 class PoreseqError(Exception):
@@ -102,6 +109,9 @@ SYMBOLS = {
     "ps_score_mutation_genotypes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, C.c_int32, c_dp, c_dp, C.POINTER(PsEditSupport), c_dp, c_i32p]),
     "ps_batch_score_mutation_genotypes": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32p, C.POINTER(c_i32p), c_i32p, C.POINTER(c_dp),
                                                     C.POINTER(c_dp), C.POINTER(C.POINTER(PsEditSupport)), C.POINTER(c_dp), C.POINTER(c_i32p)]),
+    "ps_score_mutation_phase": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, c_dp, C.c_void_p, C.c_void_p, C.c_void_p, c_i32p]),
+    "ps_batch_score_mutation_phase": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32p, c_dp, c_i32p, C.POINTER(c_dp),
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i32p)]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -141,11 +151,12 @@ SYMBOLS = {
 # library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents;
 # PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations; PSAlign.ScoreMutationSupport reduces
 # score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas, and PSAlign.ScoreMutationGenotypes does the
-# same with util.genotypes_from_deltas on top).
+# same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
 OPTIONAL = frozenset(["ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
-                      "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes"])
+                      "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes",
+                      "ps_score_mutation_phase", "ps_batch_score_mutation_phase"])
 
 # one pair's Smith-Waterman summary, in terms of swfull's index lists: their length, the matching pairs, entry 0, entry -1, the
 # entries with a 0 on either side, and the identity in % (NaN for an empty alignment)
@@ -458,6 +469,35 @@ class CApi:
         self.check(self.lib.ps_batch_score_mutation_genotypes(R, self._harr(hs), self._harr(hms), ng.ctypes.data_as(c_i32p), gp,
                                                               nf.ctypes.data_as(c_i32p), fp, sp, rp, lp, cp))
         return list(zip(scores, recs, liks, ncov))
+
+    def score_mutation_phase(self, h, hm, n_muts, n_events, window=2, min_link=0.0, max_sets=4, want_hap=True):
+        """-> (scores [M], link EDIT_LINK [M, W], phase EDIT_PHASE [M], hap EVENT_HAP [E, S] or None, n_sets): ps_score_mutation_phase
+        of one AlignData"""
+        return self.batch_score_mutation_phase([h], [hm], [n_muts], [n_events], [window], [min_link], [max_sets], want_hap)[0]
+
+    def batch_score_mutation_phase(self, hs, hms, n_muts, n_events, window, min_link, max_sets, want_hap=True):
+        """ps_batch_score_mutation_phase over the AlignData `hs`: per AlignData the list hms[i] of n_muts[i] candidate sites, its
+        event count, the window W_i (1 .. 8), the vote threshold (finite, >= 0) and the number of tagged phase sets S_i (1 .. 8).
+        One launch chain, three reductions on the device (k_link, k_phase, k_haptag), one copy back -> [(scores float64 [M],
+        link EDIT_LINK [M, W_i], phase EDIT_PHASE [M], hap EVENT_HAP [E, S_i] — None with want_hap=False, the records are then
+        neither produced nor copied —, n_sets int)]."""
+        self._need("ps_batch_score_mutation_phase")
+        R = len(hs)
+        win = np.array([int(w) for w in window] + [0], dtype=np.int32)
+        mlk = np.array([float(v) for v in min_link] + [0.0], dtype=np.float64)
+        mxs = np.array([int(v) for v in max_sets] + [0], dtype=np.int32)
+        scores = [np.empty(int(m), dtype=np.float64) for m in n_muts]
+        links = [np.zeros((int(m), max(int(w), 0)), dtype=EDIT_LINK) for m, w in zip(n_muts, win[:R])]
+        phases = [np.zeros(int(m), dtype=EDIT_PHASE) for m in n_muts]
+        haps = [np.zeros((int(e), max(int(v), 0)), dtype=EVENT_HAP) if want_hap else None for e, v in zip(n_events, mxs[:R])]
+        nsets = np.zeros(R + 1, dtype=np.int32)
+        vp = lambda arrs: (C.c_void_p * max(R, 1))(*[a.ctypes.data_as(C.c_void_p) for a in arrs])
+        sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores])
+        np_ = (c_i32p * max(R, 1))(*[nsets[i:].ctypes.data_as(c_i32p) for i in range(R)])
+        self.check(self.lib.ps_batch_score_mutation_phase(R, self._harr(hs), self._harr(hms), win.ctypes.data_as(c_i32p), _dp(mlk),
+                                                          mxs.ctypes.data_as(c_i32p), sp, vp(links), vp(phases),
+                                                          vp(haps) if want_hap else None, np_))
+        return [(scores[i], links[i], phases[i], haps[i], int(nsets[i])) for i in range(R)]
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

@@ -309,6 +309,38 @@ class RegionBatch:
         the Python events are not modified."""
         return self._support(muts_per_region, idx, groups, n_groups, alt_frac=alt_frac)
 
+    def ScoreMutationPhase(self, muts_per_region, idx=None, window=2, min_link=0.0, max_sets=4):
+        """PSAlign.ScoreMutationPhase for the regions `idx` in lock-step: ONE ps_batch_score_mutation_phase call — one scoring chain
+        over all regions, links, phase sets and read haplotypes reduced on the device, one copy back.  muts_per_region[k] is the
+        list of candidate sites of region idx[k] (may be empty); window, min_link and max_sets are one value for all regions or a
+        list of one per region.  Returns one (scores, link, phase, hap, n_sets, scored list) per region; sequences and the Python
+        events are not modified."""
+        idx, lists = self._lists(muts_per_region, idx)
+        if not idx:
+            return []
+        if any(m is None for m in lists):
+            raise ValueError("one list of edits per region")
+        each = lambda v: list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * len(idx)
+        args = list(zip(each(window), each(min_link), each(max_sets)))
+        if len(args) != len(idx):
+            raise ValueError("one window / min_link / max_sets for all regions or one per region")
+        args = [poreseqcpp.check_phase_args(*a) for a in args]
+        hs = self._open(idx, keep=True)
+        hm = []
+        try:
+            hm = [self.api.muts_create(m) for m in lists]
+            if "ps_batch_score_mutation_phase" in self.api.missing:
+                return [poreseqcpp._phase_on(self.api, h, m, len(self.pas[i].events), len(self.pas[i].sequence), *a)
+                        for i, h, m, a in zip(idx, hs, hm, args)]
+            lists_x = [self.api.muts_export(m) for m in hm]
+            res = self.api.batch_score_mutation_phase(hs, hm, [len(x[0]) for x in lists_x], [len(self.pas[i].events) for i in idx],
+                                                      [a[0] for a in args], [a[1] for a in args], [a[2] for a in args])
+            return [r + (poreseqcpp._scored_list(x[0], x[1], x[2], r[0]),) for r, x in zip(res, lists_x)]
+        finally:
+            for m in hm:
+                self.api.muts_destroy(m)
+            self._close(idx, hs, write_back=False)
+
     def Mutate(self, idx=None, seqs='self', reps=4):
         """PSAlign.Mutate (pyx:378-435) for the regions `idx`; returns {region index: total mutated bases}."""
         idx = list(range(len(self.pas))) if idx is None else list(idx)

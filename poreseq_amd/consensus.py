@@ -269,6 +269,8 @@ VCF_INFO = (("LLR", "1", "Float", "Log-likelihood change of the edit summed over
 VCF_FORMAT = (("GT", "1", "String", "Genotype: the alt-copy count with the largest likelihood over the spanning reads (uncalibrated)"),
               ("GQ", "1", "Integer", "Genotype quality: the second smallest PL, at most 99 (uncalibrated)"),
               ("PL", "G", "Integer", "Phred-scaled genotype likelihoods over the spanning reads, 0 .. ploidy alt copies (uncalibrated)"))
+# (with phase=True: the phase set of a phased het site)
+VCF_FORMAT_PS = ("PS", "1", "Integer", "Phase set: POS of the first site of the set of phased het sites the record belongs to (uncalibrated)")
 
 
 def vcf_fields(seq, start, orig, mut, offset=0):
@@ -292,7 +294,7 @@ def vcf_qual(score):
 
 
 def variant_support(pas, muts_per_region, region_starts=None, groups=None, group_names=("t", "c"), out=None, fmt="tsv", chrom="region",
-                    min_score=0.0, ploidy=None, sample="sample"):
+                    min_score=0.0, ploidy=None, sample="sample", phase=False, min_gq=20, window=2, min_link=0.0):
     """`poreseq variant -m` for one PSAlign or a list of them with the read evidence behind every score: all regions go through ONE
     lock-step RegionBatch.ScoreMutationSupport call.  muts_per_region[r] is the MutationInfo list of region r with ABSOLUTE starts
     (region_starts[r] is subtracted inside the call and added again outside, as variant_region does — on copies: the lists handed
@@ -309,11 +311,23 @@ def variant_support(pas, muts_per_region, region_starts=None, groups=None, group
       gets FORMAT lines for GT, GQ and PL, the column `sample` and GT:GQ:PL per record (which records appear is unchanged); the TSV
       gets the columns n_cover, gt, gq and gl_0 .. gl_P, the natural-log likelihood of 0 .. P alt copies relative to hom-ref.
       ploidy=None is the output without them, byte for byte.
+    phase=True (needs ploidy=2, ValueError otherwise) phases the het calls: per region the records that are written (VCF: score >
+      min_score; TSV: all) with GT 0/1 and GQ >= min_gq, stably sorted by start, go through ONE lock-step
+      RegionBatch.ScoreMutationPhase call (window, min_link; on AlignData of their own, as every call here).  util.call_phase
+      turns a het site in a set of two or more into 0|1 / 1|0; the VCF gets a FORMAT line for PS and GT:GQ:PL:PS per record, PS the
+      POS of the set's first site or '.'; the TSV gets the columns phase_set (the absolute start of the set's first site), hap and
+      vote, '.' where there is none.  Every returned tuple gains (event haplotypes int8 [E]: 1 where lik1 > lik2 for phase set 0,
+      2 where lik2 > lik1, else 0; the record (site indices into the list, link, phase, hap, n_sets) of the region's phase call).
+      phase=False writes the same bytes and returns the same tuples as without it.
     `cover` is a span test, not a likelihood test, and QUAL, GQ and PL are uncalibrated.  No PSAlign is modified."""
     from .batch import RegionBatch
-    from .util import MutationInfo, alt_fractions, call_genotypes
+    from .util import MutationInfo, alt_fractions, call_genotypes, call_phase, check_phase_args
     if fmt not in ("tsv", "vcf"):
         raise ValueError("variant_support: fmt is 'tsv' or 'vcf'")
+    if phase and ploidy != 2:
+        raise ValueError("variant_support: phase=True needs ploidy=2")
+    if phase:
+        check_phase_args(window, min_link, 4)
     fracs = None if ploidy is None else alt_fractions(ploidy)
     single = isinstance(pas, poreseqcpp.PSAlign)
     pas = [pas] if single else list(pas)
@@ -340,28 +354,71 @@ def variant_support(pas, muts_per_region, region_starts=None, groups=None, group
                 res = rb.ScoreMutationSupport(rel, groups=groups, n_groups=len(names))
             else:
                 res = rb.ScoreMutationGenotypes(rel, alt_frac=fracs, groups=groups, n_groups=len(names))
+    called = [call_genotypes(one[3], one[4], ploidy) for one in res] if ploidy is not None else []
+    pcols = [None] * len(pas)      # per region and edit what the phase adds: (GT, PS or None, vote, hap) for the sites of the phase call
+    if phase and pas:
+        picks = []
+        for one, (gts, gqs, _pls), s0 in zip(res, called, starts):
+            keep = [i for i, ms in enumerate(one[2]) if gts[i] == '0/1' and gqs[i] >= min_gq and (fmt == "tsv" or ms.score > min_score)]
+            picks.append(sorted(keep, key=lambda i: one[2][i].start))     # (stable: equal starts keep their list order)
+        sites = []
+        for one, pick in zip(res, picks):
+            row = []
+            for i in pick:
+                mi = MutationInfo()
+                mi.start, mi.orig, mi.mut = one[2][i].start, one[2][i].orig, one[2][i].mut     # (still relative to the region)
+                row.append(mi)
+            sites.append(row)
+        with RegionBatch(pas, resident=False) as rb:
+            ph = rb.ScoreMutationPhase(sites, window=window, min_link=min_link, max_sets=4)
+        out_res = []
+        for r, (pa, one, pick, p, s0) in enumerate(zip(pas, res, picks, ph, starts)):
+            _sc, plink, pphase, phap, nsets, _scored = p
+            if fmt == "vcf":
+                at = [vcf_fields(pa.sequence, one[2][i].start, one[2][i].orig, one[2][i].mut, int(s0))[0] for i in pick]
+            else:
+                at = [one[2][i].start + int(s0) for i in pick]
+            pgt, pps = call_phase(['0/1'] * len(pick), pphase, at)
+            pcols[r] = {i: (g, q, float(v), int(h)) for i, g, q, v, h in zip(pick, pgt, pps, pphase["vote"].tolist(), pphase["hap"].tolist())}
+            tag = np.zeros(len(pa.events), dtype=np.int8)
+            if phap is not None and phap.shape[0] and phap.shape[1]:
+                tag[phap["lik1"][:, 0] > phap["lik2"][:, 0]] = 1
+                tag[phap["lik2"][:, 0] > phap["lik1"][:, 0]] = 2
+            out_res.append(tuple(one) + (tag, (pick, plink, pphase, phap, nsets)))
+        res = out_res
     if out is not None:
         if fmt == "tsv":
             out.write('#start\torig\tmut\tscore' + ''.join('\tcover_{0}\tpos_{0}\tneg_{0}\tsum_{0}'.format(n) for n in names) +
-                      ('' if ploidy is None else '\tn_cover\tgt\tgq' + ''.join('\tgl_{}'.format(k) for k in range(int(ploidy) + 1))) + '\n')
+                      ('' if ploidy is None else '\tn_cover\tgt\tgq' + ''.join('\tgl_{}'.format(k) for k in range(int(ploidy) + 1))) +
+                      ('\tphase_set\thap\tvote' if phase else '') + '\n')
         else:
             out.write('##fileformat=VCFv4.2\n##source=poreseq_amd.variant_support\n')
             for tag, num, typ, desc in VCF_INFO:
                 per = '' if num == '1' else ' (groups: {})'.format(','.join(names))
                 out.write('##INFO=<ID={},Number={},Type={},Description="{}{}">\n'.format(tag, num, typ, desc, per))
             if ploidy is not None:
-                for tag, num, typ, desc in VCF_FORMAT:
+                for tag, num, typ, desc in VCF_FORMAT + ((VCF_FORMAT_PS,) if phase else ()):
                     out.write('##FORMAT=<ID={},Number={},Type={},Description="{}">\n'.format(tag, num, typ, desc))
             out.write('#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO' + ('' if ploidy is None else '\tFORMAT\t{}'.format(sample)) + '\n')
-    for pa, s0, ch, one in zip(pas, starts, chroms, res):
+    for r, (pa, s0, ch, one) in enumerate(zip(pas, starts, chroms, res)):
         scores, sup, scored = one[:3]
         lines = []
         gcol = [''] * len(scored)      # what a genotype adds behind every line
         if ploidy is not None:
-            gts, gqs, pls = call_genotypes(one[3], one[4], ploidy)
+            gts, gqs, pls = called[r]
+            if phase:      # the phased GT where there is one
+                gts = [pcols[r][i][0] if i in pcols[r] else gt for i, gt in enumerate(gts)]
             if fmt == "tsv":
                 gcol = ['\t{}\t{}\t{}\t0.0'.format(nc, gt, gq) + ''.join('\t' + repr(v) for v in row)
                         for nc, gt, gq, row in zip(np.asarray(one[4]).tolist(), gts, gqs, np.asarray(one[3], dtype=np.float64).tolist())]
+                if phase:
+                    dot = lambda v: '.' if v is None else str(v)
+                    gcol = [g + ('\t{}\t{}\t{}'.format(dot(pcols[r][i][1]), pcols[r][i][3], repr(pcols[r][i][2])) if i in pcols[r] else '\t.\t.\t.')
+                            for i, g in enumerate(gcol)]
+            elif phase:
+                gcol = ['\tGT:GQ:PL:PS\t{}:{}:{}:{}'.format(gt, gq, ','.join(str(p) for p in pl),
+                                                           pcols[r][i][1] if i in pcols[r] and pcols[r][i][1] is not None else '.')
+                        for i, (gt, gq, pl) in enumerate(zip(gts, gqs, pls))]
             else:
                 gcol = ['\tGT:GQ:PL\t{}:{}:{}'.format(gt, gq, ','.join(str(p) for p in pl)) for gt, gq, pl in zip(gts, gqs, pls)]
         for ms, rec, gc in zip(scored, sup.tolist(), gcol):

@@ -381,6 +381,48 @@ int ps_score_mutation_genotypes(ps_align* a, const ps_muts* muts, int32_t n_grou
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_genotypes: null handle");
     return ps_batch_score_mutation_genotypes(1, &a, &muts, &n_groups, &group, &n_frac, &alt_frac, &scores, &support, &lik, &n_cover);
 }
+int ps_batch_score_mutation_phase(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* window, const double* min_link,
+                                  const int32_t* max_sets, double* const* scores, ps_edit_link* const* link, ps_edit_phase* const* phase,
+                                  ps_event_hap* const* hap, int32_t* const* n_sets) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n && (!muts || !window || !min_link || !max_sets || !link || !phase)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_phase: null array");
+    std::vector<EditReq> rq(n);
+    size_t edits = 0;
+    for (int i = 0; i < n; i++) {
+        const std::string who = "ps_score_mutation_phase: region " + std::to_string(i);
+        if (!muts[i]) return fail(PS_ERR_BAD_ARG, who + ": null list");
+        if (window[i] < 1 || window[i] > LINK_MAX_WINDOW)
+            return fail(PS_ERR_BAD_ARG, who + ": window = " + std::to_string(window[i]) + ", allowed are 1 .. " + std::to_string(LINK_MAX_WINDOW));
+        if (max_sets[i] < 1 || max_sets[i] > PHASE_MAX_SETS)
+            return fail(PS_ERR_BAD_ARG, who + ": max_sets = " + std::to_string(max_sets[i]) + ", allowed are 1 .. " + std::to_string(PHASE_MAX_SETS));
+        if (!(min_link[i] >= 0.0 && min_link[i] <= 1.7976931348623157e308)) {   // (NaN fails both comparisons)
+            char msg[96];
+            snprintf(msg, sizeof msg, ": min_link = %g, allowed is a finite value >= 0", min_link[i]);
+            return fail(PS_ERR_BAD_ARG, who + msg);
+        }
+        if (!link[i]) return fail(PS_ERR_BAD_ARG, who + ": null link");
+        if (!phase[i]) return fail(PS_ERR_BAD_ARG, who + ": null phase");
+        EditReq& q = rq[i];
+        q.a = as[i]; q.muts = &muts[i]->v; q.window = window[i]; q.min_link = min_link[i]; q.max_sets = max_sets[i];
+        q.score = scores ? scores[i] : nullptr; q.link = link[i]; q.phase = phase[i];
+        q.hap = hap ? hap[i] : nullptr; q.nsets = n_sets ? n_sets[i] : nullptr;
+        edits += q.muts->size();
+    }
+    for (EditReq& q : rq)
+        if (q.muts->empty()) {   // no site: no set, and no event is tagged (no kernel sees this AlignData)
+            if (q.nsets) *q.nsets = 0;
+            if (q.hap) memset(q.hap, 0, (size_t)q.a->E * q.max_sets * sizeof(ps_event_hap));
+        }
+    if (!edits) return PS_OK;   // nothing to score anywhere: no launch
+    NEED_RT();
+    return score_edits(rt, EditKind::Phase, rq.data(), rq.size());   // k_link, k_phase and k_haptag behind k_score
+}
+int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, double min_link, int32_t max_sets, double* scores,
+                            ps_edit_link* link, ps_edit_phase* phase, ps_event_hap* hap, int32_t* n_sets) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_phase: null handle");
+    return ps_batch_score_mutation_phase(1, &a, &muts, &window, &min_link, &max_sets, &scores, &link, &phase, &hap, &n_sets);
+}
 int ps_batch_make_mutations(int32_t n, ps_align* const* a, const ps_muts* const* scored, int32_t* n_bases) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

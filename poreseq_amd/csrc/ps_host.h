@@ -202,6 +202,10 @@ struct EditReq {
     const int32_t* group = nullptr; int ngroups = 0; double* score = nullptr; ps_edit_support* rec = nullptr;
     // Genotype: [nfrac] alt fractions (checked by the caller), [M][nfrac + 1] likelihoods, [M] covering-event counts (optional)
     int nfrac = 0; const double* frac = nullptr; double* lik = nullptr; int32_t* ncover = nullptr;
+    // Phase: window, vote threshold and tagged sets (checked by the caller), [M] scores (`score`, optional), [M][window] links, [M]
+    // phase records, [E][max_sets] event records (optional), the number of sets (optional)
+    int window = 0; double min_link = 0.0; int max_sets = 0;
+    ps_edit_link* link = nullptr; ps_edit_phase* phase = nullptr; ps_event_hap* hap = nullptr; int32_t* nsets = nullptr;
     // filled by score_edits: the plan, the list of a Points call and its point_layout
     EditPlan plan;
     std::vector<Mut> own;

@@ -280,15 +280,33 @@ struct GenoArgs {
     double* lik;               // [M][nfrac + 1]
     int* ncover;               // [M]
 };
+// A phase call (ps_score_mutation_phase: k_link, k_phase and k_haptag behind k_score) has one of these per AlignData beside its
+// ScoreArgs: the window, the vote threshold, the number of tagged sets and where the records go.  `score`, `hap` and `nsets` are
+// null where the caller does not want them.
+constexpr int LINK_MAX_WINDOW = 8;
+constexpr int PHASE_MAX_SETS = 8;
+struct PhaseArgs {
+    int W;                     // 1 .. LINK_MAX_WINDOW (0: nothing to write for this AlignData)
+    int S;                     // 1 .. PHASE_MAX_SETS
+    double min_link;
+    double* score;             // NULL, or [M]
+    ps_edit_link* link;        // [M][W]
+    ps_edit_phase* phase;      // [M]
+    ps_event_hap* hap;         // NULL, or [njobs][S]
+    int* nsets;                // one
+};
 // What an edit-scoring call makes of k_score's [event][edit] matrix: a scored list (ScoreMutations), rows per position (ps_point_table),
-// scores and per-group records (ps_score_mutation_support), or those with genotype likelihoods behind them
-enum class EditKind { List, Points, Support, Genotype };
+// scores and per-group records (ps_score_mutation_support), those with genotype likelihoods behind them, or pair links, phase
+// sets and read haplotypes (ps_score_mutation_phase)
+enum class EditKind { List, Points, Support, Genotype, Phase };
 // One such call as launch_score runs it: the descriptors of its AlignData on the host (`pts` for Points, `sps` for Support and
-// Genotype, `gts` for Genotype; the others stay empty) and where their copies lie on the device (null where the vector is empty)
+// Genotype, `gts` for Genotype, `phs` for Phase; the others stay empty) and where their copies lie on the device (null where the
+// vector is empty)
 struct ScoreLaunch {
     EditKind kind = EditKind::List;
-    std::vector<ScoreArgs> sas; std::vector<PointArgs> pts; std::vector<SupportArgs> sps; std::vector<GenoArgs> gts;
+    std::vector<ScoreArgs> sas; std::vector<PointArgs> pts; std::vector<SupportArgs> sps; std::vector<GenoArgs> gts; std::vector<PhaseArgs> phs;
     const ScoreArgs* d_sas = nullptr; const PointArgs* d_pts = nullptr; const SupportArgs* d_sps = nullptr; const GenoArgs* d_gts = nullptr;
+    const PhaseArgs* d_phs = nullptr;
 };
 int launch_score(Runtime* rt, const BatchD& b, const ScoreLaunch& L);
 int launch_begin(Runtime* rt, const BatchD& b);

@@ -24,6 +24,7 @@
 //   k_backtrace   LDS-tile walker with wave-wide look-ahead and tile prefetch, then k_fill_like, k_updaterefs /
 //                 k_lb for the new band centres
 //   k_old / k_score / k_reduce   edit scoring (scoreMutation + columnMax) and the per-edit sums
+//   k_link / k_phase / k_haptag  a phase call's reductions of k_score's matrix: pair links, the scan over the sites, the reads' haplotypes
 #include <algorithm>
 #include <atomic>
 
@@ -1436,6 +1437,199 @@ __global__ __launch_bounds__(256) void k_genotype(BatchD b, const ScoreArgs* __r
     out[K] = hom;
 }
 
+// Pair links of a phase call (ps_score_mutation_phase, include/poreseq_hip.h): per edit m and w = 1 .. W the pair (m, m + w) over
+// the events that span both, as the likelihood of both alts on one chromosome copy (cis) and of one on each (trans).
+// k_genotype's shape: a thread per edit, events in order, coalesced reads of delta[e][m], the events' spans staged in LDS SUP_EV at
+// a time.  The partner terms delta[e][m + w] come from the same row (lane t reads the word w further on: the same lines, and for
+// the last threads of a block the lines of the next block's range).  The accumulators are never indexed by a runtime value: the
+// loop over w is unrolled over all LINK_MAX_WINDOW, `w <= W` (the same for the whole block) guards each, and the partner's column
+// is -0x7fffffff — spanned by no event — where m + w >= M or the partner is skipped.
+__global__ __launch_bounds__(256) void k_link(BatchD b, const ScoreArgs* __restrict__ A, const PhaseArgs* __restrict__ Q) {
+    const ScoreArgs& a = A[blockIdx.y];
+    const PhaseArgs& q = Q[blockIdx.y];
+    const int M = a.nitems_per_job, njobs = a.njobs, W = q.W;
+    if ((int)(blockIdx.x * blockDim.x) >= M || !njobs || !W) return;   // (the same for every thread of the block)
+    __shared__ int s_lo[SUP_EV], s_hi[SUP_EV];
+    const int t = threadIdx.x;
+    const int m = blockIdx.x * blockDim.x + t;
+    const bool have = m < M;
+    const int none = -0x7fffffff;
+    const int col = (have && !a.m_skip[m]) ? a.m_start[m] + 1 : none;
+    int colw[LINK_MAX_WINDOW], nb[LINK_MAX_WINDOW], ncis[LINK_MAX_WINDOW], ntr[LINK_MAX_WINDOW];
+    double cis[LINK_MAX_WINDOW], trans[LINK_MAX_WINDOW];
+#pragma unroll
+    for (int w = 0; w < LINK_MAX_WINDOW; w++) {
+        const int j = m + w + 1;
+        colw[w] = (w < W && j < M && !a.m_skip[j]) ? a.m_start[j] + 1 : none;
+        cis[w] = 0.0; trans[w] = 0.0; nb[w] = 0; ncis[w] = 0; ntr[w] = 0;
+    }
+    double s = -1e-6;
+    for (int e0 = 0; e0 < njobs; e0 += SUP_EV) {
+        if (e0) __syncthreads();   // (everyone is done with the previous events)
+        if (e0 + t < njobs) {
+            const JobOut* O = b.jobs[a.job0 + e0 + t].out;
+            const bool span = O->has_index != 0;
+            s_lo[t] = span ? O->refstart : 1;
+            s_hi[t] = span ? O->refend : 0;
+        }
+        __syncthreads();
+        const int ne = min(SUP_EV, njobs - e0);
+        if (have)
+            for (int i = 0; i < ne; i++) {
+                const double* row = a.delta + (size_t)(e0 + i) * M;
+                const double da = row[m];
+                s += da;
+                const int lo = s_lo[i], hi = s_hi[i];
+                if (lo <= col && col <= hi) {
+#pragma unroll
+                    for (int w = 0; w < LINK_MAX_WINDOW; w++)
+                        if (lo <= colw[w] && colw[w] <= hi) {   // (never true past W or past the list's end)
+                            const double db = row[m + w + 1];
+                            const double sm = da + db, r = da - db;
+                            cis[w] += (sm > 0 ? sm : 0.0) + log(0.5 + 0.5 * exp(-fabs(sm)));
+                            trans[w] += (da > db ? da : db) + log(0.5 + 0.5 * exp(-fabs(r)));
+                            nb[w]++;
+                            ncis[w] += ((da > 0 && db > 0) || (da < 0 && db < 0)) ? 1 : 0;
+                            ntr[w] += ((da > 0 && db < 0) || (da < 0 && db > 0)) ? 1 : 0;
+                        }
+                }
+            }
+    }
+    if (!have) return;
+    if (q.score) q.score[m] = s;
+#pragma unroll
+    for (int w = 0; w < LINK_MAX_WINDOW; w++)
+        if (w < W) {
+            ps_edit_link r;
+            r.cis = cis[w]; r.trans = trans[w]; r.n_both = nb[w]; r.n_cis = ncis[w]; r.n_trans = ntr[w]; r.reserved = 0;
+            q.link[(size_t)m * W + w] = r;
+        }
+}
+
+// The phase scan of a phase call: one wavefront per AlignData walks the sites in list order, PH_CHUNK at a time, a lane per site.
+// The link records the chunk's sites look back at — those of the sites c0 - LINK_MAX_WINDOW .. c0 + PH_CHUNK - 1, contiguous in
+// memory — are read by all lanes side by side and left in LDS as cis - trans and n_both > 0, and every lane takes its own site's W
+// differences into registers: everything that does not depend on the chain is done before it starts.  The chain itself is the
+// sign only: in step l every lane forms "its vote, were it site l's turn" from its differences and the wave-uniform history (the
+// last LINK_MAX_WINDOW haplotype signs, and `run`, the number of sites ending at m - 1 that share its set: phase[m - w].set ==
+// phase[m - 1].set is w <= run), lane l's decision is read with one v_readlane, and the history moves on.  A lane keeps the vote,
+// haplotype and set of its own step and the chunk's records go out side by side.  Nothing of the chain goes through memory.
+// WM is the largest window of the launch's AlignData, rounded up to 1, 2, 4 or 8: a step costs WM multiply-adds, and the history's
+// update is written as selects, not branches.
+constexpr int PH_CHUNK = 64;
+template <int WM> __global__ __launch_bounds__(64) void k_phase(const ScoreArgs* __restrict__ A, const PhaseArgs* __restrict__ Q) {
+    const ScoreArgs& a = A[blockIdx.x];
+    const PhaseArgs& q = Q[blockIdx.x];
+    const int M = a.nitems_per_job, W = q.W;
+    if (!M || !a.njobs || !W) return;
+    __shared__ double s_diff[(PH_CHUNK + LINK_MAX_WINDOW) * LINK_MAX_WINDOW];
+    __shared__ int s_ok[(PH_CHUNK + LINK_MAX_WINDOW) * LINK_MAX_WINDOW];
+    const int t = threadIdx.x;
+    const double min_link = q.min_link;
+    double h[WM];   // hap of site m - 1 .. m - WM (wave-uniform; only ever indexed by unrolled loops)
+#pragma unroll
+    for (int w = 0; w < WM; w++) h[w] = 1.0;
+    int run = 0, set = 0;
+    for (int c0 = 0; c0 < M; c0 += PH_CHUNK) {
+        const int n = min(PH_CHUNK, M - c0);
+        const int b0 = c0 - LINK_MAX_WINDOW;   // the first site whose records are staged (negative in the first chunk: none before site 0)
+        if (c0) __syncthreads();               // (everyone has taken its differences of the previous chunk)
+        for (int r = t; r < (n + LINK_MAX_WINDOW) * W; r += 64) {
+            const int site = b0 + r / W;
+            if (site < 0) continue;
+            const ps_edit_link L = q.link[(int64_t)b0 * W + r];
+            s_diff[r] = L.cis - L.trans;
+            s_ok[r] = L.n_both > 0;
+        }
+        __syncthreads();
+        const int m = c0 + t;
+        double dv[WM];
+        int okm = 0;   // bit w - 1: the pair (m - w, m) exists and has shared events
+#pragma unroll
+        for (int w = 1; w <= WM; w++) {
+            const bool use = t < n && w <= W && w <= m;
+            const int r = (t + LINK_MAX_WINDOW - w) * W + (w - 1);   // record w - 1 of site m - w
+            dv[w - 1] = use ? s_diff[use ? r : 0] : 0.0;
+            if (use && s_ok[r]) okm |= 1 << (w - 1);
+        }
+        double myvote = 0.0;
+        int myhap = 1, myset = 0;
+        for (int l = 0; l < n; l++) {
+            double vote = 0.0;
+#pragma unroll
+            for (int w = 1; w <= WM; w++)
+                if (((okm >> (w - 1)) & 1) && w <= run) vote += h[w - 1] * dv[w - 1];
+            int code = (vote != 0.0 && fabs(vote) >= min_link) ? (vote > 0 ? 1 : -1) : 0;   // (a NaN fails both)
+            if (c0 + l == 0) code = 2;   // site 0 opens set 0
+            const int c = __builtin_amdgcn_readlane(code, l);
+            const bool first = c == 2, join = c == 1 || c == -1;
+            const int hap = join ? c : 1;
+            run = join ? run + 1 : 1;
+            set = first ? 0 : (join ? set : set + 1);
+            if (t == l) { myvote = vote; myhap = hap; myset = set; }
+#pragma unroll
+            for (int w = WM - 1; w > 0; w--) h[w] = h[w - 1];
+            h[0] = (double)hap;
+        }
+        if (t < n) {
+            ps_edit_phase p;
+            p.vote = myvote; p.hap = myhap; p.set = myset;
+            q.phase[c0 + t] = p;
+        }
+    }
+    if (t == 0) *q.nsets = set + 1;
+}
+
+// Read haplotypes of a phase call: one wavefront per event adds the event's terms over the sites of every tagged phase set, by the
+// site's haplotype.  Lane l walks the sites l, l + 64, ... ascending (coalesced reads of delta[e][m] and of the phase records) into
+// partials of its own, and the 64 partials of a sum are then added in lane order by one thread: an order a host can reproduce.
+// As in k_support the accumulators are never indexed by a runtime value: the loop over the sets is unrolled over all
+// PHASE_MAX_SETS and a site adds +0.0 to the sums it does not belong to, which leaves them as they are (a sum that starts at +0.0
+// is never -0.0).
+__global__ __launch_bounds__(64) void k_haptag(BatchD b, const ScoreArgs* __restrict__ A, const PhaseArgs* __restrict__ Q) {
+    const ScoreArgs& a = A[blockIdx.y];
+    const PhaseArgs& q = Q[blockIdx.y];
+    const int M = a.nitems_per_job, njobs = a.njobs, S = q.S, e = blockIdx.x;
+    if (e >= njobs || !M || !q.W || !q.hap) return;   // (the same for every thread of the block)
+    __shared__ double s_sum[2 * PHASE_MAX_SETS][64];
+    __shared__ int s_cnt[2 * PHASE_MAX_SETS][64];
+    const int t = threadIdx.x;
+    const JobOut* O = b.jobs[a.job0 + e].out;
+    const bool span = O->has_index != 0;
+    const int lo = span ? O->refstart : 1, hi = span ? O->refend : 0;
+    double l1[PHASE_MAX_SETS], l2[PHASE_MAX_SETS];
+    int n1[PHASE_MAX_SETS], n2[PHASE_MAX_SETS];
+#pragma unroll
+    for (int k = 0; k < PHASE_MAX_SETS; k++) { l1[k] = 0.0; l2[k] = 0.0; n1[k] = 0; n2[k] = 0; }
+    const double* row = a.delta + (size_t)e * M;
+    for (int m = t; m < M; m += 64) {
+        const int col = a.m_skip[m] ? -0x7fffffff : a.m_start[m] + 1;
+        if (!(lo <= col && col <= hi)) continue;
+        const double d = row[m];
+        const ps_edit_phase p = q.phase[m];
+#pragma unroll
+        for (int k = 0; k < PHASE_MAX_SETS; k++) {
+            const bool one = p.set == k && p.hap > 0, two = p.set == k && p.hap < 0;
+            l1[k] += one ? d : 0.0; n1[k] += one ? 1 : 0;
+            l2[k] += two ? d : 0.0; n2[k] += two ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < PHASE_MAX_SETS; k++) {
+        s_sum[2 * k][t] = l1[k]; s_sum[2 * k + 1][t] = l2[k];
+        s_cnt[2 * k][t] = n1[k]; s_cnt[2 * k + 1][t] = n2[k];
+    }
+    __syncthreads();
+    if (t < 2 * S) {   // thread 2 k: lik1 / n1 of set k; thread 2 k + 1: lik2 / n2
+        double sum = 0.0;
+        int cnt = 0;
+        for (int l = 0; l < 64; l++) { sum += s_sum[t][l]; cnt += s_cnt[t][l]; }
+        ps_event_hap* out = q.hap + (size_t)e * S + (t >> 1);
+        if (t & 1) { out->lik2 = sum; out->n2 = cnt; }
+        else { out->lik1 = sum; out->n1 = cnt; }
+    }
+}
+
 // latch the reference's "stripe_width == 0" decision (cpp/Alignment.cpp:51-59) for this API call
 __global__ void k_begin(BatchD b) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1670,6 +1864,44 @@ static int launch_genotype(Runtime* rt, const BatchD& b, const ScoreLaunch& L, i
     return PS_OK;
 }
 
+// a phase call (every AlignData of it): the score and the pair links per edit, the scan over the sites, the records per event
+static int launch_phase(Runtime* rt, const BatchD& b, const ScoreLaunch& L, int maxM, int maxE) {
+    const int R = (int)L.sas.size();
+    double link_bytes = 0, phase_bytes = 0, tag_bytes = 0;
+    bool any = false, any_hap = false;
+    int maxW = 0;
+    for (int k = 0; k < R; k++) {
+        const ScoreArgs& a = L.sas[k];
+        const PhaseArgs& q = L.phs[k];
+        if (!a.njobs || !a.nitems_per_job || !q.W) continue;
+        any = true;
+        maxW = std::max(maxW, q.W);
+        link_bytes += 8.0 * a.njobs * a.nitems_per_job + 32.0 * q.W * a.nitems_per_job;
+        phase_bytes += (32.0 * q.W + 16.0) * a.nitems_per_job;
+        if (!q.hap) continue;
+        any_hap = true;
+        tag_bytes += 8.0 * a.njobs * a.nitems_per_job + 16.0 * a.nitems_per_job + 24.0 * q.S * a.njobs;
+    }
+    if (!any) return PS_OK;
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_link, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, b, L.d_sas, L.d_phs);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "link", link_bytes);
+    prof_begin(rt);
+    if (maxW <= 1) hipLaunchKernelGGL(k_phase<1>, dim3(R), dim3(64), 0, rt->stream, L.d_sas, L.d_phs);
+    else if (maxW <= 2) hipLaunchKernelGGL(k_phase<2>, dim3(R), dim3(64), 0, rt->stream, L.d_sas, L.d_phs);
+    else if (maxW <= 4) hipLaunchKernelGGL(k_phase<4>, dim3(R), dim3(64), 0, rt->stream, L.d_sas, L.d_phs);
+    else hipLaunchKernelGGL(k_phase<8>, dim3(R), dim3(64), 0, rt->stream, L.d_sas, L.d_phs);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "phase", phase_bytes);
+    if (!any_hap) return PS_OK;   // (no caller wants the events tagged)
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_haptag, dim3(maxE, R), dim3(64), 0, rt->stream, b, L.d_sas, L.d_phs);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "haptag", tag_bytes);
+    return PS_OK;
+}
+
 // edit scoring of several AlignData of one batch (L: their descriptors on the host and on the device): one launch per kernel over
 // all of them — grid.z (k_reduce: grid.y) is the AlignData, blocks past an AlignData's own sizes leave at once
 int launch_score(Runtime* rt, const BatchD& b, const ScoreLaunch& L) {
@@ -1719,6 +1951,7 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreLaunch& L) {
     case EditKind::Points: return launch_point_table(rt, L);
     case EditKind::Genotype: PS_TRY(launch_support(rt, b, L, maxM)); return launch_genotype(rt, b, L, maxM);
     case EditKind::Support: return launch_support(rt, b, L, maxM);
+    case EditKind::Phase: return launch_phase(rt, b, L, maxM, maxE);
     case EditKind::List: break;
     }
     hipLaunchKernelGGL(k_reduce, dim3((maxM + 255) / 256, R), dim3(256), 0, rt->stream, d_sas);

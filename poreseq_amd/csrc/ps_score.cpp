@@ -1,5 +1,6 @@
 // ps_score.cpp — the edit-scoring chain of libporeseq_hip.so: ScoreMutations (cpp/MakeMutations.cpp:23-69) for several AlignData at
-// once and its reductions on the device — the point-edit table, the per-group read support, the genotype likelihoods.  One call is
+// once and its reductions on the device — the point-edit table, the per-group read support, the genotype likelihoods, the phase of
+// het edits.  One call is
 // an array of EditReq records (ps_host.h) of one EditKind; it runs as named stages over a Chain, and a call that has to be cut runs
 // the same stages over sub-ranges of the same array.  The edit plans are host arithmetic in ps_editplan.h, the kernels and
 // launch_score in ps_kernels.hip.  Also here: FindPointMutations and the `likes` loop of ScoreAlignments.
@@ -43,6 +44,8 @@ struct OutAt {
     size_t best = 0, table = 0;
     bool has_rec = false;                       // Support, Genotype (sscore with `live`; lik, ncover with `live` of a genotype call)
     size_t sscore = 0, rec = 0, lik = 0, ncover = 0;
+    bool has_score = false, has_hap = false;    // Phase (link, phase, nsets with `live`)
+    size_t link = 0, phase = 0, hap = 0, nsets = 0;
 };
 
 // the tables of all AlignData on their way into "mutint": push() appends one and answers where it will lie on the device
@@ -73,12 +76,13 @@ struct Chain {
     char* d_out = nullptr;      // the output buffer of a point-table / support / genotype call
     ScoreLaunch L;
     static const char* name(EditKind k) {
-        return k == EditKind::Points ? "point_table" : k == EditKind::Genotype ? "score_mutation_genotypes" : k == EditKind::Support ? "score_mutation_support" : "score_mutations";
+        return k == EditKind::Points ? "point_table" : k == EditKind::Phase ? "score_mutation_phase" : k == EditKind::Genotype ? "score_mutation_genotypes" : k == EditKind::Support ? "score_mutation_support" : "score_mutations";
     }
     Chain(Runtime* rt_, EditKind kind_, EditReq* r_, size_t n) : rt(rt_), kind(kind_), r(r_), R((int)n), tk(name(kind_)) { L.kind = kind_; }
     bool points() const { return kind == EditKind::Points; }
     bool support() const { return kind == EditKind::Support || kind == EditKind::Genotype; }
     bool geno() const { return kind == EditKind::Genotype; }
+    bool phase() const { return kind == EditKind::Phase; }
 };
 }  // namespace
 
@@ -149,7 +153,8 @@ static void build_jobs(Chain& c) {
 }
 
 // An AlignData without events has every score at its seed, -1e-6 (score_mutations): a point-table call's rows say so, a support
-// call's records are all zero, a genotype call's likelihoods and covering-event counts too.  No kernel sees it; written here.
+// call's records are all zero, a genotype call's likelihoods and covering-event counts too, and a phase call gets what its rules give
+// for all-zero links: every site a set of its own.  No kernel sees it; written here.
 static void write_eventless(const Chain& c) {
     for (int k = 0; k < c.R; k++) {
         const EditReq& q = c.r[k];
@@ -163,6 +168,12 @@ static void write_eventless(const Chain& c) {
         if (c.geno()) {
             std::fill(q.lik, q.lik + M * (q.nfrac + 1), 0.0);
             if (q.ncover) std::fill(q.ncover, q.ncover + M, 0);
+        }
+        if (c.phase()) {
+            if (q.score) std::fill(q.score, q.score + M, -1e-6);
+            memset(q.link, 0, M * q.window * sizeof(ps_edit_link));
+            for (size_t m = 0; m < M; m++) { q.phase[m].vote = 0.0; q.phase[m].hap = 1; q.phase[m].set = (int32_t)m; }
+            if (q.nsets) *q.nsets = (int32_t)M;   // (hap has no rows)
         }
     }
 }
@@ -194,7 +205,8 @@ static int take_slab_and_realign(Chain& c) {
 // ---- stage: output layout.  Every AlignData's score array back to back at the head of "mutdbl": ONE device-to-host copy returns
 // them all (a copy per region before: 20 000 of a bench step's 25 000 copy commands, ~0.2 ms each on a loaded stream).  A point-table
 // call: the records, then the rows, of all AlignData back to back in one buffer; a support call: the scores, then the records; a
-// genotype call's likelihoods and covering-event counts follow them in the same buffer — ONE copy back each.
+// genotype call's likelihoods and covering-event counts follow them in the same buffer; a phase call: the scores, the links, the
+// phase records, the event records and the set counts — ONE copy back each.
 static void lay_out(Chain& c) {
     const int R = c.R;
     c.at.assign(R, OutAt());
@@ -211,6 +223,21 @@ static void lay_out(Chain& c) {
     }
     for (int k = 0; k < R; k++) if (c.at[k].has_best) take(&c.at[k].best, c.r[k].pos_triv.size() * sizeof(ps_point_best));
     for (int k = 0; k < R; k++) if (c.at[k].has_table) take(&c.at[k].table, c.r[k].pos_triv.size() * PT_SLOTS * sizeof(double));
+    if (c.phase()) {
+        for (int k = 0; k < R; k++) {
+            const EditReq& q = c.r[k];
+            OutAt& o = c.at[k];
+            if (!o.live) continue;
+            const size_t M = (size_t)q.plan.M;
+            o.has_score = q.score != nullptr; o.has_hap = q.hap != nullptr;
+            if (o.has_score) take(&o.sscore, M * sizeof(double));
+            take(&o.link, M * q.window * sizeof(ps_edit_link));
+            take(&o.phase, M * sizeof(ps_edit_phase));
+            if (o.has_hap) take(&o.hap, (size_t)q.a->E * q.max_sets * sizeof(ps_event_hap));
+            take(&o.nsets, 8);   // (one int32; the next double stays aligned)
+        }
+        return;
+    }
     if (!c.support()) return;
     for (int k = 0; k < R; k++) if (c.at[k].live) take(&c.at[k].sscore, (size_t)c.r[k].plan.M * sizeof(double));
     for (int k = 0; k < R; k++) if (c.at[k].has_rec) take(&c.at[k].rec, (size_t)c.r[k].plan.M * c.r[k].ngroups * sizeof(ps_edit_support));
@@ -272,26 +299,39 @@ static void fill_kind_args(Chain& c, int k, IntStage& st) {
             q.lik = (double*)(c.d_out + o.lik); q.ncover = (int*)(c.d_out + o.ncover);
         }
     }
+    if (c.phase()) {
+        PhaseArgs& q = c.L.phs[k];
+        memset(&q, 0, sizeof(q));
+        if (o.live) {
+            q.W = r.window; q.S = r.max_sets; q.min_link = r.min_link;
+            if (o.has_score) q.score = (double*)(c.d_out + o.sscore);
+            q.link = (ps_edit_link*)(c.d_out + o.link); q.phase = (ps_edit_phase*)(c.d_out + o.phase);
+            if (o.has_hap) q.hap = (ps_event_hap*)(c.d_out + o.hap);
+            q.nsets = (int*)(c.d_out + o.nsets);
+        }
+    }
 }
 
 // the edit tables and their descriptors (ScoreArgs, behind the tables in the same buffer) in one copy
 static int upload_descriptors(Chain& c, const IntStage& st) {
     ScoreLaunch& L = c.L;
     const size_t sa_at = (st.h.size() * sizeof(int) + 63) / 64 * 64;
-    const size_t pt_at = (sa_at + (size_t)c.R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them)
+    const size_t pt_at = (sa_at + (size_t)c.R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them; a phase call: its PhaseArgs)
     const size_t gt_at = (pt_at + L.sps.size() * sizeof(SupportArgs) + 63) / 64 * 64;   // (a genotype call: its GenoArgs behind the SupportArgs)
-    std::vector<char> blob(std::max(pt_at + L.pts.size() * sizeof(PointArgs), gt_at + L.gts.size() * sizeof(GenoArgs)));   // (PointArgs or SupportArgs, never both)
+    std::vector<char> blob(std::max({pt_at + L.pts.size() * sizeof(PointArgs), gt_at + L.gts.size() * sizeof(GenoArgs), pt_at + L.phs.size() * sizeof(PhaseArgs)}));   // (PointArgs, SupportArgs or PhaseArgs: one of them)
     memcpy(blob.data(), st.h.data(), st.h.size() * sizeof(int));
     memcpy(blob.data() + sa_at, L.sas.data(), (size_t)c.R * sizeof(ScoreArgs));
     if (c.points()) memcpy(blob.data() + pt_at, L.pts.data(), L.pts.size() * sizeof(PointArgs));
     if (c.support()) memcpy(blob.data() + pt_at, L.sps.data(), L.sps.size() * sizeof(SupportArgs));
     if (c.geno()) memcpy(blob.data() + gt_at, L.gts.data(), L.gts.size() * sizeof(GenoArgs));
+    if (c.phase()) memcpy(blob.data() + pt_at, L.phs.data(), L.phs.size() * sizeof(PhaseArgs));
     PS_TRY(c.rt->up(st.dp, blob.data(), blob.size()));
     const char* base = (const char*)st.dp;
     L.d_sas = (const ScoreArgs*)(base + sa_at);
     L.d_pts = c.points() ? (const PointArgs*)(base + pt_at) : nullptr;
     L.d_sps = c.support() ? (const SupportArgs*)(base + pt_at) : nullptr;
     L.d_gts = c.geno() ? (const GenoArgs*)(base + gt_at) : nullptr;
+    L.d_phs = c.phase() ? (const PhaseArgs*)(base + pt_at) : nullptr;
     return PS_OK;
 }
 
@@ -308,13 +348,13 @@ static int stage_descriptors(Chain& c) {
         dbls += E * std::max(p.nr0, 1) + E * std::max(p.M, 1) + std::max(p.M, 1) + E * (c.r[k].a->states.size() + 8);
     }
     DBuf& mb = c.rt->buf("mutint");
-    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max(sizeof(PointArgs), sizeof(SupportArgs)) + sizeof(GenoArgs)) + 64));
+    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max({sizeof(PointArgs), sizeof(SupportArgs), sizeof(PhaseArgs)}) + sizeof(GenoArgs)) + 64));
     DBuf& db = c.rt->buf("mutdbl");
     PS_TRY(db.ensure(dbls * sizeof(double)));
     c.score0 = db.as<double>();
     double* dd = c.score0 + c.score_tot;
-    if (c.points() || c.support()) {
-        DBuf& ob = c.rt->buf(c.points() ? "ptable" : "support");
+    if (c.points() || c.support() || c.phase()) {
+        DBuf& ob = c.rt->buf(c.points() ? "ptable" : c.phase() ? "phase" : "support");
         PS_TRY(ob.ensure(std::max<size_t>(c.out_bytes, 16)));
         c.d_out = ob.as<char>();
     }
@@ -325,6 +365,7 @@ static int stage_descriptors(Chain& c) {
     c.L.pts.resize(c.points() ? R : 0);
     c.L.sps.resize(c.support() ? R : 0);
     c.L.gts.resize(c.geno() ? R : 0);
+    c.L.phs.resize(c.phase() ? R : 0);
     for (int k = 0; k < R; k++) {
         PS_TRY(fill_score_args(c, k, st, &dd));
         fill_kind_args(c, k, st);
@@ -386,6 +427,22 @@ static int fetch_support(Chain& c) {
     }
     return PS_OK;
 }
+static int fetch_phase(Chain& c) {
+    char* h = nullptr;
+    PS_TRY(fetch_block(c, &h));
+    for (int k = 0; k < c.R; k++) {
+        const EditReq& q = c.r[k];
+        const OutAt& o = c.at[k];
+        const size_t M = (size_t)q.plan.M;
+        if (!o.live) continue;
+        if (o.has_score) memcpy(q.score, h + o.sscore, M * sizeof(double));
+        memcpy(q.link, h + o.link, M * q.window * sizeof(ps_edit_link));
+        memcpy(q.phase, h + o.phase, M * sizeof(ps_edit_phase));
+        if (o.has_hap) memcpy(q.hap, h + o.hap, (size_t)q.a->E * q.max_sets * sizeof(ps_event_hap));
+        if (q.nsets) memcpy(q.nsets, h + o.nsets, sizeof(int32_t));
+    }
+    return PS_OK;
+}
 static int fetch_list(Chain& c) {
     std::vector<double*> dl(c.R, nullptr);
     double* all_scores = nullptr;
@@ -440,7 +497,7 @@ static int run_chain(Runtime* rt, EditKind kind, EditReq* r, size_t n) {
     if (c.tk.on) { PS_HIP(hipStreamSynchronize(rt->stream)); }
     c.tk.lap("realign fwd+back (rest)");
     PS_TRY(launch(c));
-    PS_TRY(kind == EditKind::Points ? fetch_points(c) : c.support() ? fetch_support(c) : fetch_list(c));
+    PS_TRY(kind == EditKind::Points ? fetch_points(c) : c.support() ? fetch_support(c) : c.phase() ? fetch_phase(c) : fetch_list(c));
     c.tk.lap("score edits");
     return PS_OK;
 }

@@ -11,7 +11,7 @@ import copy
 import numpy as np
 
 from . import _capi
-from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas, genotypes_from_deltas, check_alt_frac
+from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas, genotypes_from_deltas, check_alt_frac, phase_from_deltas, check_phase_args
 
 
 def _api():
@@ -102,6 +102,21 @@ def _genotypes_on(api, h, hm, n_events, seq_len, grp, G, frac):
     else:
         scores, sup, lik, n_cover = api.score_mutation_genotypes(h, hm, len(start), grp, G, frac)
     return scores, sup, _scored_list(start, orig, mut, scores), lik, n_cover
+
+
+def _phase_on(api, h, hm, n_events, seq_len, window, min_link, max_sets):
+    """(scores, link, phase, hap, n_sets, scored list) of the site list `hm` on the AlignData `h`: ps_score_mutation_phase, or — a
+    library without the entry point — the literal reductions of its score_mutation_deltas and of the refs it leaves
+    (util.phase_from_deltas; the scores are support_from_deltas')"""
+    start, orig, mut, _ = api.muts_export(hm)
+    if "ps_score_mutation_phase" in api.missing:
+        deltas = api.score_mutation_deltas(h, hm, n_events, len(start))
+        spans = spans_from_refs(api.align_event_refs(h, n_events))
+        scores, _ = support_from_deltas(deltas, np.zeros(n_events, dtype=np.int32), 1, spans, start, seq_len)
+        link, phase, hap, n_sets = phase_from_deltas(deltas, spans, start, seq_len, window, min_link, max_sets)
+    else:
+        scores, link, phase, hap, n_sets = api.score_mutation_phase(h, hm, len(start), n_events, window, min_link, max_sets)
+    return scores, link, phase, hap, n_sets, _scored_list(start, orig, mut, scores)
 
 
 class PSAlign:
@@ -285,6 +300,26 @@ class PSAlign:
             hm = d.api.find_point_mutations(d.h) if muts is None else d.api.muts_create(muts)
             try:
                 return _genotypes_on(d.api, d.h, hm, len(self.events), len(self.sequence), grp, G, frac)
+            finally:
+                d.api.muts_destroy(hm)
+
+    def ScoreMutationPhase(self, muts, window=2, min_link=0.0, max_sets=4):
+        """Phase of heterozygous edits (ps_score_mutation_phase): (scores [M], link [M, W], phase [M], hap [E, S], n_sets, scored
+        list).  `muts` is the list of candidate sites — a driver passes its het calls sorted by position; any list is taken and
+        "order" is list order — scored as by ScoreMutations (scores are its bits).  link[m, w - 1] (_capi.EDIT_LINK) compares, over
+        the events that span both, "both alts on one chromosome copy" (cis) with "one alt on each" (trans) for the pair (m, m + w),
+        w = 1 .. window (1 .. 8).  phase[m] (_capi.EDIT_PHASE) is a scan in list order: a site joins the set of the site before
+        it when the vote of its links into that set is not 0 and at least min_link in size (hap -1 / +1: on the other / the same
+        copy as the alt of the set's first site), else it opens a new set.  hap[e, k] (_capi.EVENT_HAP) adds event e's terms over
+        the sites of set k (k < max_sets, 1 .. 8) by their hap: the event is from the first copy where lik1 > lik2.  All three
+        are reduced on the device (k_link, k_phase, k_haptag) and return in one copy; `self` is not modified.  An edit's terms are
+        treated as independent of the other edit of a pair, and everything here is uncalibrated.  util.call_phase turns phase
+        into 0|1 / 1|0 and PS.  ValueError for arguments that do not fit."""
+        W, lim, S = check_phase_args(window, min_link, max_sets)
+        with PSAlign._Data(self) as d:
+            hm = d.api.muts_create(muts)
+            try:
+                return _phase_on(d.api, d.h, hm, len(self.events), len(self.sequence), W, lim, S)
             finally:
                 d.api.muts_destroy(hm)
 

@@ -128,3 +128,35 @@ def random_point_mutations(rng, sequence, n):
             m.orig, m.mut = "", _B[k - 4]
         out.append(m)
     return out
+
+
+def make_diploid_region(length, n_events, seed, swalign, sites, params=None):
+    """A region of a diploid sample: two truths, hap A and hap B, that differ by a substitution at every position of `sites`
+    (ascending, each below length - 4); a draft that carries hap A's base at the even entries of `sites` and hap B's at the odd
+    ones; and n_events reads that alternate A, B, A, ... (event e of make_region(..., draft_error=0, truth=hap A or hap B): the
+    draft has the truths' length, so the reads' alignments hold on it as they are).
+    Returns (draft, events, event haplotypes [n_events] 0 = A / 1 = B, the edit per site — the MutationInfo that turns the draft's
+    base into the other copy's —, its carrier per site: 1 (B) at even entries, 0 (A) at odd ones).  A correct phasing of the edits
+    puts them in one set with hap +1, -1, +1, ... and has lik1 > lik2 exactly for the B reads.  `make_region` is unchanged."""
+    from .util import MutationInfo
+    sites = [int(s) for s in sites]
+    kids = np.random.SeedSequence(seed).spawn(n_events + 2)
+    hap_a = random_sequence(np.random.default_rng(kids[0]), length)
+    rngd = np.random.default_rng(kids[1])
+    b = list(hap_a)
+    for s in sites:
+        b[s] = _B[(_B.index(hap_a[s]) + 1 + int(rngd.integers(0, 3))) % 4]
+    hap_b = "".join(b)
+    ev_a = make_region(length, n_events, seed, swalign, params, draft_error=0, truth=hap_a)[1]
+    ev_b = make_region(length, n_events, seed, swalign, params, draft_error=0, truth=hap_b)[1]
+    events = [ev_b[e] if e % 2 else ev_a[e] for e in range(n_events)]
+    draft = list(hap_a)
+    edits, carrier = [], []
+    for k, s in enumerate(sites):
+        if k % 2:
+            draft[s] = hap_b[s]
+        m = MutationInfo()
+        m.start, m.orig, m.mut = s, draft[s], (hap_a[s] if k % 2 else hap_b[s])
+        edits.append(m)
+        carrier.append(0 if k % 2 else 1)
+    return "".join(draft), events, [e % 2 for e in range(n_events)], edits, carrier

@@ -300,3 +300,141 @@ def call_genotypes(lik, n_cover, ploidy):
         gqs.append(min(99, sorted(pl)[1]))
         pls.append(pl)
     return gts, gqs, pls
+
+
+def check_phase_args(window, min_link, max_sets):
+    """(W, min_link, S) of a phase call; ValueError for a window outside 1 .. 8, max_sets outside 1 .. 8 or a min_link that is negative
+    or not finite (NaN included)"""
+    W, S, v = int(window), int(max_sets), float(min_link)
+    if W != window or not 1 <= W <= 8:
+        raise ValueError("phase: window = %r, allowed are 1 .. 8" % (window,))
+    if S != max_sets or not 1 <= S <= 8:
+        raise ValueError("phase: max_sets = %r, allowed are 1 .. 8" % (max_sets,))
+    if not (v >= 0.0 and v <= 1.7976931348623157e308):
+        raise ValueError("phase: min_link = %r, allowed is a finite value >= 0" % (min_link,))
+    return W, v, S
+
+
+def phase_scan(link, min_link):
+    """The phase scan of ps_score_mutation_phase on link records [M, W] (_capi.EDIT_LINK), in float64 — the rule is defined on the
+    records alone, so this replays a device result bit for bit.  Site 0: vote 0.0, hap +1, set 0.  Site m > 0: vote = 0.0; for
+    w = 1 .. min(W, m) with i = m - w and L = link[i, w - 1]: if set[i] == set[m - 1] and L.n_both > 0, vote += hap[i] * (L.cis -
+    L.trans).  vote != 0 and |vote| >= min_link (a NaN fails both): the site joins set[m - 1] with hap = +1 if vote > 0 else -1;
+    otherwise it opens set[m - 1] + 1 with hap +1.  Returns (phase [M] of _capi.EDIT_PHASE, n_sets)."""
+    import numpy as np
+    from ._capi import EDIT_PHASE
+    link = np.asarray(link)
+    M = link.shape[0]
+    W = link.shape[1] if link.ndim == 2 else 0
+    phase = np.zeros(M, dtype=EDIT_PHASE)
+    if not M:
+        return phase, 0
+    cis, trans, both = link["cis"].tolist(), link["trans"].tolist(), link["n_both"].tolist()
+    hap, sets, votes = [1], [0], [0.0]
+    lim = float(min_link)
+    for m in range(1, M):
+        vote = 0.0
+        for w in range(1, min(W, m) + 1):
+            i = m - w
+            if sets[i] == sets[m - 1] and both[i][w - 1] > 0:
+                vote = vote + hap[i] * (cis[i][w - 1] - trans[i][w - 1])
+        if vote != 0.0 and abs(vote) >= lim:
+            sets.append(sets[m - 1])
+            hap.append(1 if vote > 0 else -1)
+        else:
+            sets.append(sets[m - 1] + 1)
+            hap.append(1)
+        votes.append(vote)
+    phase["vote"], phase["hap"], phase["set"] = votes, hap, sets
+    return phase, sets[-1] + 1
+
+
+def phase_from_deltas(deltas, spans, starts, seq_len, window, min_link, max_sets):
+    """The definition of what ps_score_mutation_phase reduces on the device, in numpy float64 — and the path of a library without the
+    entry point.  deltas [E, M], spans [E, 2], starts [M], seq_len as `support_from_deltas` takes them (cover is its test); window W
+    in 1 .. 8, min_link finite and >= 0, max_sets S in 1 .. 8.
+    Returns (link [M, W] of _capi.EDIT_LINK, phase [M] of _capi.EDIT_PHASE, hap [E, S] of _capi.EVENT_HAP, n_sets):
+      link[m, w - 1]  the pair (m, j = m + w), all zero where j >= M.  Over the events e ascending that cover both, da = delta[e][m],
+                      db = delta[e][j], s = da + db, r = da - db:  cis += (s if s > 0 else 0.0) + log(0.5 + 0.5 exp(-|s|)) — both
+                      alts on one copy —, trans += max(da, db) + log(0.5 + 0.5 exp(-|r|)) — one on each —, n_both counts the events,
+                      n_cis those with both terms > 0 or both < 0, n_trans those with one > 0 and the other < 0.
+      phase           `phase_scan` of the links.
+      hap[e, k]       over the sites m of set k (k < S) that e covers: lik1 / n1 sum and count those with hap +1, lik2 / n2 those
+                      with hap -1; the adds run as the device runs them — partial l = 0.0 plus the terms of m = l, l + 64, ...
+                      ascending, then the 64 partials into 0.0 in order.
+    The model treats an edit's terms as independent of the other edit of a pair; everything derived is uncalibrated."""
+    import numpy as np
+    from ._capi import EDIT_LINK, EVENT_HAP
+    W, lim, S = check_phase_args(window, min_link, max_sets)
+    deltas = np.asarray(deltas, dtype=np.float64)
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    E, M = (deltas.shape[0], starts.size) if deltas.ndim == 2 else (0, starts.size)
+    deltas = deltas.reshape(E, M)
+    spans = np.asarray(spans, dtype=np.int64).reshape(E, 2)
+    col = starts + 1
+    live = starts <= int(seq_len)
+    cover = live[None, :] & (spans[:, :1] <= col[None, :]) & (col[None, :] <= spans[:, 1:])      # [E, M]
+    link = np.zeros((M, W), dtype=EDIT_LINK)
+    with np.errstate(all='ignore'):
+        for w in range(1, W + 1):
+            n = M - w
+            if n <= 0:
+                break
+            cis, trans = np.zeros(n), np.zeros(n)
+            for e in range(E):
+                both = cover[e, :n] & cover[e, w:]
+                if not both.any():
+                    continue
+                da, db = deltas[e, :n][both], deltas[e, w:][both]
+                s, r = da + db, da - db
+                cis[both] = cis[both] + (np.where(s > 0, s, 0.0) + np.log(0.5 + 0.5 * np.exp(-np.abs(s))))
+                trans[both] = trans[both] + (np.where(da > db, da, db) + np.log(0.5 + 0.5 * np.exp(-np.abs(r))))
+                link["n_both"][:n, w - 1][both] += 1
+                link["n_cis"][:n, w - 1][both] += ((da > 0) & (db > 0)) | ((da < 0) & (db < 0))
+                link["n_trans"][:n, w - 1][both] += ((da > 0) & (db < 0)) | ((da < 0) & (db > 0))
+            link["cis"][:n, w - 1], link["trans"][:n, w - 1] = cis, trans
+    phase, n_sets = phase_scan(link, lim)
+    hap = np.zeros((E, S), dtype=EVENT_HAP)
+    rows = (M + 63) // 64
+    pad = rows * 64 - M
+    d = np.pad(deltas, ((0, 0), (0, pad))).reshape(E, rows, 64)
+    for k in range(min(S, n_sets)):
+        for sign, lik, cnt in ((1, "lik1", "n1"), (-1, "lik2", "n2")):
+            member = cover & ((phase["set"] == k) & (phase["hap"] == sign))[None, :]
+            mk = np.pad(member, ((0, 0), (0, pad))).reshape(E, rows, 64)
+            part = np.zeros((E, 64))
+            for row in range(rows):
+                part = part + np.where(mk[:, row], d[:, row], 0.0)      # (+0.0 leaves a sum that began at +0.0 as it is)
+            tot = np.zeros(E)
+            for lane in range(64):
+                tot = tot + part[:, lane]
+            hap[lik][:, k] = tot
+            hap[cnt][:, k] = member.sum(axis=1)
+    return link, phase, hap, n_sets
+
+
+def call_phase(gts, phase, pos=None):
+    """(phased GT strings [M], PS values [M]) from the unphased genotypes of the sites of one phase call and its phase records
+    (_capi.EDIT_PHASE).  A '0/1' site in a phase set of two or more sites becomes '1|0' (hap +1: its alt is on the copy that
+    carries the alt of the set's first site) or '0|1' (hap -1), and its PS is that of the set: pos[first site of the set] — the VCF
+    POS when `pos` holds the sites' POS — or, without `pos`, the first site's index.  A site alone in its set, and every GT that is
+    not '0/1', stays as it is with PS None.  Host only; uncalibrated, like the votes it rests on."""
+    import numpy as np
+    gts = list(gts)
+    phase = np.asarray(phase)
+    if phase.shape != (len(gts),):
+        raise ValueError("call_phase: %d genotypes for %d phase records" % (len(gts), phase.size))
+    sets, haps = phase["set"].tolist(), phase["hap"].tolist()
+    first, size = {}, {}
+    for m, k in enumerate(sets):
+        first.setdefault(k, m)
+        size[k] = size.get(k, 0) + 1
+    out, ps = [], []
+    for m, (gt, k, h) in enumerate(zip(gts, sets, haps)):
+        if gt != '0/1' or size[k] < 2:
+            out.append(gt)
+            ps.append(None)
+            continue
+        out.append('1|0' if h > 0 else '0|1')
+        ps.append(first[k] if pos is None else pos[first[k]])
+    return out, ps
