@@ -293,18 +293,10 @@ int ps_batch_point_table(int32_t n_regions, ps_align* const* a, double* const* t
     PS_TRY(batch_handles(n_regions, a, &as));
     if (n_regions && !n) return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: null position counts");
     std::vector<EditReq> rq(n_regions);
-    for (int i = 0; i < n_regions; i++) {
-        const int64_t have = (int64_t)as[i]->states.size();
-        if (n[i] != have)
-            return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: region " + std::to_string(i) + " was given n = " + std::to_string(n[i]) + ", its sequence has " +
-                                        std::to_string(have) + " positions (length - 4)");
-        rq[i].a = as[i]; rq[i].table = table ? table[i] : nullptr; rq[i].best = best ? best[i] : nullptr;
-    }
-    if (!n_regions) return PS_OK;
-    NEED_RT();
+    for (int i = 0; i < n_regions; i++) { rq[i].a = as[i]; rq[i].table = table ? table[i] : nullptr; rq[i].best = best ? best[i] : nullptr; rq[i].npos_given = n[i]; }
     // ScorePoints (ScoreMutations on FindPointMutations' list, at the scoring width the AlignData carries), reduced on the device to a
     // row per position (k_point_table) instead of a scored list
-    return score_edits(rt, EditKind::Points, rq.data(), rq.size());
+    return score_edits(nullptr, EditKind::Points, rq.data(), rq.size());
 }
 int ps_point_table(ps_align* a, double* table, ps_point_best* best, int64_t n) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_point_table: null handle");
@@ -316,24 +308,11 @@ int ps_batch_score_mutation_support(int32_t n, ps_align* const* a, const ps_muts
     PS_TRY(batch_handles(n, a, &as));
     if (n && (!muts || !n_groups || !group || !support)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_support: null array");
     std::vector<EditReq> rq(n);
-    size_t edits = 0;
     for (int i = 0; i < n; i++) {
-        const std::string who = "ps_score_mutation_support: region " + std::to_string(i);
-        if (!muts[i]) return fail(PS_ERR_BAD_ARG, who + ": null list");
-        if (n_groups[i] < 1 || n_groups[i] > SUPPORT_MAX_GROUPS)
-            return fail(PS_ERR_BAD_ARG, who + ": n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(SUPPORT_MAX_GROUPS));
-        if (!group[i]) return fail(PS_ERR_BAD_ARG, who + ": null group array");
-        if (!support[i]) return fail(PS_ERR_BAD_ARG, who + ": null support array");
-        for (int e = 0; e < as[i]->E; e++)
-            if (group[i][e] < 0 || group[i][e] >= n_groups[i])
-                return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(group[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
         EditReq& q = rq[i];
-        q.a = as[i]; q.muts = &muts[i]->v; q.group = group[i]; q.ngroups = n_groups[i]; q.score = scores ? scores[i] : nullptr; q.rec = support[i];
-        edits += q.muts->size();
+        q.a = as[i]; q.muts = muts[i] ? &muts[i]->v : nullptr; q.group = group[i]; q.ngroups = n_groups[i]; q.score = scores ? scores[i] : nullptr; q.rec = support[i];
     }
-    if (!edits) return PS_OK;   // nothing to score anywhere: no launch
-    NEED_RT();
-    return score_edits(rt, EditKind::Support, rq.data(), rq.size());   // k_support instead of k_reduce behind k_score
+    return score_edits(nullptr, EditKind::Support, rq.data(), rq.size());   // k_support instead of k_reduce behind k_score
 }
 int ps_score_mutation_support(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group, double* scores, ps_edit_support* support) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_score_mutation_support: null handle");
@@ -346,35 +325,12 @@ int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_mu
     PS_TRY(batch_handles(n, a, &as));
     if (n && (!muts || !n_groups || !group || !n_frac || !lik)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_genotypes: null array");
     std::vector<EditReq> rq(n);
-    size_t edits = 0;
     for (int i = 0; i < n; i++) {
-        const std::string who = "ps_score_mutation_genotypes: region " + std::to_string(i);
-        if (!muts[i]) return fail(PS_ERR_BAD_ARG, who + ": null list");
-        if (n_groups[i] < 1 || n_groups[i] > SUPPORT_MAX_GROUPS)
-            return fail(PS_ERR_BAD_ARG, who + ": n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(SUPPORT_MAX_GROUPS));
-        if (!group[i]) return fail(PS_ERR_BAD_ARG, who + ": null group array");
-        for (int e = 0; e < as[i]->E; e++)
-            if (group[i][e] < 0 || group[i][e] >= n_groups[i])
-                return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(group[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
-        if (n_frac[i] < 0 || n_frac[i] > GENO_MAX_FRAC)
-            return fail(PS_ERR_BAD_ARG, who + ": n_frac = " + std::to_string(n_frac[i]) + ", allowed are 0 .. " + std::to_string(GENO_MAX_FRAC));
-        const double* f = alt_frac ? alt_frac[i] : nullptr;
-        if (n_frac[i] > 0 && !f) return fail(PS_ERR_BAD_ARG, who + ": null alt_frac with n_frac = " + std::to_string(n_frac[i]));
-        for (int k = 0; k < n_frac[i]; k++)
-            if (!(f[k] >= 1e-6 && f[k] <= 1.0 - 1e-6)) {   // (NaN fails both comparisons)
-                char msg[96];
-                snprintf(msg, sizeof msg, ": alt_frac[%d] = %g, allowed is 1e-06 .. 1 - 1e-06", k, f[k]);
-                return fail(PS_ERR_BAD_ARG, who + msg);
-            }
-        if (!lik[i]) return fail(PS_ERR_BAD_ARG, who + ": null lik");
         EditReq& q = rq[i];
-        q.a = as[i]; q.muts = &muts[i]->v; q.group = group[i]; q.ngroups = n_groups[i]; q.nfrac = n_frac[i]; q.frac = f;
+        q.a = as[i]; q.muts = muts[i] ? &muts[i]->v : nullptr; q.group = group[i]; q.ngroups = n_groups[i]; q.nfrac = n_frac[i]; q.frac = alt_frac ? alt_frac[i] : nullptr;
         q.score = scores ? scores[i] : nullptr; q.rec = support ? support[i] : nullptr; q.lik = lik[i]; q.ncover = n_cover ? n_cover[i] : nullptr;
-        edits += q.muts->size();
     }
-    if (!edits) return PS_OK;   // nothing to score anywhere: no launch
-    NEED_RT();
-    return score_edits(rt, EditKind::Genotype, rq.data(), rq.size());   // k_genotype behind k_support
+    return score_edits(nullptr, EditKind::Genotype, rq.data(), rq.size());   // k_genotype behind k_support
 }
 int ps_score_mutation_genotypes(ps_align* a, const ps_muts* muts, int32_t n_groups, const int32_t* group, int32_t n_frac, const double* alt_frac,
                                 double* scores, ps_edit_support* support, double* lik, int32_t* n_cover) {
@@ -388,35 +344,13 @@ int ps_batch_score_mutation_phase(int32_t n, ps_align* const* a, const ps_muts* 
     PS_TRY(batch_handles(n, a, &as));
     if (n && (!muts || !window || !min_link || !max_sets || !link || !phase)) return fail(PS_ERR_BAD_ARG, "ps_batch_score_mutation_phase: null array");
     std::vector<EditReq> rq(n);
-    size_t edits = 0;
     for (int i = 0; i < n; i++) {
-        const std::string who = "ps_score_mutation_phase: region " + std::to_string(i);
-        if (!muts[i]) return fail(PS_ERR_BAD_ARG, who + ": null list");
-        if (window[i] < 1 || window[i] > LINK_MAX_WINDOW)
-            return fail(PS_ERR_BAD_ARG, who + ": window = " + std::to_string(window[i]) + ", allowed are 1 .. " + std::to_string(LINK_MAX_WINDOW));
-        if (max_sets[i] < 1 || max_sets[i] > PHASE_MAX_SETS)
-            return fail(PS_ERR_BAD_ARG, who + ": max_sets = " + std::to_string(max_sets[i]) + ", allowed are 1 .. " + std::to_string(PHASE_MAX_SETS));
-        if (!(min_link[i] >= 0.0 && min_link[i] <= 1.7976931348623157e308)) {   // (NaN fails both comparisons)
-            char msg[96];
-            snprintf(msg, sizeof msg, ": min_link = %g, allowed is a finite value >= 0", min_link[i]);
-            return fail(PS_ERR_BAD_ARG, who + msg);
-        }
-        if (!link[i]) return fail(PS_ERR_BAD_ARG, who + ": null link");
-        if (!phase[i]) return fail(PS_ERR_BAD_ARG, who + ": null phase");
         EditReq& q = rq[i];
-        q.a = as[i]; q.muts = &muts[i]->v; q.window = window[i]; q.min_link = min_link[i]; q.max_sets = max_sets[i];
+        q.a = as[i]; q.muts = muts[i] ? &muts[i]->v : nullptr; q.window = window[i]; q.min_link = min_link[i]; q.max_sets = max_sets[i];
         q.score = scores ? scores[i] : nullptr; q.link = link[i]; q.phase = phase[i];
         q.hap = hap ? hap[i] : nullptr; q.nsets = n_sets ? n_sets[i] : nullptr;
-        edits += q.muts->size();
     }
-    for (EditReq& q : rq)
-        if (q.muts->empty()) {   // no site: no set, and no event is tagged (no kernel sees this AlignData)
-            if (q.nsets) *q.nsets = 0;
-            if (q.hap) memset(q.hap, 0, (size_t)q.a->E * q.max_sets * sizeof(ps_event_hap));
-        }
-    if (!edits) return PS_OK;   // nothing to score anywhere: no launch
-    NEED_RT();
-    return score_edits(rt, EditKind::Phase, rq.data(), rq.size());   // k_link, k_phase and k_haptag behind k_score
+    return score_edits(nullptr, EditKind::Phase, rq.data(), rq.size());   // k_link, k_phase and k_haptag behind k_score
 }
 int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, double min_link, int32_t max_sets, double* scores,
                             ps_edit_link* link, ps_edit_phase* phase, ps_event_hap* hap, int32_t* n_sets) {

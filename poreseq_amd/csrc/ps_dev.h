@@ -1,4 +1,4 @@
-// ps_dev.h — device-side helpers shared by the kernel files (ps_kernels.hip, ps_sweep.hip): band arithmetic, the emission
+// ps_dev.h — device-side helpers shared by the kernel files (ps_kernels.hip, ps_edit.hip, ps_sweep.hip): band arithmetic, the emission
 // log-density with its exact quotients, address-space and wave-uniform helpers.  See ps_kernels.hip for the reference citations.
 #ifndef PS_DEV_H_
 #define PS_DEV_H_

@@ -3,7 +3,7 @@
 // (cpp/MakeMutations.cpp, cpp/EventUtil.cpp): ScoreAlignments and MakeMutations.  ScoreMutations and its reductions — the edit-scoring
 // chain — are in ps_score.cpp, the edit plans in ps_editplan.h, FindMutations in ps_find.cpp.  The runtime, its streams and par_for
 // are in ps_runtime.cpp; device memory — pools, shares, slabs, the AlignData slab cache — in ps_mem.cpp, its arithmetic in ps_plan.h.
-// All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_sw.hip,
+// All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_edit.hip, ps_sw.hip,
 // ps_viterbi.hip); there is no CPU implementation of it in this library.
 #include "ps_host.h"
 #include "ps_sane.h"

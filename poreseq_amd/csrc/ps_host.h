@@ -189,20 +189,20 @@ int align_slab_take(Runtime* rt, size_t bytes, void** out, size_t* cap);   // an
 void align_slab_give(void* slab, size_t cap, void* last_stream);           // and back to it (or freed)
 int make_mutations_multi(Runtime* rt, const std::vector<Align*>& as, std::vector<std::vector<Mut>> muts, std::vector<int>* nbases);
 // One AlignData of an edit-scoring call (ps_score.cpp): its handle, its edit list and, of the outputs below, those the call's EditKind
-// means — host arrays, null where the caller does not want one.  A lock-step call is an array of these; a sub-batch (a call cut to
+// means — host arrays, null where the caller does not want one; score_edits checks the ranges and the required ones.  A lock-step call is an array of these; a sub-batch (a call cut to
 // fit the share, or halved because its bands came out wider than guessed) is a sub-range of the same array.
 struct EditReq {
     Align* a = nullptr;
     const std::vector<Mut>* muts = nullptr;   // the list to score (Points: FindPointMutations', made by score_edits into `own`)
     // List: the scored copy of the list, and [E][M] every event's term of every edit's score (optional)
     std::vector<Mut>* out = nullptr; double* delta = nullptr;
-    // Points: [states][9] rows and [states] per-position records (either may be null)
-    double* table = nullptr; ps_point_best* best = nullptr;
-    // Support, Genotype: [E] group ids below ngroups (checked by the caller), [M] scores (optional), [M][ngroups] records (Genotype: optional)
+    // Points: [states][9] rows and [states] per-position records (either may be null), the position count the caller sized them for
+    double* table = nullptr; ps_point_best* best = nullptr; int64_t npos_given = 0;
+    // Support, Genotype: [E] group ids below ngroups, [M] scores (optional), [M][ngroups] records (Genotype: optional)
     const int32_t* group = nullptr; int ngroups = 0; double* score = nullptr; ps_edit_support* rec = nullptr;
-    // Genotype: [nfrac] alt fractions (checked by the caller), [M][nfrac + 1] likelihoods, [M] covering-event counts (optional)
+    // Genotype: [nfrac] alt fractions, [M][nfrac + 1] likelihoods, [M] covering-event counts (optional)
     int nfrac = 0; const double* frac = nullptr; double* lik = nullptr; int32_t* ncover = nullptr;
-    // Phase: window, vote threshold and tagged sets (checked by the caller), [M] scores (`score`, optional), [M][window] links, [M]
+    // Phase: window, vote threshold and tagged sets, [M] scores (`score`, optional), [M][window] links, [M]
     // phase records, [E][max_sets] event records (optional), the number of sets (optional)
     int window = 0; double min_link = 0.0; int max_sets = 0;
     ps_edit_link* link = nullptr; ps_edit_phase* phase = nullptr; ps_event_hap* hap = nullptr; int32_t* nsets = nullptr;
@@ -211,7 +211,8 @@ struct EditReq {
     std::vector<Mut> own;
     std::vector<int> pos_first, pos_triv;
 };
-// ScoreMutations (cpp/MakeMutations.cpp:23-69) and its reductions for reqs[0 .. n - 1] in one launch chain
+// ScoreMutations (cpp/MakeMutations.cpp:23-69) and its reductions for reqs[0 .. n - 1] in one launch chain (rt: null for a reduction,
+// whose runtime is taken once its arguments are checked and there is an edit to score)
 int score_edits(Runtime* rt, EditKind kind, EditReq* reqs, size_t n);
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);

@@ -217,7 +217,7 @@ struct LikeGroup {
 // the runtime BatchD.fastdiv as a kernel's template argument: launch(std::true_type / std::false_type)
 template <class F> void with_fastdiv(int fastdiv, F&& launch) { if (fastdiv) launch(std::true_type()); else launch(std::false_type()); }
 
-// ---- kernel launchers (ps_kernels.hip) ------------------------------------------------------
+// ---- kernel launchers (ps_kernels.hip; launch_score: ps_edit.hip) ------------------------------------------------------
 int launch_updaterefs(Runtime* rt, const BatchD& b);
 int launch_lb(Runtime* rt, const BatchD& b, int which /*0: lb_off, 1: lbn_off*/, int maxlbn);
 int launch_lo(Runtime* rt, const BatchD& b, int ndir, int64_t maxS);

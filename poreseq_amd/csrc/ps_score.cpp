@@ -3,13 +3,14 @@
 // het edits.  One call is
 // an array of EditReq records (ps_host.h) of one EditKind; it runs as named stages over a Chain, and a call that has to be cut runs
 // the same stages over sub-ranges of the same array.  The edit plans are host arithmetic in ps_editplan.h, the kernels and
-// launch_score in ps_kernels.hip.  Also here: FindPointMutations and the `likes` loop of ScoreAlignments.
+// launch_score in ps_edit.hip.  Also here: FindPointMutations and the `likes` loop of ScoreAlignments.
 #include "ps_host.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 namespace ps {
 
@@ -34,18 +35,61 @@ void find_point_mutations(const Align* a, std::vector<Mut>* out) {
 }
 
 namespace {
+// ---- the output plan.  What a call returns besides the scored list, by name; which of them a kind has is kind_outputs()
+enum Out { O_SCORE, O_BEST, O_TABLE, O_REC, O_LIK, O_NCOVER, O_LINK, O_PHASE, O_HAP, O_NSETS, O_COUNT };
+// the caller's array for one of them (null: not wanted, or not of this kind) ...
+void* out_host(const EditReq& q, Out o) {
+    void* const h[O_COUNT] = {q.score, q.best, q.table, q.rec, q.lik, q.ncover, q.link, q.phase, q.hap, q.nsets};
+    return h[o];
+}
+// ... and its size — the one statement of it (include/poreseq_hip.h documents the same shapes): the layout, the descriptors, the
+// copy back and the values written without a kernel all come here
+size_t out_bytes(const EditReq& q, Out o) {
+    const size_t M = q.muts->size(), E = (size_t)q.a->E, npos = q.pos_triv.size();
+    switch (o) {
+    case O_SCORE: return M * sizeof(double);
+    case O_BEST: return npos * sizeof(ps_point_best);
+    case O_TABLE: return npos * PT_SLOTS * sizeof(double);
+    case O_REC: return M * q.ngroups * sizeof(ps_edit_support);
+    case O_LIK: return M * (q.nfrac + 1) * sizeof(double);
+    case O_NCOVER: return M * sizeof(int32_t);
+    case O_LINK: return M * q.window * sizeof(ps_edit_link);
+    case O_PHASE: return M * sizeof(ps_edit_phase);
+    case O_HAP: return E * q.max_sets * sizeof(ps_event_hap);
+    case O_NSETS: return sizeof(int32_t);
+    case O_COUNT: break;
+    }
+    return 0;
+}
+std::vector<Out> kind_outputs(EditKind kind) {
+    switch (kind) {
+    case EditKind::Points: return {O_BEST, O_TABLE};
+    case EditKind::Support: return {O_SCORE, O_REC};
+    case EditKind::Genotype: return {O_SCORE, O_REC, O_LIK, O_NCOVER};
+    case EditKind::Phase: return {O_SCORE, O_LINK, O_PHASE, O_HAP, O_NSETS};
+    case EditKind::List: break;
+    }
+    return {};
+}
+// Does one of its kind's outputs get a segment on the device?  `live`: the AlignData has events and edits, the kernels have
+// something to score.  A point-table call's rows and records: where wanted.  The scores of a support or genotype call: always
+// (k_support or k_genotype writes them, wanted or not); of a phase call: where wanted.  Support and event records: where wanted.
+bool out_present(EditKind kind, const EditReq& q, bool live, Out o) {
+    switch (o) {
+    case O_BEST: case O_TABLE: return out_host(q, o) && q.a->E;
+    case O_SCORE: return live && (kind != EditKind::Phase || q.score);
+    case O_REC: case O_HAP: return live && out_host(q, o);
+    default: return live;
+    }
+}
 // Where one AlignData's results lie on the device — the one statement of it: the descriptors point there and the copy back reads
-// from there.  `score`: doubles into the score block at the head of "mutdbl" (every kind).  The others: bytes into the call's own
-// output buffer ("ptable" or "support"), valid where the flag beside them is set.
+// from there.  `score`: doubles into the score block at the head of "mutdbl" (every kind).  `seg`: the outputs above, bytes into
+// the call's own output buffer ("ptable", "support" or "phase"); `host` may be null where the device writes one nobody asked for.
+struct OutSeg { bool on = false; void* host = nullptr; size_t bytes = 0, at = 0; };
 struct OutAt {
-    bool live = false;        // it has events and edits: the kernels have something to score
+    bool live = false;
     size_t score = 0;
-    bool has_best = false, has_table = false;   // Points
-    size_t best = 0, table = 0;
-    bool has_rec = false;                       // Support, Genotype (sscore with `live`; lik, ncover with `live` of a genotype call)
-    size_t sscore = 0, rec = 0, lik = 0, ncover = 0;
-    bool has_score = false, has_hap = false;    // Phase (link, phase, nsets with `live`)
-    size_t link = 0, phase = 0, hap = 0, nsets = 0;
+    OutSeg seg[O_COUNT];
 };
 
 // the tables of all AlignData on their way into "mutint": push() appends one and answers where it will lie on the device
@@ -84,8 +128,6 @@ struct Chain {
     bool geno() const { return kind == EditKind::Genotype; }
     bool phase() const { return kind == EditKind::Phase; }
 };
-}  // namespace
-
 // ---- stage: columns.  Which columns of the score matrices will the edit lists read?  A short list (FindMutations' found edits, the
 // rounds of MakeMutations' recursion: tens to hundreds of edits per region) reads a few percent of them: the fills then run as strip
 // sweeps that keep those columns only (ps_sweep.hip, k_sweeps) — a few MB per alignment instead of 2 x 110 MB.  A list that
@@ -152,31 +194,24 @@ static void build_jobs(Chain& c) {
     }
 }
 
-// An AlignData without events has every score at its seed, -1e-6 (score_mutations): a point-table call's rows say so, a support
-// call's records are all zero, a genotype call's likelihoods and covering-event counts too, and a phase call gets what its rules give
-// for all-zero links: every site a set of its own.  No kernel sees it; written here.
-static void write_eventless(const Chain& c) {
-    for (int k = 0; k < c.R; k++) {
-        const EditReq& q = c.r[k];
-        if (q.a->E) continue;
-        const size_t M = (size_t)q.plan.M;
-        if (c.points()) point_rows_seed(q.pos_triv, q.table, q.best);
-        if (c.support()) {
-            if (q.score) std::fill(q.score, q.score + M, -1e-6);
-            if (q.rec) memset(q.rec, 0, M * q.ngroups * sizeof(ps_edit_support));
-        }
-        if (c.geno()) {
-            std::fill(q.lik, q.lik + M * (q.nfrac + 1), 0.0);
-            if (q.ncover) std::fill(q.ncover, q.ncover + M, 0);
-        }
-        if (c.phase()) {
-            if (q.score) std::fill(q.score, q.score + M, -1e-6);
-            memset(q.link, 0, M * q.window * sizeof(ps_edit_link));
-            for (size_t m = 0; m < M; m++) { q.phase[m].vote = 0.0; q.phase[m].hap = 1; q.phase[m].set = (int32_t)m; }
-            if (q.nsets) *q.nsets = (int32_t)M;   // (hap has no rows)
-        }
+// Values no kernel writes, for every AlignData no kernel sees.  One without events has every score at its seed, -1e-6
+// (score_mutations): a point-table call's rows say so, a support call's records are all zero, a genotype call's likelihoods and
+// covering-event counts too, and a phase call gets what its rules give for all-zero links: every site a set of its own.  One with
+// events and an empty list has arrays of no length to write — except a phase call's: no site, no set, and no event is tagged.
+void write_unseen(EditKind kind, EditReq* r, size_t n) {
+    auto zero = [](const EditReq& q, Out o) { if (void* h = out_host(q, o)) memset(h, 0, out_bytes(q, o)); };
+    for (size_t k = 0; k < n; k++) {
+        const EditReq& q = r[k];
+        const size_t M = q.muts->size();
+        if (M && q.a->E) continue;
+        if (kind == EditKind::Points) { if (!q.a->E) point_rows_seed(q.pos_triv, q.table, q.best); continue; }
+        if (q.score) std::fill(q.score, q.score + out_bytes(q, O_SCORE) / sizeof(double), -1e-6);
+        for (Out o : {O_REC, O_LIK, O_NCOVER, O_LINK, O_HAP}) zero(q, o);
+        if (q.phase) for (size_t m = 0; m < M; m++) { q.phase[m].vote = 0.0; q.phase[m].hap = 1; q.phase[m].set = (int32_t)m; }
+        if (q.nsets) *q.nsets = (int32_t)M;
     }
 }
+}  // namespace
 
 // ---- stage: realign.  Takes the slab of a call on full matrices, builds the batch and enqueues the fills, so that they run while
 // the host prepares the edit tables.  PS_SPLIT: the bands came out wider than guessed and nothing was launched.
@@ -203,47 +238,24 @@ static int take_slab_and_realign(Chain& c) {
 }
 
 // ---- stage: output layout.  Every AlignData's score array back to back at the head of "mutdbl": ONE device-to-host copy returns
-// them all (a copy per region before: 20 000 of a bench step's 25 000 copy commands, ~0.2 ms each on a loaded stream).  A point-table
-// call: the records, then the rows, of all AlignData back to back in one buffer; a support call: the scores, then the records; a
-// genotype call's likelihoods and covering-event counts follow them in the same buffer; a phase call: the scores, the links, the
-// phase records, the event records and the set counts — ONE copy back each.
+// them all (a copy per region before: 20 000 of a bench step's 25 000 copy commands, ~0.2 ms each on a loaded stream).  A call
+// with outputs of its own (kind_outputs) gets them in one buffer, AlignData by AlignData, every segment on a multiple of 8 bytes —
+// ONE copy back.
 static void lay_out(Chain& c) {
-    const int R = c.R;
-    c.at.assign(R, OutAt());
-    size_t& n = c.out_bytes;
-    auto take = [&](size_t* at, size_t bytes) { *at = n; n += bytes; };
-    for (int k = 0; k < R; k++) {
+    c.at.assign(c.R, OutAt());
+    const std::vector<Out> outs = kind_outputs(c.kind);
+    for (int k = 0; k < c.R; k++) {
         const EditReq& q = c.r[k];
         OutAt& o = c.at[k];
         o.live = q.plan.M > 0 && q.a->E > 0;
         o.score = c.score_tot; c.score_tot += (size_t)std::max(q.plan.M, 1);
-        o.has_best = c.points() && q.best && q.a->E;
-        o.has_table = c.points() && q.table && q.a->E;
-        o.has_rec = c.support() && o.live && q.rec;
-    }
-    for (int k = 0; k < R; k++) if (c.at[k].has_best) take(&c.at[k].best, c.r[k].pos_triv.size() * sizeof(ps_point_best));
-    for (int k = 0; k < R; k++) if (c.at[k].has_table) take(&c.at[k].table, c.r[k].pos_triv.size() * PT_SLOTS * sizeof(double));
-    if (c.phase()) {
-        for (int k = 0; k < R; k++) {
-            const EditReq& q = c.r[k];
-            OutAt& o = c.at[k];
-            if (!o.live) continue;
-            const size_t M = (size_t)q.plan.M;
-            o.has_score = q.score != nullptr; o.has_hap = q.hap != nullptr;
-            if (o.has_score) take(&o.sscore, M * sizeof(double));
-            take(&o.link, M * q.window * sizeof(ps_edit_link));
-            take(&o.phase, M * sizeof(ps_edit_phase));
-            if (o.has_hap) take(&o.hap, (size_t)q.a->E * q.max_sets * sizeof(ps_event_hap));
-            take(&o.nsets, 8);   // (one int32; the next double stays aligned)
+        for (Out x : outs) {
+            if (!out_present(c.kind, q, o.live, x)) continue;
+            OutSeg& s = o.seg[x];
+            s.on = true; s.host = out_host(q, x); s.bytes = out_bytes(q, x); s.at = c.out_bytes;
+            c.out_bytes += (s.bytes + 7) / 8 * 8;
         }
-        return;
     }
-    if (!c.support()) return;
-    for (int k = 0; k < R; k++) if (c.at[k].live) take(&c.at[k].sscore, (size_t)c.r[k].plan.M * sizeof(double));
-    for (int k = 0; k < R; k++) if (c.at[k].has_rec) take(&c.at[k].rec, (size_t)c.r[k].plan.M * c.r[k].ngroups * sizeof(ps_edit_support));
-    if (!c.geno()) return;
-    for (int k = 0; k < R; k++) if (c.at[k].live) take(&c.at[k].lik, (size_t)c.r[k].plan.M * (c.r[k].nfrac + 1) * sizeof(double));
-    for (int k = 0; k < R; k++) if (c.at[k].live) take(&c.at[k].ncover, (size_t)c.r[k].plan.M * sizeof(int32_t));
 }
 
 // ---- stage: descriptors.  One AlignData's ScoreArgs: its tables into `st`, its arrays carved off "mutdbl" at *dd.  (The oldall
@@ -270,68 +282,74 @@ static int fill_score_args(Chain& c, int k, IntStage& st, double** dd) {
     return PS_OK;
 }
 
-// the record a point-table, support or genotype call keeps beside one AlignData's ScoreArgs
+// the records a call's kind keeps beside one AlignData's ScoreArgs; their output pointers come from the plan, null where a segment is absent
 static void fill_kind_args(Chain& c, int k, IntStage& st) {
     const EditReq& r = c.r[k];
     const OutAt& o = c.at[k];
-    if (c.points()) {
+    auto dev = [&](Out x) -> char* { return o.seg[x].on ? c.d_out + o.seg[x].at : nullptr; };
+    if (c.kind == EditKind::Points) {
         PointArgs& q = c.L.pts[k];
         memset(&q, 0, sizeof(q));
         q.pos_first = st.push(r.pos_first); q.pos_triv = st.push(r.pos_triv); q.npos = (int)r.pos_triv.size();
-        if (o.has_table) q.table = (double*)(c.d_out + o.table);
-        if (o.has_best) q.best = (ps_point_best*)(c.d_out + o.best);
+        q.table = (double*)dev(O_TABLE); q.best = (ps_point_best*)dev(O_BEST);
         if (!q.table && !q.best) q.npos = 0;
     }
-    if (c.support()) {
+    if (c.kind == EditKind::Support || c.kind == EditKind::Genotype) {
         SupportArgs& q = c.L.sps[k];
         memset(&q, 0, sizeof(q));
         q.group = st.push(std::vector<int>(r.group, r.group + r.a->E));
-        if (o.has_rec) { q.ngroups = r.ngroups; q.score = (double*)(c.d_out + o.sscore); q.out = (ps_edit_support*)(c.d_out + o.rec); }
+        if (o.seg[O_REC].on) { q.ngroups = r.ngroups; q.score = (double*)dev(O_SCORE); q.out = (ps_edit_support*)dev(O_REC); }
     }
-    if (c.geno()) {
+    if (c.kind == EditKind::Genotype) {
         GenoArgs& q = c.L.gts[k];
         memset(&q, 0, sizeof(q));
         q.nfrac = -1;
         if (o.live) {
             q.nfrac = r.nfrac;
             for (int i = 0; i < q.nfrac; i++) { q.f[i] = r.frac[i]; q.g[i] = 1.0 - q.f[i]; }
-            if (!o.has_rec) q.score = (double*)(c.d_out + o.sscore);   // (k_support writes nothing for this AlignData)
-            q.lik = (double*)(c.d_out + o.lik); q.ncover = (int*)(c.d_out + o.ncover);
+            if (!o.seg[O_REC].on) q.score = (double*)dev(O_SCORE);   // (k_support writes nothing for this AlignData)
+            q.lik = (double*)dev(O_LIK); q.ncover = (int*)dev(O_NCOVER);
         }
     }
-    if (c.phase()) {
+    if (c.kind == EditKind::Phase) {
         PhaseArgs& q = c.L.phs[k];
         memset(&q, 0, sizeof(q));
         if (o.live) {
             q.W = r.window; q.S = r.max_sets; q.min_link = r.min_link;
-            if (o.has_score) q.score = (double*)(c.d_out + o.sscore);
-            q.link = (ps_edit_link*)(c.d_out + o.link); q.phase = (ps_edit_phase*)(c.d_out + o.phase);
-            if (o.has_hap) q.hap = (ps_event_hap*)(c.d_out + o.hap);
-            q.nsets = (int*)(c.d_out + o.nsets);
+            q.score = (double*)dev(O_SCORE); q.link = (ps_edit_link*)dev(O_LINK); q.phase = (ps_edit_phase*)dev(O_PHASE);
+            q.hap = (ps_event_hap*)dev(O_HAP); q.nsets = (int*)dev(O_NSETS);
         }
     }
 }
 
-// the edit tables and their descriptors (ScoreArgs, behind the tables in the same buffer) in one copy
-static int upload_descriptors(Chain& c, const IntStage& st) {
-    ScoreLaunch& L = c.L;
-    const size_t sa_at = (st.h.size() * sizeof(int) + 63) / 64 * 64;
-    const size_t pt_at = (sa_at + (size_t)c.R * sizeof(ScoreArgs) + 63) / 64 * 64;   // (a point-table call: its PointArgs behind them; a phase call: its PhaseArgs)
-    const size_t gt_at = (pt_at + L.sps.size() * sizeof(SupportArgs) + 63) / 64 * 64;   // (a genotype call: its GenoArgs behind the SupportArgs)
-    std::vector<char> blob(std::max({pt_at + L.pts.size() * sizeof(PointArgs), gt_at + L.gts.size() * sizeof(GenoArgs), pt_at + L.phs.size() * sizeof(PhaseArgs)}));   // (PointArgs, SupportArgs or PhaseArgs: one of them)
+// The record arrays of a call, sized for R AlignData: its ScoreArgs and what its kind keeps beside them — nothing (List), one array,
+// or two (Genotype: SupportArgs and GenoArgs).  Per array: where it lies on the host, its bytes, and how launch_score is told where
+// its copy lies on the device.
+struct RecArray { const void* host; size_t bytes; std::function<void(const char*)> placed; };
+template <class T> static RecArray rec_array(std::vector<T>& h, const T** d, int R) {
+    h.resize(R);
+    return {h.data(), (size_t)R * sizeof(T), [d](const char* at) { *d = (const T*)at; }};
+}
+static std::vector<RecArray> record_arrays(ScoreLaunch& L, int R) {
+    std::vector<RecArray> v = {rec_array(L.sas, &L.d_sas, R)};
+    if (L.kind == EditKind::Points) v.push_back(rec_array(L.pts, &L.d_pts, R));
+    if (L.kind == EditKind::Support || L.kind == EditKind::Genotype) v.push_back(rec_array(L.sps, &L.d_sps, R));
+    if (L.kind == EditKind::Genotype) v.push_back(rec_array(L.gts, &L.d_gts, R));
+    if (L.kind == EditKind::Phase) v.push_back(rec_array(L.phs, &L.d_phs, R));
+    return v;
+}
+static size_t align64(size_t n) { return (n + 63) / 64 * 64; }
+
+// the edit tables and their descriptors (the record arrays, each on a multiple of 64 bytes behind the tables in the same buffer) in one copy
+static int upload_descriptors(Chain& c, const IntStage& st, const std::vector<RecArray>& recs) {
+    std::vector<size_t> at;
+    size_t end = st.h.size() * sizeof(int);
+    for (const RecArray& p : recs) { at.push_back(align64(end)); end = at.back() + p.bytes; }
+    std::vector<char> blob(end);   // (sized once: the tables of a Refine-sized call are tens of MB)
     memcpy(blob.data(), st.h.data(), st.h.size() * sizeof(int));
-    memcpy(blob.data() + sa_at, L.sas.data(), (size_t)c.R * sizeof(ScoreArgs));
-    if (c.points()) memcpy(blob.data() + pt_at, L.pts.data(), L.pts.size() * sizeof(PointArgs));
-    if (c.support()) memcpy(blob.data() + pt_at, L.sps.data(), L.sps.size() * sizeof(SupportArgs));
-    if (c.geno()) memcpy(blob.data() + gt_at, L.gts.data(), L.gts.size() * sizeof(GenoArgs));
-    if (c.phase()) memcpy(blob.data() + pt_at, L.phs.data(), L.phs.size() * sizeof(PhaseArgs));
+    for (size_t i = 0; i < recs.size(); i++) memcpy(blob.data() + at[i], recs[i].host, recs[i].bytes);
     PS_TRY(c.rt->up(st.dp, blob.data(), blob.size()));
-    const char* base = (const char*)st.dp;
-    L.d_sas = (const ScoreArgs*)(base + sa_at);
-    L.d_pts = c.points() ? (const PointArgs*)(base + pt_at) : nullptr;
-    L.d_sps = c.support() ? (const SupportArgs*)(base + pt_at) : nullptr;
-    L.d_gts = c.geno() ? (const GenoArgs*)(base + gt_at) : nullptr;
-    L.d_phs = c.phase() ? (const PhaseArgs*)(base + pt_at) : nullptr;
+    for (size_t i = 0; i < recs.size(); i++) recs[i].placed((const char*)st.dp + at[i]);
     return PS_OK;
 }
 
@@ -343,35 +361,32 @@ static int stage_descriptors(Chain& c) {
         const EditPlan& p = c.r[k].plan;
         const size_t E = (size_t)c.r[k].a->E;
         ints += (size_t)p.M * 7 + (size_t)p.M * p.ncolmax + p.nr0 + 16;
-        if (c.points()) ints += c.r[k].pos_first.size() + c.r[k].pos_triv.size();
-        if (c.support()) ints += E;
+        ints += c.r[k].pos_first.size() + c.r[k].pos_triv.size() + E;   // (a point-table call's position tables, a support or genotype call's group ids)
         dbls += E * std::max(p.nr0, 1) + E * std::max(p.M, 1) + std::max(p.M, 1) + E * (c.r[k].a->states.size() + 8);
     }
+    const std::vector<RecArray> recs = record_arrays(c.L, R);
+    size_t desc = align64(ints * sizeof(int));
+    for (const RecArray& a : recs) desc += align64(a.bytes);
     DBuf& mb = c.rt->buf("mutint");
-    PS_TRY(mb.ensure(ints * sizeof(int) + 128 + (size_t)R * (sizeof(ScoreArgs) + std::max({sizeof(PointArgs), sizeof(SupportArgs), sizeof(PhaseArgs)}) + sizeof(GenoArgs)) + 64));
+    PS_TRY(mb.ensure(desc));
     DBuf& db = c.rt->buf("mutdbl");
     PS_TRY(db.ensure(dbls * sizeof(double)));
     c.score0 = db.as<double>();
     double* dd = c.score0 + c.score_tot;
-    if (c.points() || c.support() || c.phase()) {
-        DBuf& ob = c.rt->buf(c.points() ? "ptable" : c.phase() ? "phase" : "support");
+    if (const char* name = c.points() ? "ptable" : c.phase() ? "phase" : c.support() ? "support" : nullptr) {
+        DBuf& ob = c.rt->buf(name);
         PS_TRY(ob.ensure(std::max<size_t>(c.out_bytes, 16)));
         c.d_out = ob.as<char>();
     }
     IntStage st;
     st.dp = mb.as<int>();
     st.h.reserve(ints);
-    c.L.sas.resize(R);
-    c.L.pts.resize(c.points() ? R : 0);
-    c.L.sps.resize(c.support() ? R : 0);
-    c.L.gts.resize(c.geno() ? R : 0);
-    c.L.phs.resize(c.phase() ? R : 0);
     for (int k = 0; k < R; k++) {
         PS_TRY(fill_score_args(c, k, st, &dd));
         fill_kind_args(c, k, st);
         if (!c.at[k].live) { c.L.sas[k].njobs = 0; c.L.sas[k].nitems_per_job = 0; }   // nothing to score for this AlignData: its blocks leave at once
     }
-    return upload_descriptors(c, st);
+    return upload_descriptors(c, st, recs);
 }
 
 // ---- stage: launch.  The lb tables of the new alignment, the profile's traffic model, the scoring kernels
@@ -392,55 +407,15 @@ static int launch(Chain& c) {
     return launch_score(c.rt, c.b.d, c.L);
 }
 
-// ---- stage: fetch, one routine per kind.  The output buffer of a point-table, support or genotype call comes back in one copy
-static int fetch_block(Chain& c, char** h) {
-    *h = nullptr;
-    if (c.out_bytes) PS_TRY(c.rt->down((void**)h, c.d_out, c.out_bytes));
+// ---- stage: fetch.  The output buffer of a call that has one comes back in one copy, and every segment of the plan that the
+// caller wants goes to its array; a scored list comes back from the score block (fetch_list)
+static int fetch_outputs(Chain& c) {
+    char* h = nullptr;
+    if (c.out_bytes) PS_TRY(c.rt->down((void**)&h, c.d_out, c.out_bytes));
     PS_HIP(hipStreamSynchronize(c.rt->stream));
-    return PS_OK;
-}
-static int fetch_points(Chain& c) {
-    char* h = nullptr;
-    PS_TRY(fetch_block(c, &h));
-    for (int k = 0; k < c.R; k++) {
-        const EditReq& q = c.r[k];
-        const size_t npos = q.pos_triv.size();
-        if (!npos) continue;
-        if (c.at[k].has_best) memcpy(q.best, h + c.at[k].best, npos * sizeof(ps_point_best));
-        if (c.at[k].has_table) memcpy(q.table, h + c.at[k].table, npos * PT_SLOTS * sizeof(double));
-    }
-    return PS_OK;
-}
-static int fetch_support(Chain& c) {
-    char* h = nullptr;
-    PS_TRY(fetch_block(c, &h));
-    for (int k = 0; k < c.R; k++) {
-        const EditReq& q = c.r[k];
-        const OutAt& o = c.at[k];
-        const size_t M = (size_t)q.plan.M;
-        if (!o.live) continue;
-        if (q.score) memcpy(q.score, h + o.sscore, M * sizeof(double));
-        if (q.rec) memcpy(q.rec, h + o.rec, M * q.ngroups * sizeof(ps_edit_support));
-        if (!c.geno()) continue;
-        memcpy(q.lik, h + o.lik, M * (q.nfrac + 1) * sizeof(double));
-        if (q.ncover) memcpy(q.ncover, h + o.ncover, M * sizeof(int32_t));
-    }
-    return PS_OK;
-}
-static int fetch_phase(Chain& c) {
-    char* h = nullptr;
-    PS_TRY(fetch_block(c, &h));
-    for (int k = 0; k < c.R; k++) {
-        const EditReq& q = c.r[k];
-        const OutAt& o = c.at[k];
-        const size_t M = (size_t)q.plan.M;
-        if (!o.live) continue;
-        if (o.has_score) memcpy(q.score, h + o.sscore, M * sizeof(double));
-        memcpy(q.link, h + o.link, M * q.window * sizeof(ps_edit_link));
-        memcpy(q.phase, h + o.phase, M * sizeof(ps_edit_phase));
-        if (o.has_hap) memcpy(q.hap, h + o.hap, (size_t)q.a->E * q.max_sets * sizeof(ps_event_hap));
-        if (q.nsets) memcpy(q.nsets, h + o.nsets, sizeof(int32_t));
-    }
+    for (const OutAt& o : c.at)
+        for (const OutSeg& s : o.seg)
+            if (s.on && s.host) memcpy(s.host, h + s.at, s.bytes);
     return PS_OK;
 }
 static int fetch_list(Chain& c) {
@@ -480,7 +455,7 @@ static int run_chain(Runtime* rt, EditKind kind, EditReq* r, size_t n) {
     if (!c.sparse && over_share(n, 2, need)) return in_share_chunks(n, 2, need, sub);   // sub-batches that fit a slab
     PS_TRY(upload_keep(c));
     build_jobs(c);
-    write_eventless(c);
+    write_unseen(kind, r, n);
     if (c.specs.empty()) return PS_OK;
     {
         const int rc = take_slab_and_realign(c);
@@ -497,13 +472,74 @@ static int run_chain(Runtime* rt, EditKind kind, EditReq* r, size_t n) {
     if (c.tk.on) { PS_HIP(hipStreamSynchronize(rt->stream)); }
     c.tk.lap("realign fwd+back (rest)");
     PS_TRY(launch(c));
-    PS_TRY(kind == EditKind::Points ? fetch_points(c) : c.support() ? fetch_support(c) : c.phase() ? fetch_phase(c) : fetch_list(c));
+    PS_TRY(kind == EditKind::List ? fetch_list(c) : fetch_outputs(c));
     c.tk.lap("score edits");
     return PS_OK;
 }
 
-// One edit-scoring call: sizes every list, checks the arguments — here, once, for every kind — and runs the chain.
+// ---- argument checks of one AlignData of a point-table, support, genotype or phase call (`i`: its place in the call), in the order
+// the C ABI reports them
+static int check_groups(const EditReq& q, const std::string& who, bool need_records) {
+    if (q.ngroups < 1 || q.ngroups > SUPPORT_MAX_GROUPS)
+        return fail(PS_ERR_BAD_ARG, who + ": n_groups = " + std::to_string(q.ngroups) + ", allowed are 1 .. " + std::to_string(SUPPORT_MAX_GROUPS));
+    if (!q.group) return fail(PS_ERR_BAD_ARG, who + ": null group array");
+    if (need_records && !q.rec) return fail(PS_ERR_BAD_ARG, who + ": null support array");
+    for (int e = 0; e < q.a->E; e++)
+        if (q.group[e] < 0 || q.group[e] >= q.ngroups)
+            return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(q.group[e]) + ", n_groups = " + std::to_string(q.ngroups));
+    return PS_OK;
+}
+static int check_request(EditKind kind, const EditReq& q, size_t i) {
+    char msg[96];
+    if (kind == EditKind::List) return PS_OK;   // (its callers have no ranges to check)
+    if (kind == EditKind::Points) {
+        const int64_t have = (int64_t)q.a->states.size();
+        if (q.npos_given != have)
+            return fail(PS_ERR_BAD_ARG, "ps_batch_point_table: region " + std::to_string(i) + " was given n = " + std::to_string(q.npos_given) + ", its sequence has " +
+                                        std::to_string(have) + " positions (length - 4)");
+        return PS_OK;
+    }
+    const std::string who = std::string(kind == EditKind::Support ? "ps_score_mutation_support" : kind == EditKind::Genotype ? "ps_score_mutation_genotypes" : "ps_score_mutation_phase") +
+                            ": region " + std::to_string(i);
+    if (!q.muts) return fail(PS_ERR_BAD_ARG, who + ": null list");
+    if (kind == EditKind::Support) return check_groups(q, who, true);
+    if (kind == EditKind::Genotype) {
+        PS_TRY(check_groups(q, who, false));
+        if (q.nfrac < 0 || q.nfrac > GENO_MAX_FRAC)
+            return fail(PS_ERR_BAD_ARG, who + ": n_frac = " + std::to_string(q.nfrac) + ", allowed are 0 .. " + std::to_string(GENO_MAX_FRAC));
+        if (q.nfrac > 0 && !q.frac) return fail(PS_ERR_BAD_ARG, who + ": null alt_frac with n_frac = " + std::to_string(q.nfrac));
+        for (int k = 0; k < q.nfrac; k++)
+            if (!(q.frac[k] >= 1e-6 && q.frac[k] <= 1.0 - 1e-6)) {   // (NaN fails both comparisons)
+                snprintf(msg, sizeof msg, ": alt_frac[%d] = %g, allowed is 1e-06 .. 1 - 1e-06", k, q.frac[k]);
+                return fail(PS_ERR_BAD_ARG, who + msg);
+            }
+        if (!q.lik) return fail(PS_ERR_BAD_ARG, who + ": null lik");
+        return PS_OK;
+    }
+    if (q.window < 1 || q.window > LINK_MAX_WINDOW)
+        return fail(PS_ERR_BAD_ARG, who + ": window = " + std::to_string(q.window) + ", allowed are 1 .. " + std::to_string(LINK_MAX_WINDOW));
+    if (q.max_sets < 1 || q.max_sets > PHASE_MAX_SETS)
+        return fail(PS_ERR_BAD_ARG, who + ": max_sets = " + std::to_string(q.max_sets) + ", allowed are 1 .. " + std::to_string(PHASE_MAX_SETS));
+    if (!(q.min_link >= 0.0 && q.min_link <= 1.7976931348623157e308)) {   // (NaN fails both comparisons)
+        snprintf(msg, sizeof msg, ": min_link = %g, allowed is a finite value >= 0", q.min_link);
+        return fail(PS_ERR_BAD_ARG, who + msg);
+    }
+    if (!q.link) return fail(PS_ERR_BAD_ARG, who + ": null link");
+    if (!q.phase) return fail(PS_ERR_BAD_ARG, who + ": null phase");
+    return PS_OK;
+}
+
+// One edit-scoring call: checks the arguments — here, once, for every kind — sizes every list and runs the chain.  `rt`: the
+// caller's runtime; a null one (the point-table, support, genotype and phase entry points) is taken here, and only when there is
+// something for the device to do: a call without a region, or without an edit in any list, ends before that.
 int score_edits(Runtime* rt, EditKind kind, EditReq* reqs, size_t n) {
+    for (size_t k = 0; k < n; k++) PS_TRY(check_request(kind, reqs[k], k));
+    if (!rt) {
+        size_t edits = 0;
+        for (size_t k = 0; k < n; k++) edits += kind == EditKind::Points ? 1 : reqs[k].muts->size();
+        if (!edits) { write_unseen(kind, reqs, n); return PS_OK; }   // nothing to score anywhere: no launch
+        PS_TRY(runtime(&rt));
+    }
     par_for((int)n, [&](int k) {   // (a Refine list is 80 000 edits per region: copied and sized side by side)
         EditReq& q = reqs[k];
         if (kind == EditKind::Points) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction counts per anti-diagonal of k_fill from the gfx950 ISA (no GPU needed):
-    hipcc ... -S --cuda-device-only poreseq_amd/csrc/ps_kernels.hip -o /tmp/k.s ; python3 tools/isa_step_count.py /tmp/k.s [kernel substring]
+    hipcc ... -S --cuda-device-only poreseq_amd/csrc/ps_kernels.hip -o /tmp/k.s   (the edit-scoring kernels: ps_edit.hip) ; python3 tools/isa_step_count.py /tmp/k.s [kernel substring]
 Splits the kernel at its s_barrier instructions (one per anti-diagonal), classifies every instruction and prints the table of the
 steady-state steps (the unrolled 8-step FAST bodies are the runs of similar-sized intervals) plus one step's listing."""
 import collections, re, sys
