@@ -1,5 +1,6 @@
 // ps_extract.h — the tail of FindMutations for one AlignData on plain host data (cpp/FindMutations.cpp:51-183): likelihood differences
-// along the pairwise alignments -> clamped CUSUM -> greedy extraction of candidate edits.  No HIP headers
+// along the pairwise alignments -> clamped CUSUM -> greedy extraction of candidate edits; and MapAlignments' lookup for one level
+// (cpp/EventUtil.cpp:22-51).  No HIP headers
 // (tests/native/extract_check.cpp compiles this text with g++ and holds the extraction to a rescan with std::max_element on every
 // round, as the reference does); ps_find.cpp feeds it the Smith-Waterman lists and the likelihood vectors that came off the device.
 #ifndef PS_EXTRACT_H_
@@ -15,6 +16,15 @@
 namespace ps {
 
 constexpr size_t EXTRACT_BLK = 128;   // entries per block maximum
+
+// MapAlignments' lookup for one level (cpp/EventUtil.cpp:22-51): a / b are fillinds' lists of the sequence against a seed, `ra` the
+// level's ref_align into the sequence.  -> its ref_align into the seed: b at the first entry of a that is not below ra
+// (std::lower_bound), 0 for an empty list or an ra outside [a.front(), a.back()]
+inline double map_alignment(const std::vector<int>& a, const std::vector<int>& b, int ra) {
+    if (a.empty() || ra < a.front() || ra > a.back()) return 0.0;
+    const size_t k = std::lower_bound(a.begin(), a.end(), ra) - a.begin();
+    return k < b.size() ? (double)b[k] : 0.0;
+}
 
 // cpp/FindMutations.cpp:51-94 for one seed: ia / ib are fillinds' lists of the sequence against the seed (1-based), shifted and
 // trimmed in place to valid 0-based indices; base / rl the per-base cumulative likelihoods of the sequence / the seed.  -> the

@@ -270,6 +270,13 @@ JobSpec Align::job(int e) {
     s.out = d_out + e;
     return s;
 }
+JobSpec Align::job(int e, const std::vector<int>* other, double* ra, double* rl, double* ri, JobOut* out) {
+    JobSpec s = job(e);   // the event's data; the other sequence's states and the alignment to it on top
+    s.states = other;
+    s.ra = ra + off[e]; s.rl = rl + off[e]; s.ri = ri + off[e];
+    s.out = out;
+    return s;
+}
 
 // device -> host mirror of ref_align / ref_like in two halves, so that several AlignData can share one synchronisation
 int Align::refs_to_host_async(Runtime* rt) {
@@ -514,6 +521,14 @@ double share_need(const Align* a, int ndir) {
 }
 double share_cap(int ndir) { return ndir == 2 ? dense_cap_bytes() : device_share_bytes(); }
 
+// The scores of a batch's jobs, gathered into one array on the device and enqueued for one copy back (instead of one per AlignData)
+int gather_best(Runtime* rt, const Batch& b, double** best) {
+    DBuf& gb = rt->buf("best");
+    PS_TRY(gb.ensure(b.jobs.size() * sizeof(double)));
+    PS_TRY(launch_gather_best(rt, b.d, gb.as<double>()));
+    return rt->down(best, gb.p, b.jobs.size());
+}
+
 // ScoreAlignments, cpp/MakeMutations.cpp:148-195, for several AlignData in one launch chain (independent regions in lock-step)
 int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes) {
     auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
@@ -533,15 +548,9 @@ int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std
         if (rc == PS_SPLIT) return in_halves(as.size(), sub);   // bands wider than share_need guessed: two halves, one after the other
         PS_TRY(rc);
     }
-    // the jobs' scores, gathered into one array on the device: one copy back instead of one per AlignData
     for (Align* a : as) a->host_refs_valid = false;
     double* best = nullptr;
-    {
-        DBuf& gb = rt->buf("best");
-        PS_TRY(gb.ensure(specs.size() * sizeof(double)));
-        PS_TRY(launch_gather_best(rt, b.d, gb.as<double>()));
-        PS_TRY(rt->down(&best, gb.p, specs.size()));
-    }
+    PS_TRY(gather_best(rt, b, &best));
     bool any_likes = false;
     for (size_t k = 0; k < as.size(); k++) if (likes[k]) { any_likes = true; PS_TRY(as[k]->refs_to_host_async(rt)); }
     PS_HIP(hipStreamSynchronize(rt->stream));

@@ -88,6 +88,8 @@ struct Align {
                const double* model, const double* trans, const char* evseq, const int64_t* evseq_off,
                const ps_params* params);
     JobSpec job(int e);   // event e against this AlignData's own sequence
+    // event e against another sequence: its states, reference arrays of all events of this AlignData (laid out like the slab's), its result record
+    JobSpec job(int e, const std::vector<int>* other, double* ra, double* rl, double* ri, JobOut* out);
     int base_batch(Runtime* rt, Batch* b, int ndir, int lb_extra);   // job(e) of every event
     int refs_to_host(Runtime* rt);
     int refs_to_host_async(Runtime* rt);   // enqueue; refs_finish() after the stream has been synchronised
@@ -139,10 +141,24 @@ void par_for(int n, const std::function<void(int)>& fn);
 int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes);
 int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seeds,
                          const std::vector<std::vector<Mut>*>& outs);
-// chunks of forward-only (AlignData, candidate sequence) units under this runtime's share (ps_find.cpp): FindMutations' seeds, ps_score_sequences
-struct FwdUnit { const Align* a; int C; };   // the AlignData whose events are aligned, the states of the sequence they are aligned to
-double fwd_chunk_cap();                      // bytes one chunk may take
-size_t fwd_chunk_end(const std::vector<FwdUnit>& units, size_t q0, double cap, int p_seen, size_t limit, size_t* nref);
+// Every event of an AlignData aligned forward-only to a sequence that is not its own, for any number of such (AlignData, sequence)
+// units, in as many launch chains (chunks) as this runtime's share of the device allows (ps_fwd.cpp): FindMutations' seeds,
+// ps_score_sequences.  The driver cuts the chunks, sizes and carves "seed_refs" and "seed_out", builds the jobs, runs updaterefs and
+// realign, and cuts a chunk again whose bands came out wider than guessed; the two callbacks are what the callers differ in.
+struct FwdUnit { Align* a; const std::vector<int>* states; };   // the events of `a` against this sequence
+struct FwdChunk {                      // what a callback sees of the chunk being run
+    size_t q0 = 0, q1 = 0, nref = 0, njobs = 0;   // units [q0, q1), their levels, their jobs (unit by unit, event by event)
+    std::vector<size_t> roff;          // level offset of unit q - q0 in the chunk's arrays (event e of it: + a->off[e])
+    double *d_ra = nullptr, *d_rl = nullptr, *d_ri = nullptr;   // [nref] each: ref_align, ref_like, ref_index of the chunk's jobs
+    Batch b;                           // (collect) after the fills
+};
+typedef std::function<int(FwdChunk&)> FwdStep;
+// place: put ref_align of the chunk's jobs into d_ra and clear d_rl, enqueued on rt->stream (staging taken here is released with the
+// chunk).  collect: after realign; read what the caller wants and return with the stream idle.  what: "seed" / "variant", for the
+// trace.  tk: laps "seed batch build" before the fills.  *nchunks: chunks that ran to the end.
+int fwd_chunks(Runtime* rt, const std::vector<FwdUnit>& units, const char* what, const FwdStep& place, const FwdStep& collect,
+               int* nchunks = nullptr, Tick* tk = nullptr);
+int gather_best(Runtime* rt, const Batch& b, double** best);   // the jobs' maxima through "best": *best[job] is readable once the stream has been synchronised
 // Variant.py:48-61 (`variant -v`) for several AlignData: scores[r][s * E + e] = ScoreEvents()[e] of a copy of as[r] realigned to seqs[r][s],
 // accuracy[r][s] = swalign's identity in % (may be nullptr); no AlignData is modified (ps_variant.hip)
 int score_sequences_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seqs,

@@ -1,5 +1,5 @@
 // ps_plan.h — the arithmetic of the device-memory plan: pure, host-only, no HIP include.  Shared by the library (ps_mem.cpp decides
-// with it, ps_host.cpp and ps_find.cpp size their batches with it) and by a host test of it (tests/native/plan_check.cpp).
+// with it, ps_host.cpp and ps_fwd.cpp size their batches with it) and by a host test of it (tests/native/plan_check.cpp).
 //
 // The plan (309 GB on an MI355X, or this process's fraction of it):
 //   27 %  three slabs of 9 % each for the full forward + backward score matrices of dense ScoreMutations calls
@@ -80,6 +80,20 @@ template <class Need> size_t share_cut(size_t k0, size_t n, double cap, Need&& n
         bytes += add;
     }
     return k;
+}
+
+// Where the chunk that starts at item q0 of n ends when nothing is to be balanced: as many items, in order, as `cap` bytes hold, at
+// most `limit` of them, always at least one (an item larger than `cap` goes alone).  The chunks of candidate-sequence alignments
+// (fwd_chunks, ps_fwd.cpp): share_cut would move their boundaries.
+template <class Need> size_t greedy_cut(size_t q0, size_t n, double cap, size_t limit, Need&& need) {
+    size_t q1 = q0;
+    double bytes = 0;
+    while (q1 < n) {
+        const double add = need(q1);
+        if (q1 > q0 && (bytes + add > cap || q1 - q0 >= limit)) break;
+        bytes += add; q1++;
+    }
+    return q1;
 }
 
 }  // namespace ps

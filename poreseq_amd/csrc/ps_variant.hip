@@ -6,7 +6,7 @@
 //     a small record — the one device-to-host copy before the scores (the band certificate needs the host anyway)
 //   k_remap: every (variant, event) job's ref_align from the event's current one, the pair's table and record (ps_remap.h)
 //   updaterefs, forward fills and backtrace of the jobs (realign), their maxima gathered into one array
-// chunked by this runtime's share of the device like FindMutations' candidate sequences (fwd_chunk_end).  No index list, ref_align
+// chunked by this runtime's share of the device like FindMutations' candidate sequences (fwd_chunks, ps_fwd.cpp).  No index list, ref_align
 // mirror or remapped alignment crosses PCIe, and the AlignData are only read.
 #include <map>
 
@@ -92,78 +92,31 @@ int score_sequences_multi(Runtime* rt, const std::vector<Align*>& as, const std:
     for (size_t u = 0; u < U; u++) if (as[units[u].r]->E) live.push_back(u);
     par_for((int)live.size(), [&](int q) { Unit& un = units[live[q]]; un.states = states_of((*seqs[un.r])[un.s]); });
     std::vector<FwdUnit> fu(live.size());
-    for (size_t q = 0; q < live.size(); q++) fu[q] = {as[units[live[q]].r], (int)units[live[q]].states.size()};
+    for (size_t q = 0; q < live.size(); q++) fu[q] = {as[units[live[q]].r], &units[live[q]].states};
     std::vector<std::vector<double>> best_of(U);   // per unit: E scores
-    const double cap = fwd_chunk_cap();
-    size_t q0 = 0, limit = (size_t)-1;
-    int p_seen = 0, nchunks = 0;
-    while (q0 < live.size()) {
-        size_t nref = 0;
-        const size_t q1 = fwd_chunk_end(fu, q0, cap, p_seen, limit, &nref);
-        const size_t stage_mark = rt->stage.mark();
-        DBuf& rb = rt->buf("seed_refs");
-        PS_TRY(rb.ensure((size_t)3 * std::max<size_t>(nref, 1) * sizeof(double)));
-        double* d_ra = rb.as<double>();
-        double* d_rl = d_ra + nref;
-        double* d_ri = d_rl + nref;
-        std::vector<RemapUnit> rus(q1 - q0);
-        std::vector<size_t> roff(q1 - q0 + 1, 0);
-        size_t njobs = 0;
-        for (size_t q = q0; q < q1; q++) {
+    int nchunks = 0;
+    auto place = [&](FwdChunk& c) -> int {   // every job's ref_align through its pair's table, on the device
+        std::vector<RemapUnit> rus(c.q1 - c.q0);
+        for (size_t q = c.q0; q < c.q1; q++) {
             const Align* a = fu[q].a;
             const SwResult& al = als[live[q]];
-            roff[q - q0 + 1] = roff[q - q0] + (size_t)a->ntot;
-            rus[q - q0] = {a->d_ra, mb.as<int>() + al.map_off, a->ntot, (int64_t)roff[q - q0], {al.map_lo, al.map_hi, al.map_has0, al.map_y0}};
-            njobs += a->E;
+            rus[q - c.q0] = {a->d_ra, mb.as<int>() + al.map_off, a->ntot, (int64_t)c.roff[q - c.q0], {al.map_lo, al.map_hi, al.map_has0, al.map_y0}};
         }
-        PS_TRY(launch_remap(rt, rus, d_ra, d_rl));
-        DBuf& ob = rt->buf("seed_out");
-        PS_TRY(ob.ensure(njobs * sizeof(JobOut)));   // (before the out pointers are taken: ensure() may move the buffer)
-        PS_HIP(hipMemsetAsync(ob.p, 0, njobs * sizeof(JobOut), rt->stream));
-        std::vector<JobSpec> specs;
-        for (size_t q = q0; q < q1; q++) {
-            Align* a = as[units[live[q]].r];
-            for (int e = 0; e < a->E; e++) {
-                JobSpec s = a->job(e);   // the event's data; the variant's states and its re-mapped alignment on top
-                s.states = &units[live[q]].states;
-                const size_t o = roff[q - q0] + a->off[e];
-                s.ra = d_ra + o; s.rl = d_rl + o; s.ri = d_ri + o;
-                s.out = ob.as<JobOut>() + specs.size();
-                specs.push_back(s);
-            }
-        }
-        Batch b;
-        PS_TRY(b.build(rt, specs, 1, 0));
-        PS_TRY(launch_updaterefs(rt, b.d));   // EventData::setData of the copy's AlignData ends with updaterefs (cpp/EventData.h:223)
-        {
-            const int rc = realign(rt, b, q1 - q0 > 1 ? PLAN_OVER_GUESS * cap : 0.0);
-            if (rc == PS_SPLIT) {   // wider bands than guessed: cut the chunk again with the width it asked for
-                if (trace_on()) fprintf(stderr, "[ps] variant chunk of %zu cut again: %d slots per anti-diagonal\n", q1 - q0, b.P);
-                p_seen = std::max(p_seen, b.P);
-                limit = std::max<size_t>(1, (q1 - q0) / 2);
-                PS_HIP(hipStreamSynchronize(rt->stream));
-                rt->stage.release(stage_mark);
-                continue;
-            }
-            PS_TRY(rc);
-        }
-        p_seen = std::max(p_seen, b.P);
+        return launch_remap(rt, rus, c.d_ra, c.d_rl);
+    };
+    auto collect = [&](FwdChunk& c) -> int {   // the jobs' maxima
         double* best = nullptr;
-        DBuf& gb = rt->buf("best");
-        PS_TRY(gb.ensure(specs.size() * sizeof(double)));
-        PS_TRY(launch_gather_best(rt, b.d, gb.as<double>()));
-        PS_TRY(rt->down(&best, gb.p, specs.size()));
+        PS_TRY(gather_best(rt, c.b, &best));
         PS_HIP(hipStreamSynchronize(rt->stream));
         size_t j = 0;
-        for (size_t q = q0; q < q1; q++) {
+        for (size_t q = c.q0; q < c.q1; q++) {
             std::vector<double>& v = best_of[live[q]];
             v.resize(fu[q].a->E);
             for (double& x : v) x = std::max(best[j++], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
         }
-        rt->stage.release(stage_mark);   // the stream is idle: this chunk's staging memory can be reused
-        nchunks++;
-        q0 = q1;
-    }
+        return PS_OK;
+    };
+    PS_TRY(fwd_chunks(rt, fu, "variant", place, collect, &nchunks));
     if (rt->prof_on) { Prof& pr = rt->prof["variant_chunks"]; pr.launches += nchunks; pr.units += (double)U; }
     if (trace_on()) fprintf(stderr, "[ps] score_sequences: %zu distinct sequences of %d regions, %d smith-waterman launches, %d alignment chunks\n", U, R, sw_nchunks, nchunks);
     tk.lap("remap + realign");

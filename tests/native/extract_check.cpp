@@ -10,6 +10,7 @@
 //   short_vec    the winning vector is shorter than one block
 //   empty_vec    a trial with an empty vector among its seeds;  no_seeds: a trial without seeds
 // Part 2 runs the whole tail (seed_cusum + extraction) from likelihood vectors and index lists against the same restatement.
+// Part 3 holds MapAlignments' lower_bound lookup (map_alignment) to a scan, on named cases and on random lists.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -108,6 +109,14 @@ static std::vector<double> naive_cusum(const std::vector<int>& a, const std::vec
     return cs;
 }
 
+// MapAlignments' rule for one level (cpp/EventUtil.cpp:22-51) restated as a scan: a level whose ref_align lies within the range of the
+// sequence's list goes to the seed's index at the first pair whose sequence index has reached it; any other level is not aligned (0)
+static double naive_map(const std::vector<int>& a, const std::vector<int>& b, int ra) {
+    if (a.empty() || ra < a[0] || ra > a[a.size() - 1]) return 0.0;
+    for (size_t k = 0; k < a.size(); k++) if (a[k] >= ra) return (double)b[k];
+    return 0.0;
+}
+
 static bool same(const std::vector<Mut>& a, const std::vector<Mut>& b) {
     if (a.size() != b.size()) return false;
     for (size_t k = 0; k < a.size(); k++) if (a[k].start != b[k].start || a[k].orig != b[k].orig || a[k].mut != b[k].mut) return false;
@@ -197,6 +206,31 @@ int main(int argc, char** argv) {
         const int rc = ps::extract_edits(bases, seeds, ia, ib, base, lkp, &got);
         naive_extract(bases, seeds, na, nb, dl, &want, false);
         if (rc != 0 || !same(got, want) || ia != na || ib != nb) { if (bad++ < 5) printf("whole tail, trial %ld: rc %d, %zu edits, want %zu\n", it, rc, got.size(), want.size()); }
+    }
+    // 3. MapAlignments' lookup (cpp/EventUtil.cpp:22-51) against its restatement, on the cases named there and on random lists
+    {
+        const std::vector<int> none, a = {3, 4, 4, 4, 7, 9, 9, 12}, b = {10, 11, 12, 13, 14, 15, 16, 17};
+        struct { const std::vector<int>* a; const std::vector<int>* b; int ra; double want; } cases[] = {
+            {&none, &none, 5, 0.0},    // an empty list
+            {&a, &b, 2, 0.0},          // below the first entry
+            {&a, &b, 13, 0.0},         // above the last
+            {&a, &b, 3, 10.0},         // the first entry itself
+            {&a, &b, 4, 11.0},         // a repeated index: the first of its entries
+            {&a, &b, 5, 14.0},         // between two entries: the next one up (7) ...
+            {&a, &b, 8, 15.0},         // ... and of a repeated one (9) the first
+            {&a, &b, 12, 17.0},        // a hit on the last entry
+            {&a, &b, 0, 0.0},          // ref_align of a level that is not aligned
+        };
+        for (const auto& c : cases) {
+            const double got = ps::map_alignment(*c.a, *c.b, c.ra);
+            if (got != c.want || got != naive_map(*c.a, *c.b, c.ra)) { if (bad++ < 5) printf("map_alignment(%d): %g, want %g\n", c.ra, got, c.want); }
+        }
+    }
+    for (long it = 0; it < trials; it++) {
+        std::vector<int> a, b;
+        lists(below(40), 30, 30, 1 + below(3), &a, &b);
+        for (int ra = -1; ra < 36; ra++)
+            if (ps::map_alignment(a, b, ra) != naive_map(a, b, ra)) { if (bad++ < 5) printf("map_alignment, trial %ld: ra %d\n", it, ra); }
     }
     printf("tie_blocks=%ld tie_seeds=%ld run_span=%ld fill_span=%ld no_zero_before=%ld no_zero_after=%ld short_vec=%ld empty_vec=%ld no_seeds=%ld\n",
            tie_blocks, tie_seeds, run_span, fill_span, no_zero_before, no_zero_after, short_vec, empty_vec, no_seeds);

@@ -79,6 +79,33 @@ int main(int argc, char** argv) {
         CHECK(k0 == n && chunks <= n);
     }
     CHECK(share_cut(3, 3, 1e9, [](size_t) { return 1.0; }) == 3);         // nothing left: nothing cut
+    // 4. greedy_cut (the chunks of candidate-sequence alignments): in order, as many as the cap holds, at most `limit`, at least one
+    {
+        const std::vector<double> need = {3, 4, 5, 20, 1, 1, 8, 2};
+        auto f = [&](size_t k) { return need[k]; };
+        const size_t n = need.size(), any = (size_t)-1;
+        CHECK(greedy_cut(0, n, 44, any, f) == n && greedy_cut(0, n, 1e9, any, f) == n);   // everything fits (3 + ... + 2 = 44)
+        CHECK(greedy_cut(0, n, 1e9, 1, f) == 1 && greedy_cut(3, n, 1e9, 1, f) == 4);      // a limit of 1: one item, whatever the cap
+        CHECK(greedy_cut(0, n, 1e9, 3, f) == 3 && greedy_cut(6, n, 1e9, 3, f) == n);      // (a limit past the end: the end)
+        CHECK(greedy_cut(3, n, 10, any, f) == 4);                                         // an item larger than the cap goes alone
+        CHECK(greedy_cut(0, n, 10, any, f) == 2 && greedy_cut(2, n, 10, any, f) == 3);    // ... and does not join the items before it
+        CHECK(greedy_cut(0, n, 12, any, f) == 3);                                         // 3 + 4 + 5 lands exactly on the cap: all three
+        CHECK(greedy_cut(0, n, 11.999, any, f) == 2);
+        CHECK(greedy_cut(4, n, 10, any, f) == 7 && greedy_cut(4, n, 10, 2, f) == 6);      // q0 in the middle: 1 + 1 + 8 from there, or the limit
+        CHECK(greedy_cut(n, n, 10, any, f) == n);                                         // nothing left: nothing cut
+        size_t calls = 0;                                                                  // every item is sized once, and the one that ends the chunk
+        CHECK(greedy_cut(0, n, 10, any, [&](size_t k) { calls++; return need[k]; }) == 2 && calls == 3);
+    }
+    for (long it = 0; it < trials; it++) {   // against a literal restatement, over random lists
+        const size_t n = 1 + rnd() % 30, q0 = rnd() % n, limit = it % 4 == 0 ? (size_t)-1 : 1 + rnd() % 8;
+        std::vector<double> need(n);
+        for (double& v : need) v = (double)(rnd() % 64);
+        const double cap = (double)(rnd() % 256);
+        size_t want = q0 + 1;
+        double sum = need[q0];
+        while (want < n && want - q0 < limit && sum + need[want] <= cap) sum += need[want++];
+        CHECK(greedy_cut(q0, n, cap, limit, [&](size_t k) { return need[k]; }) == want);
+    }
     printf("failures=%ld\n", bad);
     return bad != 0;
 }

@@ -262,6 +262,63 @@ def test_a_call_cut_into_several_chunks_gives_the_same_results():
         assert res["rows"][k] == GOLD["L10000"]["variants"][vid]["scores"], vid
 
 
+def _recut_case():
+    """one synthetic region of 900 bases with 8 events at the default realign_width, and four distinct candidate sequences: the
+    draft, the truth, a copy with an SNV and a copy with a deletion and an insertion"""
+    from poreseq_amd.util import DEFAULT_PARAMS
+    p = dict(DEFAULT_PARAMS, verbose=0)
+    draft, events, truth = synth.make_region(900, 8, 7500, B.oracle_swalign, p)
+    snv = draft[:450] + ("A" if draft[450] != "A" else "C") + draft[451:]
+    indel = draft[:300] + draft[302:600] + "G" + draft[600:]
+    seqs = [draft, truth, snv, indel]
+    assert len(set(seqs)) == 4
+    return draft, events, p, seqs
+
+
+_RECUT_CHILD = r"""
+import sys
+sys.path[:0] = [%(root)r, %(tests)r]
+import backends as B
+from test_hip_variant_seqs import _recut_case
+from poreseq_amd.poreseqcpp import PSAlign
+draft, events, p, seqs = _recut_case()
+rows = B.make_pa(PSAlign, draft, events, p).ScoreSequences(seqs)
+print("RESULT", rows.shape[0], rows.shape[1], rows.tobytes().hex())
+"""
+# PORESEQ_MAX_BATCH_GB at which the first chunk of _recut_case holds two sequences on the 64-slot guess and is cut again on the real
+# width.  Without strip sweeps a chunk is sized by matrix_bytes(S, P, 1) = (S + 24) * P * 18 per job, S = levels + states + 1.  The
+# region's events have 844 to 870 levels, 6866 in all, and a sequence of 898 to 900 bases has at most 896 states: at P = 64 one
+# sequence's eight jobs take (6866 + 8 * (896 + 25)) * 64 * 18 = 16.4 MB.  A budget of 40 MB holds two of them (32.8 MB) and not three
+# (49.2 MB).  realign_width 300 needs far more than 64 slots per anti-diagonal (guess_slots_w(300) = 384), and at any width above
+# 64 slots — 128 or more — the two sequences' matrices take at least 65.6 MB, over 1.2 x 40 MB = 48 MB: the chunk is cut again, to
+# one sequence per chunk.  (0.2, FindMutations' budget at this shape, would hold all four sequences: 65.6 MB; they are cut again only
+# if the real width is 256 slots or more, 4 x 16.4 x 4 = 262 MB against 240 MB.)
+RECUT_GB = "0.04"
+
+
+def test_variant_chunks_are_cut_again_when_the_bands_are_wider_than_guessed():
+    """ps_score_sequences sizes its chunks on a guess of the band footprint, through the chunk driver it shares with FindMutations
+    (fwd_chunks); with a guess far too small (PORESEQ_DEBUG_GUESS_P) the first chunk must be cut again, and the scores stay the same
+    bytes: those of the plain run and of the oracle's literal loop.  Two child processes, as the guess is read once."""
+    code = _RECUT_CHILD % {"root": B.ROOT, "tests": os.path.join(B.ROOT, "tests")}
+
+    def run(extra):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=dict(os.environ, PORESEQ_TRACE="1", **extra))
+        assert r.returncode == 0, r.stderr[-2000:]
+        n, e, data = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][0].split()[1:]
+        return (int(n), int(e), bytes.fromhex(data)), r.stderr
+
+    plain, err0 = run({})
+    cut, err1 = run({"PORESEQ_DEBUG_GUESS_P": "64", "PORESEQ_NO_SWEEP": "1", "PORESEQ_MAX_BATCH_GB": RECUT_GB})
+    print("\n".join(l for l in err1.splitlines() if "chunk" in l or "over the share" in l))
+    assert "[ps] score_sequences:" in err0 and "variant chunk" not in err0 and "cut again" not in err0    # (traced, and nothing to report)
+    assert "variant chunk" in err1 and "cut again" in err1
+    assert cut == plain
+    draft, events, p, seqs = _recut_case()
+    want = np.array(_literal_loop(B.make_pa(B.OraclePSAlign, draft, copy.deepcopy(events), p), seqs), dtype=np.float64)
+    assert plain == (len(seqs), len(events), want.tobytes())
+
+
 def test_variant_sequences_prints_the_reference_lines():
     draft, events, p, vs = _case("L3000")
     pa = B.make_pa(PSAlign, draft, events, p)
