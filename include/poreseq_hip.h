@@ -303,7 +303,18 @@ int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, do
  * HIP library keeps that contract per host thread: each thread owns a glibc random_r() state (the TYPE_3
  * additive-feedback generator rand() itself uses), initially seeded with 1 like an unseeded process, without
  * the process-wide lock behind rand() that serialises concurrent regions.  ps_srand re-seeds the calling
- * thread's generator (srand(seed) in the oracle / reference builds of this ABI). */
+ * thread's generator (srand(seed) in the oracle / reference builds of this ABI).
+ *
+ * nkeep == 0 asks for the one deterministic back-trace: p[T-1] = the first maximum of the final scores, p[i-1] = bp[i][p[i]] over
+ * the T kept positions.  The recursion starts every maximum at -1e300 with back-pointer -1, so a kept position where every state's
+ * emission is -inf or below -1e300, or where the running scores have passed -1e300, leaves -1 in all 1024 states, and so does every
+ * later one.  Finite, unmarked data gets there (a level mean or deviation near 1e151 or above).  Where some bp[i][p[i]], i >= 1, is
+ * -1 there is no path: ps_viterbi_mutate, ps_batch_viterbi_mutate, ps_debug_viterbi and ps_debug_viterbi_steps answer
+ * PS_ERR_BAD_ARG, the message naming the entry point, the region index of a lock-step call and the first such kept position
+ * ("ps_batch_viterbi_mutate: region 1: no state is reachable at kept position 100 (...)").  A lock-step call with one such region
+ * is refused as a whole; the AlignData stays usable for every other call.  bp[0] is never followed, so T = 1 always has a path.
+ * The stochastic back-traces (nkeep > 0) do not read back-pointers and run on such tables as the reference does.  (The reference
+ * itself indexes with the -1 here; the reference shim of this ABI is not to be called with nkeep == 0 on such data.) */
 int ps_srand(uint32_t seed);
 /* The next n deviates rand() / (RAND_MAX + 1.0) of the calling thread's generator (consumes them). */
 int ps_rand_draw(int64_t n, double* out);

@@ -52,7 +52,12 @@ int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, i
         char* prev = (rng && rng[i]) ? setstate(rng[i]->st) : nullptr;
         int rc = ps_viterbi_mutate(a[i], nkeep, skip, stay, mmin, mmax, 0, &out[i]);
         if (prev) setstate(prev);
-        if (rc) return rc;
+        if (rc) {   // the batch is refused as a whole; a refusal of the single call is renamed after this one and its region
+            const std::string single = "ps_viterbi_mutate: ", msg = g_err;
+            if (msg.compare(0, single.size(), single) == 0) g_err = "ps_batch_viterbi_mutate: region " + std::to_string(i) + ": " + msg.substr(single.size());
+            for (int k = 0; k < i; k++) { ps_seqs_destroy(out[k]); out[k] = nullptr; }
+            return rc;
+        }
     }
     return PS_OK;
 }

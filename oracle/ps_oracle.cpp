@@ -697,15 +697,30 @@ void vit_walk(std::vector<Event>& ev, double skip, double stay, VTable& S, std::
 
 // the back-traces, ref: cpp/Viterbi.cpp:358-426: state paths [max(nkeep, 1)][T]; deviate() is called in the reference's order
 // (per kept path, one per back-step)
+// The deterministic trace (nkeep == 0) follows back-pointers, and the reference is undefined where one of them is -1 (a state none of
+// whose candidates beat the -1e300 the maximum starts from: vstep).  Here that is an answer: *dead becomes the kept position of the
+// first step, counted back from where the trace stopped, all of whose states lack a back-pointer, and no path is returned.  The
+// back-pointer of kept position 0 leads to the start vector and is not followed, so one kept position always has a path.
 template <class Dev>
-std::vector<std::vector<int>> vit_paths(const VTable& S, int nkeep, double skip, double stay, double mmin, double mmax, Dev deviate) {
+std::vector<std::vector<int>> vit_paths(const VTable& S, int nkeep, double skip, double stay, double mmin, double mmax, Dev deviate, int* dead) {
     std::vector<std::vector<int>> out;
     const int start = argmax(S.back()->lik);
     const int n = (int)S.size() - 1;
     std::vector<int> path;
+    *dead = -1;
     if (nkeep == 0) {
         int c = start;
-        for (int i = n - 1; i >= 0; i--) { path.push_back(c); c = S[i + 1]->bp[c]; }
+        for (int i = n - 1; i >= 0; i--) {
+            path.push_back(c);
+            if (i == 0) break;
+            c = S[i + 1]->bp[c];
+            if (c >= 0) continue;
+            auto none_left = [&](int t) { for (int b : S[t + 1]->bp) if (b >= 0) return false; return true; };
+            int first = i;
+            while (first > 0 && none_left(first - 1)) first--;
+            *dead = first;
+            return out;
+        }
         std::reverse(path.begin(), path.end());
         out.push_back(path);
         return out;
@@ -727,13 +742,19 @@ inline double libc_deviate() { return rand() / (double(RAND_MAX) + 1); }
 
 // ref: cpp/Viterbi.cpp:239-426
 std::vector<std::string> viterbi_mutate(std::vector<Event>& ev, int nkeep, double skip, double stay,
-                                        double mmin, double mmax) {
+                                        double mmin, double mmax, int* dead) {
     VTable S;
     vit_walk(ev, skip, stay, S, nullptr);
     std::vector<std::string> out;
-    for (const std::vector<int>& path : vit_paths(S, nkeep, skip, stay, mmin, mmax, libc_deviate))
+    for (const std::vector<int>& path : vit_paths(S, nkeep, skip, stay, mmin, mmax, libc_deviate, dead))
         if (!path.empty()) out.push_back(path_to_bases(path));
     return out;
+}
+// the refusal of a deterministic trace that has no path (vit_paths); region < 0: not a lock-step call
+int fail_unreachable(const char* call, int region, int pos) {
+    g_err = std::string(call) + ": " + (region >= 0 ? "region " + std::to_string(region) + ": " : std::string()) + "no state is reachable at kept position " +
+            std::to_string(pos) + " (every emission there is -inf or below -1e300, or the running scores have passed -1e300)";
+    return PS_ERR_BAD_ARG;
 }
 
 }  // namespace
@@ -925,7 +946,10 @@ int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
 int ps_viterbi_mutate(ps_align* a, int32_t nkeep, double skip, double stay, double mmin, double mmax,
                       int32_t, ps_seqs** out) {
     if (!a || !out || a->d.ev.empty()) return fail(PS_ERR_BAD_ARG, "ps_viterbi_mutate");
-    ps_seqs* s = new ps_seqs(); s->v = viterbi_mutate(a->d.ev, nkeep, skip, stay, mmin, mmax); *out = s;
+    int dead = -1;
+    std::vector<std::string> v = viterbi_mutate(a->d.ev, nkeep, skip, stay, mmin, mmax, &dead);
+    if (dead >= 0) return fail_unreachable("ps_viterbi_mutate", -1, dead);
+    ps_seqs* s = new ps_seqs(); s->v = std::move(v); *out = s;
     return PS_OK;
 }
 int ps_swfull(const char* s1, int64_t n1, const char* s2, int64_t n2, int32_t* score, double* acc,
@@ -997,7 +1021,9 @@ int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t, int32_t nkeep, doub
         T[r] = (int)rows.size();
         if (T[r] > cap_T) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: a region has more positions than cap_T");
         std::vector<std::vector<int>> pt;
-        if (T[r]) pt = vit_paths(S, nkeep, skip, stay, mmin, mmax, libc_deviate);
+        int dead = -1;
+        if (T[r]) pt = vit_paths(S, nkeep, skip, stay, mmin, mmax, libc_deviate, &dead);
+        if (dead >= 0) return fail_unreachable("ps_debug_viterbi", r, dead);
         const size_t to = (size_t)r * cap_T * NS;
         if (obs) for (int t = 0; t < T[r]; t++) std::copy(rows[t].begin(), rows[t].end(), obs + to + (size_t)t * NS);
         vit_export(S, pt, bp ? bp + to : nullptr, lik_final ? lik_final + (size_t)r * NS : nullptr, fwd && nkeep ? fwd + to : nullptr,
@@ -1021,7 +1047,9 @@ int ps_debug_viterbi_steps(int32_t R, const int32_t* T, const double* obs, const
         }
         std::vector<std::vector<int>> pt;
         const double* next = rnd ? rnd + (size_t)nkeep * t_off : nullptr;
-        if (T[r]) pt = vit_paths(S, nkeep, skip, stay, mmin, mmax, [&]() { return *next++; });
+        int dead = -1;
+        if (T[r]) pt = vit_paths(S, nkeep, skip, stay, mmin, mmax, [&]() { return *next++; }, &dead);
+        if (dead >= 0) return fail_unreachable("ps_debug_viterbi_steps", r, dead);
         vit_export(S, pt, bp ? bp + t_off * NS : nullptr, lik_final ? lik_final + (size_t)r * NS : nullptr,
                    fwd && nkeep ? fwd + t_off * NS : nullptr, paths ? paths + (size_t)np * t_off : nullptr, (size_t)T[r]);
         t_off += T[r];

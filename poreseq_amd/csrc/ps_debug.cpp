@@ -91,7 +91,7 @@ int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nke
     std::vector<std::vector<std::string>> seqs(R);
     std::vector<std::vector<std::string>*> outs(R);
     for (int r = 0; r < R; r++) outs[r] = &seqs[r];
-    PS_TRY(viterbi_mutate_multi(rt, as, std::vector<RandState*>(R, nullptr), nkeep, skip, stay, mmin, mmax, outs, &tap));
+    PS_TRY(viterbi_mutate_multi(rt, as, std::vector<RandState*>(R, nullptr), nkeep, skip, stay, mmin, mmax, outs, &tap, "ps_debug_viterbi"));
     for (int r = 0; r < R; r++) T[r] = tap.T[r];
     for (int r = 0; r < R; r++) if (tap.T[r] > cap_T) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: a region has more positions than cap_T");
     const int np = std::max(nkeep, 1);
@@ -128,7 +128,7 @@ int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs,
     std::vector<GivenDeviates> giv(R);
     size_t t_off = 0;
     for (int r = 0; r < R; r++) {
-        regs[r].T = T[r];
+        regs[r].T = T[r]; regs[r].index = r;
         giv[r].next = rnd ? rnd + (size_t)nkeep * t_off : nullptr;
         regs[r].rng = &giv[r]; regs[r].draw = draw_given;
         t_off += T[r];
@@ -136,7 +136,7 @@ int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs,
     VitTap tap;
     tap.obs_rows = obs;
     std::vector<std::vector<std::vector<int>>> pt;
-    PS_TRY(viterbi_device_multi(rt, regs, nkeep, skip, stay, mmin, mmax, &pt, &tap));
+    PS_TRY(viterbi_device_multi(rt, regs, nkeep, skip, stay, mmin, mmax, &pt, &tap, "ps_debug_viterbi_steps"));
     if (bp && !tap.bp.empty()) memcpy(bp, tap.bp.data(), tap.bp.size() * sizeof(short));
     if (fwd && !tap.fwd.empty()) memcpy(fwd, tap.fwd.data(), tap.fwd.size() * sizeof(double));
     if (lik_final) memcpy(lik_final, tap.lik_final.data(), (size_t)R * NS * sizeof(double));

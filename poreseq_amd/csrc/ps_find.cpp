@@ -391,7 +391,7 @@ static void vit_draw(void* rng, double* rnd, size_t n) {
 // ViterbiMutate (cpp/Viterbi.cpp:239-426) for several AlignData in lock-step; rngs[r] = the region's generator (nullptr: the
 // calling thread's); tap: the device tables for ps_debug_viterbi (ps_internal.h), a null pointer otherwise
 int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
-                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap) {
+                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap, const char* who, bool lockstep) {
     Tick tk("viterbi_mutate");
     const int R = (int)as.size();
     for (int r = 0; r < R; r++) outs[r]->clear();
@@ -415,6 +415,7 @@ int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::
         regs[r].E = as[r]->E; regs[r].T = gath[r].T; regs[r].obsin = gath[r].obsin.data(); regs[r].d_model = as[r]->d_model;
         as[r]->last_stream = (void*)rt->stream;   // (the Viterbi kernels read the model tables in the AlignData's slab)
         regs[r].rng = rngs[r]; regs[r].draw = vit_draw;
+        regs[r].index = lockstep ? r : -1;
     }
     std::vector<std::vector<std::vector<int>>> paths;
     {
@@ -428,7 +429,7 @@ int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::
             double acc = 0;
             for (; k1 < regs.size(); k1++) { const double add = need(k1); if (k1 > k0 && acc + add > cap) break; acc += add; }
             std::vector<std::vector<std::vector<int>>> part;
-            const int rc = viterbi_device_multi(rt, std::vector<VitRegionH>(regs.begin() + k0, regs.begin() + k1), nkeep, skip, stay, mmin, mmax, &part, tap);
+            const int rc = viterbi_device_multi(rt, std::vector<VitRegionH>(regs.begin() + k0, regs.begin() + k1), nkeep, skip, stay, mmin, mmax, &part, tap, who);
             if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { cap *= 0.5; continue; }   // (nothing of this sub-batch has been drawn yet: allocation comes first)
             PS_TRY(rc);
             for (auto& pr : part) paths.push_back(std::move(pr));
@@ -443,7 +444,7 @@ int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::
 
 int viterbi_mutate(Runtime* rt, Align* a, int nkeep, double skip, double stay, double mmin, double mmax,
                    std::vector<std::string>* out, bool verbose) {
-    const int rc = viterbi_mutate_multi(rt, {a}, {nullptr}, nkeep, skip, stay, mmin, mmax, {out});
+    const int rc = viterbi_mutate_multi(rt, {a}, {nullptr}, nkeep, skip, stay, mmin, mmax, {out}, nullptr, "ps_viterbi_mutate", false);
     if (verbose && rc == PS_OK) {
         // the reference's progress line (cpp/Viterbi.cpp:258-259, 357-370): "Viterbi", a dot whenever the reference position passes a
         // multiple of 200, a newline.  The positions walked: from the first event's start to where no event is aligned any more —

@@ -164,7 +164,8 @@ int gather_best(Runtime* rt, const Batch& b, double** best);   // the jobs' maxi
 int score_sequences_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seqs,
                           const std::vector<double*>& scores, const std::vector<double*>& accuracy);
 int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
-                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap = nullptr);
+                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap = nullptr, const char* who = "ps_batch_viterbi_mutate", bool lockstep = true);
+// (who, lockstep: the entry point, and whether a region index, that a refusal of the deterministic back-trace names)
 std::string info_string();   // process-wide state in one line (ps_info)
 struct MemInfo { size_t slabs = 0, slab_bytes = 0; int slabs_planned = 0; long long pool_bytes = 0; };
 MemInfo mem_info();          // ps_mem.cpp's part of it: slabs allocated (and their bytes) of how many, bytes in the pools of this process

@@ -320,6 +320,7 @@ void sw_band_counters(int64_t out[5]);   // band mode: pairs banded, fell back, 
 // Viterbi (ps_viterbi.hip): one region of a batched ViterbiMutate call, host side
 struct VitRegionH {
     int E = 0, T = 0;
+    int index = -1;                      // of the region in the caller's lock-step batch, named in a refusal (-1: not a batch)
     const double* obsin = nullptr;       // [T][E][4]: level, sd, log sd, present
     const double* d_model = nullptr;     // device, [E][6][1024]
     void* rng = nullptr;                 // the region's generator state, handed to draw()
@@ -339,7 +340,8 @@ struct VitTap {
     std::vector<std::vector<std::vector<int>>> paths;   // per region [nkeep or 1][T] states
 };
 int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, int nkeep, double skip, double stay, double mmin, double mmax,
-                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap = nullptr);
+                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap = nullptr, const char* who = "ViterbiMutate");
+// (who: the entry point a refusal of the deterministic back-trace names, ps_vitpath.h)
 
 void prof_flush(Runtime* rt);   // deferred mode: read the queued event pairs (drains the stream)
 void prof_begin(Runtime* rt);

@@ -20,6 +20,7 @@
 #include <atomic>
 
 #include "ps_internal.h"
+#include "ps_vitpath.h"
 
 namespace ps {
 
@@ -415,7 +416,7 @@ __global__ __launch_bounds__(VT_THREADS) void k_vit_trace(const VitReg* __restri
 }
 
 int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, int nkeep, double skip, double stay, double mmin, double mmax,
-                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap) {
+                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap, const char* who) {
     const int R = (int)regions.size();
     paths->assign(R, {});
     std::vector<VitReg> regs(R);
@@ -530,8 +531,14 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
         for (int r = 0; r < R; r++) {
             if (!regions[r].T) continue;
             std::vector<int> p(regions[r].T);
-            int c = starts[r];
-            for (int i = regions[r].T - 1; i >= 0; i--) { p[i] = c; c = bp[((size_t)regs[r].t_off + i) * NS + c]; }
+            // a back-pointer of -1 on the path (a dead max-plus row) refuses the whole call
+            const int64_t dead = vit_follow_bp(bp, regs[r].t_off, regions[r].T, NS, starts[r], p.data());
+            if (dead >= 0) {
+                paths->assign(R, {});
+                return fail(PS_ERR_BAD_ARG, std::string(who) + ": " + (regions[r].index >= 0 ? "region " + std::to_string(regions[r].index) + ": " : std::string()) +
+                                                "no state is reachable at kept position " + std::to_string(dead) +
+                                                " (every emission there is -inf or below -1e300, or the running scores have passed -1e300)");
+            }
             (*paths)[r].push_back(p);
         }
         if (tap) std::copy(paths->begin(), paths->end(), tap->paths.end() - R);

@@ -7,6 +7,14 @@ and test_hip_edge_values.py (the HIP path against the oracle).  Every case is th
   tier C  finite data outside the range: the IEEE-division builds
   tier D  tables whose emissions are infinite or NaN: -infinity and NaN are marked — the DP and the edit scoring
           run on them, ViterbiMutate refuses them; a +infinity emission is refused by ps_align_create
+  tier E  `vit_*`: finite, unmarked data (IEEE-division builds) that kills ViterbiMutate's max-plus vector.  On a three-event
+          region (BASE3) the trimmed mean drops nothing, so a single level whose emission is -inf or below -1e300 for every state
+          leaves its kept position with back-pointer -1 and score -1e300 in all 1024 states, and every later position with it; so
+          does a run of levels whose sum passes -1e300.  The rule: the deterministic back-trace (nkeep == 0) is p[T - 1] = argmax of
+          the final scores, p[i - 1] = bp[i][p[i]]; where some bp[i][p[i]], i >= 1, is -1 the call answers PS_ERR_BAD_ARG naming the
+          entry point, the region of a lock-step call and the first dead kept position.  bp[0] is never followed.  The stochastic
+          back-traces (nkeep > 0) are defined on such tables and run.  `vit_trimmed` is the control on the four-event base region:
+          the one -inf per state is the dropped quarter and no position dies.
 
 `synth.make_region`'s seeded streams are not touched.
 """
@@ -23,6 +31,7 @@ from poreseq_amd.util import DEFAULT_PARAMS, MutationInfo
 
 P0 = dict(DEFAULT_PARAMS, verbose=0)
 BASE = (260, 4, 5150)          # make_region(L, events, seed)
+BASE3 = (260, 3, 5150)         # three events: at most three levels on a position, so the trimmed mean drops none (tier E)
 LO, HI = 2.0 ** -128, 2.0 ** 128            # ps_sane.h: divisors, magnitudes of non-zero means
 LAM_LO, LAM_HI = 2.0 ** -200, 2.0 ** 200    # lambda = sd_mean^3 / sd_stdv^2
 
@@ -54,6 +63,15 @@ CASES = {
     "ieee_small": ([(1, "stdv", 40, 1e-120), (2, "stdv", 7, 1e-120), (1, "mean", 60, 1e120)], [], {}),
     "ieee_big": ([(1, "stdv", 40, 1e120), (2, "stdv", 7, 1e120), (1, "mean", 60, 1e120)], [], {}),
     "model_sdmean_big": ([], [(1, "sd_mean", _S7, 1e40)], {}),
+    # ---- tier E, on BASE3: finite, unmarked levels that kill ViterbiMutate's max-plus vector.  With three
+    # events the trimmed mean drops nothing, so one level whose emission is -inf (d d or e e overflows) or below -1e300 for every
+    # state makes the kept position's row -inf or below -1e300; vit_accum keeps every row above -1e300 and lets the running score pass it
+    "vit_mean_overflow": ([(1, "mean", 100, 1e160)], [], {}),
+    "vit_stdv_overflow": ([(1, "stdv", 100, 1e160)], [], {}),
+    "vit_below_big": ([(1, "mean", 100, 1e151)], [], {}),
+    "vit_accum": ([(1, "mean", slice(100, 114), 1.5e150)], [], {}),
+    # the control on the four-event BASE: the one -inf of each state is the lowest quarter, dropped; no row dies
+    "vit_trimmed": ([(1, "mean", 100, 1e160)], [], {}),
     # ---- tier D, marked: emissions of -infinity or NaN.  The DP and the edit scoring run on them; ViterbiMutate refuses them
     "mean_nan": ([(1, "mean", 40, float("nan"))], [], {}),
     "mean_inf": ([(1, "mean", 40, float("inf")), (2, "stdv", 9, float("inf"))], [], {}),
@@ -73,7 +91,13 @@ TIER_C = ("ieee_small", "ieee_big", "model_sdmean_big", "corner_overflow")     #
 TIER_D_MARKED = ("mean_nan", "mean_inf", "sd_neg", "model_nan", "model_sd_neg")
 TIER_D_REFUSED = ("sd_zero", "sd_zero_run", "model_sd_zero", "lam_inf", "off_inf")
 TIER_D = TIER_D_MARKED + TIER_D_REFUSED
-FINITE = ("base",) + TIER_A + TIER_B + TIER_C
+TIER_E_DEAD = ("vit_mean_overflow", "vit_stdv_overflow", "vit_below_big", "vit_accum")
+TIER_E = TIER_E_DEAD + ("vit_trimmed",)
+ON_BASE3 = TIER_E_DEAD
+# tier E: the first kept position all of whose states have back-pointer -1 (every later one has too), pinned by test_edge_values.py
+VIT_FIRST_DEAD = {"vit_mean_overflow": 100, "vit_stdv_overflow": 100, "vit_below_big": 100, "vit_accum": 109}
+UNREACHABLE = "no state is reachable at kept position %d "
+FINITE = ("base",) + TIER_A + TIER_B + TIER_C + TIER_E
 # what the message of a tier-D refusal names first
 NAMED = {"mean_nan": "event 1, level 40:", "mean_inf": "event 1, level 40:", "sd_neg": "event 1, level 40:", "model_nan": "event 1, model row 0:",
          "model_sd_neg": "event 1, model row 0:", "sd_zero": "event 1, level 40:", "sd_zero_run": "event 1, level 40:",
@@ -82,17 +106,18 @@ NAMED = {"mean_nan": "event 1, level 40:", "mean_inf": "event 1, level 40:", "sd
 _made = {}
 
 
-def _base():
-    if "base" not in _made:
-        draft, events, _ = synth.make_region(*BASE, B.oracle_swalign, P0)
-        _made["base"] = (draft, events)
-    return _made["base"]
+def _base(name="base"):
+    key = BASE3 if name in ON_BASE3 else BASE
+    if key not in _made:
+        draft, events, _ = synth.make_region(*key, B.oracle_swalign, P0)
+        _made[key] = (draft, events)
+    return _made[key]
 
 
 def region(name):
     """(draft, events, params) of a case; the caller owns the copies"""
     levels, model, par = CASES[name]
-    draft, events = _base()
+    draft, events = _base(name)
     events = copy.deepcopy(events)
     params = dict(P0, **par)
     for e, field, at, value in levels:
@@ -113,7 +138,7 @@ def altered_events(name):
 
 def altered_levels(name):
     """(event, level index >= 0) of every overwritten level"""
-    _, events = _base()
+    _, events = _base(name)
     out = []
     for e, _field, at, _v in CASES[name][0]:
         n = events[e].mean.size

@@ -45,7 +45,7 @@ def test_tiers_a_and_b_pass_the_host_predicate(name):
     assert EC.host_verdict(events, par) == ("unmarked", "fast")
 
 
-@pytest.mark.parametrize("name", EC.TIER_C)
+@pytest.mark.parametrize("name", EC.TIER_C + EC.TIER_E)
 def test_tier_c_takes_the_ieee_builds(name):
     _draft, events, par = EC.region(name)
     assert EC.host_verdict(events, par) == ("unmarked", "ieee")
@@ -164,6 +164,79 @@ def test_outliers_kill_the_references_forward_vector():
         assert np.all(np.isfinite(t["obs"])) and np.all(np.isfinite(t["lik_final"]))
         if first < 245:
             assert t["obs"][first].max() < -745
+
+
+# ---- tier E: finite, unmarked data that kills ViterbiMutate's max-plus vector ------------------------------------------------------
+def oracle_viterbi_tables(name):
+    import tiled_cases as TC
+    return EC.oracle_once(("vit", name), lambda: TC.viterbi_tables(B.oracle_api(), *EC.region(name), 16))
+
+
+@pytest.mark.parametrize("name", EC.TIER_E_DEAD)
+def test_tier_e_kills_the_max_plus_vector_where_pinned(name):
+    """finite levels; the kept position named in edge_cases.VIT_FIRST_DEAD and every later one have back-pointer -1 in all 1024
+    states and the final scores are all -1e300.  The dying row's emissions are all -inf (d d or e e overflows), all finite and
+    below -1e300 (vit_below_big), or — vit_accum — no emission of the table is below -1e300: the running score passes it, over five
+    partly dead rows.  The forward vector dies at row 100 in every case (exp = 0)."""
+    import viterbi_cases as K
+    import viterbi_ref as V
+    _draft, events, _par = EC.region(name)
+    assert len(events) == 3 and all(np.all(np.isfinite(getattr(ev, f))) for ev in events for f in ("mean", "stdv"))
+    t = oracle_viterbi_tables(name)
+    first = EC.VIT_FIRST_DEAD[name]
+    assert t["T"] == 245
+    counts = np.count_nonzero(t["bp"] == -1, axis=1)
+    assert np.all(counts[first:] == 1024) and np.all(t["lik_final"] == -1e300)
+    assert not np.any(np.isnan(t["obs"])) and t["obs"].max() < 1e300
+    if name == "vit_accum":
+        assert t["obs"].min() > -1e300
+        assert np.all(counts[:104] == 0) and np.all((counts[104:first] > 0) & (counts[104:first] < 1024)), counts[98:112]
+    else:
+        assert np.all(counts[:first] == 0)
+        row = t["obs"][first]
+        assert np.all(row < -1e300) and (np.all(np.isfinite(row)) if name == "vit_below_big" else np.all(np.isneginf(row)))
+        assert np.all(np.isfinite(np.delete(t["obs"], first, axis=0)))
+    bp, lik = V.run64(t["obs"], K.SKIP, K.STAY)
+    assert np.array_equal(t["bp"], bp) and np.array_equal(t["lik_final"], lik)
+    assert EC.live_forward_rows(t["fwd"]) == 100 and np.all(np.isnan(t["fwd"][100:].sum(axis=1)))
+
+
+def test_tier_e_control_trims_its_minus_infinity():
+    """four events with a level on position 100: the -inf is the lowest quarter of every state's list and is dropped.  No
+    back-pointer is -1, every emission row is finite, and row 100 alone differs from the base region's"""
+    base, t = oracle_viterbi_tables("base"), oracle_viterbi_tables("vit_trimmed")
+    assert t["T"] == base["T"] == 245 and np.all(t["bp"] >= 0) and np.all(np.isfinite(t["obs"])) and np.all(np.isfinite(t["lik_final"]))
+    assert np.flatnonzero(np.any(t["obs"] != base["obs"], axis=1)).tolist() == [100]
+    assert EC.live_forward_rows(t["fwd"]) == 245
+    # the same level on the three-event region is vit_mean_overflow
+    assert EC.CASES["vit_trimmed"] == EC.CASES["vit_mean_overflow"]
+
+
+@pytest.mark.parametrize("name", EC.TIER_E_DEAD)
+def test_tier_e_deterministic_decode_is_refused_by_the_oracle(name):
+    """ps_viterbi_mutate, ps_batch_viterbi_mutate and ps_debug_viterbi with nkeep = 0 answer PS_ERR_BAD_ARG naming the entry point,
+    the region of a lock-step call and the first dead position; the same handle then runs the stochastic call"""
+    import tiled_cases as TC
+    from poreseq_amd._capi import PoreseqError
+    orc = B.oracle_api()
+    draft, events, par = EC.region(name)
+    where = EC.UNREACHABLE % EC.VIT_FIRST_DEAD[name]
+    h, hb, rngs = orc.align_create(draft, events, par), orc.align_create(*EC.region("base")), [orc.rng_create(1), orc.rng_create(1)]
+    try:
+        for call, who in ((lambda: orc.viterbi_mutate(h, 0, *TC.VIT, 0), "ps_viterbi_mutate: no state"),
+                          (lambda: orc.batch_viterbi_mutate([hb, h], rngs, 0, *TC.VIT), "ps_batch_viterbi_mutate: region 1: "),
+                          (lambda: orc.debug_viterbi([hb, h], 400, 0, *TC.VIT), "ps_debug_viterbi: region 1: ")):
+            with pytest.raises(PoreseqError) as err:
+                call()
+            assert "(-1)" in str(err.value) and who in str(err.value) and where in str(err.value), str(err.value)
+        B.reset_rand()
+        seqs = orc.viterbi_mutate(h, 16, *TC.VIT, 0)
+        assert len(seqs) == 16 and orc.score_alignments(h, len(events)).tolist() == list(EC.oracle_calls(name)["ScoreEvents"])
+    finally:
+        for r in rngs:
+            orc.rng_destroy(r)
+        orc.align_destroy(h)
+        orc.align_destroy(hb)
 
 
 def test_off0_finds_nothing_and_off_big_scores_high():

@@ -7,6 +7,9 @@ parts of the library that exist only for them.
           (ii) ordinary data under PORESEQ_EXACT_DIV=1 at the smallest shapes that reach each instance
   tier D  tables whose emissions are infinite or NaN: -infinity and NaN run through the DP and the edit scoring and are refused by
           ViterbiMutate; a +infinity emission is refused by ps_align_create (PS_ERR_BAD_ARG, the message names the offender)
+  tier E  finite, unmarked data whose trimmed-mean emissions kill ViterbiMutate's max-plus vector (back-pointer -1 in every state
+          from one kept position on): tables and stochastic paths exact under every emission build, the deterministic back-trace
+          refused by the rule of DESIGN.md section 2
 
 Every comparison is at tolerance 0 with NaN matched as a mask, except the forward probabilities of ViterbiMutate, which keep the rule
 and the helper of test_hip_viterbi_tables.py.  The oracle's results are computed once per case (edge_cases.oracle_once); the oracle
@@ -39,7 +42,7 @@ def hip(draft, events, par):
     return B.make_pa(PSAlign, draft, copy.deepcopy(events), par)
 
 
-IEEE = EC.TIER_C + EC.TIER_D_MARKED      # cases whose tables fail the range predicate: every launch divides
+IEEE = EC.TIER_C + EC.TIER_D_MARKED + EC.TIER_E      # cases whose tables fail the range predicate: every launch divides
 FILL_FORMS = ("fill_pair", "fill_pair_fwd", "fill_cmp", "fill_512", "fill_1024", "fill_wide")
 SCORE_CLASSES = ("score_g7", "score_g8", "score_g16", "score_g32", "score_g64")
 
@@ -158,23 +161,27 @@ def test_lock_step_batch_of_base_spike_skip0(fwd_kernel):
 
 
 @need_ld
-@pytest.mark.parametrize("name", ("spike", "sd_small"))
+@pytest.mark.parametrize("name", ("spike", "sd_small") + EC.TIER_E)
 def test_viterbi_tables_under_every_emission_build(name):
     """T, the trimmed-mean emissions, back-pointers, final scores and state paths exact on every row; forward vectors by the rule of
     test_hip_viterbi_tables.py on the rows where the reference has one.  From the first position whose emissions are all below
-    -745 nats (exp = 0 for every state: row 96 of `spike`, row 7 of `sd_small`) the reference normalises 0 / 0 and carries NaN to the
-    end; its back-steps then fall through to the last state (`r < cs` is never true).  The device's vector must be dead there too
-    — every row total 0 or NaN, which makes k_vit_trace fall through the same way — and the paths, compared exactly, say that it is."""
+    -745 nats (exp = 0 for every state: row 96 of `spike`, row 7 of `sd_small`, row 100 of tier E) the reference normalises 0 / 0 and
+    carries NaN to the end; its back-steps then fall through to the last state (`r < cs` is never true).  The device's vector must
+    be dead there too — every row total 0 or NaN, which makes k_vit_trace fall through the same way — and the paths, compared
+    exactly, say that it is.  Tier E: the insertion sort and the trimmed mean of all three emission kernels meet -inf entries
+    (dropped in `vit_trimmed`, summed in the others), and k_vit_steps rows that are dead or dying (edge_cases.VIT_FIRST_DEAD)."""
     draft, events, par = EC.region(name)
     want = EC.oracle_once(("vit", name), lambda: TC.viterbi_tables(B.oracle_api(), draft, events, par, 16))
     alive = EC.live_forward_rows(want["fwd"])
-    assert 5 <= alive < want["T"]
+    assert alive == want["T"] if name == "vit_trimmed" else 5 <= alive < want["T"]
     builds = K.admitted_builds(len(events))
     assert builds == [1, 2, 3]
     for b in [0] + builds:
         got = TC.viterbi_tables(_capi.load_hip(), draft, events, par, 16, b)
         what = "%s, build %d" % (name, b)
         check_region(got, want, what, forward=False)
+        if name in EC.VIT_FIRST_DEAD:
+            assert np.all(got["bp"][EC.VIT_FIRST_DEAD[name]:] == -1) and np.all(got["lik_final"] == -1e300)
         if b in (0, builds[-1]):
             check_forward({"fwd": got["fwd"][:alive]}, {"fwd": want["fwd"][:alive]}, want["obs"][:alive], what)
             tot = got["fwd"][alive:].sum(axis=1)
@@ -201,7 +208,7 @@ def test_tier_c_data_outside_the_range(name, fwd_kernel):
 
 
 @stepped_down
-@pytest.mark.parametrize("name", EC.TIER_C)
+@pytest.mark.parametrize("name", EC.TIER_C + EC.TIER_E)
 def test_tier_c_steps_down_to_one_wavefront(name, fwd_kernel):
     """two or four wavefronts per sweep are asked for; the multi-wavefront builds exist with tabulated reciprocals only, so pick_form
     answers with one: strip sweeps ran, none of them on two or four wavefronts, same results"""
@@ -345,6 +352,66 @@ def test_exact_div_fill_1024_thread_form(exact_div, fwd_kernel):
 def test_exact_div_fill_wide(exact_div, fwd_kernel):
     """k_fill_wide<false>: realign_width 1000 on 1 090 bases, footprints of 1 025 and 1 030 rows, P = 1 152 > 1 024"""
     fill_calls("wide", ("fill_wide",))
+
+
+# ---- tier E: finite, unmarked data that kills ViterbiMutate's max-plus vector ----------------------------------------------------
+@two_families
+@pytest.mark.parametrize("name", EC.TIER_E)
+def test_tier_e_dp_and_calls_match_oracle(name, fwd_kernel):
+    """the DP matrices carry a level row whose emission is -inf (or below -1e300) for every state, from finite input; the call set
+    includes Mutate('viterbi'), whose 16 stochastic back-traces run over the dead tables.  The two- and four-wavefront sweeps are
+    asked for in test_tier_c_steps_down_to_one_wavefront: these tables divide, so they step down"""
+    check_dp(name, fwd_kernel)
+    check_calls(name, fwd_kernel)
+
+
+def test_tier_e_lock_step_batch_and_the_refused_decode():
+    """(base, vit_mean_overflow, vit_trimmed) in one lock-step batch: Mutate('viterbi') equals the three run alone and the oracle.
+    With nkeep = 0 the dead region is refused by ps_viterbi_mutate, ps_batch_viterbi_mutate and ps_debug_viterbi — PS_ERR_BAD_ARG
+    naming the entry point, region 1 of the lock-step calls and kept position 100 — the batch as a whole; the same handles then
+    answer ScoreEvents as before, and the live regions decode"""
+    names = ("base", "vit_mean_overflow", "vit_trimmed")
+    regs = [EC.region(n) for n in names]
+
+    def viterbi_alone(cls, r):
+        B.reset_rand()
+        pa = B.make_pa(cls, r[0], copy.deepcopy(r[1]), r[2])
+        return pa.Mutate(seqs="viterbi"), pa.sequence, EC.refs(pa)
+
+    want = EC.oracle_once(("tier_e_batch",), lambda: [viterbi_alone(B.OraclePSAlign, r) for r in regs])
+    single = [viterbi_alone(PSAlign, r) for r in regs]
+    pas = [hip(*r) for r in regs]
+    with RegionBatch(pas) as rb:
+        nv = rb.Mutate(seqs="viterbi")
+        rb.sync()
+    for r, pa in enumerate(pas):
+        for other in (single[r], want[r]):
+            assert (nv[r], pa.sequence) == other[:2] and EC.same_arrays(EC.refs(pa), other[2]), names[r]
+    api, orc = _capi.load_hip(), B.oracle_api()
+    where = EC.UNREACHABLE % EC.VIT_FIRST_DEAD["vit_mean_overflow"]
+    hs = [api.align_create(r[0], copy.deepcopy(r[1]), r[2]) for r in regs]
+    rngs = [api.rng_create(1) for _ in regs]
+    try:
+        for call, who in ((lambda: api.viterbi_mutate(hs[1], 0, *TC.VIT, 0), "ps_viterbi_mutate: no state"),
+                          (lambda: api.batch_viterbi_mutate(hs, rngs, 0, *TC.VIT), "ps_batch_viterbi_mutate: region 1: "),
+                          (lambda: api.debug_viterbi(hs, 400, 0, *TC.VIT), "ps_debug_viterbi: region 1: ")):
+            with pytest.raises(_capi.PoreseqError) as err:
+                call()
+            assert "(-1)" in str(err.value) and who in str(err.value) and where in str(err.value), str(err.value)
+        for k in (0, 2):
+            ho = orc.align_create(regs[k][0], copy.deepcopy(regs[k][1]), regs[k][2])
+            try:
+                assert api.viterbi_mutate(hs[k], 0, *TC.VIT, 0) == orc.viterbi_mutate(ho, 0, *TC.VIT, 0)
+            finally:
+                orc.align_destroy(ho)
+        assert api.batch_viterbi_mutate([hs[0], hs[2]], [rngs[0], rngs[2]], 0, *TC.VIT) == [api.viterbi_mutate(hs[k], 0, *TC.VIT, 0) for k in (0, 2)]
+        for h, r, name in zip(hs, regs, names):      # (last: scoring writes the alignments back, which the walk reads)
+            assert api.score_alignments(h, len(r[1])).tolist() == list(EC.oracle_calls(name)["ScoreEvents"]), name
+    finally:
+        for g in rngs:
+            api.rng_destroy(g)
+        for h in hs:
+            api.align_destroy(h)
 
 
 # ---- tier D ---------------------------------------------------------------------------------------------------------------------

@@ -7,9 +7,16 @@ recursion (viterbi_ref.fwd_error, units of 2^-53); the device must stay within 4
 reach on the same rows (device exp / log are 1-2 ulp where libm is under 1, and the sums associate differently).
 
 Measured maxima of the oracle, units of 2^-53: 2.1 at T = 1, 27 at T = 9, 42 at T = 33, 27 .. 33 over the trough cases, 16 .. 38 over
-the regions.  The device's figures have NOT been measured on an MI355X yet (every test prints both figures before it asserts); a
-float64 restatement of the device's scheme on the CPU (family sums, one power-of-two scale per step) reaches 1.7 / 6.8 / 9.3 and
-8.1 .. 10.5 on the same rows, and with the earlier every-8-steps scale its totals reach 0 in the -150 and -300 troughs.
+the regions.  The device on an MI355X (every test prints both figures before it asserts): 1.7 at T = 1, 7.4 at T = 9, 8.8 at
+T = 33, 8.6 .. 12.2 over the trough cases, 8.7 .. 12.5 over the regions; a float64 restatement of the device's scheme on the CPU
+(family sums, one power-of-two scale per step) reaches 1.7 / 6.8 / 9.3 and 8.1 .. 10.5 on the same rows, and with the earlier
+every-8-steps scale its totals reach 0 in the -150 and -300 troughs.
+
+Rows that kill the max-plus vector (viterbi_cases.DEAD_CASES: -inf rows, rows below -1e300, running scores that pass -1e300, half
+dead rows, one live state, live scores that absorb every addend): back-pointers of -1 and scores of exactly -1e300 must come out of
+the family reduction bit for bit; the forward rule holds on the rows before the reference's own vector dies (device 3.4 .. 8.0
+against the oracle's 12.1 .. 25.5 there) and a dead vector is required after; the deterministic back-trace is refused where it
+would follow a -1.
 """
 
 import numpy as np
@@ -120,6 +127,86 @@ def test_back_steps_one_by_one(nkeep, T, seed):
     assert np.all(hip["paths"][:, T - 1] == start)
     assert not K.check_back_steps(hip["paths"], V.run_ld(rows, K.SKIP, K.STAY), rnd, nkeep, min_margin=2.0 ** -40)
     assert np.array_equal(hip["paths"], orc["paths"])
+
+
+# ---- rows that kill the max-plus vector, wholly or partly (viterbi_cases.DEAD_CASES; tests/test_viterbi_tables.py pins what each
+# case does to the ordered scan and to the reference's forward vector) -----------------------------------------------------------
+def check_forward_until_dead(hip, orc, rows, what):
+    """check_forward on the rows before the first whose long-double total is 0; from that row on the reference carries NaN and the
+    device's vector must be dead as well: every row total 0 or NaN, which makes k_vit_trace fall through to the last state as the
+    reference does (the paths, compared exactly, say that it did)"""
+    _, alive = K.run_ld_until_dead(rows, K.SKIP, K.STAY)
+    assert np.all(np.isnan(orc["fwd"][alive:])) and np.all(np.isfinite(orc["fwd"][:alive]))
+    if alive:
+        check_forward({"fwd": hip["fwd"][:alive]}, {"fwd": orc["fwd"][:alive]}, rows[:alive], what)
+    tot = hip["fwd"][alive:].sum(axis=1)
+    assert np.all((tot == 0) | np.isnan(tot)), (what, tot)
+
+
+@pytest.mark.parametrize("name", tuple(K.DEAD_CASES))
+def test_dead_rows_tables_and_stochastic_paths(name):
+    """back-pointers (-1 where no candidate is above -1e300) and final scores exact through the family reduction: members at exactly
+    -1e300, `second` on the sentinel, live scores that absorb every addend; 16 stochastic paths the oracle's"""
+    T = K.DEAD_CASES[name][0]
+    rows = K.dead_rows(name)
+    rnd = K.deviates(16, T, K.DEAD_SEED.get(name, 5))
+    hip, orc = run_steps(rows, rnd, 16)
+    check_exact(hip, orc, rows)
+    assert K.dead_counts(hip["bp"]) == K.DEAD_CASES[name][2]
+    assert np.array_equal(hip["paths"], orc["paths"])
+    check_forward_until_dead(hip, orc, rows, name)
+    if name in K.DEAD_SEED:
+        assert not K.check_back_steps(hip["paths"], V.run_ld(rows, K.SKIP, K.STAY), rnd, 16, min_margin=2.0 ** -40)
+
+
+@pytest.mark.parametrize("name", tuple(K.DEAD_CASES))
+def test_dead_rows_deterministic_decode(name):
+    """nkeep = 0: a path that meets a back-pointer of -1 is refused by both backends, naming the first dead position; the partly dead
+    cases and T = 1 return the oracle's path, which holds no -1"""
+    rows = K.dead_rows(name)
+    if name in K.FULLY_DEAD:
+        for api in (_capi.load_hip(), B.oracle_api()):
+            K.refused_steps(api, [rows], 0, K.FIRST_DEAD[name])
+        # the library is as usable as before
+        live = K.random_rows(9, 31)
+        hip, orc = run_steps(live, None, 0)
+        check_exact(hip, orc, live)
+        assert np.array_equal(hip["paths"], orc["paths"])
+    else:
+        hip, orc = run_steps(rows, None, 0)
+        check_exact(hip, orc, rows)
+        assert np.array_equal(hip["paths"], orc["paths"]) and hip["paths"].min() >= 0
+        if name == "T1_neginf":
+            assert hip["paths"].tolist() == [[0]]
+
+
+@pytest.mark.parametrize("at", range(K.SWEEP_T))
+def test_a_dead_row_at_every_index(at):
+    """an all -inf row in each phase of the unrolled 4 + 4 loop and of its prefetch clamp"""
+    rows = K.sweep_rows(at)
+    hip, orc = run_steps(rows, K.deviates(16, K.SWEEP_T, at), 16)
+    check_exact(hip, orc, rows)
+    assert K.dead_counts(hip["bp"]) == (0,) * at + (1024,) * (K.SWEEP_T - at)
+    assert np.array_equal(hip["paths"], orc["paths"])
+    check_forward_until_dead(hip, orc, rows, "dead row %d of %d" % (at, K.SWEEP_T))
+    K.refused_steps(_capi.load_hip(), [rows], 0, at)
+
+
+def test_batch_with_a_dead_region():
+    """R = 3 of (dead from row 4, T = 0, live): under stochastic back-traces each region's tables equal its run alone by bytes; the
+    deterministic decode of the batch is refused as a whole and names region 0"""
+    hip = _capi.load_hip()
+    rows, rnd = K.dead_batch()
+    got = hip.debug_viterbi_steps(rows, rnd, 16, *ARGS)
+    assert [g["T"] for g in got] == [9, 0, 17]
+    for r in (0, 2):
+        alone = hip.debug_viterbi_steps([rows[r]], [rnd[r]], 16, *ARGS)[0]
+        for k in TABLES:
+            assert got[r][k].tobytes() == alone[k].tobytes(), (r, k)
+        check_exact(got[r], alone, rows[r])
+    K.refused_steps(hip, rows, 0, 4)
+    K.refused_steps(hip, rows[::-1], 2, 4)
+    assert np.array_equal(hip.debug_viterbi_steps(rows[1:], None, 0, *ARGS)[1]["paths"], B.oracle_api().debug_viterbi_steps(rows[2:], None, 0, *ARGS)[0]["paths"])
 
 
 # ---- the handle hook: vit_gather, the emission kernel, steps, log, trace on real AlignData -----------------------------------

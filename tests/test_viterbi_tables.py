@@ -2,7 +2,11 @@
 and the preconditions of the crafted inputs that tests/test_hip_viterbi_tables.py feeds to the HIP kernels.  No GPU needed.
 
 The oracle's forward vectors (serial float64 sums, libm exp, normalised every step) measured against the long-double recursion,
-in units of 2^-53 (viterbi_ref.fwd_error): 2.1 at T = 1, 27 at T = 9, 42 at T = 33, 27 .. 33 over the trough cases."""
+in units of 2^-53 (viterbi_ref.fwd_error): 2.1 at T = 1, 27 at T = 9, 42 at T = 33, 27 .. 33 over the trough cases.
+
+Rows that kill the max-plus vector (viterbi_cases.DEAD_CASES) are pinned here first: how many back-pointers of -1 each row gets
+under the ordered scan, where the reference's forward vector dies, that the oracle refuses the deterministic back-trace there
+ and what it names, and that the deviates of the partly dead cases keep clear of every boundary."""
 import numpy as np
 import pytest
 
@@ -101,6 +105,105 @@ def test_steps_batch_equals_regions_alone():
         alone = steps(rows[r], rnd[r], 4)
         for k in ("bp", "lik_final", "fwd", "paths"):
             assert np.array_equal(got[r][k], alone[k]), (r, k)
+
+
+# ---- rows that kill the max-plus vector (viterbi_cases.DEAD_CASES) -----------------------------------------------------------------
+def walk(bp, lik):
+    """the deterministic path by the rule of DESIGN.md section 2; bp[0] is not followed"""
+    c, out = int(np.argmax(lik)), []
+    for i in range(len(bp) - 1, -1, -1):
+        out.append(c)
+        assert i == 0 or bp[i][c] >= 0
+        c = int(bp[i][c])
+    return out[::-1]
+
+
+@pytest.mark.parametrize("name", tuple(K.DEAD_CASES))
+def test_dead_rows_are_what_their_names_say(name):
+    """the preconditions of the dead-row tests: back-pointers of -1 per row as listed, by the ordered scan and by the oracle; final
+    scores of the fully dead cases all -1e300 (of `straddle` all -9.9e299: the live states tie exactly); the deterministic decode
+    refused where the last row is dead and T > 1, the ordered scan's own path otherwise"""
+    T, _, counts = K.DEAD_CASES[name]
+    rows = K.dead_rows(name)
+    assert rows.shape == (T, V.NS) and not np.any(np.isnan(rows))
+    bp, lik = V.run64(rows, K.SKIP, K.STAY)
+    assert K.dead_counts(bp) == counts
+    got = steps(rows, K.deviates(16, T, 5), 16)
+    assert np.array_equal(got["bp"], bp) and np.array_equal(got["lik_final"], lik)
+    if name == "accum":
+        assert rows.min() > -1e300
+    if name == "below_big":
+        assert np.all(np.isfinite(rows))
+    if name in K.FULLY_DEAD or name == "T1_neginf":
+        assert np.all(lik == -1e300)
+    if name == "straddle":
+        assert np.all(lik == -9.9e299)
+    if name in K.FULLY_DEAD:
+        assert counts[K.FIRST_DEAD[name]] == 1024 and (K.FIRST_DEAD[name] == 0 or counts[K.FIRST_DEAD[name] - 1] == 0)
+        K.refused_steps(B.oracle_api(), [rows], 0, K.FIRST_DEAD[name])
+    else:
+        path = steps(rows)["paths"][0].tolist()
+        assert path == walk(bp, lik) and min(path) >= 0
+        if name == "T1_neginf":
+            assert path == [0]
+
+
+@pytest.mark.parametrize("at", range(K.SWEEP_T))
+def test_a_dead_row_at_every_index(at):
+    rows = K.sweep_rows(at)
+    bp, lik = V.run64(rows, K.SKIP, K.STAY)
+    assert K.dead_counts(bp) == (0,) * at + (1024,) * (K.SWEEP_T - at) and np.all(lik == -1e300)
+    got = steps(rows, K.deviates(16, K.SWEEP_T, at), 16)
+    assert np.array_equal(got["bp"], bp) and np.array_equal(got["lik_final"], lik)
+    assert np.all(np.isnan(got["fwd"][at:])) and np.all(np.isfinite(got["fwd"][:at]))
+    # a back-step from position i weighs with the forward row of position i: over a dead row it falls through to the last state
+    assert np.all(got["paths"][:, max(at - 1, 0):K.SWEEP_T - 1] == V.NS - 1)
+    K.refused_steps(B.oracle_api(), [rows], 0, at)
+
+
+@need_ld
+@pytest.mark.parametrize("name", tuple(K.DEAD_CASES))
+def test_dead_rows_forward_vectors(name):
+    """the reference's forward vector dies (0 / 0, NaN to the end) at the first row whose exp(obs) is 0 for every state that has
+    weight — row 4, row 2 of `accum`, never for the two cases that keep live states with ordinary emissions; the oracle's rows before
+    that stand against the long-double recursion as everywhere else"""
+    T = K.DEAD_CASES[name][0]
+    rows = K.dead_rows(name)
+    ref, alive = K.run_ld_until_dead(rows, K.SKIP, K.STAY)
+    want = {"neginf_mid": 4, "neginf_first": 0, "neginf_last": 8, "below_big": 4, "accum": 2, "half_neginf": 9, "one_alive": 9, "straddle": 4,
+            "T1_neginf": 0}[name]
+    assert alive == want
+    got = steps(rows, K.deviates(16, T, 5), 16)
+    assert np.all(np.isnan(got["fwd"][alive:])) and np.all(np.isfinite(got["fwd"][:alive]))
+    if alive:
+        err = V.fwd_error(got["fwd"][:alive], ref)
+        print("oracle forward error, %s: %.1f units of 2^-53" % (name, err))
+        assert err < 250.0
+
+
+@need_ld
+@pytest.mark.parametrize("name", tuple(K.DEAD_SEED))
+def test_partly_dead_back_steps_and_deviate_margins(name):
+    """every stochastic back-step of the oracle over the partly dead rows is the long-double pick, and no deviate of the chosen seed
+    lies within 2^-40 of a boundary (the GPU test excuses no step on the strength of this)"""
+    rows = K.dead_rows(name)
+    rnd = K.deviates(16, len(rows), K.DEAD_SEED[name])
+    got = steps(rows, rnd, 16)
+    assert not K.check_back_steps(got["paths"], V.run_ld(rows, K.SKIP, K.STAY), rnd, 16, min_margin=2.0 ** -40)
+
+
+def test_steps_batch_with_a_dead_region():
+    """a dead region beside a live one: both equal their runs alone under stochastic back-traces, and the deterministic decode of the
+    batch is refused as a whole, naming region 0"""
+    rows, rnd = K.dead_batch()
+    got = B.oracle_api().debug_viterbi_steps(rows, rnd, 16, *ARGS)
+    for r in (0, 2):
+        alone = steps(rows[r], rnd[r], 16)
+        for k in ("bp", "lik_final", "fwd", "paths"):
+            assert np.array_equal(got[r][k], alone[k], equal_nan=k == "fwd"), (r, k)
+    K.refused_steps(B.oracle_api(), rows, 0, 4)
+    rows[0], rows[2] = rows[2], rows[0]
+    K.refused_steps(B.oracle_api(), rows, 2, 4)
 
 
 @pytest.mark.parametrize("key", K.REGIONS[2:4])

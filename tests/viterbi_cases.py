@@ -52,6 +52,81 @@ def equal_rows():
     return np.full((9, NS), -3.25)
 
 
+# ---- rows that kill the max-plus vector, wholly or partly.  k_vit_steps starts every maximum at -1e300 with back-pointer -1 (as the
+# reference): a state none of whose candidates is above -1e300 keeps both, and once a whole row has, every later sum rounds back to
+# -1e300 and every later row is dead too.  name -> (T, [(rows, states, value)], back-pointers of -1 per row)
+DEAD_BASE = (9, 7)                     # random_rows(T, seed)
+_ALL, _EVEN, _ODD = slice(None), slice(0, None, 2), slice(1, None, 2)
+_MID = (0, 0, 0, 0, 1024, 1024, 1024, 1024, 1024)
+DEAD_CASES = {
+    "neginf_mid": (9, [(4, _ALL, -np.inf)], _MID),
+    "neginf_first": (9, [(0, _ALL, -np.inf)], (1024,) * 9),
+    "neginf_last": (9, [(8, _ALL, -np.inf)], (0,) * 8 + (1024,)),
+    "below_big": (9, [(4, _ALL, -2e300)], _MID),                                  # finite, below the sentinel
+    "accum": (9, [(slice(2, 6), _ALL, -3.5e299)], _MID),                          # no row below -1e300: the running score passes it at row 4
+    "half_neginf": (9, [(4, _EVEN, -np.inf)], (0, 0, 0, 0, 512, 64, 0, 0, 0)),
+    "one_alive": (9, [(4, _ALL, -np.inf), (4, 5, -3.0)], (0, 0, 0, 0, 1023, 939, 0, 0, 0)),
+    # live scores of -9.9e299 absorb every later addend: all live states tie exactly for the rest of the table
+    "straddle": (9, [(4, _EVEN, -1.5e300), (4, _ODD, -9.9e299)], (0, 0, 0, 0, 512, 64, 0, 0, 0)),
+    "T1_neginf": (1, [(0, _ALL, -np.inf)], (1024,)),
+}
+FULLY_DEAD = ("neginf_mid", "neginf_first", "neginf_last", "below_big", "accum")       # deterministic decode refused
+FIRST_DEAD = {"neginf_mid": 4, "neginf_first": 0, "neginf_last": 8, "below_big": 4, "accum": 4}   # the kept position the refusal names
+PARTLY_DEAD = ("half_neginf", "one_alive", "straddle")                                 # a path exists
+SWEEP_T = 17                            # an all -inf row at every index of random_rows(17, 7): each phase of the 4 + 4 unrolled loop
+UNREACHABLE = "no state is reachable at kept position %d "
+# deviate seeds of the nkeep = 16 runs: test_viterbi_tables.py asserts that none of these puts a deviate within 2^-40 of a boundary
+DEAD_SEED = {"half_neginf": 41, "one_alive": 42}
+
+
+def dead_rows(name):
+    T, changes, _ = DEAD_CASES[name]
+    rows = random_rows(*DEAD_BASE)[:T].copy()
+    for r, s, v in changes:
+        rows[r, s] = v
+    return rows
+
+
+def dead_batch():
+    """(rows, deviates for nkeep = 16) of R = 3: a region that dies at row 4, one without positions, a live one"""
+    rows = [dead_rows("neginf_mid"), random_rows(0, 32), random_rows(17, 33)]
+    return rows, [deviates(16, 9, 31), np.zeros((16, 0)), deviates(16, 17, 33)]
+
+
+def sweep_rows(at):
+    rows = random_rows(SWEEP_T, 7)
+    rows[at] = -np.inf
+    return rows
+
+
+def dead_counts(bp):
+    return tuple(int(n) for n in np.count_nonzero(np.asarray(bp) == -1, axis=1))
+
+
+def run_ld_until_dead(rows, skip, stay):
+    """(long-double forward rows before the first whose total is 0, that row's index or T): from there the reference normalises
+    0 / 0 and carries NaN"""
+    f = np.asarray(V.start()[1], dtype=V.LD)
+    out = []
+    for t, o in enumerate(rows):
+        with np.errstate(all="ignore"):
+            f = V.step_ld(f, o, skip, stay)
+        if not np.all(np.isfinite(f)):
+            return np.array(out, dtype=V.LD).reshape(len(out), NS), t
+        out.append(f)
+    return np.array(out, dtype=V.LD).reshape(len(out), NS), len(rows)
+
+
+def refused_steps(api, rows_list, region, position):
+    """the deterministic decode of these rows is refused, naming the hook, the region and the kept position"""
+    import pytest
+    from poreseq_amd._capi import PoreseqError
+    with pytest.raises(PoreseqError) as err:
+        api.debug_viterbi_steps(rows_list, None, 0, SKIP, STAY, MMIN, MMAX)
+    msg = str(err.value)
+    assert "(-1)" in msg and "ps_debug_viterbi_steps: region %d: " % region in msg and UNREACHABLE % position in msg, msg
+
+
 def deviates(nkeep, T, seed):
     """[nkeep][T] on the generator's 2^-31 grid, with the grid's two ends at a few back-steps"""
     r = np.random.default_rng(seed).integers(0, 2 ** 31, (nkeep, T)).astype(np.float64) / 2.0 ** 31
