@@ -297,6 +297,50 @@ int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, do
                             double* scores /* [M] or NULL */, ps_edit_link* link /* [M][window] */, ps_edit_phase* phase /* [M] */,
                             ps_event_hap* hap /* [n_events][max_sets] or NULL */, int32_t* n_sets /* one, or NULL */);
 
+/* Alignment census and the sums of a shift / scale refit, per event, reduced on the device from the alignment the handle holds
+ * (k_align_stats).  The pore model of every read arrives scaled by numbers that were fitted before the read was aligned to
+ * anything (EventData.py:140-168); with an event-to-sequence alignment in hand they can be refitted by weighted least squares of
+ * the level means against the model means of the states they aligned to.  The library returns the sufficient statistics; the fit
+ * itself is six lines on the host (poreseq_amd.util.fit_scaling).
+ *
+ * realign != 0 runs exactly ps_score_alignments' chain first — forward fill, then backtrace per event — and `scores` (may be NULL)
+ * gets the bits ps_score_alignments returns.  The realignment stays in the handle as after any scoring call (a resident driver
+ * announces the call with ps_align_new_call + ps_align_keep_refs); the records are reduced from the refs the backtrace just wrote,
+ * in the same launch chain, and scores and records come back in one device-to-host copy.
+ * realign == 0 reduces the refs the handle holds now and launches no DP; `scores` must then be NULL (PS_ERR_BAD_ARG otherwise).
+ * A NULL `stats` is PS_ERR_BAD_ARG.  An AlignData without events is PS_OK and launches nothing.
+ *
+ * One event's record.  The event has n levels with ra[i] (ref_align) and mean[i]; the sequence has S states, states[j - 1]
+ * belonging to DP column j (cpp/Alignment.cpp:125); the event's model rows are m_k = level_mean[k], s_k = level_stdv[k].
+ *   A level is ALIGNED iff ra[i] > 0 (the test of cpp/EventData.h:121), INSERTED iff ra[i] < 0, UNALIGNED otherwise (0, NaN); its
+ *   column is c = (int)fmin(ra[i], 2147483647.0).  n_levels = n; n_aligned, n_insert, n_unaligned count the three kinds.
+ *   first_col / last_col   the columns of the first and the last aligned level, both 0 when there is none.
+ *   Census.  Walk in level order carrying p, the column of the previous ALIGNED level, and prev_rep; inserted and unaligned
+ *       levels in between change neither.  An aligned level with a predecessor has d = c - p:  d == 0: n_extend++ if prev_rep,
+ *       else n_stay++;  d == 1: n_step++;  d > 1: n_jump++ and n_gap_cols += d - 1;  d < 0: n_back++.  Then prev_rep = (d == 0).
+ *       The first aligned level sets prev_rep = false.
+ *       The census is of the ref ARRAY, not of the path's moves: a -1 level is either U_INSERT or UL_IGNORE
+ *       (cpp/Alignment.cpp:559-573) and the array cannot tell them apart; a "stay" here is a repeated column, whatever move made it.
+ *   Fit terms.  An aligned level with 1 <= c <= S and k = states[c - 1] >= 0 enters the fit and counts in n_fit; any other aligned
+ *       level (a column past the sequence, a column 0 from an entry in (0, 1), a 5-mer with a base outside ACGT) counts in n_nostate.
+ *       For a level that enters, every operation rounded once (IEEE double, no contraction):
+ *           w = 1.0 / (s_k * s_k);  wm = w * m_k;  r = mean[i] - m_k;
+ *           sw += w;  swm += wm;  swmm += wm * m_k;  swr += w * r;  swmr += wm * r;  swrr += (w * r) * r.
+ *   Order of the adds (a host can reproduce the bits, as for ps_event_hap): partial t = +0.0 takes the qualifying levels
+ *       i = t, t + 256, t + 512, ... ascending; the 256 partials are then added into +0.0 for t = 0 .. 255.
+ * The batch form is one launch for all regions; a batch whose realignment does not fit device memory is cut between AlignData,
+ * never inside one.  Not part of the reference's interface.  Not built: drift (the ABI carries no level times), the stdv channel's
+ * scale_sd / var_sd (the inverse Gaussian has no closed form), per-k-mer model re-estimation, and transition parameters (they need
+ * the backtrace's moves, not the array). */
+typedef struct ps_event_stats {
+    int32_t n_levels, n_aligned, n_insert, n_unaligned;
+    int32_t n_step, n_stay, n_extend, n_jump, n_back;
+    int32_t n_nostate, n_fit, first_col, last_col, reserved /* 0 */;
+    int64_t n_gap_cols;
+    double sw, swm, swmm, swr, swmr, swrr;
+} ps_event_stats;   /* 112 bytes, no padding */
+int ps_align_stats(ps_align* a, int32_t realign, double* scores /* [E] or NULL */, ps_event_stats* stats /* [E] */);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -362,6 +406,8 @@ int ps_batch_score_mutation_genotypes(int32_t n, ps_align* const* a, const ps_mu
 int ps_batch_score_mutation_phase(int32_t n, ps_align* const* a, const ps_muts* const* muts, const int32_t* window /* [n] */,
                                   const double* min_link /* [n] */, const int32_t* max_sets /* [n] */, double* const* scores,
                                   ps_edit_link* const* link, ps_edit_phase* const* phase, ps_event_hap* const* hap, int32_t* const* n_sets);
+/* ps_align_stats for every AlignData in one launch chain and ONE copy back: stats[i] has n_events(i) records (never NULL, also for an AlignData without events); with realign != 0 scores[i] — entries or the whole array may be NULL — has n_events(i) entries, with realign == 0 every scores[i] must be NULL. */
+int ps_batch_align_stats(int32_t n, ps_align* const* a, int32_t realign, double* const* scores, ps_event_stats* const* stats);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -445,7 +491,8 @@ int ps_set_device_fraction(double fraction);
  * algorithmic bytes of the named kernel class ("fill" = k_fill, "sweep" = the strip sweeps k_sweep / k_sweeps / k_sweep2 and their _w builds,
  * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written, "genotype" = k_genotype: 8 per (event, edit) read, 8 (n_frac + 1) + 4 per edit written,
  * "link" = k_link: 8 per (event, edit) read, 32 window per edit written, "phase" = k_phase: 32 window per edit read, 16 per edit written,
- * "haptag" = k_haptag: 8 per (event, edit) and 16 per edit read, 24 max_sets per event written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
+ * "haptag" = k_haptag: 8 per (event, edit) and 16 per edit read, 24 max_sets per event written,
+ * "align_stats" = k_align_stats: 16 per level read, 112 per event written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
  * "fill_pair" / "fill_pair_fwd" / "fill_cmp" / "fill_512" / "fill_1024" / "fill_wide" (which form a k_fill launch took), "score_g7" .. "score_g64"
  * (k_score's size classes) and "fill_ieee" / "sweep_ieee" / "score_ieee" (launches that took the IEEE-division build);
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =

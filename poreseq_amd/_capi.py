@@ -59,6 +59,11 @@ EDIT_PHASE = np.dtype([("vote", np.float64), ("hap", np.int32), ("set", np.int32
 EVENT_HAP = np.dtype([("lik1", np.float64), ("lik2", np.float64), ("n1", np.int32), ("n2", np.int32)])
 LINK_MAX_WINDOW = 8
 PHASE_MAX_SETS = 8
+# ps_event_stats (112 bytes, no padding): one event's alignment census and the sums of its scaling fit, what align_stats /
+# batch_align_stats hand out
+EVENT_STATS = np.dtype([(k, np.int32) for k in ("n_levels", "n_aligned", "n_insert", "n_unaligned", "n_step", "n_stay", "n_extend", "n_jump",
+                                                "n_back", "n_nostate", "n_fit", "first_col", "last_col", "reserved")] +
+                       [("n_gap_cols", np.int64)] + [(k, np.float64) for k in ("sw", "swm", "swmm", "swr", "swmr", "swrr")])
 
 
 class PoreseqError(Exception):
@@ -112,6 +117,8 @@ SYMBOLS = {
     "ps_score_mutation_phase": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, c_dp, C.c_void_p, C.c_void_p, C.c_void_p, c_i32p]),
     "ps_batch_score_mutation_phase": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i32p, c_dp, c_i32p, C.POINTER(c_dp),
                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i32p)]),
+    "ps_align_stats": (C.c_int, [C.c_void_p, C.c_int32, c_dp, C.c_void_p]),
+    "ps_batch_align_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(c_dp), C.POINTER(C.c_void_p)]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -151,9 +158,10 @@ SYMBOLS = {
 # library does export (sw_summaries from swfull; PSAlign.ScoreSequences runs the reference's loop of Copy / RealignTo / ScoreEvents;
 # PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations; PSAlign.ScoreMutationSupport reduces
 # score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas, and PSAlign.ScoreMutationGenotypes does the
-# same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas).
+# same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas;
+# PSAlign.AlignStats reduces the refs the library holds with util.align_stats_from_refs, after its score_alignments).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
+OPTIONAL = frozenset(["ps_align_stats", "ps_batch_align_stats", "ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
                       "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes",
                       "ps_score_mutation_phase", "ps_batch_score_mutation_phase"])
@@ -498,6 +506,25 @@ class CApi:
                                                           mxs.ctypes.data_as(c_i32p), sp, vp(links), vp(phases),
                                                           vp(haps) if want_hap else None, np_))
         return [(scores[i], links[i], phases[i], haps[i], int(nsets[i])) for i in range(R)]
+
+    def align_stats(self, h, n_events, realign=True):
+        """-> (scores float64 [E] or None, stats EVENT_STATS [E]): ps_align_stats of one AlignData"""
+        return self.batch_align_stats([h], [n_events], realign)[0]
+
+    def batch_align_stats(self, hs, n_events, realign=True):
+        """ps_batch_align_stats over the AlignData `hs` with n_events[i] events: per event the census of its ref_align array and
+        the sums of the shift / scale fit of its model (include/poreseq_hip.h has the definition), one launch of k_align_stats and
+        one copy back -> [(scores float64 [E] or None, stats EVENT_STATS [E])].  realign=True runs ScoreAlignments' chain first
+        (scores are score_alignments' bits and the realignment stays in the handle); realign=False reduces the refs the handle
+        holds, launches no DP and returns None for the scores."""
+        self._need("ps_batch_align_stats")
+        R = len(hs)
+        recs = [np.zeros(max(int(e), 1), dtype=EVENT_STATS) for e in n_events]      # (one spare record: never a null pointer)
+        scores = [np.zeros(max(int(e), 1), dtype=np.float64) for e in n_events] if realign else None
+        rp = (C.c_void_p * max(R, 1))(*[r.ctypes.data_as(C.c_void_p) for r in recs])
+        sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores]) if realign else None
+        self.check(self.lib.ps_batch_align_stats(R, self._harr(hs), 1 if realign else 0, sp, rp))
+        return [(scores[i][:int(e)] if realign else None, recs[i][:int(e)]) for i, e in enumerate(n_events)]
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

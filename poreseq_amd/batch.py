@@ -164,6 +164,36 @@ class RegionBatch:
             self._close(idx, hs, write_back=False)
         return [s.tolist() for s in sc]
 
+    def AlignStats(self, idx=None, realign=True):
+        """PSAlign.AlignStats for the regions `idx` in lock-step: ONE ps_batch_align_stats call — with realign the launch chain of
+        ScoreEvents over all regions, then one k_align_stats launch over all their events, one copy back.  Returns one (scores
+        float64 [E] or None, stats _capi.EVENT_STATS [E]) per region; sequences and events are not modified (a resident handle's
+        refs come out as they went in)."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        hs = self._open(idx, keep=True)
+        try:
+            if "ps_batch_align_stats" in self.api.missing:
+                return [poreseqcpp._align_stats_on(self.api, h, self.pas[i].events, bool(realign)) for i, h in zip(idx, hs)]
+            return self.api.batch_align_stats(hs, [len(self.pas[i].events) for i in idx], bool(realign))
+        finally:
+            self._close(idx, hs, write_back=False)
+
+    def Recalibrate(self, idx=None, var=True, **fit_kw):
+        """PSAlign.Recalibrate for the regions `idx`: one lock-step AlignStats, then util.fit_scaling / util.apply_scaling on the
+        Python events' models.  A resident AlignData holds the models it was created with, so the handles of the regions whose
+        models changed are written back (sync) and dropped; the next call rebuilds them.  Returns one list of fits per region."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        out = []
+        for i, (_, stats) in zip(idx, self.AlignStats(idx, realign=True)):
+            fits = poreseqcpp._recalibrate(self.pas[i].events, stats, var, fit_kw)
+            if any(f.ok for f in fits) and i in self._h:
+                self.sync([i])
+                self.drop([i])
+            out.append(fits)
+        return out
+
     def ScoreSequences(self, seqs_per_region, idx=None):
         """PSAlign.ScoreSequences for the regions `idx` on their resident AlignData, all regions' sequences in one chain:
         seqs_per_region[k] are the candidate sequences of region idx[k] (may be empty).  Returns one ndarray

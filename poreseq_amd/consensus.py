@@ -43,7 +43,14 @@ def test_start(events, refseq, summaries):
     return seq, chosen
 
 
-def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None):
+def _recalibrate_kw(recalibrate):
+    """None / False: no recalibration; True: the defaults; a dict: keyword arguments of Recalibrate (var and util.fit_scaling's)"""
+    if recalibrate is None or recalibrate is False:
+        return None
+    return dict(recalibrate) if isinstance(recalibrate, dict) else {}
+
+
+def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None, recalibrate=None):
     """Run the consensus schedule in place on `pa`; returns (sequence, accuracy_vs_refseq).
 
     The call sequence is the reference's (Mutate.py:39-101) and has to be: a region with fewer than 5 events is handed
@@ -58,6 +65,10 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     (util.phred_from_margin of one PointTable pass after the schedule's last call, cut by the same `end_trim` slice; uncalibrated),
     or None for a region handed back untouched.  The pass changes nothing else: sequence, accuracy, log and the events' ref_align /
     ref_like are what they are without it, and it draws no random numbers.
+    `recalibrate` (not in the reference; off by default): True, or a dict of keyword arguments for it, runs one `pa.Recalibrate()`
+    before Mutate('self') — every read's model shift / scale / var refitted on its alignment to the start sequence
+    (util.fit_scaling), in place on the events' models — and logs ("Recalibrate", reads whose model changed, sequence).  None or
+    False is the schedule as it is without the argument: same calls, same log, same random draws.  Unmeasured on real data.
     """
     params = pa.params if params is None else params
     pa.params.setdefault('verbose', 0)
@@ -83,6 +94,10 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
             log.append((name, n, pa.sequence))
         return n
 
+    recal = _recalibrate_kw(recalibrate)
+    if recal is not None:
+        changed = call("Recalibrate", lambda: sum(1 for f in pa.Recalibrate(**recal) if f.ok))
+        _report(verbose, "recalibrated the models of %d of %d reads" % (changed, len(pa.events)))
     call("Mutate:self", lambda: pa.Mutate(reps=reps))
     if verbose > 0:
         _report(verbose, "identity after seeding from the reads: %.1f%%" % identity(pa.sequence, refseq)[0])
@@ -112,7 +127,7 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
 
 
 def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True, test=False, accuracies=None,
-                      qualities=None):
+                      qualities=None, recalibrate=None):
     """The consensus schedule of `consensus_region` for several independent regions in lock-step (poreseq_amd.batch):
     every PSAlign call of the schedule is issued once for all regions that still take part in it, so each phase is one
     launch chain on the GPU.  Returns [(sequence, accuracy)] in the order of `pas`; each entry equals what
@@ -129,6 +144,8 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
     returned sequence (see consensus_region), None for a region with fewer than 5 events.  They come from ONE lock-step
     RegionBatch.PointTable(table=False) over all refined regions after the schedule's last call; everything else the function returns
     or writes is bit for bit what it is without `qualities`.
+    `recalibrate`: as consensus_region takes it; one lock-step RegionBatch.Recalibrate over all refined regions before Mutate('self'),
+    logged per region as ("Recalibrate", reads whose model changed, sequence).  None or False: the schedule as it is without it.
     """
     from .batch import RegionBatch
     n = len(pas)
@@ -171,7 +188,11 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
                     batch.drop()
                     batch.close()
                 raise
+        recal = _recalibrate_kw(recalibrate)
         with (batch if batch is not None else RegionBatch(pas, resident=resident)) as rb:
+            if recal is not None:
+                for i, fits in zip(todo, rb.Recalibrate(todo, **recal)):
+                    note(i, "Recalibrate", sum(1 for f in fits if f.ok))
             tot = rb.Mutate(todo, reps=reps)
             for i in todo:
                 note(i, "Mutate:self", tot[i])

@@ -234,6 +234,31 @@ int ps_batch_score_alignments(int32_t n, ps_align* const* a, double* const* scor
     }
     return score_alignments_multi(rt, as, sc, lk);
 }
+int ps_batch_align_stats(int32_t n, ps_align* const* a, int32_t realign, double* const* scores, ps_event_stats* const* stats) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n && !stats) return fail(PS_ERR_BAD_ARG, "ps_batch_align_stats: null stats");
+    std::vector<double*> sc(n, nullptr);
+    std::vector<ps_event_stats*> st(n);
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        if (!stats[i]) return fail(PS_ERR_BAD_ARG, "ps_batch_align_stats: null stats");
+        if (scores && scores[i]) {
+            if (!realign) return fail(PS_ERR_BAD_ARG, "ps_batch_align_stats: scores without a realignment (realign == 0 launches no DP: scores must be NULL)");
+            sc[i] = scores[i];
+        }
+        st[i] = stats[i];
+        any = any || as[i]->E > 0;
+    }
+    if (!any) return PS_OK;   // (no events anywhere: nothing is launched)
+    NEED_RT();
+    return align_stats_multi(rt, as, realign != 0, sc, st);
+}
+int ps_align_stats(ps_align* a, int32_t realign, double* scores, ps_event_stats* stats) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_align_stats: null handle");
+    if (!stats) return fail(PS_ERR_BAD_ARG, "ps_align_stats: null stats");
+    return ps_batch_align_stats(1, &a, realign, &scores, &stats);
+}
 int ps_batch_find_mutations(int32_t n, ps_align* const* a, const ps_seqs* const* seeds, ps_muts** out) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

@@ -574,6 +574,72 @@ int score_alignments(Runtime* rt, Align* a, double* scores, double* likes) {
     return score_alignments_multi(rt, {a}, {scores}, {likes});
 }
 
+// ps_align_stats / ps_batch_align_stats (include/poreseq_hip.h): with `re`, ScoreAlignments' chain as above and then k_align_stats
+// over the refs the backtrace just wrote; without it k_align_stats over the refs the handles hold, and no DP.  Either way one
+// launch of it for all AlignData, and scores and records return in one copy.  scores[k] may be null.
+int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<double*>& scores, const std::vector<ps_event_stats*>& stats) {
+    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
+        return align_stats_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), re, std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
+                                 std::vector<ps_event_stats*>(stats.begin() + k0, stats.begin() + k1));
+    };
+    auto need = [&](size_t k) { return share_need(as[k], 1); };
+    if (re && over_share(as.size(), 1, need)) return in_share_chunks(as.size(), 1, need, sub);   // (cut between AlignData, as ScoreAlignments is)
+    std::vector<JobSpec> specs;
+    for (Align* a : as)
+        for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
+    if (specs.empty()) return PS_OK;
+    Batch b;   // (also without a realignment: it puts every sequence's states on the device)
+    PS_TRY(b.build(rt, specs, 1, 0));
+    if (re) {
+        const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
+        if (rc == PS_SPLIT) return in_halves(as.size(), sub);
+        PS_TRY(rc);
+        for (Align* a : as) a->host_refs_valid = false;
+    }
+    const size_t nj = specs.size();
+    std::vector<StatJob> sj(nj);
+    std::vector<StatRegion> sr(as.size());
+    int maxE = 0;
+    double bytes = 0;
+    {
+        size_t q = 0;
+        for (size_t k = 0; k < as.size(); k++) {
+            const Align* a = as[k];
+            sr[k].job0 = (int)q; sr[k].njobs = a->E;
+            maxE = std::max(maxE, a->E);
+            for (int e = 0; e < a->E; e++, q++) {
+                const JobD& j = b.jobs[q];
+                sj[q].ra = j.ra; sj[q].mean = a->d_mean + a->off[e]; sj[q].model = a->d_model + (size_t)e * 6 * NS;
+                sj[q].st = j.st; sj[q].n = j.n0; sj[q].S = j.C;
+                bytes += 16.0 * j.n0 + sizeof(ps_event_stats);
+            }
+        }
+    }
+    // descriptors in; records and, behind them, the scores out
+    const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
+    const size_t out_recs = nj * sizeof(ps_event_stats), out_bytes = out_recs + (re ? nj * sizeof(double) : 0);
+    DBuf& din = rt->buf("astats_in");
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(din.ensure(in_bytes));
+    PS_TRY(dout.ensure(out_bytes));
+    PS_TRY(rt->up(din.p, sj.data(), in_jobs));
+    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
+    PS_TRY(launch_align_stats(rt, din.as<StatJob>(), (const StatRegion*)((char*)din.p + in_jobs), (int)sr.size(), maxE, bytes, dout.as<ps_event_stats>()));
+    if (re) PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + out_recs)));
+    void* back = nullptr;
+    PS_TRY(rt->down(&back, dout.p, out_bytes));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    const ps_event_stats* recs = (const ps_event_stats*)back;
+    const double* best = (const double*)((const char*)back + out_recs);
+    size_t q = 0;
+    for (size_t k = 0; k < as.size(); k++)
+        for (int e = 0; e < as[k]->E; e++, q++) {
+            stats[k][e] = recs[q];
+            if (re && scores[k]) scores[k][e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
+        }
+    return PS_OK;
+}
+
 // One greedy pass of MakeMutations (ps_greedy.h: sort, apply, defer, shift) on the AlignData's sequence
 static int greedy_apply(Align* a, std::vector<Mut>& muts, std::vector<Mut>* later, bool talk) {
     bool changed = false;

@@ -139,6 +139,9 @@ int score_alignments(Runtime* rt, Align* a, double* scores, double* likes);
 // the *_multi forms run the same call for several AlignData (independent regions) in one launch chain
 void par_for(int n, const std::function<void(int)>& fn);
 int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes);
+// ps_batch_align_stats: per event the census of ref_align and the sums of the scaling fit (ps_stats.hip), after ScoreAlignments'
+// chain (re) or of the refs as they are; scores[k] may be null (must be without re), stats[k] has E records
+int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<double*>& scores, const std::vector<ps_event_stats*>& stats);
 int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seeds,
                          const std::vector<std::vector<Mut>*>& outs);
 // Every event of an AlignData aligned forward-only to a sequence that is not its own, for any number of such (AlignData, sequence)

@@ -312,6 +312,19 @@ int launch_score(Runtime* rt, const BatchD& b, const ScoreLaunch& L);
 int launch_begin(Runtime* rt, const BatchD& b);
 int launch_gather_best(Runtime* rt, const BatchD& b, double* out);   // out[job] = the job's forward maxScore (JobOut.best)
 
+// Alignment census and the sums of the scaling fit (ps_stats.hip, ps_align_stats): one event as k_align_stats sees it, and one
+// AlignData's events inside the call's list of them
+struct StatJob {
+    const double* ra;     // ref_align [n]
+    const double* mean;   // level means [n]
+    const double* model;  // the event's model, rows of NS: level_mean, level_stdv (the first two of d_model's six)
+    const int* st;        // 5-mer states of the sequence [S]
+    int n, S;
+};
+struct StatRegion { int job0, njobs; };
+// grid (maxE, nregs): out[job] for every job of every region; alg_bytes for the profile ("align_stats")
+int launch_align_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxE, double alg_bytes, ps_event_stats* d_out);
+
 // Smith-Waterman (ps_sw.hip)
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,
               std::vector<int>* inds1, std::vector<int>* inds2);

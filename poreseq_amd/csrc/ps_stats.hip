@@ -1,0 +1,150 @@
+// ps_stats.hip — ps_align_stats: the census of an event's ref_align array and the sufficient statistics of a shift / scale refit
+// of its model, reduced on the device (include/poreseq_hip.h has the definition of a record; this file follows it line by line).
+//
+//   k_align_stats   grid (events of the largest AlignData, AlignData), 256 threads per event, as the reductions of ps_edit.hip
+//
+// The levels are read coalesced in tiles of 256.  What the census needs of a level — the column of the previous ALIGNED level and
+// whether that level repeated its own predecessor — is "the last two aligned columns in front of it", and those come from a scan:
+// a run of levels is summarised by a Tail (how many aligned levels it holds, capped at two, and the columns of its last two), two
+// runs are joined by keeping the last two of both, which is associative.  A tile is scanned within each wavefront by cross-lane
+// moves (six steps over 64 lanes), the four wavefronts meet through LDS, and the tile's Tail is carried to the next.  No level
+// ever looks back over the array: a run of -1 levels costs what any other run costs.
+// Accumulators live in registers and are never indexed by a runtime value.  Sums: thread t adds the qualifying levels t, t + 256,
+// ... in ascending order into partials that start at +0.0, and one thread per sum then adds the 256 partials in t order — the
+// order the header defines, which a host can replay bit for bit.  Counts are integers and are reduced in any order.
+#include "ps_internal.h"
+
+namespace ps {
+
+static_assert(sizeof(ps_event_stats) == 112, "ps_event_stats has no padding");
+
+namespace {
+
+struct Tail { int n, c1, c2; };   // aligned levels in the run (0, 1, 2 = two or more); column of the last, of the one before it
+
+__device__ inline Tail tail_join(const Tail a, const Tail b) {   // the run a followed by the run b
+    Tail r;
+    r.n = b.n == 0 ? a.n : (b.n == 1 ? min(a.n + 1, 2) : 2);
+    r.c1 = b.n ? b.c1 : a.c1;
+    r.c2 = b.n == 2 ? b.c2 : (b.n == 1 ? a.c1 : a.c2);
+    return r;
+}
+__device__ inline Tail tail_up(const Tail x, int d) {   // lane l gets the Tail of lane l - d of its wavefront (lanes below d: their own)
+    Tail r;
+    r.n = __shfl_up(x.n, d, 64); r.c1 = __shfl_up(x.c1, d, 64); r.c2 = __shfl_up(x.c2, d, 64);
+    return r;
+}
+__device__ inline int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ inline long long wave_sum(long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+constexpr int ST_NCNT = 10;   // n_aligned, n_insert, n_unaligned, n_step, n_stay, n_extend, n_jump, n_back, n_nostate, n_fit
+
+__global__ __launch_bounds__(256) void k_align_stats(const StatJob* __restrict__ J, const StatRegion* __restrict__ R, ps_event_stats* __restrict__ out) {
+    const StatRegion rg = R[blockIdx.y];
+    if ((int)blockIdx.x >= rg.njobs) return;   // (the same for every thread of the block)
+    const StatJob j = J[rg.job0 + blockIdx.x];
+    __shared__ int s_tail[4][3];
+    __shared__ double s_sum[6][256];
+    __shared__ int s_cnt[ST_NCNT][4];
+    __shared__ long long s_gap[4];
+    __shared__ int s_first;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (t == 0) s_first = 0;
+    Tail carry = {0, 0, 0};   // of all tiles so far; every thread keeps its own copy
+    int n_al = 0, n_ins = 0, n_un = 0, n_step = 0, n_stay = 0, n_ext = 0, n_jump = 0, n_back = 0, n_nost = 0, n_fit = 0;
+    long long gap = 0;
+    double sw = 0.0, swm = 0.0, swmm = 0.0, swr = 0.0, swmr = 0.0, swrr = 0.0;
+    for (int base = 0; base < j.n; base += 256) {
+        const int i = base + t;
+        const bool in = i < j.n;
+        const double ra = in ? j.ra[i] : 0.0;
+        const double mean = in ? j.mean[i] : 0.0;
+        const bool al = ra > 0.0;
+        const int c = al ? (int)fmin(ra, 2147483647.0) : 0;
+        // inclusive scan of the tile's Tails within the wavefront, then the Tail of everything in front of this level
+        Tail inc = {al ? 1 : 0, c, 0};
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const Tail o = tail_up(inc, d);
+            if (lane >= d) inc = tail_join(o, inc);
+        }
+        if (lane == 63) { s_tail[w][0] = inc.n; s_tail[w][1] = inc.c1; s_tail[w][2] = inc.c2; }
+        Tail pre = tail_up(inc, 1);
+        if (lane == 0) pre = Tail{0, 0, 0};
+        __syncthreads();
+        Tail front = carry;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const Tail wk = {s_tail[k][0], s_tail[k][1], s_tail[k][2]};
+            if (k < w) front = tail_join(front, wk);
+            carry = tail_join(carry, wk);
+        }
+        pre = tail_join(front, pre);
+        __syncthreads();   // (s_tail is written again by the next tile)
+        if (!in) continue;
+        if (!al) { if (ra < 0.0) n_ins++; else n_un++; continue; }
+        n_al++;
+        if (pre.n == 0) s_first = c;   // (one level of the event: a single writer)
+        else {
+            const int d = c - pre.c1;   // both in 0 .. 2^31 - 1
+            const bool prev_rep = pre.n == 2 && pre.c1 == pre.c2;
+            if (d == 0) { if (prev_rep) n_ext++; else n_stay++; }
+            else if (d == 1) n_step++;
+            else if (d > 1) { n_jump++; gap += d - 1; }
+            else n_back++;
+        }
+        const int k = (c >= 1 && c <= j.S) ? j.st[c - 1] : -1;
+        if (k < 0 || k >= NS) { n_nost++; continue; }
+        n_fit++;
+        const double mk = j.model[k], sk = j.model[NS + k];
+        const double wt = 1.0 / (sk * sk), wm = wt * mk, r = mean - mk;
+        sw += wt; swm += wm; swmm += wm * mk; swr += wt * r; swmr += wm * r; swrr += (wt * r) * r;
+    }
+    s_sum[0][t] = sw; s_sum[1][t] = swm; s_sum[2][t] = swmm; s_sum[3][t] = swr; s_sum[4][t] = swmr; s_sum[5][t] = swrr;
+    {
+        const int c0 = wave_sum(n_al), c1 = wave_sum(n_ins), c2 = wave_sum(n_un), c3 = wave_sum(n_step), c4 = wave_sum(n_stay);
+        const int c5 = wave_sum(n_ext), c6 = wave_sum(n_jump), c7 = wave_sum(n_back), c8 = wave_sum(n_nost), c9 = wave_sum(n_fit);
+        const long long g = wave_sum(gap);
+        if (lane == 0) {
+            s_cnt[0][w] = c0; s_cnt[1][w] = c1; s_cnt[2][w] = c2; s_cnt[3][w] = c3; s_cnt[4][w] = c4;
+            s_cnt[5][w] = c5; s_cnt[6][w] = c6; s_cnt[7][w] = c7; s_cnt[8][w] = c8; s_cnt[9][w] = c9;
+            s_gap[w] = g;
+        }
+    }
+    __syncthreads();
+    ps_event_stats* o = out + rg.job0 + blockIdx.x;
+    if (t < 6) {   // one thread per sum, partials in t order
+        double sum = 0.0;
+        for (int l = 0; l < 256; l++) sum += s_sum[t][l];
+        double* dst = &o->sw;   // sw, swm, swmm, swr, swmr, swrr lie in this order
+        dst[t] = sum;
+    } else if (t == 64) {
+        auto cnt = [&](int k) { return s_cnt[k][0] + s_cnt[k][1] + s_cnt[k][2] + s_cnt[k][3]; };
+        o->n_levels = j.n; o->n_aligned = cnt(0); o->n_insert = cnt(1); o->n_unaligned = cnt(2);
+        o->n_step = cnt(3); o->n_stay = cnt(4); o->n_extend = cnt(5); o->n_jump = cnt(6); o->n_back = cnt(7);
+        o->n_nostate = cnt(8); o->n_fit = cnt(9);
+        o->first_col = carry.n ? s_first : 0; o->last_col = carry.n ? carry.c1 : 0; o->reserved = 0;
+        o->n_gap_cols = s_gap[0] + s_gap[1] + s_gap[2] + s_gap[3];
+    }
+}
+
+}  // namespace
+
+int launch_align_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxE, double alg_bytes, ps_event_stats* d_out) {
+    if (nregs <= 0 || maxE <= 0) return PS_OK;
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_align_stats, dim3(maxE, nregs), dim3(256), 0, rt->stream, d_jobs, d_regs, d_out);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "align_stats", alg_bytes);
+    return PS_OK;
+}
+
+}  // namespace ps

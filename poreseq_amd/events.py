@@ -188,6 +188,16 @@ class PSEvent:
         self.ref_align = new
         self.makecontiguous()
 
+    def getrefstats(self):
+        """(skips, stays, insertions) of ref_align as fractions of the levels that are not 0 (EventData.py:264-286): the columns from
+        1 to the largest aligned one that no level points at, the levels beyond the first on a column that several point at, and the
+        negative entries.  An event without such levels divides by zero, as the reference does (numpy: nan or inf)."""
+        ra = self.ref_align
+        per_column = np.bincount(np.int64(ra[ra >= 0]))[1:]      # levels per column, column 0 (not aligned) left out
+        total = float(np.sum(ra != 0))
+        with np.errstate(all="ignore"):
+            return (np.sum(per_column == 0) / total, np.sum(np.maximum(0, per_column - 1)) / total, np.sum(ra < 0) / total)
+
     def setparams(self, params):
         """'skip_t' -> model.prob_skip for template models, '_c' for complement (EventData.py:288-312)."""
         for k in params:

@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _capi
 from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas, genotypes_from_deltas, check_alt_frac, phase_from_deltas, check_phase_args
+from .util import align_stats_from_refs, fit_scaling, apply_scaling
 
 
 def _api():
@@ -119,6 +120,31 @@ def _phase_on(api, h, hm, n_events, seq_len, window, min_link, max_sets):
     return scores, link, phase, hap, n_sets, _scored_list(start, orig, mut, scores)
 
 
+def _align_stats_on(api, h, events, realign):
+    """(scores float64 [E] or None, stats _capi.EVENT_STATS [E]) of the AlignData `h`, whose events are `events`: ps_align_stats,
+    or — a library without the entry point — its score_alignments (with `realign`) and then the literal reduction of the refs the
+    handle holds (util.align_stats_from_refs)"""
+    E = len(events)
+    if "ps_align_stats" not in api.missing:
+        return api.align_stats(h, E, realign)
+    scores = api.score_alignments(h, E) if realign else None
+    refs = api.align_event_refs(h, E)
+    states = api.seq_to_states(api.align_sequence(h))
+    stats = np.zeros(E, dtype=_capi.EVENT_STATS)
+    for e, ev in enumerate(events):
+        stats[e] = align_stats_from_refs(states, ev.mean, refs[e], ev.model.level_mean, ev.model.level_stdv)
+    return scores, stats
+
+
+def _recalibrate(events, stats, var, fit_kw):
+    """fit_scaling of every record, applied to the models of the events whose fit is ok -> the fits"""
+    fits = fit_scaling(stats, **fit_kw)
+    for ev, f in zip(events, fits):
+        if f.ok:
+            apply_scaling(ev, f, var=var)
+    return fits
+
+
 class PSAlign:
     """All data of reads aligned to a reference (pyx:189-472).
 
@@ -193,6 +219,24 @@ class PSAlign:
         """Total likelihood score of each event (pyx:263-276).  Does not write ref_align back."""
         with PSAlign._Data(self) as d:
             return d.api.score_alignments(d.h, len(self.events)).tolist()
+
+    def AlignStats(self, realign=True):
+        """Per event the census of its alignment and the sums of a shift / scale refit of its model (ps_align_stats): (scores,
+        stats).  realign=True aligns every event as ScoreEvents does — scores are ScoreEvents' bits, as float64 [E] — and reduces the
+        alignment that leaves, on the device, in the same launch chain (k_align_stats); realign=False reduces ref_align as the
+        events carry it, runs no DP and returns None for the scores.  stats is a structured array (_capi.EVENT_STATS [E]): the
+        levels by kind, the steps between consecutive aligned levels by size, and sw .. swrr for util.fit_scaling.  Like
+        ScoreEvents it does not write ref_align back; `self` is not modified."""
+        with PSAlign._Data(self) as d:
+            return _align_stats_on(d.api, d.h, self.events, bool(realign))
+
+    def Recalibrate(self, var=True, **fit_kw):
+        """Refit every event's model scaling on its alignment to self.sequence: one AlignStats() pass, util.fit_scaling(**fit_kw) per
+        event, and util.apply_scaling(var=var) IN PLACE on the model of every event whose fit is ok (the others keep theirs).
+        Returns the fits, one util.ScalingFit per event.  Sequence, ref_align and ref_like are not touched.  What this does to
+        consensus accuracy on real data has not been measured."""
+        _, stats = self.AlignStats(realign=True)
+        return _recalibrate(self.events, stats, var, fit_kw)
 
     def ScoreSequences(self, seqs):
         """ndarray [len(seqs)][len(events)]: row s is what `pav = self.Copy(); pav.RealignTo(seqs[s]); pav.ScoreEvents()` returns,

@@ -438,3 +438,126 @@ def call_phase(gts, phase, pos=None):
         out.append('1|0' if h > 0 else '0|1')
         ps.append(first[k] if pos is None else pos[first[k]])
     return out, ps
+
+
+def align_stats_from_refs(states, mean, ra, level_mean, level_stdv):
+    """One event's ps_event_stats record (_capi.EVENT_STATS, shape ()) — the definition of include/poreseq_hip.h in numpy float64, and
+    the path of a library without ps_align_stats.  states: the 5-mer states of the sequence (states[j - 1] belongs to column j);
+    mean, ra: the event's level means and ref_align; level_mean, level_stdv: its model rows.
+    A level is aligned iff ra > 0, inserted iff ra < 0, unaligned otherwise; its column is c = int(min(ra, 2147483647.0)).  The
+    census compares every aligned level's column with that of the aligned level before it (d = 0: stay, or extend when that one
+    was itself a repeat; 1: step; > 1: jump over d - 1 columns; < 0: back); it is a census of the array, not of the path's moves.
+    An aligned level with 1 <= c <= len(states) and states[c - 1] >= 0 enters the fit with w = 1 / s_k^2, wm = w m_k, r = mean - m_k:
+    sw, swm, swmm, swr, swmr, swrr are the sums of w, wm, wm m_k, w r, wm r, (w r) r, added as the device adds them — partial t =
+    0.0 plus the terms of the levels t, t + 256, ... ascending, then the 256 partials into 0.0 in order."""
+    import numpy as np
+    from ._capi import EVENT_STATS
+    states = np.asarray(states, dtype=np.int64).reshape(-1)
+    mean = np.asarray(mean, dtype=np.float64).reshape(-1)
+    ra = np.asarray(ra, dtype=np.float64).reshape(-1)
+    lm = np.asarray(level_mean, dtype=np.float64).reshape(-1)
+    ls = np.asarray(level_stdv, dtype=np.float64).reshape(-1)
+    n, S = ra.size, states.size
+    rec = np.zeros((), dtype=EVENT_STATS)
+    with np.errstate(all='ignore'):
+        al = ra > 0
+        rec["n_levels"], rec["n_aligned"], rec["n_insert"] = n, int(al.sum()), int((ra < 0).sum())
+        rec["n_unaligned"] = n - int(rec["n_aligned"]) - int(rec["n_insert"])
+        col = np.zeros(n, dtype=np.int64)
+        col[al] = np.minimum(ra[al], 2147483647.0).astype(np.int64)
+        c = col[al]
+        if c.size:
+            rec["first_col"], rec["last_col"] = c[0], c[-1]
+            d = np.diff(c)
+            rep = d == 0
+            prev_rep = np.concatenate([[False], rep[:-1]])
+            rec["n_extend"], rec["n_stay"] = int((rep & prev_rep).sum()), int((rep & ~prev_rep).sum())
+            rec["n_step"], rec["n_jump"], rec["n_back"] = int((d == 1).sum()), int((d > 1).sum()), int((d < 0).sum())
+            rec["n_gap_cols"] = int((d[d > 1] - 1).sum())
+        k = np.full(n, -1, dtype=np.int64)
+        has = al & (col >= 1) & (col <= S)
+        k[has] = states[col[has] - 1]
+        fit = has & (k >= 0) & (k < lm.size)
+        rec["n_fit"] = int(fit.sum())
+        rec["n_nostate"] = int(rec["n_aligned"]) - int(rec["n_fit"])
+        kk = np.where(fit, k, 0)
+        mk, sk = lm[kk], ls[kk]
+        w = 1.0 / (sk * sk)
+        wm = w * mk
+        r = mean - mk
+        rows = (n + 255) // 256
+        pad = rows * 256 - n
+        tile = lambda a: np.pad(np.where(fit, a, 0.0), (0, pad)).reshape(rows, 256)
+        for name, term in (("sw", w), ("swm", wm), ("swmm", wm * mk), ("swr", w * r), ("swmr", wm * r), ("swrr", (w * r) * r)):
+            t = tile(term)
+            part = np.zeros(256)
+            for row in range(rows):
+                part = part + t[row]      # (+0.0 for a level that does not enter leaves a sum that began at +0.0 as it is)
+            tot = np.float64(0.0)
+            for lane in range(256):
+                tot = tot + part[lane]
+            rec[name] = tot
+    return rec
+
+
+class ScalingFit(tuple):
+    """(scale, shift, var, ok, n_fit) of fit_scaling, with the fields by name"""
+    __slots__ = ()
+    _fields = ("scale", "shift", "var", "ok", "n_fit")
+
+    def __new__(cls, scale, shift, var, ok, n_fit):
+        return tuple.__new__(cls, (float(scale), float(shift), float(var), bool(ok), int(n_fit)))
+
+    scale = property(lambda self: self[0])
+    shift = property(lambda self: self[1])
+    var = property(lambda self: self[2])
+    ok = property(lambda self: self[3])
+    n_fit = property(lambda self: self[4])
+
+    def __repr__(self):
+        return "ScalingFit(scale=%r, shift=%r, var=%r, ok=%r, n_fit=%r)" % tuple(self)
+
+
+def fit_scaling(stats, min_levels=100, min_spread=1e-6, scale_limits=(0.5, 2.0), var_limits=(0.25, 4.0)):
+    """The shift / scale / var refit of one read's model from its ps_event_stats record (or a list of fits for an array of
+    records): the weighted least-squares line of the residuals r = mean - m_k against the model means m_k, weights 1 / s_k^2:
+        det = sw swmm - swm^2;  da = (sw swmr - swm swr) / det;  db = (swmm swr - swm swmr) / det;
+        scale = 1 + da;  shift = db;  rss = swrr - da swmr - db swr;  var = sqrt(max(rss, 0) / n_fit)
+    so that level_mean * scale + shift fits the read's levels, and level_stdv * var their scatter.  Returns ScalingFit(scale, shift,
+    var, ok, n_fit).  ok iff n_fit >= min_levels, det > min_spread * sw * swmm (the aligned states' means are spread out enough to
+    tell a scale from a shift) and scale / var lie inside their limits (and are finite); a fit that is not ok is the identity
+    (1, 0, 1).  The limits are guards with documented defaults — a read whose refit leaves them is more likely misaligned than
+    mis-scaled — not measurements.  Host only; drift, the stdv channel's scale_sd / var_sd, per-k-mer re-estimation and transition
+    parameters are not fitted."""
+    import math
+    import numpy as np
+    if isinstance(stats, np.ndarray) and stats.ndim > 0:
+        return [fit_scaling(s, min_levels, min_spread, scale_limits, var_limits) for s in stats.reshape(-1)]
+    n_fit = int(stats["n_fit"])
+    sw, swm, swmm, swr, swmr, swrr = (float(stats[k]) for k in ("sw", "swm", "swmm", "swr", "swmr", "swrr"))
+    ident = ScalingFit(1.0, 0.0, 1.0, False, n_fit)
+    det = sw * swmm - swm * swm
+    if n_fit < int(min_levels) or n_fit <= 0 or not (det > float(min_spread) * sw * swmm) or not math.isfinite(det):
+        return ident
+    da = (sw * swmr - swm * swr) / det
+    db = (swmm * swr - swm * swmr) / det
+    scale, shift = 1.0 + da, db
+    rss = swrr - da * swmr - db * swr
+    var = math.sqrt(max(rss, 0.0) / n_fit) if rss == rss else float("nan")
+    if not (math.isfinite(scale) and math.isfinite(shift) and math.isfinite(var)):
+        return ident
+    if not (scale_limits[0] <= scale <= scale_limits[1] and var_limits[0] <= var <= var_limits[1]):
+        return ident
+    return ScalingFit(scale, shift, var, True, n_fit)
+
+
+def apply_scaling(event, fit, var=True):
+    """Apply a ScalingFit to an event's model in place: level_mean = level_mean * scale + shift and, with var, level_stdv =
+    level_stdv * var.  Nothing else of the event or the model is touched (new arrays: a table shared with another model object
+    is not written through)."""
+    import numpy as np
+    m = event.model
+    m.level_mean = np.asarray(m.level_mean, dtype=np.float64) * float(fit.scale) + float(fit.shift)
+    if var:
+        m.level_stdv = np.asarray(m.level_stdv, dtype=np.float64) * float(fit.var)
+    return event
