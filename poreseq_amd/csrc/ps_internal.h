@@ -325,7 +325,7 @@ struct StatRegion { int job0, njobs; };
 // grid (maxE, nregs): out[job] for every job of every region; alg_bytes for the profile ("align_stats")
 int launch_align_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxE, double alg_bytes, ps_event_stats* d_out);
 
-// Smith-Waterman (ps_sw.hip)
+// Smith-Waterman (kernels: ps_sw.hip, host side: ps_swhost.cpp)
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,
               std::vector<int>* inds1, std::vector<int>* inds2);
 void sw_band_counters(int64_t out[5]);   // band mode: pairs banded, fell back, maxima near a band edge, band cells, full-matrix cells

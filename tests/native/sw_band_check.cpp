@@ -1,4 +1,5 @@
-// sw_band_check.cpp — host check of the band mode of the Smith-Waterman fill (poreseq_amd/csrc/ps_sw.hip).
+// sw_band_check.cpp — host check of the band mode of the Smith-Waterman fill (poreseq_amd/csrc/ps_sw.hip).  The region of a strip, the
+// bound B and the threshold U are the kernels' own: band_win / band_q0 / col_hi, band_bound and band_u of poreseq_amd/csrc/ps_swplan.h.
 //
 // The fill in band mode computes, for every 512-column strip s, only its rows [512 s + 1 - wb, 512 s + 512 + wb]; every other cell
 // counts as 0.  The result is taken only under the certificate the traceback kernel checks: the banded maximum exceeds
@@ -15,25 +16,31 @@
 #include <string>
 #include <vector>
 
+#include "../../poreseq_amd/csrc/ps_swplan.h"
+
+using namespace ps;
+
 struct Res { int score = 0, bi = 0, bj = 0; std::vector<int> a, b; bool ok = true; };
 
-static const int STRIP = 512;
+static int bound(int i, int j, int wb) { return band_bound(i, j, wb); }
 
-static int bound(int i, int j, int wb) { return 5 * std::min(i, j) - 8 * std::max(0, wb + 1 - std::abs(i - j)); }
-
-static bool in_region(int i, int j, int n1, int wb) {   // 1-based cell (i, j) computed by the band fill
-    const int s = (j - 1) / STRIP;
-    return i >= std::max(1, STRIP * s + 1 - wb) && i <= std::min(n1, STRIP * s + STRIP + wb);
+static bool in_region(int i, int j, const SwPair& p) {   // 1-based cell (i, j) computed by the band fill: the rows of its strip
+    const int s = (j - 1) / SWBS;
+    const SwWin w = band_win<true>(p, s);
+    return i >= 64 * band_q0<true>(w) + 1 && i <= col_hi<true>(p, w);
 }
 
 // wb = 0: the full matrix.  H is (n1 + 1) x (n2 + 1), column-major is not needed: the maximum is searched column by column.
 static Res sw(const std::string& s1, const std::string& s2, int wb, std::vector<int32_t>& H) {
     const int n1 = (int)s1.size(), n2 = (int)s2.size(), W = n2 + 1;
     H.assign((size_t)(n1 + 1) * W, 0);
+    SwPair p;
+    SwPools pools;
+    sw_lay_out(p, n1, n2, wb, SW_LISTS, PKK, SWBW, pools);
     auto h = [&](int i, int j) -> int32_t& { return H[(size_t)i * W + j]; };
     for (int i = 1; i <= n1; i++)
         for (int j = 1; j <= n2; j++) {
-            if (wb && !in_region(i, j, n1, wb)) continue;
+            if (wb && !in_region(i, j, p)) continue;
             const int d = h(i - 1, j - 1) + (s1[i - 1] == s2[j - 1] ? 5 : -4);
             h(i, j) = std::max(std::max(0, d), std::max(h(i - 1, j) - 8, h(i, j - 1) - 8));
         }
@@ -42,8 +49,7 @@ static Res sw(const std::string& s1, const std::string& s2, int wb, std::vector<
         for (int i = 1; i <= n1; i++)
             if (h(i, j) > r.score) { r.score = h(i, j); r.bi = i; r.bj = j; }
     if (wb) {
-        const int u = 5 * std::max(0, std::max(std::min(n1, n2 - wb - 1), std::min(n2, n1 - wb - 1)));
-        if (r.score <= u) { r.ok = false; return r; }
+        if (r.score <= band_u(n1, n2, wb)) { r.ok = false; return r; }
     }
     if (r.score <= 0) { r.bi = r.bj = 0; return r; }
     int i = r.bi, j = r.bj;

@@ -123,3 +123,44 @@ def test_find_mutations_band_force_equals_off_and_oracle():
         assert r[0] == res[0][0] and r[1] == res[0][1]
         for x, y in zip(r[2], res[0][2]):
             assert np.array_equal(x, y)
+
+
+# pairs at the edge of a band strip (512 columns) and of its row window: one column or row more or less than a strip, a strip's
+# worth of columns against one row block, a single row against a second strip of one column
+EDGE_LENGTHS = [(511, 513), (512, 512), (513, 511), (64, 512), (1, 513)]
+_edge = {}
+
+
+def _edge_cases():
+    """the pairs and the oracle's index lists and the summaries read off them, computed once"""
+    if not _edge:
+        rng = np.random.default_rng(513)
+        pairs = []
+        for n1, n2 in EDGE_LENGTHS:
+            base = synth.random_sequence(rng, max(n1, n2))
+            s2 = list(base[:n2])
+            for k in range(5, n2, 17):
+                s2[k] = "ACGT"[int(rng.integers(0, 4))]
+            pairs.append((base[:n1], "".join(s2)))
+        lists = [B.oracle_api().swfull(a, b) for a, b in pairs]
+        _edge.update(pairs=pairs, lists=lists, sums=[_capi.summary_from_lists(a, b, *w) for (a, b), w in zip(pairs, lists)])
+    return _edge["pairs"], _edge["lists"], _edge["sums"]
+
+
+@pytest.mark.parametrize("mode,width", [("force", "64"), ("force", "128"), ("off", "128")])
+def test_strip_edge_pairs_lists_and_summaries(mode, width):
+    """index lists (swfull) and summaries (one batch) of pairs whose lengths sit on a strip's edge, banded at two widths and on the
+    full matrix, exactly the oracle's swfull and summary_from_lists of it (the layout these pairs stress: test_sw_layout.py)"""
+    pairs, want_lists, want_sums = _edge_cases()
+    hip = _capi.load_hip()
+    with _env(PORESEQ_SW_BAND=mode, PORESEQ_SW_BAND_W=width):
+        c0 = _counters()
+        got_lists = [hip.swfull(a, b) for a, b in pairs]
+        got_sums = hip.sw_summaries(pairs)
+        d = _delta(c0, _counters())
+    assert d["banded"] == (2 * len(pairs) if mode == "force" else 0)
+    for n, g, w in zip(EDGE_LENGTHS, got_lists, want_lists):
+        assert g[0] == w[0] and ((g[1] == w[1]) or (np.isnan(g[1]) and np.isnan(w[1]))), (n, g[:2], w[:2])
+        assert np.array_equal(g[2], w[2]) and np.array_equal(g[3], w[3]), n
+    for n, g, w in zip(EDGE_LENGTHS, got_sums, want_sums):
+        assert tuple(g)[:-1] == tuple(w)[:-1] and ((g.accuracy == w.accuracy) or (np.isnan(g.accuracy) and np.isnan(w.accuracy))), (n, g, w)
