@@ -26,6 +26,14 @@
  * Indices follow the reference: mutation `start` is a 0-based base index,
  * ref_align values are 1-based state indices (0 = unaligned, -1 = inserted
  * level), Smith-Waterman index lists are 1-based with 0 = gap.
+ *
+ * Domain of ref_align: any double.  A level is aligned iff its entry is > 0 (an entry in (0, 1) is
+ * column 0, a fraction truncates; NaN, 0 and -1 are not aligned).  ps_align_create, ps_align_stats and
+ * the scoring calls take every value.  ViterbiMutate walks the positions from (int)ref_align of the
+ * first aligned level to that of the last: an entry that is not below 2^31 (+inf included) has no
+ * defined conversion, and ps_viterbi_mutate, ps_batch_viterbi_mutate and ps_debug_viterbi answer
+ * PS_ERR_BAD_ARG for it, naming the event and the level, before any kernel of the call.  The walk is
+ * linear in the largest entry.
  */
 #ifndef PORESEQ_HIP_H_
 #define PORESEQ_HIP_H_

@@ -756,6 +756,20 @@ int fail_unreachable(const char* call, int region, int pos) {
             std::to_string(pos) + " (every emission there is -inf or below -1e300, or the running scores have passed -1e300)";
     return PS_ERR_BAD_ARG;
 }
+// ViterbiMutate walks refind from the smallest refstart to the largest refend, both (int)ref_align of an aligned level: an entry that
+// is not below 2^31 (+inf included) has no defined conversion (cpp/EventData.h:135-136) — refused, naming the event and the level
+int vit_refuses_refs(const std::vector<Event>& ev, const char* call, int region) {
+    for (size_t e = 0; e < ev.size(); e++)
+        for (int t = 0; t < ev[e].n; t++)
+            if (ev[e].ref_align[t] >= 2147483648.0) {
+                char val[64];
+                snprintf(val, sizeof(val), "%g", ev[e].ref_align[t]);
+                g_err = std::string(call) + ": " + (region >= 0 ? "region " + std::to_string(region) + ": " : std::string()) + "event " + std::to_string(e) +
+                        ", level " + std::to_string(t) + ": ref_align = " + val + " is not below 2^31 (ViterbiMutate walks the positions from (int)ref_align)";
+                return PS_ERR_BAD_ARG;
+            }
+    return PS_OK;
+}
 
 }  // namespace
 
@@ -946,6 +960,7 @@ int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
 int ps_viterbi_mutate(ps_align* a, int32_t nkeep, double skip, double stay, double mmin, double mmax,
                       int32_t, ps_seqs** out) {
     if (!a || !out || a->d.ev.empty()) return fail(PS_ERR_BAD_ARG, "ps_viterbi_mutate");
+    if (int rc = vit_refuses_refs(a->d.ev, "ps_viterbi_mutate", -1)) return rc;
     int dead = -1;
     std::vector<std::string> v = viterbi_mutate(a->d.ev, nkeep, skip, stay, mmin, mmax, &dead);
     if (dead >= 0) return fail_unreachable("ps_viterbi_mutate", -1, dead);
@@ -1015,6 +1030,7 @@ int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t, int32_t nkeep, doub
     const int np = std::max(nkeep, 1);
     for (int r = 0; r < n; r++) {
         if (!a[r] || a[r]->d.ev.empty()) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: no events");
+        if (int rc = vit_refuses_refs(a[r]->d.ev, "ps_debug_viterbi", r)) return rc;
         VTable S;
         std::vector<std::vector<double>> rows;
         vit_walk(a[r]->d.ev, skip, stay, S, &rows);

@@ -315,12 +315,31 @@ namespace {
 struct VitGather { std::vector<double> obsin; int T = 0; };
 }  // namespace
 
+// The walk runs from the smallest refstart to the largest refend, both (int)ref_align of an aligned level (cpp/EventData.h:135-136):
+// an entry that is not below 2^31, +inf included, has no defined conversion and would send vit_gather towards 2^31 — refused, naming
+// the event and the level (region < 0: not a lock-step call).  The DP and the census take any double (include/poreseq_hip.h).
+static int vit_refuses_refs(const Align& a, const char* who, int region) {
+    for (int e = 0; e < a.E; e++) {
+        const double* ra = a.h_ra.data() + a.off[e];
+        for (int t = 0; t < a.n[e]; t++)
+            if (ra[t] >= 2147483648.0) {
+                char val[64];
+                snprintf(val, sizeof(val), "%g", ra[t]);
+                return fail(PS_ERR_BAD_ARG, std::string(who) + ": " + (region >= 0 ? "region " + std::to_string(region) + ": " : std::string()) + "event " + std::to_string(e) +
+                                                ", level " + std::to_string(t) + ": ref_align = " + val + " is not below 2^31 (ViterbiMutate walks the positions from (int)ref_align)");
+            }
+    }
+    return PS_OK;
+}
+
 static void vit_gather(const Align* a, const double* h_ri, const JobOut* info, VitGather* g) {
     const int E = a->E;
     // first level whose ref_index equals an integer position (std::find in getrefstates, cpp/EventData.h:192),
-    // as a flat table per event indexed by position (positions outside [0, maxpos] never match)
+    // as a flat table per event indexed by position + 1 (positions outside [-1, maxpos] never match)
     // (extrapolated ref_index values past refend can be integers too and do take part, so the table
-    // spans every integer-valued entry)
+    // spans every integer-valued entry).  The table starts at position -1: a read without an aligned level has refstart = -1, the
+    // walk then begins there, and std::find meets the -1 markers that an un-interpolated hole keeps (behind an aligned level 0,
+    // cpp/EventData.h:157) or a head that the line through the end levels crosses at -1; no position lies below -1.
     int maxpos = 0;
     for (int e = 0; e < E; e++) {
         if (!info[e].has_index) continue;
@@ -333,12 +352,12 @@ static void vit_gather(const Align* a, const double* h_ri, const JobOut* info, V
     std::vector<std::vector<int>> first(E);
     for (int e = 0; e < E; e++) {
         if (!info[e].has_index) continue;  // empty ref_index: getrefstates finds nothing
-        first[e].assign((size_t)maxpos + 1, -1);
+        first[e].assign((size_t)maxpos + 2, -1);
         const double* ri = h_ri + a->off[e];
         for (int t = 0; t < a->n[e]; t++) {
             const double v = ri[t];
-            if (v >= 0.0 && v <= (double)maxpos && v == std::floor(v)) {
-                int& slot = first[e][(size_t)v];
+            if (v >= -1.0 && v <= (double)maxpos && v == std::floor(v)) {
+                int& slot = first[e][(size_t)((int)v + 1)];
                 if (slot < 0) slot = t;
             }
         }
@@ -354,11 +373,11 @@ static void vit_gather(const Align* a, const double* h_ri, const JobOut* info, V
         const size_t at = obsin.size();
         obsin.resize(at + (size_t)E * 4, 0.0);
         for (int e = 0; e < E; e++) {
-            if (refind < 0 || refind > maxpos || first[e].empty() || first[e][refind] < 0) continue;
+            if (refind < -1 || refind > maxpos || first[e].empty() || first[e][refind + 1] < 0) continue;
             const double* ra = a->h_ra.data() + a->off[e];
             const double* mean = a->h_mean.data() + a->off[e];
             const double* stdv = a->h_stdv.data() + a->off[e];
-            int t = first[e][refind], cnt = 1;
+            int t = first[e][refind + 1], cnt = 1;
             // getrefstates keeps following levels while ref_align <= refind, using those > 0 (cpp/EventData.h:197-201)
             double lsum = 0, ssum = 0;
             lsum += mean[t]; ssum += stdv[t];
@@ -407,6 +426,7 @@ int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::
     PS_HIP(hipStreamSynchronize(rt->stream));
     for (int r = 0; r < R; r++) as[r]->refs_finish();
     tk.lap("refs D2H");
+    for (int r = 0; r < R; r++) PS_TRY(vit_refuses_refs(*as[r], who, lockstep ? r : -1));   // on the host copy, before any kernel of the call
     std::vector<VitGather> gath(R);
     par_for(R, [&](int r) { vit_gather(as[r], h_ri[r], info[r], &gath[r]); });
     tk.lap("gather levels");
