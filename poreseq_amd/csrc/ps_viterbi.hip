@@ -483,6 +483,7 @@ int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, in
             return fail(PS_ERR_BAD_ARG, "ViterbiMutate: the emission build asked for does not take this many events");
     }
     prof_begin(rt);
+    if (rt->prof_on && !(tap && tap->obs_rows)) rt->prof[build == 1 ? "vit_obs_lds" : (build == 2 ? "vit_obs_64" : "vit_obs_256")].launches++;   // (which emission build ran: a host-side count, no event pair)
     if (tap && tap->obs_rows) {   // rows from the caller instead of the emission kernel (ps_debug_viterbi_steps)
         std::vector<double> eo((size_t)ttot * NS);
         for (size_t k = 0; k < eo.size(); k++) eo[k] = std::exp(tap->obs_rows[k]);
