@@ -438,6 +438,25 @@ int ps_batch_sw_summary(int64_t n, const char* const* seq1, const int64_t* n1, c
 /* Sequence::populateStates (cpp/Sequence.h:64-100); states needs max(n-4,0) entries. */
 int ps_seq_to_states(const char* seq, int64_t n, int32_t* states, int64_t* n_states);
 
+/* ---- scratch poison (a test hook; nothing in the library calls it and no environment variable enables it) ----
+ * Pools, dense slabs, cached AlignData slabs and pinned staging memory are scratch between API calls.  This
+ * hook drains the calling thread's streams and then overwrites, over its whole capacity, everything that thread's next call could
+ * find left over: every named device pool of its runtime, every dense slab no call holds, every cached AlignData slab (after its
+ * pending event), the pinned host buffers and the staging arena.  A live AlignData's own slab, a busy dense slab and other
+ * threads' runtimes are not touched.  index_word goes into every 32-bit word of every buffer that may hold an index, offset, count,
+ * flag, state id or loop bound (the default class); value_word into every double of the pools that csrc/ps_poison.h lists as
+ * VALUE: scores that are only compared, added and copied.  Pass an index word that is in range wherever one is used (1) and the
+ * results of a correct library do not change.  report (may be NULL when cap is 0) gets one record per buffer name, at most cap of
+ * them; n_report (may be NULL) the number there are.  Names: a pool's own; "host:<name>" for a pinned host buffer; "slab" (all dense
+ * slabs, skipped = the busy ones), "align_cache", "stage".  The checker libraries do not export it. */
+typedef struct ps_poison_report {
+    char name[32];
+    int64_t bytes;      /* bytes overwritten; 0: not allocated, or skipped */
+    int32_t cls;        /* 0 index word, 1 value word, 2 exempt (carries state between calls on purpose: left alone) */
+    int32_t skipped;    /* buffers of this name that were left alone: busy dense slabs, an exempt pool */
+} ps_poison_report;
+int ps_debug_poison(uint32_t index_word, uint64_t value_word, ps_poison_report* report, int32_t cap, int32_t* n_report);
+
 /* ---- kernel-level test hooks (K1/K2 matrices vs oracle dumps) ----
  * Runs Alignment::update (cpp/Alignment.cpp:63-73) for one event on the current sequence
  * and returns the dense (n_levels+1) x (n_states+1) forward or backward main matrix with

@@ -66,6 +66,16 @@ EVENT_STATS = np.dtype([(k, np.int32) for k in ("n_levels", "n_aligned", "n_inse
                        [("n_gap_cols", np.int64)] + [(k, np.float64) for k in ("sw", "swm", "swmm", "swr", "swmr", "swrr")])
 
 
+class PsPoisonReport(C.Structure):
+    # ps_poison_report, include/poreseq_hip.h
+    _fields_ = [("name", C.c_char * 32), ("bytes", C.c_int64), ("cls", C.c_int32), ("skipped", C.c_int32)]
+
+
+PoisonReport = collections.namedtuple("PoisonReport", "bytes cls skipped")
+POISON_CLASSES = ("INDEX", "VALUE", "EXEMPT")   # PoisonClass, csrc/ps_poison.h
+POISON_1E300 = int(np.float64(1e300).view(np.uint64))   # the bits of +1e300: finite, wins every max, wrecks every sum
+
+
 class PoreseqError(Exception):
     pass
 
@@ -138,6 +148,7 @@ SYMBOLS = {
                                       C.POINTER(PsSwSummary)]),
     "ps_seq_to_states": (C.c_int, [C.c_char_p, C.c_int64, c_i32p, c_i64p]),
     "ps_debug_fill": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_dp, c_dp, c_u8p, c_u8p]),
+    "ps_debug_poison": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(PsPoisonReport), C.c_int32, c_i32p]),
     "ps_debug_viterbi": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_int64, c_i32p, c_dp, c_i16p, c_dp, c_dp, c_i16p]),
     "ps_debug_viterbi_steps": (C.c_int, [C.c_int32, c_i32p, c_dp, c_dp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -161,7 +172,7 @@ SYMBOLS = {
 # same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas;
 # PSAlign.AlignStats reduces the refs the library holds with util.align_stats_from_refs, after its score_alignments).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_align_stats", "ps_batch_align_stats", "ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps",
+OPTIONAL = frozenset(["ps_align_stats", "ps_batch_align_stats", "ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
                       "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes",
                       "ps_score_mutation_phase", "ps_batch_score_mutation_phase"])
@@ -681,6 +692,19 @@ class CApi:
         self.check(self.lib.ps_debug_fill(h, ev, direction, _dp(main), _dp(stay),
                                           sm.ctypes.data_as(c_u8p), ss.ctypes.data_as(c_u8p)))
         return main, stay, sm, ss
+
+    def debug_poison(self, index_word=1, value_word=POISON_1E300):
+        """overwrite the scratch memory the calling thread's next call could find left over (ps_debug_poison): the index word
+        into every 32-bit word of the pools that may hold indices, counts or flags, the value word into every double of the
+        value-only pools -> {buffer name: PoisonReport(bytes, cls, skipped)}"""
+        self._need("ps_debug_poison")
+        cap = 128
+        rep = (PsPoisonReport * cap)()
+        n = C.c_int32(0)
+        self.check(self.lib.ps_debug_poison(int(index_word) & 0xffffffff, int(value_word) & 0xffffffffffffffff, rep, cap, C.byref(n)))
+        if n.value > cap:
+            raise PoreseqError("ps_debug_poison: %d report records, room for %d" % (n.value, cap))
+        return {rep[k].name.decode(): PoisonReport(int(rep[k].bytes), POISON_CLASSES[rep[k].cls], int(rep[k].skipped)) for k in range(n.value)}
 
     def debug_viterbi(self, handles, cap_T, nkeep, skip, stay, mmin, mmax, obs_build=0):
         """the tables of ViterbiMutate for a batch of AlignData (ps_debug_viterbi) -> per region a dict: T, obs [T][1024],

@@ -474,6 +474,11 @@ int ps_debug_fill(ps_align* a, int32_t e, int32_t dir, double* main, double* sta
     NEED_RT();
     return debug_fill(rt, &a->a, e, dir, main, stay, sm, ss);
 }
+int ps_debug_poison(uint32_t index_word, uint64_t value_word, ps_poison_report* report, int32_t cap, int32_t* n_report) {
+    if (cap < 0 || (cap && !report)) return fail(PS_ERR_BAD_ARG, "ps_debug_poison");
+    NEED_RT();
+    return debug_poison(rt, index_word, value_word, report, cap, n_report);
+}
 int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t build, int32_t nkeep, double skip, double stay, double mmin, double mmax,
                      int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
     std::vector<Align*> as;

@@ -241,6 +241,8 @@ int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds,
 int viterbi_mutate(Runtime* rt, Align* a, int nkeep, double skip, double stay, double mmin, double mmax,
                    std::vector<std::string>* out, bool verbose = false);
 int debug_fill(Runtime* rt, Align* a, int ev, int dir, double* main, double* stay, uint8_t* sm, uint8_t* ss);
+// ps_debug_poison (ps_mem.cpp): overwrites the scratch memory the calling thread's next call could find left over (ps_poison.h)
+int debug_poison(Runtime* rt, uint32_t index_word, uint64_t value_word, ps_poison_report* rep, int32_t cap, int32_t* n_rep);
 // ps_debug_viterbi / ps_debug_viterbi_steps (include/poreseq_hip.h): the tables of a ViterbiMutate call
 int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
                   int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths);

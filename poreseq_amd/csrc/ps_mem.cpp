@@ -3,6 +3,7 @@
 // runtime's share, the slabs for full score matrices and the cache of AlignData slabs.  The plan's numbers and formulas are in
 // ps_plan.h; every hipMalloc and hipFree of the library is in this file.
 #include "ps_host.h"
+#include "ps_poison.h"
 
 #include <algorithm>
 #include <atomic>
@@ -348,6 +349,91 @@ int align_slab_take(Runtime* rt, size_t bytes, void** out, size_t* cap) {
     *cap = want;
     return PS_OK;
 }
+// ---- ps_debug_poison: overwrite what the calling thread's next call could find left over -----------------------------------------
+// A test hook (ps_poison.h has the class of every pool).  Plain vector stores; tails that are no multiple of 16 bytes word by word.
+__global__ void k_poison(uint4* __restrict__ p, size_t n16, size_t tail_words, size_t tail_bytes, unsigned lo, unsigned hi) {
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t i = t0; i < n16; i += step) p[i] = make_uint4(lo, hi, lo, hi);
+    unsigned* w = (unsigned*)(p + n16);
+    if (t0 < tail_words) w[t0] = (t0 & 1) ? hi : lo;
+    unsigned char* c = (unsigned char*)(w + tail_words);
+    if (t0 < tail_bytes) c[t0] = (unsigned char)lo;
+}
+static int poison_device(Runtime* rt, void* p, size_t bytes, unsigned lo, unsigned hi) {
+    if (!p || !bytes) return PS_OK;
+    const size_t n16 = bytes / 16, rest = bytes % 16;
+    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((n16 + 255) / 256, 1), 256 * 64);
+    hipLaunchKernelGGL(k_poison, dim3(blocks), dim3(256), 0, rt->stream, (uint4*)p, n16, rest / 4, rest % 4, lo, hi);
+    PS_LAUNCH_CHECK();
+    return PS_OK;
+}
+static void poison_host(void* p, size_t bytes, unsigned word) {
+    if (!p) return;
+    unsigned* w = (unsigned*)p;
+    std::fill(w, w + bytes / 4, word);
+    memset((char*)p + bytes / 4 * 4, (int)(word & 255), bytes % 4);
+}
+
+int debug_poison(Runtime* rt, uint32_t index_word, uint64_t value_word, ps_poison_report* rep, int32_t cap, int32_t* n_rep) {
+    int n = 0;
+    auto say = [&](const std::string& name, size_t bytes, PoisonClass cls, int skipped) {
+        if (rep && n < cap) {
+            ps_poison_report& r = rep[n];
+            memset(&r, 0, sizeof(r));
+            strncpy(r.name, name.c_str(), sizeof(r.name) - 1);
+            r.bytes = (int64_t)bytes; r.cls = (int32_t)cls; r.skipped = skipped;
+        }
+        n++;
+    };
+    // nothing of this thread's may be in flight, and nothing it staged may still be wanted
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    if (rt->stream2) PS_HIP(hipStreamSynchronize(rt->stream2));
+    const unsigned vlo = (unsigned)(value_word & 0xffffffffu), vhi = (unsigned)(value_word >> 32);
+    for (auto& kv : rt->pool) {
+        const PoisonEntry* e = poison_entry(kv.first.c_str());
+        const PoisonClass cls = e ? e->cls : PoisonClass::INDEX;
+        if (cls == PoisonClass::EXEMPT) { say(kv.first, 0, cls, kv.second.p ? 1 : 0); continue; }
+        const bool val = cls == PoisonClass::VALUE;
+        PS_TRY(poison_device(rt, kv.second.p, kv.second.cap, val ? vlo : index_word, val ? vhi : index_word));
+        say(kv.first, kv.second.p ? kv.second.cap : 0, cls, 0);
+    }
+    {   // the dense slabs no call holds (the lock is kept over the fill: a taker must not start before it has run)
+        std::lock_guard<std::mutex> lk(g_slab_mu);
+        size_t bytes = 0;
+        int busy = 0;
+        for (Slab* sl : g_slabs) {
+            if (sl->busy) { busy++; continue; }
+            PS_TRY(poison_device(rt, sl->p, sl->bytes, index_word, index_word));
+            bytes += sl->bytes;
+        }
+        PS_HIP(hipStreamSynchronize(rt->stream));
+        say("slab", bytes, PoisonClass::INDEX, busy);
+    }
+    {   // the cached AlignData slabs, each after the last work of its previous owner (a live AlignData's slab is not in the cache)
+        std::lock_guard<std::mutex> lk(g_aslab_mu);
+        size_t bytes = 0;
+        for (CachedSlab& c : g_aslabs) {
+            if (c.pending) PS_HIP(hipEventSynchronize(c.ev));
+            PS_TRY(poison_device(rt, c.p, c.cap, index_word, index_word));
+            bytes += c.cap;
+        }
+        PS_HIP(hipStreamSynchronize(rt->stream));
+        say("align_cache", bytes, PoisonClass::INDEX, 0);
+    }
+    for (auto& kv : rt->hpool) {
+        poison_host(kv.second.p, kv.second.cap, index_word);
+        say("host:" + kv.first, kv.second.p ? kv.second.cap : 0, PoisonClass::INDEX, 0);
+    }
+    {
+        size_t bytes = 0;
+        for (Stage::Chunk& c : rt->stage.chunks) { poison_host(c.p, c.cap, index_word); bytes += c.cap; }
+        say("stage", bytes, PoisonClass::INDEX, 0);
+    }
+    if (n_rep) *n_rep = n;
+    return PS_OK;
+}
+
 // what ps_info's line says about this file's state
 MemInfo mem_info() {
     MemInfo m;

@@ -373,10 +373,9 @@ static int stage_descriptors(Chain& c) {
     PS_TRY(db.ensure(dbls * sizeof(double)));
     c.score0 = db.as<double>();
     double* dd = c.score0 + c.score_tot;
-    if (const char* name = c.points() ? "ptable" : c.phase() ? "phase" : c.support() ? "support" : nullptr) {
-        DBuf& ob = c.rt->buf(name);
-        PS_TRY(ob.ensure(std::max<size_t>(c.out_bytes, 16)));
-        c.d_out = ob.as<char>();
+    if (DBuf* ob = c.points() ? &c.rt->buf("ptable") : c.phase() ? &c.rt->buf("phase") : c.support() ? &c.rt->buf("support") : nullptr) {
+        PS_TRY(ob->ensure(std::max<size_t>(c.out_bytes, 16)));
+        c.d_out = ob->as<char>();
     }
     IntStage st;
     st.dp = mb.as<int>();

@@ -71,9 +71,9 @@ def covers(spans, starts, L, e, m):
     return starts[m] <= L and spans[e] is not None and spans[e][0] <= starts[m] + 1 <= spans[e][1]
 
 
-def loop(draft, events, params, muts, groups, G):
-    """(scores float64 [M], support _capi.EDIT_SUPPORT [M, G]) by the definition"""
-    starts, delta, spans = oracle_terms(draft, events, params, muts)
+def loop(draft, events, params, muts, groups, G, terms=None):
+    """(scores float64 [M], support _capi.EDIT_SUPPORT [M, G]) by the definition; terms: oracle_terms' result when the caller has it"""
+    starts, delta, spans = oracle_terms(draft, events, params, muts) if terms is None else terms
     E, M, L = len(events), len(starts), len(draft)
     scores = np.zeros(M, dtype=np.float64)
     sup = np.zeros((M, G), dtype=_capi.EDIT_SUPPORT)
