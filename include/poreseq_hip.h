@@ -337,9 +337,9 @@ int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, do
  *   Order of the adds (a host can reproduce the bits, as for ps_event_hap): partial t = +0.0 takes the qualifying levels
  *       i = t, t + 256, t + 512, ... ascending; the 256 partials are then added into +0.0 for t = 0 .. 255.
  * The batch form is one launch for all regions; a batch whose realignment does not fit device memory is cut between AlignData,
- * never inside one.  Not part of the reference's interface.  Not built: drift (the ABI carries no level times), the stdv channel's
- * scale_sd / var_sd (the inverse Gaussian has no closed form), per-k-mer model re-estimation, and transition parameters (they need
- * the backtrace's moves, not the array). */
+ * never inside one.  Not part of the reference's interface.  Not built: drift (the ABI carries no level times) and transition
+ * parameters (they need the backtrace's moves, not the array).  The stdv channel's scale_sd / var_sd and per-k-mer model
+ * re-estimation are fitted from ps_kmer_stats' tables (below). */
 typedef struct ps_event_stats {
     int32_t n_levels, n_aligned, n_insert, n_unaligned;
     int32_t n_step, n_stay, n_extend, n_jump, n_back;
@@ -348,6 +348,38 @@ typedef struct ps_event_stats {
     double sw, swm, swmm, swr, swmr, swrr;
 } ps_event_stats;   /* 112 bytes, no padding */
 int ps_align_stats(ps_align* a, int32_t realign, double* scores /* [E] or NULL */, ps_event_stats* stats /* [E] */);
+
+/* Per-k-mer model statistics by event group, reduced on the device from the alignment the handle holds (k_kmer_stats): for every
+ * group of events and every one of the 1024 5-mer states the sufficient statistics of a re-estimation of that state's model rows —
+ * level mean and variance, the stdv channel's mean — and, summed over the states, of the stdv channel's scale_sd / var_sd.  The
+ * fits are a few lines on the host (poreseq_amd.util.fit_kmers, fit_scaling_sd).
+ *
+ * `realign` and `scores` are ps_align_stats': realign != 0 runs ps_score_alignments' chain first, `scores` (may be NULL) gets its
+ * bits and the realignment stays in the handle; realign == 0 reduces the refs the handle holds, launches no DP, and `scores` must
+ * be NULL (PS_ERR_BAD_ARG otherwise).  groups[e] is the group of event e, 0 .. n_groups - 1, n_groups is 1 .. 256
+ * (PS_KMER_MAX_GROUPS); table has n_groups rows of 1024 records (ps_kmer_cell), row g for group g.  PS_ERR_BAD_ARG: n_groups outside 1 .. 256,
+ * an id outside 0 .. n_groups - 1, a NULL table, NULL groups with events.  An AlignData without events is PS_OK, launches nothing
+ * and gets an all-zero table; a group without events has all-zero rows.
+ *
+ * Which levels enter is ps_align_stats' n_fit rule: a level with ra[i] > 0 whose column c = (int)fmin(ra[i], 2147483647.0) has
+ * 1 <= c <= S and whose state k = states[c - 1] lies in 0 .. 1023.  With the event's model rows m_k = level_mean[k], s_k =
+ * level_stdv[k], mu_k = sd_mean[k] and lam_k = sd_lambda[k] (= sd_mean^3 / sd_stdv^2), every operation rounded once (IEEE double,
+ * no contraction):
+ *     z = (mean[i] - m_k) / s_k;  u = stdv[i] / mu_k;  p = lam_k / mu_k;
+ *     n += 1;  sz += z;  szz += z * z;  sp += p;  spu += p * u;  spv += p / u          into table[groups[e]][k].
+ * Order of the adds (a host can reproduce the bits): every sum of one (g, k) starts at +0.0 and is serial — the events of group g
+ * in event order, within an event the levels in ascending order.  Non-finite inputs propagate by IEEE rules into the cells they
+ * touch and nowhere else.
+ * Invariant: the sum of n over a table equals the sum of n_fit of ps_align_stats' records on the same refs.
+ * The batch form is one launch of k_kmer_stats for all regions and one copy back; a batch whose realignment or whose tables do not
+ * fit device memory is cut between AlignData, never inside one.  Not part of the reference's interface. */
+#define PS_KMER_MAX_GROUPS 256
+typedef struct ps_kmer_cell {
+    int64_t n;
+    double sz, szz, sp, spu, spv;
+} ps_kmer_cell;   /* 48 bytes, no padding (C has one name space for types and functions: the record cannot carry the call's name) */
+int ps_kmer_stats(ps_align* a, int32_t realign, const int32_t* groups /* [E] */, int32_t n_groups,
+                  double* scores /* [E] or NULL */, ps_kmer_cell* table /* [n_groups][1024] */);
 
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
@@ -416,6 +448,9 @@ int ps_batch_score_mutation_phase(int32_t n, ps_align* const* a, const ps_muts* 
                                   ps_edit_link* const* link, ps_edit_phase* const* phase, ps_event_hap* const* hap, int32_t* const* n_sets);
 /* ps_align_stats for every AlignData in one launch chain and ONE copy back: stats[i] has n_events(i) records (never NULL, also for an AlignData without events); with realign != 0 scores[i] — entries or the whole array may be NULL — has n_events(i) entries, with realign == 0 every scores[i] must be NULL. */
 int ps_batch_align_stats(int32_t n, ps_align* const* a, int32_t realign, double* const* scores, ps_event_stats* const* stats);
+/* ps_kmer_stats for every AlignData in one launch chain, ONE launch of k_kmer_stats and one copy back: groups[i] has n_events(i) ids (may be NULL for an AlignData without events), n_groups[i] is 1 .. 256, table[i] has n_groups[i] x 1024 records (never NULL); scores as in ps_batch_align_stats. */
+int ps_batch_kmer_stats(int32_t n, ps_align* const* a, int32_t realign, const int32_t* const* groups, const int32_t* n_groups /* [n] */,
+                        double* const* scores, ps_kmer_cell* const* table);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -519,7 +554,8 @@ int ps_set_device_fraction(double fraction);
  * "score", "viterbi", "sw", "point_table" = k_point_table: 8 bytes per (event, edit) read, 88 per position written, "support" = k_support: 8 bytes per (event, edit) read, 8 + 24 n_groups per edit written, "genotype" = k_genotype: 8 per (event, edit) read, 8 (n_frac + 1) + 4 per edit written,
  * "link" = k_link: 8 per (event, edit) read, 32 window per edit written, "phase" = k_phase: 32 window per edit read, 16 per edit written,
  * "haptag" = k_haptag: 8 per (event, edit) and 16 per edit read, 24 max_sets per event written,
- * "align_stats" = k_align_stats: 16 per level read, 112 per event written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
+ * "align_stats" = k_align_stats: 16 per level read, 112 per event written,
+ * "kmer_stats" = k_kmer_stats: 24 per level read, 48 * 1024 * n_groups per region written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
  * "fill_pair" / "fill_pair_fwd" / "fill_cmp" / "fill_512" / "fill_1024" / "fill_wide" (which form a k_fill launch took), "score_g7" .. "score_g64"
  * (k_score's size classes) and "fill_ieee" / "sweep_ieee" / "score_ieee" (launches that took the IEEE-division build);
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =

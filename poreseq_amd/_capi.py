@@ -65,6 +65,11 @@ EVENT_STATS = np.dtype([(k, np.int32) for k in ("n_levels", "n_aligned", "n_inse
                                                 "n_back", "n_nostate", "n_fit", "first_col", "last_col", "reserved")] +
                        [("n_gap_cols", np.int64)] + [(k, np.float64) for k in ("sw", "swm", "swmm", "swr", "swmr", "swrr")])
 
+# ps_kmer_cell (48 bytes, no padding): one (event group, 5-mer state) of the tables kmer_stats / batch_kmer_stats hand out
+KMER_STATS = np.dtype([("n", np.int64)] + [(k, np.float64) for k in ("sz", "szz", "sp", "spu", "spv")])
+KMER_MAX_GROUPS = 256
+KMER_TILE = 512      # levels k_kmer_stats stages per step (csrc/ps_internal.h); the tests put events on both sides of its edges
+
 
 class PsPoisonReport(C.Structure):
     # ps_poison_report, include/poreseq_hip.h
@@ -129,6 +134,8 @@ SYMBOLS = {
                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i32p)]),
     "ps_align_stats": (C.c_int, [C.c_void_p, C.c_int32, c_dp, C.c_void_p]),
     "ps_batch_align_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(c_dp), C.POINTER(C.c_void_p)]),
+    "ps_kmer_stats": (C.c_int, [C.c_void_p, C.c_int32, c_i32p, C.c_int32, c_dp, C.c_void_p]),
+    "ps_batch_kmer_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(c_i32p), c_i32p, C.POINTER(c_dp), C.POINTER(C.c_void_p)]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -170,9 +177,10 @@ SYMBOLS = {
 # PSAlign.PointTable builds its arrays from find_point_mutations + score_mutations; PSAlign.ScoreMutationSupport reduces
 # score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas, and PSAlign.ScoreMutationGenotypes does the
 # same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas;
-# PSAlign.AlignStats reduces the refs the library holds with util.align_stats_from_refs, after its score_alignments).
+# PSAlign.AlignStats reduces the refs the library holds with util.align_stats_from_refs, after its score_alignments, and
+# PSAlign.KmerStats does the same with util.kmer_stats_from_refs).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_align_stats", "ps_batch_align_stats", "ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
+OPTIONAL = frozenset(["ps_kmer_stats", "ps_batch_kmer_stats", "ps_align_stats", "ps_batch_align_stats","ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
                       "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes",
                       "ps_score_mutation_phase", "ps_batch_score_mutation_phase"])
@@ -536,6 +544,30 @@ class CApi:
         sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores]) if realign else None
         self.check(self.lib.ps_batch_align_stats(R, self._harr(hs), 1 if realign else 0, sp, rp))
         return [(scores[i][:int(e)] if realign else None, recs[i][:int(e)]) for i, e in enumerate(n_events)]
+
+    def kmer_stats(self, h, n_events, groups, n_groups, realign=True):
+        """-> (scores float64 [E] or None, table KMER_STATS [G, 1024]): ps_kmer_stats of one AlignData"""
+        return self.batch_kmer_stats([h], [n_events], [groups], [n_groups], realign)[0]
+
+    def batch_kmer_stats(self, hs, n_events, groups, n_groups, realign=True):
+        """ps_batch_kmer_stats over the AlignData `hs` with n_events[i] events: groups[i] gives every event of AlignData i a group id
+        0 .. n_groups[i] - 1 (1 .. 256 groups); per group and 5-mer state the sums of a re-estimation of that state's model rows
+        (include/poreseq_hip.h has the definition), one launch of k_kmer_stats and one copy back -> [(scores float64 [E] or None,
+        table KMER_STATS [G_i, 1024])].  realign as in batch_align_stats."""
+        self._need("ps_batch_kmer_stats")
+        R = len(hs)
+        grp = [np.ascontiguousarray(np.append(np.asarray(g, dtype=np.int32).reshape(-1), np.int32(0))) for g in groups]   # (one spare id: never a null pointer)
+        for g, e in zip(grp, n_events):
+            if g.size != int(e) + 1:
+                raise ValueError("kmer_stats: %d group ids for %d events" % (g.size - 1, int(e)))
+        ng = np.array([int(g) for g in n_groups] + [0], dtype=np.int32)
+        tabs = [np.zeros((min(max(int(g), 1), KMER_MAX_GROUPS), 1024), dtype=KMER_STATS) for g in n_groups]
+        scores = [np.zeros(max(int(e), 1), dtype=np.float64) for e in n_events] if realign else None
+        gp = (c_i32p * max(R, 1))(*[g.ctypes.data_as(c_i32p) for g in grp])
+        tp = (C.c_void_p * max(R, 1))(*[t.ctypes.data_as(C.c_void_p) for t in tabs])
+        sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores]) if realign else None
+        self.check(self.lib.ps_batch_kmer_stats(R, self._harr(hs), 1 if realign else 0, gp, ng.ctypes.data_as(c_i32p), sp, tp))
+        return [(scores[i][:int(e)] if realign else None, tabs[i]) for i, e in enumerate(n_events)]
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

@@ -194,6 +194,57 @@ class RegionBatch:
             out.append(fits)
         return out
 
+    def _kmer_groups(self, idx, groups, n_groups):
+        from .util import kmer_groups
+        gs = [None] * len(idx) if groups is None else list(groups)
+        ns = list(n_groups) if isinstance(n_groups, (list, tuple)) else [n_groups] * len(idx)
+        if len(gs) != len(idx) or len(ns) != len(idx):
+            raise ValueError("one grouping per region")
+        return [kmer_groups(self.pas[i].events, g, n) for i, g, n in zip(idx, gs, ns)]
+
+    def KmerStats(self, idx=None, groups=None, n_groups=None, realign=True):
+        """PSAlign.KmerStats for the regions `idx` in lock-step: ONE ps_batch_kmer_stats call — with realign the launch chain of
+        ScoreEvents over all regions, then one k_kmer_stats launch over all their events, one copy back.  `groups`: None (every
+        region by strand) or one list of ids (or None) per region; `n_groups`: None, one number for all regions or one per region.
+        Returns one (scores float64 [E] or None, table _capi.KMER_STATS [G, 1024]) per region; sequences and events are not
+        modified (a resident handle's refs come out as they went in)."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        gg = self._kmer_groups(idx, groups, n_groups)
+        hs = self._open(idx, keep=True)
+        try:
+            if "ps_batch_kmer_stats" in self.api.missing:
+                return [poreseqcpp._kmer_stats_on(self.api, h, self.pas[i].events, g, G, bool(realign)) for i, h, (g, G) in zip(idx, hs, gg)]
+            return self.api.batch_kmer_stats(hs, [len(self.pas[i].events) for i in idx], [g for g, _ in gg], [G for _, G in gg], bool(realign))
+        finally:
+            self._close(idx, hs, write_back=False)
+
+    def RefitKmers(self, idx=None, pool=True, groups=None, n_groups=None, **fit_kw):
+        """PSAlign.RefitKmers for the regions `idx`: one lock-step KmerStats, then util.fit_kmers / util.apply_kmers on the Python
+        events' models.  pool=True (the regions carry the same reads' models under the same grouping) adds the regions' tables
+        (util.add_kmer_stats, in the order of `idx`) and fits once for all of them; pool=False fits every region on its own table.
+        A resident AlignData holds the models it was created with, so the handles of the regions whose models changed are written
+        back (sync) and dropped; the next call rebuilds them.  Returns the fits per region, one util.KmerFit per group (with
+        pool=True every region gets the same list)."""
+        from .util import add_kmer_stats, fit_kmers
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        gg = self._kmer_groups(idx, groups, n_groups)
+        tables = [t for _, t in self.KmerStats(idx, [g for g, _ in gg], [G for _, G in gg], realign=True)]
+        if pool:
+            if len(set(G for _, G in gg)) != 1:
+                raise ValueError("RefitKmers(pool=True): the regions have different numbers of groups")
+            fits = [fit_kmers(add_kmer_stats(tables), **fit_kw)] * len(idx)
+        else:
+            fits = [fit_kmers(t, **fit_kw) for t in tables]
+        for i, (g, _), f in zip(idx, gg, fits):
+            if poreseqcpp._refit_kmers(self.pas[i].events, g, f) and i in self._h:
+                self.sync([i])
+                self.drop([i])
+        return fits
+
     def ScoreSequences(self, seqs_per_region, idx=None):
         """PSAlign.ScoreSequences for the regions `idx` on their resident AlignData, all regions' sequences in one chain:
         seqs_per_region[k] are the candidate sequences of region idx[k] (may be empty).  Returns one ndarray

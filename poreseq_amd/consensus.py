@@ -50,7 +50,14 @@ def _recalibrate_kw(recalibrate):
     return dict(recalibrate) if isinstance(recalibrate, dict) else {}
 
 
-def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None, recalibrate=None):
+def _refit_kmers_kw(refit_kmers):
+    """None / False: no per-k-mer refit; True: the defaults; a dict: keyword arguments of RefitKmers (groups and util.fit_kmers')"""
+    if refit_kmers is None or refit_kmers is False:
+        return None
+    return dict(refit_kmers) if isinstance(refit_kmers, dict) else {}
+
+
+def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None, recalibrate=None, refit_kmers=False):
     """Run the consensus schedule in place on `pa`; returns (sequence, accuracy_vs_refseq).
 
     The call sequence is the reference's (Mutate.py:39-101) and has to be: a region with fewer than 5 events is handed
@@ -69,6 +76,11 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     before Mutate('self') — every read's model shift / scale / var refitted on its alignment to the start sequence
     (util.fit_scaling), in place on the events' models — and logs ("Recalibrate", reads whose model changed, sequence).  None or
     False is the schedule as it is without the argument: same calls, same log, same random draws.  Unmeasured on real data.
+    `refit_kmers` (not in the reference; off by default): True, or a dict of keyword arguments for it, runs one `pa.RefitKmers()`
+    right after the optional recalibration and before Mutate('self') — per strand (or the given groups) and 5-mer state the level
+    mean, level variance and stdv-channel mean re-estimated on the alignment to the start sequence (util.fit_kmers), in place on
+    the events' models — and logs ("RefitKmers", k-mers fitted over the groups, sequence).  False or None is the schedule as it is
+    without the argument.  What it does to accuracy on real data is unmeasured.
     """
     params = pa.params if params is None else params
     pa.params.setdefault('verbose', 0)
@@ -98,6 +110,10 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     if recal is not None:
         changed = call("Recalibrate", lambda: sum(1 for f in pa.Recalibrate(**recal) if f.ok))
         _report(verbose, "recalibrated the models of %d of %d reads" % (changed, len(pa.events)))
+    refit = _refit_kmers_kw(refit_kmers)
+    if refit is not None:
+        fitted = call("RefitKmers", lambda: sum(f.n_fitted for f in pa.RefitKmers(**refit)))
+        _report(verbose, "refitted %d k-mer rows" % fitted)
     call("Mutate:self", lambda: pa.Mutate(reps=reps))
     if verbose > 0:
         _report(verbose, "identity after seeding from the reads: %.1f%%" % identity(pa.sequence, refseq)[0])
@@ -127,7 +143,7 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
 
 
 def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True, test=False, accuracies=None,
-                      qualities=None, recalibrate=None):
+                      qualities=None, recalibrate=None, refit_kmers=False):
     """The consensus schedule of `consensus_region` for several independent regions in lock-step (poreseq_amd.batch):
     every PSAlign call of the schedule is issued once for all regions that still take part in it, so each phase is one
     launch chain on the GPU.  Returns [(sequence, accuracy)] in the order of `pas`; each entry equals what
@@ -146,6 +162,9 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
     or writes is bit for bit what it is without `qualities`.
     `recalibrate`: as consensus_region takes it; one lock-step RegionBatch.Recalibrate over all refined regions before Mutate('self'),
     logged per region as ("Recalibrate", reads whose model changed, sequence).  None or False: the schedule as it is without it.
+    `refit_kmers`: as consensus_region takes it; one lock-step RegionBatch.RefitKmers(pool=False) over all refined regions — every
+    region fitted on its own table, as consensus_region does — after the recalibration and before Mutate('self'), logged per region
+    as ("RefitKmers", k-mers fitted over the groups, sequence).  Unmeasured on real data.
     """
     from .batch import RegionBatch
     n = len(pas)
@@ -189,10 +208,14 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
                     batch.close()
                 raise
         recal = _recalibrate_kw(recalibrate)
+        refit = _refit_kmers_kw(refit_kmers)
         with (batch if batch is not None else RegionBatch(pas, resident=resident)) as rb:
             if recal is not None:
                 for i, fits in zip(todo, rb.Recalibrate(todo, **recal)):
                     note(i, "Recalibrate", sum(1 for f in fits if f.ok))
+            if refit is not None:
+                for i, fits in zip(todo, rb.RefitKmers(todo, pool=False, **refit)):
+                    note(i, "RefitKmers", sum(f.n_fitted for f in fits))
             tot = rb.Mutate(todo, reps=reps)
             for i in todo:
                 note(i, "Mutate:self", tot[i])

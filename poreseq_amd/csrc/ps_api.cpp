@@ -259,6 +259,44 @@ int ps_align_stats(ps_align* a, int32_t realign, double* scores, ps_event_stats*
     if (!stats) return fail(PS_ERR_BAD_ARG, "ps_align_stats: null stats");
     return ps_batch_align_stats(1, &a, realign, &scores, &stats);
 }
+int ps_batch_kmer_stats(int32_t n, ps_align* const* a, int32_t realign, const int32_t* const* groups, const int32_t* n_groups, double* const* scores,
+                        ps_kmer_cell* const* table) {
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n && !table) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null table");
+    if (n && !n_groups) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null n_groups");
+    std::vector<double*> sc(n, nullptr);
+    std::vector<ps_kmer_cell*> tb(n);
+    std::vector<const int32_t*> gr(n, nullptr);
+    std::vector<int> ng(n);
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        if (!table[i]) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null table");
+        if (n_groups[i] < 1 || n_groups[i] > PS_KMER_MAX_GROUPS)
+            return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(PS_KMER_MAX_GROUPS));
+        if (as[i]->E > 0 && (!groups || !groups[i])) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null groups");
+        for (int e = 0; e < as[i]->E; e++)
+            if (groups[i][e] < 0 || groups[i][e] >= n_groups[i])
+                return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: event " + std::to_string(e) + " has group " + std::to_string(groups[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
+        if (scores && scores[i]) {
+            if (!realign) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: scores without a realignment (realign == 0 launches no DP: scores must be NULL)");
+            sc[i] = scores[i];
+        }
+        tb[i] = table[i]; ng[i] = n_groups[i]; gr[i] = groups ? groups[i] : nullptr;
+        any = any || as[i]->E > 0;
+    }
+    if (!any) {   // (no events anywhere: nothing is launched, the tables are all zero)
+        for (int i = 0; i < n; i++) memset(tb[i], 0, (size_t)ng[i] * NS * sizeof(ps_kmer_cell));
+        return PS_OK;
+    }
+    NEED_RT();
+    return kmer_stats_multi(rt, as, realign != 0, gr, ng, sc, tb);
+}
+int ps_kmer_stats(ps_align* a, int32_t realign, const int32_t* groups, int32_t n_groups, double* scores, ps_kmer_cell* table) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_kmer_stats: null handle");
+    if (!table) return fail(PS_ERR_BAD_ARG, "ps_kmer_stats: null table");
+    return ps_batch_kmer_stats(1, &a, realign, &groups, &n_groups, &scores, &table);
+}
 int ps_batch_find_mutations(int32_t n, ps_align* const* a, const ps_seqs* const* seeds, ps_muts** out) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

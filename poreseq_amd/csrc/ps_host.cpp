@@ -574,6 +574,35 @@ int score_alignments(Runtime* rt, Align* a, double* scores, double* likes) {
     return score_alignments_multi(rt, {a}, {scores}, {likes});
 }
 
+// The descriptors of k_align_stats and k_kmer_stats for the AlignData `as`, whose events are the jobs of `b` in order: one StatJob
+// per event, one StatRegion per AlignData.  groups (k_kmer_stats; null otherwise): per AlignData the events' group ids and the
+// number of groups; the regions' table rows follow each other.  Returns the levels of all events.
+static double stat_descriptors(const std::vector<Align*>& as, const Batch& b, const std::vector<const int32_t*>* groups, const std::vector<int>* ngroups,
+                               std::vector<StatJob>* sj, std::vector<StatRegion>* sr, int* maxE) {
+    sj->assign(b.jobs.size(), StatJob());
+    sr->assign(as.size(), StatRegion());
+    *maxE = 0;
+    double levels = 0;
+    size_t q = 0;
+    int tab = 0;
+    for (size_t k = 0; k < as.size(); k++) {
+        const Align* a = as[k];
+        StatRegion& r = (*sr)[k];
+        r.job0 = (int)q; r.njobs = a->E; r.ngroups = groups ? (*ngroups)[k] : 0; r.tab0 = tab;
+        tab += r.ngroups;
+        *maxE = std::max(*maxE, a->E);
+        for (int e = 0; e < a->E; e++, q++) {
+            const JobD& j = b.jobs[q];
+            StatJob& s = (*sj)[q];
+            s.ra = j.ra; s.mean = a->d_mean + a->off[e]; s.stdv = a->d_stdv + a->off[e]; s.model = a->d_model + (size_t)e * 6 * NS;
+            s.st = j.st; s.n = j.n0; s.S = j.C;
+            s.grp = groups ? (*groups)[k][e] : 0; s.pad = 0;
+            levels += j.n0;
+        }
+    }
+    return levels;
+}
+
 // ps_align_stats / ps_batch_align_stats (include/poreseq_hip.h): with `re`, ScoreAlignments' chain as above and then k_align_stats
 // over the refs the backtrace just wrote; without it k_align_stats over the refs the handles hold, and no DP.  Either way one
 // launch of it for all AlignData, and scores and records return in one copy.  scores[k] may be null.
@@ -597,24 +626,10 @@ int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const
         for (Align* a : as) a->host_refs_valid = false;
     }
     const size_t nj = specs.size();
-    std::vector<StatJob> sj(nj);
-    std::vector<StatRegion> sr(as.size());
+    std::vector<StatJob> sj;
+    std::vector<StatRegion> sr;
     int maxE = 0;
-    double bytes = 0;
-    {
-        size_t q = 0;
-        for (size_t k = 0; k < as.size(); k++) {
-            const Align* a = as[k];
-            sr[k].job0 = (int)q; sr[k].njobs = a->E;
-            maxE = std::max(maxE, a->E);
-            for (int e = 0; e < a->E; e++, q++) {
-                const JobD& j = b.jobs[q];
-                sj[q].ra = j.ra; sj[q].mean = a->d_mean + a->off[e]; sj[q].model = a->d_model + (size_t)e * 6 * NS;
-                sj[q].st = j.st; sj[q].n = j.n0; sj[q].S = j.C;
-                bytes += 16.0 * j.n0 + sizeof(ps_event_stats);
-            }
-        }
-    }
+    const double bytes = 16.0 * stat_descriptors(as, b, nullptr, nullptr, &sj, &sr, &maxE) + (double)nj * sizeof(ps_event_stats);
     // descriptors in; records and, behind them, the scores out
     const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
     const size_t out_recs = nj * sizeof(ps_event_stats), out_bytes = out_recs + (re ? nj * sizeof(double) : 0);
@@ -637,6 +652,69 @@ int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const
             stats[k][e] = recs[q];
             if (re && scores[k]) scores[k][e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
         }
+    return PS_OK;
+}
+
+// ps_kmer_stats / ps_batch_kmer_stats (include/poreseq_hip.h): align_stats_multi's shape — the same Batch, the same optional
+// realignment with the same split rules, one launch of k_kmer_stats for all AlignData, tables and scores back in one copy.  A batch
+// whose tables (48 KiB per group) exceed this runtime's share is cut between AlignData as well.  Every as[k] has events or not;
+// tables[k] has ngroups[k] x NS cells and is written in full.
+int kmer_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<const int32_t*>& groups, const std::vector<int>& ngroups,
+                     const std::vector<double*>& scores, const std::vector<ps_kmer_cell*>& tables) {
+    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
+        return kmer_stats_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), re, std::vector<const int32_t*>(groups.begin() + k0, groups.begin() + k1),
+                                std::vector<int>(ngroups.begin() + k0, ngroups.begin() + k1), std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
+                                std::vector<ps_kmer_cell*>(tables.begin() + k0, tables.begin() + k1));
+    };
+    size_t rows = 0;
+    int maxG = 0;
+    for (int g : ngroups) { rows += (size_t)g; maxG = std::max(maxG, g); }
+    const size_t out_tabs = rows * NS * sizeof(ps_kmer_cell);
+    if (as.size() > 1 && (double)out_tabs > device_share_bytes()) return in_halves(as.size(), sub);
+    auto need = [&](size_t k) { return share_need(as[k], 1); };
+    if (re && over_share(as.size(), 1, need)) return in_share_chunks(as.size(), 1, need, sub);   // (cut between AlignData, as ScoreAlignments is)
+    std::vector<JobSpec> specs;
+    for (Align* a : as)
+        for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
+    if (specs.empty()) {
+        for (size_t k = 0; k < as.size(); k++) memset(tables[k], 0, (size_t)ngroups[k] * NS * sizeof(ps_kmer_cell));
+        return PS_OK;
+    }
+    Batch b;   // (also without a realignment: it puts every sequence's states on the device)
+    PS_TRY(b.build(rt, specs, 1, 0));
+    if (re) {
+        const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
+        if (rc == PS_SPLIT) return in_halves(as.size(), sub);
+        PS_TRY(rc);
+        for (Align* a : as) a->host_refs_valid = false;
+    }
+    const size_t nj = specs.size();
+    std::vector<StatJob> sj;
+    std::vector<StatRegion> sr;
+    int maxE = 0;
+    const double bytes = 24.0 * stat_descriptors(as, b, &groups, &ngroups, &sj, &sr, &maxE) + (double)out_tabs;
+    // descriptors in; tables and, behind them, the scores out
+    const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
+    const size_t out_bytes = out_tabs + (re ? nj * sizeof(double) : 0);
+    DBuf& din = rt->buf("astats_in");
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(din.ensure(in_bytes));
+    PS_TRY(dout.ensure(out_bytes));
+    PS_TRY(rt->up(din.p, sj.data(), in_jobs));
+    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
+    PS_TRY(launch_kmer_stats(rt, din.as<StatJob>(), (const StatRegion*)((char*)din.p + in_jobs), (int)sr.size(), maxG, bytes, dout.as<ps_kmer_cell>()));
+    if (re) PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + out_tabs)));
+    void* back = nullptr;
+    PS_TRY(rt->down(&back, dout.p, out_bytes));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    const ps_kmer_cell* tabs = (const ps_kmer_cell*)back;
+    const double* best = (const double*)((const char*)back + out_tabs);
+    size_t q = 0;
+    for (size_t k = 0; k < as.size(); k++) {
+        memcpy(tables[k], tabs + (size_t)sr[k].tab0 * NS, (size_t)ngroups[k] * NS * sizeof(ps_kmer_cell));
+        for (int e = 0; e < as[k]->E; e++, q++)
+            if (re && scores[k]) scores[k][e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
+    }
     return PS_OK;
 }
 

@@ -142,6 +142,9 @@ int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std
 // ps_batch_align_stats: per event the census of ref_align and the sums of the scaling fit (ps_stats.hip), after ScoreAlignments'
 // chain (re) or of the refs as they are; scores[k] may be null (must be without re), stats[k] has E records
 int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<double*>& scores, const std::vector<ps_event_stats*>& stats);
+// ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation (ps_stats.hip), the same chain
+int kmer_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<const int32_t*>& groups, const std::vector<int>& ngroups,
+                     const std::vector<double*>& scores, const std::vector<ps_kmer_cell*>& tables);
 int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seeds,
                          const std::vector<std::vector<Mut>*>& outs);
 // Every event of an AlignData aligned forward-only to a sequence that is not its own, for any number of such (AlignData, sequence)

@@ -320,10 +320,17 @@ struct StatJob {
     const double* model;  // the event's model, rows of NS: level_mean, level_stdv (the first two of d_model's six)
     const int* st;        // 5-mer states of the sequence [S]
     int n, S;
+    const double* stdv;   // level stdvs [n] (k_kmer_stats)
+    int grp, pad;         // the event's group (k_kmer_stats; 0 for k_align_stats)
 };
-struct StatRegion { int job0, njobs; };
+struct StatRegion { int job0, njobs, ngroups, tab0; };   // ngroups, tab0: the region's groups and its first table row (k_kmer_stats)
 // grid (maxE, nregs): out[job] for every job of every region; alg_bytes for the profile ("align_stats")
 int launch_align_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxE, double alg_bytes, ps_event_stats* d_out);
+// Per-k-mer model statistics (ps_stats.hip, ps_kmer_stats): grid (KMER_BLOCKS x maxG, nregs); d_out[(tab0 + g) * NS + k] for every
+// group g of every region; alg_bytes for the profile ("kmer_stats")
+constexpr int KMER_TILE = 512;     // levels staged in LDS per step
+constexpr int KMER_BLOCKS = 4;     // workgroups per (region, group): 256 k-mers each
+int launch_kmer_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxG, double alg_bytes, ps_kmer_cell* d_out);
 
 // Smith-Waterman (kernels: ps_sw.hip, host side: ps_swhost.cpp)
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,

@@ -72,7 +72,7 @@ constexpr PoisonEntry POISON_TABLE[] = {
     {"phase", PoisonClass::INDEX, "links, set ids, haplotype tags"},
     // alignment census (ps_host.cpp)
     {"astats_in", PoisonClass::INDEX, "StatJob / StatRegion: pointers and sizes"},
-    {"astats", PoisonClass::INDEX, "ps_event_stats carries counts"},
+    {"astats", PoisonClass::INDEX, "ps_event_stats and ps_kmer_cell carry counts"},
     // Viterbi (ps_viterbi.hip)
     {"vit_regs", PoisonClass::INDEX, "VitReg: pointers, sizes, offsets"},
     {"vit_posreg", PoisonClass::INDEX, "region of every position"},

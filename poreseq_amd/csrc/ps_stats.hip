@@ -1,4 +1,4 @@
-// ps_stats.hip — ps_align_stats: the census of an event's ref_align array and the sufficient statistics of a shift / scale refit
+// ps_stats.hip — ps_align_stats and ps_kmer_stats.  ps_align_stats: the census of an event's ref_align array and the sufficient statistics of a shift / scale refit
 // of its model, reduced on the device (include/poreseq_hip.h has the definition of a record; this file follows it line by line).
 //
 //   k_align_stats   grid (events of the largest AlignData, AlignData), 256 threads per event, as the reductions of ps_edit.hip
@@ -12,11 +12,29 @@
 // Accumulators live in registers and are never indexed by a runtime value.  Sums: thread t adds the qualifying levels t, t + 256,
 // ... in ascending order into partials that start at +0.0, and one thread per sum then adds the 256 partials in t order — the
 // order the header defines, which a host can replay bit for bit.  Counts are integers and are reduced in any order.
+//
+//   k_kmer_stats    grid (KMER_BLOCKS x groups of the region with the most, AlignData), 256 threads: ps_kmer_stats' tables
+//
+// A histogram whose bins hold floating-point sums with a DEFINED order of the adds (per (group, k-mer): events in event order,
+// levels ascending, serial), so no atomics and no tree.  A workgroup owns one (region, group, block of 256 k-mers) and thread t one
+// k-mer of the block; its six accumulators live in registers.  The workgroup streams the group's events in order in tiles of
+// KMER_TILE levels.  Load step: thread t takes the levels t, t + 256 of the tile (coalesced), qualifies them by the n_fit rule,
+// looks the state up and — only for a state of this workgroup's block — gathers the four model values, does the three divisions
+// once and stores the state id and z, u, p to LDS (id -1 otherwise).  Scan step, after a barrier: every thread walks the tile's ids
+// in level order, four per 16-byte LDS read and four such reads in flight (all lanes read the same address: a broadcast, no bank
+// conflict; the walk is bound by LDS latency), and on a match adds
+// that level's terms from LDS to its registers; a second barrier before the next tile overwrites the stage.
+// Choice: KMER_BLOCKS = 4 blocks of 256 k-mers (the levels are staged four times, but a lone region with two groups puts eight
+// workgroups on the chip instead of two, and each does a quarter of the divisions), KMER_TILE = 512: LDS 512 x (4 + 3 x 8) =
+// 14 336 bytes per workgroup, so LDS (160 KiB per CU) admits more workgroups per CU than the four the guides advise to plan
+// for; a larger tile would only save barriers (two per 512 walk steps already).
 #include "ps_internal.h"
 
 namespace ps {
 
 static_assert(sizeof(ps_event_stats) == 112, "ps_event_stats has no padding");
+static_assert(sizeof(ps_kmer_cell) == 48, "ps_kmer_cell has no padding");
+static_assert(KMER_BLOCKS * 256 == NS && KMER_TILE % 256 == 0 && KMER_TILE % 16 == 0, "a thread per k-mer, the walk takes sixteen ids per step");
 
 namespace {
 
@@ -136,7 +154,81 @@ __global__ __launch_bounds__(256) void k_align_stats(const StatJob* __restrict__
     }
 }
 
+__global__ __launch_bounds__(256) void k_kmer_stats(const StatJob* __restrict__ J, const StatRegion* __restrict__ R, ps_kmer_cell* __restrict__ out) {
+    const StatRegion rg = R[blockIdx.y];
+    const int g = (int)blockIdx.x / KMER_BLOCKS, kb = (int)blockIdx.x % KMER_BLOCKS;
+    if (g >= rg.ngroups) return;   // (the same for every thread of the block)
+    __shared__ __attribute__((aligned(16))) int s_k[KMER_TILE];
+    __shared__ double s_z[KMER_TILE], s_u[KMER_TILE], s_p[KMER_TILE];
+    const int t = threadIdx.x, mine = kb * 256 + t;
+    long long n = 0;
+    double sz = 0.0, szz = 0.0, sp = 0.0, spu = 0.0, spv = 0.0;
+    for (int q = 0; q < rg.njobs; q++) {
+        const StatJob j = J[rg.job0 + q];
+        if (j.grp != g) continue;   // (uniform: the barriers below are met by all threads or by none)
+        for (int base = 0; base < j.n; base += KMER_TILE) {
+            const int m = min(KMER_TILE, j.n - base);
+#pragma unroll
+            for (int l = t; l < KMER_TILE; l += 256) {
+                int k = -1;
+                if (l < m) {
+                    const double ra = j.ra[base + l];
+                    if (ra > 0.0) {
+                        const int c = (int)fmin(ra, 2147483647.0);
+                        if (c >= 1 && c <= j.S) k = j.st[c - 1];
+                    }
+                    if (k < 0 || k >= NS || (k >> 8) != kb) k = -1;
+                }
+                if (k >= 0) {
+                    const double mk = j.model[k], sk = j.model[NS + k], mu = j.model[3 * NS + k], lam = j.model[4 * NS + k];
+                    s_z[l] = (j.mean[base + l] - mk) / sk;
+                    s_u[l] = j.stdv[base + l] / mu;
+                    s_p[l] = lam / mu;
+                }
+                s_k[l] = k;
+            }
+            __syncthreads();
+            auto take = [&](int l) {
+                const double z = s_z[l], u = s_u[l], p = s_p[l];
+                n++; sz += z; szz += z * z; sp += p; spu += p * u; spv += p / u;
+            };
+            for (int l = 0; l < m; l += 16) {   // (ids behind m are -1 up to the end of the tile; four reads in flight: the walk is LDS latency)
+                const int4* ids = reinterpret_cast<const int4*>(&s_k[l]);
+                const int4 a = ids[0], b = ids[1], c = ids[2], d = ids[3];
+                if (a.x == mine) take(l);
+                if (a.y == mine) take(l + 1);
+                if (a.z == mine) take(l + 2);
+                if (a.w == mine) take(l + 3);
+                if (b.x == mine) take(l + 4);
+                if (b.y == mine) take(l + 5);
+                if (b.z == mine) take(l + 6);
+                if (b.w == mine) take(l + 7);
+                if (c.x == mine) take(l + 8);
+                if (c.y == mine) take(l + 9);
+                if (c.z == mine) take(l + 10);
+                if (c.w == mine) take(l + 11);
+                if (d.x == mine) take(l + 12);
+                if (d.y == mine) take(l + 13);
+                if (d.z == mine) take(l + 14);
+                if (d.w == mine) take(l + 15);
+            }
+            __syncthreads();   // (the stage is written again by the next tile)
+        }
+    }
+    ps_kmer_cell* o = out + ((size_t)(rg.tab0 + g) * NS + mine);
+    o->n = n; o->sz = sz; o->szz = szz; o->sp = sp; o->spu = spu; o->spv = spv;
+}
+
 }  // namespace
+
+int launch_kmer_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxG, double alg_bytes, ps_kmer_cell* d_out) {
+    if (nregs <= 0 || maxG <= 0) return PS_OK;
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_kmer_stats, dim3(KMER_BLOCKS * maxG, nregs), dim3(256), 0, rt->stream, d_jobs, d_regs, d_out);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "kmer_stats", alg_bytes);
+    return PS_OK;
+}
 
 int launch_align_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxE, double alg_bytes, ps_event_stats* d_out) {
     if (nregs <= 0 || maxE <= 0) return PS_OK;

@@ -13,6 +13,7 @@ import numpy as np
 from . import _capi
 from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas, genotypes_from_deltas, check_alt_frac, phase_from_deltas, check_phase_args
 from .util import align_stats_from_refs, fit_scaling, apply_scaling
+from .util import kmer_groups, kmer_stats_from_refs, fit_kmers, apply_kmers
 
 
 def _api():
@@ -145,6 +146,32 @@ def _recalibrate(events, stats, var, fit_kw):
     return fits
 
 
+def _kmer_stats_on(api, h, events, grp, G, realign):
+    """(scores float64 [E] or None, table _capi.KMER_STATS [G, 1024]) of the AlignData `h`, whose events are `events`: ps_kmer_stats,
+    or — a library without the entry point — its score_alignments (with `realign`) and then the literal reduction of the refs the
+    handle holds (util.kmer_stats_from_refs)"""
+    E = len(events)
+    if "ps_kmer_stats" not in api.missing:
+        return api.kmer_stats(h, E, grp, G, realign)
+    scores = api.score_alignments(h, E) if realign else None
+    refs = api.align_event_refs(h, E)
+    states = api.seq_to_states(api.align_sequence(h))
+    return scores, kmer_stats_from_refs(states, events, refs, grp, G)
+
+
+def _refit_kmers(events, grp, fits):
+    """apply_kmers of every event's group's fit, in place on the events' models -> the events whose model changed"""
+    changed, seen = 0, set()
+    for ev, g in zip(events, np.asarray(grp).tolist()):
+        f = fits[g]
+        if f.n_fitted:
+            if id(ev.model) not in seen:      # (a model object shared by several events is refitted once)
+                seen.add(id(ev.model))
+                apply_kmers(ev, f)
+            changed += 1
+    return changed
+
+
 class PSAlign:
     """All data of reads aligned to a reference (pyx:189-472).
 
@@ -237,6 +264,30 @@ class PSAlign:
         consensus accuracy on real data has not been measured."""
         _, stats = self.AlignStats(realign=True)
         return _recalibrate(self.events, stats, var, fit_kw)
+
+    def KmerStats(self, groups=None, n_groups=None, realign=True):
+        """Per event group and 5-mer state the sums of a re-estimation of that state's model rows (ps_kmer_stats): (scores, table).
+        `groups` gives every event a group id 0 .. G - 1 — by default its strand, 0 template and 1 complement — and `n_groups` = G
+        (1 .. 256; default 2 for strands, else the largest id + 1): the events of a group are taken to share what is wrong with
+        their models.  realign=True aligns every event as ScoreEvents does (scores are its bits, float64 [E]) and reduces the
+        alignment that leaves, on the device, in the same launch chain (k_kmer_stats); realign=False reduces ref_align as the
+        events carry it, runs no DP and returns None for the scores.  table is a structured array (_capi.KMER_STATS [G, 1024]): n,
+        sz, szz, sp, spu, spv for util.fit_kmers / util.fit_scaling_sd, every sum added serially — events in event order, levels
+        ascending.  `self` is not modified.  ValueError for groups that do not fit."""
+        grp, G = kmer_groups(self.events, groups, n_groups)
+        with PSAlign._Data(self) as d:
+            return _kmer_stats_on(d.api, d.h, self.events, grp, G, bool(realign))
+
+    def RefitKmers(self, groups=None, n_groups=None, **fit_kw):
+        """Re-estimate the models per k-mer on the alignment to self.sequence: one KmerStats() pass, util.fit_kmers(**fit_kw) per
+        group, and util.apply_kmers IN PLACE on the model of every event of the group (a group without a fitted k-mer keeps its
+        models).  Returns the fits, one util.KmerFit per group.  Sequence, ref_align and ref_like are not touched.  What this does
+        to consensus accuracy on real data has not been measured."""
+        grp, G = kmer_groups(self.events, groups, n_groups)
+        _, table = self.KmerStats(grp, G, realign=True)
+        fits = fit_kmers(table, **fit_kw)
+        _refit_kmers(self.events, grp, fits)
+        return fits
 
     def ScoreSequences(self, seqs):
         """ndarray [len(seqs)][len(events)]: row s is what `pav = self.Copy(); pav.RealignTo(seqs[s]); pav.ScoreEvents()` returns,

@@ -527,8 +527,8 @@ def fit_scaling(stats, min_levels=100, min_spread=1e-6, scale_limits=(0.5, 2.0),
     var, ok, n_fit).  ok iff n_fit >= min_levels, det > min_spread * sw * swmm (the aligned states' means are spread out enough to
     tell a scale from a shift) and scale / var lie inside their limits (and are finite); a fit that is not ok is the identity
     (1, 0, 1).  The limits are guards with documented defaults — a read whose refit leaves them is more likely misaligned than
-    mis-scaled — not measurements.  Host only; drift, the stdv channel's scale_sd / var_sd, per-k-mer re-estimation and transition
-    parameters are not fitted."""
+    mis-scaled — not measurements.  Host only; drift and transition parameters are not fitted; the stdv channel's scale_sd / var_sd and
+    per-k-mer re-estimation are fit_scaling_sd's and fit_kmers', from ps_kmer_stats' tables."""
     import math
     import numpy as np
     if isinstance(stats, np.ndarray) and stats.ndim > 0:
@@ -560,4 +560,226 @@ def apply_scaling(event, fit, var=True):
     m.level_mean = np.asarray(m.level_mean, dtype=np.float64) * float(fit.scale) + float(fit.shift)
     if var:
         m.level_stdv = np.asarray(m.level_stdv, dtype=np.float64) * float(fit.var)
+    return event
+
+
+# ---- per-k-mer model statistics (ps_kmer_stats) and the refits made from them ----------------------------------------------------
+KMER_MAX_GROUPS = 256
+
+
+def kmer_groups(events, groups=None, n_groups=None):
+    """(group ids int32 [E], G) of a k-mer statistics call (PSAlign.KmerStats): `support_groups`' rules with up to 256 groups.
+    `groups` defaults to the strand of every event (0 template, 1 complement, from ev.model.complement) and `n_groups` to 2 for
+    that default, otherwise to the largest id + 1.  ValueError for a list that is not one id per event, G outside 1 .. 256 or an
+    id outside 0 .. G - 1."""
+    import numpy as np
+    E = len(events)
+    if groups is None:
+        groups = [1 if getattr(ev.model, 'complement', False) else 0 for ev in events]
+        if n_groups is None:
+            n_groups = 2
+    grp = np.asarray(list(groups), dtype=np.int64).reshape(-1)
+    if grp.size != E:
+        raise ValueError("kmer_stats: %d group ids for %d events" % (grp.size, E))
+    G = int(n_groups) if n_groups is not None else (int(grp.max()) + 1 if E else 1)
+    if not 1 <= G <= KMER_MAX_GROUPS:
+        raise ValueError("kmer_stats: n_groups = %d, allowed are 1 .. %d" % (G, KMER_MAX_GROUPS))
+    bad = np.flatnonzero((grp < 0) | (grp >= G))
+    if bad.size:
+        raise ValueError("kmer_stats: event %d has group %d, n_groups = %d" % (int(bad[0]), int(grp[bad[0]]), G))
+    return grp.astype(np.int32), G
+
+
+def model_lambda(sd_mean, sd_stdv):
+    """sd_lambda = sd_mean^3 / sd_stdv^2 of every model row as the library's host tables hold it (pow of the C library, then one
+    division; cpp/EventData.h:48-73)"""
+    import numpy as np
+    three, two = np.float64(3.0), np.float64(2.0)
+    with np.errstate(all='ignore'):
+        return np.array([np.float64(a) ** three / np.float64(b) ** two for a, b in zip(np.asarray(sd_mean, dtype=np.float64).reshape(-1).tolist(),
+                                                                                       np.asarray(sd_stdv, dtype=np.float64).reshape(-1).tolist())], dtype=np.float64)
+
+
+def kmer_stats_from_refs(states, events, refs, groups, n_groups):
+    """The table of ps_kmer_stats (_capi.KMER_STATS [n_groups, 1024]) — the definition of include/poreseq_hip.h in numpy float64
+    scalars, and the path of a library without the entry point.  states: the 5-mer states of the sequence (states[j - 1] belongs to
+    column j); events: the event objects (mean, stdv and the model rows are read); refs: one ref_align array per event; groups:
+    one id 0 .. n_groups - 1 per event.
+    A level enters iff ra > 0, its column c = int(min(ra, 2147483647.0)) has 1 <= c <= len(states) and k = states[c - 1] lies in
+    0 .. 1023 (ps_align_stats' n_fit rule).  With the event's rows m_k, s_k, mu_k = sd_mean[k], lam_k = sd_mean[k]^3 / sd_stdv[k]^2:
+    z = (mean - m_k) / s_k, u = stdv / mu_k, p = lam_k / mu_k; n += 1, sz += z, szz += z z, sp += p, spu += p u, spv += p / u into
+    table[group][k], every sum serial from 0.0: events in event order, levels ascending."""
+    import numpy as np
+    from ._capi import KMER_STATS
+    states = np.asarray(states, dtype=np.int64).reshape(-1)
+    S = states.size
+    G = int(n_groups)
+    n = np.zeros((G, 1024), dtype=np.int64)
+    sums = np.zeros((5, G, 1024), dtype=np.float64)
+    with np.errstate(all='ignore'):
+        for ev, ra, g in zip(events, refs, np.asarray(groups).reshape(-1).tolist()):
+            ra = np.asarray(ra, dtype=np.float64).reshape(-1)
+            al = ra > 0
+            col = np.zeros(ra.size, dtype=np.int64)
+            col[al] = np.minimum(ra[al], 2147483647.0).astype(np.int64)
+            has = al & (col >= 1) & (col <= S)
+            k = np.full(ra.size, -1, dtype=np.int64)
+            k[has] = states[col[has] - 1]
+            idx = np.flatnonzero(has & (k >= 0) & (k < 1024))
+            if not idx.size:
+                continue
+            md = ev.model
+            lm, ls = np.asarray(md.level_mean, dtype=np.float64), np.asarray(md.level_stdv, dtype=np.float64)
+            mu = np.asarray(md.sd_mean, dtype=np.float64)
+            lam = model_lambda(mu, md.sd_stdv)
+            kk = k[idx]
+            z = (np.asarray(ev.mean, dtype=np.float64)[idx] - lm[kk]) / ls[kk]
+            u = np.asarray(ev.stdv, dtype=np.float64)[idx] / mu[kk]
+            p = lam[kk] / mu[kk]
+            terms = (z, z * z, p, p * u, p / u)
+            row = sums[:, g, :]
+            for i, kq in enumerate(kk.tolist()):
+                n[g, kq] += 1
+                for q in range(5):
+                    row[q, kq] = row[q, kq] + terms[q][i]
+    table = np.zeros((G, 1024), dtype=KMER_STATS)
+    table["n"] = n
+    for q, name in enumerate(("sz", "szz", "sp", "spu", "spv")):
+        table[name] = sums[q]
+    return table
+
+
+def add_kmer_stats(tables):
+    """Pool k-mer tables of the same grouping (e.g. one per region of a lock-step batch): a host sum, field by field, in list
+    order, starting from the first table.  Returns a new table."""
+    import numpy as np
+    tables = list(tables)
+    if not tables:
+        raise ValueError("add_kmer_stats: no tables")
+    out = np.array(tables[0], copy=True)
+    with np.errstate(all='ignore'):
+        for t in tables[1:]:
+            if t.shape != out.shape:
+                raise ValueError("add_kmer_stats: tables of %r and %r" % (out.shape, t.shape))
+            for name in out.dtype.names:
+                out[name] = out[name] + t[name]
+    return out
+
+
+class KmerFit(object):
+    """fit_kmers' result for one event group, arrays of 1024: n (levels), dmean (shift of level_mean in units of level_stdv), vscale
+    (factor on level_stdv^2), sd_scale (factor on sd_mean), kept (identity: fewer than min_count levels or a non-finite term) and
+    clamped (a limit cut the result)"""
+    __slots__ = ("n", "dmean", "vscale", "sd_scale", "kept", "clamped")
+
+    def __init__(self, n, dmean, vscale, sd_scale, kept, clamped):
+        self.n, self.dmean, self.vscale, self.sd_scale, self.kept, self.clamped = n, dmean, vscale, sd_scale, kept, clamped
+
+    @property
+    def n_fitted(self):
+        return int((~self.kept).sum())
+
+    def __repr__(self):
+        return "KmerFit(%d of 1024 k-mers fitted, %d clamped)" % (self.n_fitted, int(self.clamped.sum()))
+
+
+def fit_kmers(table, prior=8.0, min_count=1, mean_limit=3.0, var_limits=(0.25, 4.0), sd_limits=(0.5, 2.0)):
+    """Per-k-mer model refit from a ps_kmer_stats table [G, 1024] (or one row [1024]): one KmerFit per group (one KmerFit for a
+    row).  With c = n / (n + prior), a shrinkage towards the model as it is (a k-mer seen `prior` times moves halfway):
+        dmean = c sz / n;  vscale = 1 + c ((szz - sz sz / n) / n - 1);  sd_scale = 1 + c (spu / sp - 1)
+    — the mean of the standardised residuals, their variance about that mean, and the maximiser of the inverse-Gaussian likelihood
+    in a factor on sd_mean at fixed lambda.  A k-mer with n < max(min_count, 1) or a non-finite term keeps the identity (0, 1, 1) and
+    is flagged `kept`; dmean is clamped to +-mean_limit, vscale to var_limits, sd_scale to sd_limits, flagged `clamped`.  The limits
+    are guards with documented defaults, not measurements.  Host only."""
+    import numpy as np
+    table = np.asarray(table)
+    if table.ndim == 2:
+        return [fit_kmers(row, prior, min_count, mean_limit, var_limits, sd_limits) for row in table]
+    n = table["n"].astype(np.int64)
+    nf = n.astype(np.float64)
+    with np.errstate(all='ignore'):
+        c = nf / (nf + float(prior))
+        mz = table["sz"] / nf
+        dmean = c * mz
+        vscale = 1.0 + c * ((table["szz"] - table["sz"] * table["sz"] / nf) / nf - 1.0)
+        sd_scale = 1.0 + c * (table["spu"] / table["sp"] - 1.0)
+        kept = (n < max(int(min_count), 1)) | ~(np.isfinite(dmean) & np.isfinite(vscale) & np.isfinite(sd_scale))
+        for name in ("sz", "szz", "sp", "spu", "spv"):
+            kept |= ~np.isfinite(table[name])
+    dmean, vscale, sd_scale = np.where(kept, 0.0, dmean), np.where(kept, 1.0, vscale), np.where(kept, 1.0, sd_scale)
+    lim = abs(float(mean_limit))
+    cd, cv, cs = np.clip(dmean, -lim, lim), np.clip(vscale, var_limits[0], var_limits[1]), np.clip(sd_scale, sd_limits[0], sd_limits[1])
+    clamped = (cd != dmean) | (cv != vscale) | (cs != sd_scale)
+    return KmerFit(n, cd, cv, cs, kept, clamped)
+
+
+class ScalingSdFit(tuple):
+    """(a, D, ok, n) of fit_scaling_sd, with the fields by name"""
+    __slots__ = ()
+    _fields = ("a", "D", "ok", "n")
+
+    def __new__(cls, a, D, ok, n):
+        return tuple.__new__(cls, (float(a), float(D), bool(ok), int(n)))
+
+    a = property(lambda self: self[0])
+    D = property(lambda self: self[1])
+    ok = property(lambda self: self[2])
+    n = property(lambda self: self[3])
+
+    def __repr__(self):
+        return "ScalingSdFit(a=%r, D=%r, ok=%r, n=%r)" % tuple(self)
+
+
+def fit_scaling_sd(table, min_levels=100, a_limits=(0.5, 2.0), var_limits=(0.25, 4.0)):
+    """The stdv channel's scale_sd / var_sd refit of one event group, in closed form from the row sums of its ps_kmer_stats row
+    [1024] (a table [G, 1024] gives a list, one fit per group).  The stdv of a level on state k is inverse Gaussian with mean mu_k
+    and shape lam_k; its log-likelihood holds -0.5 lam (x - mu)^2 / (mu^2 x).  With a common factor a on every mu_k (lam_k
+    fixed), u = x / mu_k and p = lam_k / mu_k that term is -0.5 p (u / a^2 - 2 / a + 1 / u), so
+        a = sum spu / sum sp                                  the exact maximiser (d/da = 0), the scale_sd factor
+        D = (sum spv - (sum sp)^2 / sum spu) / sum n          the mean deviance at a — 1 when the model is right — the var_sd
+                                                              factor: the maximiser of a common factor 1 / D on every lam_k
+    Returns ScalingSdFit(a, D, ok, n).  ok iff n >= min_levels and a, D are finite and inside their limits; a fit that is not ok is
+    the identity (1, 1).  Host only; the limits are guards, not measurements."""
+    import math
+    import numpy as np
+    table = np.asarray(table)
+    if table.ndim == 2:
+        return [fit_scaling_sd(row, min_levels, a_limits, var_limits) for row in table]
+    n = int(table["n"].sum())
+    with np.errstate(all='ignore'):
+        sp, spu, spv = (float(np.sum(table[k])) for k in ("sp", "spu", "spv"))
+    ident = ScalingSdFit(1.0, 1.0, False, n)
+    if n < int(min_levels) or n <= 0 or not (sp > 0 and spu > 0):
+        return ident
+    a = spu / sp
+    D = (spv - sp * sp / spu) / n
+    if not (math.isfinite(a) and math.isfinite(D)) or not (a_limits[0] <= a <= a_limits[1] and var_limits[0] <= D <= var_limits[1]):
+        return ident
+    return ScalingSdFit(a, D, True, n)
+
+
+def apply_kmers(event, fit):
+    """Apply a KmerFit to an event's model in place (new arrays): level_mean += dmean * level_stdv, level_stdv *= sqrt(vscale) —
+    the mean first: dmean is in units of the level_stdv the statistics were taken with — and sd_mean *= sd_scale.  sd_scale was
+    fitted at fixed lambda = sd_mean^3 / sd_stdv^2, and the model stores sd_stdv, not lambda: sd_stdv *= sd_scale^1.5 keeps every
+    lambda where it was.  Nothing else of the event is touched."""
+    import numpy as np
+    m = event.model
+    ls = np.asarray(m.level_stdv, dtype=np.float64)
+    m.level_mean = np.asarray(m.level_mean, dtype=np.float64) + fit.dmean * ls
+    m.level_stdv = ls * np.sqrt(fit.vscale)
+    m.sd_mean = np.asarray(m.sd_mean, dtype=np.float64) * fit.sd_scale
+    m.sd_stdv = np.asarray(m.sd_stdv, dtype=np.float64) * fit.sd_scale ** 1.5
+    return event
+
+
+def apply_scaling_sd(event, a, D=1.0):
+    """Apply fit_scaling_sd's (a, D) to an event's model in place (new arrays): sd_mean *= a, sd_stdv *= a^1.5 sqrt(D).
+    The fit moves every mu to a mu and every lambda to lambda / D; the model stores sd_stdv with lambda = sd_mean^3 / sd_stdv^2, so
+    sd_stdv'^2 = (a mu)^3 / (lambda / D) = a^3 D sd_stdv^2.  (A factor a sqrt(D) on sd_stdv would move lambda to a lambda / D, and
+    a second fit would then answer D = a instead of 1.)  A second fit_scaling_sd after this gives a = 1, D = 1."""
+    import numpy as np
+    m = event.model
+    m.sd_mean = np.asarray(m.sd_mean, dtype=np.float64) * float(a)
+    m.sd_stdv = np.asarray(m.sd_stdv, dtype=np.float64) * (float(a) ** 1.5 * float(D) ** 0.5)
     return event
