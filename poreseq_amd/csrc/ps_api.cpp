@@ -138,7 +138,8 @@ int ps_seqs_export(const ps_seqs* s, int64_t* off, char* pool) {
 int ps_score_alignments(ps_align* a, double* scores, double* likes) {
     if (!a || (!scores && a->a.E)) return fail(PS_ERR_BAD_ARG, "ps_score_alignments");
     NEED_RT();
-    return score_alignments(rt, &a->a, scores, likes);
+    OwnReq q{&a->a, scores, likes};
+    return own_forward(rt, OwnKind::Score, true, &q, 1);
 }
 int ps_find_point_mutations(ps_align* a, ps_muts** out) {
     if (!a || !out) return fail(PS_ERR_BAD_ARG, "ps_find_point_mutations");
@@ -227,32 +228,43 @@ int ps_batch_score_alignments(int32_t n, ps_align* const* a, double* const* scor
     PS_TRY(batch_handles(n, a, &as));
     if (n && !scores) return fail(PS_ERR_BAD_ARG, "ps_batch_score_alignments");
     NEED_RT();
-    std::vector<double*> sc(n), lk(n);
+    std::vector<OwnReq> rq(n);
     for (int i = 0; i < n; i++) {
         if (!scores[i] && as[i]->E) return fail(PS_ERR_BAD_ARG, "ps_batch_score_alignments: null scores");
-        sc[i] = scores[i]; lk[i] = likes ? likes[i] : nullptr;
+        rq[i].a = as[i]; rq[i].scores = scores[i]; rq[i].likes = likes ? likes[i] : nullptr;
     }
-    return score_alignments_multi(rt, as, sc, lk);
+    return own_forward(rt, OwnKind::Score, true, rq.data(), rq.size());
+}
+// What ps_batch_align_stats and ps_batch_kmer_stats check alike.  Per AlignData, in the order of their other checks: the output,
+// and scores only with a realignment
+static int stats_output(const std::string& who, const char* what, const void* out) { return out ? PS_OK : fail(PS_ERR_BAD_ARG, who + ": null " + what); }
+static int stats_scores(const std::string& who, int32_t realign, double* const* scores, int i, OwnReq* q) {
+    if (!scores || !scores[i]) return PS_OK;
+    if (!realign) return fail(PS_ERR_BAD_ARG, who + ": scores without a realignment (realign == 0 launches no DP: scores must be NULL)");
+    q->scores = scores[i];
+    return PS_OK;
+}
+// and their end: no events anywhere launches nothing and takes no runtime (the tables of the k-mer call are all zero)
+static int stats_run(OwnKind kind, int32_t realign, std::vector<OwnReq>& rq) {
+    if (std::none_of(rq.begin(), rq.end(), [](const OwnReq& q) { return q.a->E > 0; })) {
+        for (const OwnReq& q : rq) if (q.table) memset(q.table, 0, (size_t)q.ngroups * NS * sizeof(ps_kmer_cell));
+        return PS_OK;
+    }
+    NEED_RT();
+    return own_forward(rt, kind, realign != 0, rq.data(), rq.size());
 }
 int ps_batch_align_stats(int32_t n, ps_align* const* a, int32_t realign, double* const* scores, ps_event_stats* const* stats) {
+    const std::string who = "ps_batch_align_stats";
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
-    if (n && !stats) return fail(PS_ERR_BAD_ARG, "ps_batch_align_stats: null stats");
-    std::vector<double*> sc(n, nullptr);
-    std::vector<ps_event_stats*> st(n);
-    bool any = false;
+    if (n) PS_TRY(stats_output(who, "stats", stats));
+    std::vector<OwnReq> rq(n);
     for (int i = 0; i < n; i++) {
-        if (!stats[i]) return fail(PS_ERR_BAD_ARG, "ps_batch_align_stats: null stats");
-        if (scores && scores[i]) {
-            if (!realign) return fail(PS_ERR_BAD_ARG, "ps_batch_align_stats: scores without a realignment (realign == 0 launches no DP: scores must be NULL)");
-            sc[i] = scores[i];
-        }
-        st[i] = stats[i];
-        any = any || as[i]->E > 0;
+        PS_TRY(stats_output(who, "stats", stats[i]));
+        PS_TRY(stats_scores(who, realign, scores, i, &rq[i]));
+        rq[i].a = as[i]; rq[i].stats = stats[i];
     }
-    if (!any) return PS_OK;   // (no events anywhere: nothing is launched)
-    NEED_RT();
-    return align_stats_multi(rt, as, realign != 0, sc, st);
+    return stats_run(OwnKind::AlignStats, realign, rq);
 }
 int ps_align_stats(ps_align* a, int32_t realign, double* scores, ps_event_stats* stats) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_align_stats: null handle");
@@ -261,36 +273,23 @@ int ps_align_stats(ps_align* a, int32_t realign, double* scores, ps_event_stats*
 }
 int ps_batch_kmer_stats(int32_t n, ps_align* const* a, int32_t realign, const int32_t* const* groups, const int32_t* n_groups, double* const* scores,
                         ps_kmer_cell* const* table) {
+    const std::string who = "ps_batch_kmer_stats";
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
-    if (n && !table) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null table");
-    if (n && !n_groups) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null n_groups");
-    std::vector<double*> sc(n, nullptr);
-    std::vector<ps_kmer_cell*> tb(n);
-    std::vector<const int32_t*> gr(n, nullptr);
-    std::vector<int> ng(n);
-    bool any = false;
+    if (n) { PS_TRY(stats_output(who, "table", table)); PS_TRY(stats_output(who, "n_groups", n_groups)); }
+    std::vector<OwnReq> rq(n);
     for (int i = 0; i < n; i++) {
-        if (!table[i]) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null table");
+        PS_TRY(stats_output(who, "table", table[i]));
         if (n_groups[i] < 1 || n_groups[i] > PS_KMER_MAX_GROUPS)
-            return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(PS_KMER_MAX_GROUPS));
-        if (as[i]->E > 0 && (!groups || !groups[i])) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: null groups");
+            return fail(PS_ERR_BAD_ARG, who + ": n_groups = " + std::to_string(n_groups[i]) + ", allowed are 1 .. " + std::to_string(PS_KMER_MAX_GROUPS));
+        if (as[i]->E > 0) PS_TRY(stats_output(who, "groups", groups ? groups[i] : nullptr));
         for (int e = 0; e < as[i]->E; e++)
             if (groups[i][e] < 0 || groups[i][e] >= n_groups[i])
-                return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: event " + std::to_string(e) + " has group " + std::to_string(groups[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
-        if (scores && scores[i]) {
-            if (!realign) return fail(PS_ERR_BAD_ARG, "ps_batch_kmer_stats: scores without a realignment (realign == 0 launches no DP: scores must be NULL)");
-            sc[i] = scores[i];
-        }
-        tb[i] = table[i]; ng[i] = n_groups[i]; gr[i] = groups ? groups[i] : nullptr;
-        any = any || as[i]->E > 0;
+                return fail(PS_ERR_BAD_ARG, who + ": event " + std::to_string(e) + " has group " + std::to_string(groups[i][e]) + ", n_groups = " + std::to_string(n_groups[i]));
+        PS_TRY(stats_scores(who, realign, scores, i, &rq[i]));
+        rq[i].a = as[i]; rq[i].table = table[i]; rq[i].ngroups = n_groups[i]; rq[i].group = groups ? groups[i] : nullptr;
     }
-    if (!any) {   // (no events anywhere: nothing is launched, the tables are all zero)
-        for (int i = 0; i < n; i++) memset(tb[i], 0, (size_t)ng[i] * NS * sizeof(ps_kmer_cell));
-        return PS_OK;
-    }
-    NEED_RT();
-    return kmer_stats_multi(rt, as, realign != 0, gr, ng, sc, tb);
+    return stats_run(OwnKind::KmerStats, realign, rq);
 }
 int ps_kmer_stats(ps_align* a, int32_t realign, const int32_t* groups, int32_t n_groups, double* scores, ps_kmer_cell* table) {
     if (!a) return fail(PS_ERR_BAD_ARG, "ps_kmer_stats: null handle");

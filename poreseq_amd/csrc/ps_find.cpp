@@ -83,14 +83,14 @@ static int sw_enqueue(Find& f) {
 // Its error is the caller's to return once the second stream has been drained.
 static int base_realign(Find& f) {
     std::vector<std::vector<double>> sc(f.R);
-    std::vector<double*> scp(f.R), lkp(f.R);
+    std::vector<OwnReq> rq(f.R);
     f.base.resize(f.R);
     for (int r = 0; r < f.R; r++) {
         f.base[r].assign(std::max<size_t>(f.as[r]->bases.size(), 4) + 1, 0.0);
         sc[r].assign(std::max(f.as[r]->E, 1), 0.0);
-        scp[r] = sc[r].data(); lkp[r] = f.base[r].data();
+        rq[r].a = f.as[r]; rq[r].scores = sc[r].data(); rq[r].likes = f.base[r].data();
     }
-    const int rc = score_alignments_multi(f.rt, f.as, scp, lkp);
+    const int rc = own_forward(f.rt, OwnKind::Score, true, rq.data(), rq.size());
     f.tk.lap("base realign");
     return rc;
 }

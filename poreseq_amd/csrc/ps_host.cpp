@@ -1,12 +1,12 @@
-// ps_host.cpp — host side of libporeseq_hip.so above the runtime: sequences, AlignData, alignment batches and realign() (which
-// fill runs for a batch, in which form), and the refinement-loop logic that the reference keeps in C++ above its Alignment class
-// (cpp/MakeMutations.cpp, cpp/EventUtil.cpp): ScoreAlignments and MakeMutations.  ScoreMutations and its reductions — the edit-scoring
-// chain — are in ps_score.cpp, the edit plans in ps_editplan.h, FindMutations in ps_find.cpp.  The runtime, its streams and par_for
+// ps_host.cpp — host side of libporeseq_hip.so above the runtime: alignment batches (Batch::build / place), realign() (which fill
+// runs for a batch, in which form), what a lock-step call may take of the device (guess_slots, share_need, share_cap), and
+// MakeMutations (cpp/MakeMutations.cpp).  struct Align — AlignData — is in ps_align.cpp; ScoreAlignments and the two statistics
+// calls, one chain over the events' own sequences, in ps_own.cpp; ScoreMutations and its reductions — the edit-scoring chain — in
+// ps_score.cpp, the edit plans in ps_editplan.h, FindMutations in ps_find.cpp.  The runtime, its streams and par_for
 // are in ps_runtime.cpp; device memory — pools, shares, slabs, the AlignData slab cache — in ps_mem.cpp, its arithmetic in ps_plan.h.
 // All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_edit.hip, ps_sw.hip,
 // ps_viterbi.hip); there is no CPU implementation of it in this library.
 #include "ps_host.h"
-#include "ps_sane.h"
 
 #include <algorithm>
 #include <atomic>
@@ -126,207 +126,7 @@ double Batch::fill_alg_bytes() const {
     return t;
 }
 
-// ------------------------------------------------------------------------------------------ AlignData
-Align::~Align() {
-    if (d_keep) (void)hipFree(d_keep);
-    align_slab_give(slab, slab_cap, last_stream);   // (back to the cache of ps_mem.cpp, or freed)
-}
-
-int Align::create(Runtime* rt, const char* seq, int64_t seq_len, int32_t n_events, const int64_t* level_off,
-                  const double* mean, const double* stdv, const double* ref_align, const double* ref_like,
-                  const double* model, const double* trans, const char* evseq, const int64_t* evseq_off,
-                  const ps_params* params) {
-    bases.assign(seq, (size_t)seq_len);
-    states = states_of(bases);
-    if (params) par = *params;
-    E = n_events;
-    n.resize(E); off.resize(E + 1);
-    for (int e = 0; e <= E; e++) off[e] = E ? level_off[e] - level_off[0] : 0;
-    for (int e = 0; e < E; e++) { n[e] = (int)(off[e + 1] - off[e]); if (n[e] < 0) return fail(PS_ERR_BAD_ARG, "level_off not monotone"); }
-    ntot = E ? off[E] : 0;
-    const int64_t base = E ? level_off[0] : 0;
-    evseqs.resize(E);
-    if (evseq && evseq_off) for (int e = 0; e < E; e++) evseqs[e].assign(evseq + evseq_off[e], evseq + evseq_off[e + 1]);
-    // +infinity emissions are refused, the other values outside the reference's domain marked (ps_sane.h)
-    nonfinite.clear();
-    {
-        char msg[200];
-        if (offset_refused(par.lik_offset)) { snprintf(msg, sizeof msg, "lik_offset %g is not finite", par.lik_offset); return fail(PS_ERR_BAD_ARG, msg); }
-        for (int e = 0; e < E; e++) {
-            for (int64_t t = off[e]; t < off[e + 1]; t++) {
-                const double m = mean[base + t], sd = stdv[base + t];
-                if (level_plus_inf(sd)) {
-                    snprintf(msg, sizeof msg, "event %d, level %lld: stdv %g (the emission of the mirrored row is +infinity)", e, (long long)(t - off[e]), sd);
-                    return fail(PS_ERR_BAD_ARG, msg);
-                }
-                if (nonfinite.empty() && level_nonfinite(m, sd)) {
-                    snprintf(msg, sizeof msg, "event %d, level %lld: mean %g, stdv %g", e, (long long)(t - off[e]), m, sd);
-                    nonfinite = msg;
-                }
-            }
-        }
-    }
-    h_mean.assign(mean + base, mean + base + ntot);
-    h_stdv.assign(stdv + base, stdv + base + ntot);
-    h_ra.assign(ref_align + base, ref_align + base + ntot);
-    h_rl.assign(ref_like + base, ref_like + base + ntot);
-    host_refs_valid = true;
-    // derived model columns with the host libm, exactly as ModelData::setData / setParams (cpp/EventData.h:48-73)
-    std::vector<double> lsd(ntot), mdl((size_t)E * 6 * NS), tr((size_t)E * 4);
-    for (int64_t t = 0; t < ntot; t++) lsd[t] = std::log(h_stdv[t]);
-    for (int e = 0; e < E; e++) {
-        const double* src = model + (size_t)e * 4 * NS;
-        double* dst = mdl.data() + (size_t)e * 6 * NS;
-        for (int k = 0; k < NS; k++) {
-            const double lm = src[k], ls = src[NS + k], sm = src[2 * NS + k], ss = src[3 * NS + k];
-            const double lam = model_lambda(sm, ss);
-            if (model_row_plus_inf(ls, lam) || (nonfinite.empty() && model_row_nonfinite(lm, ls, sm, lam))) {   // (rare: the message is built only then)
-                char msg[200];
-                snprintf(msg, sizeof msg, "event %d, model row %d: level_mean %g, level_stdv %g, sd_mean %g, sd_stdv %g", e, k, lm, ls, sm, ss);
-                if (model_row_plus_inf(ls, lam)) return fail(PS_ERR_BAD_ARG, std::string(msg) + " (its emissions are +infinity)");
-                nonfinite = msg;
-            }
-            dst[k] = lm; dst[NS + k] = ls; dst[2 * NS + k] = std::log(ls);
-            dst[3 * NS + k] = sm; dst[4 * NS + k] = lam; dst[5 * NS + k] = std::log(lam);
-        }
-        for (int k = 0; k < 4; k++) tr[e * 4 + k] = std::log(trans[e * 4 + k]);
-    }
-    h_model = mdl;
-    h_trans = tr;
-    // k_fill's tables: model rows with the reciprocals of the two model divisors, level records per direction with the
-    // reciprocal of the level stdv (correctly rounded: host IEEE division)
-    std::vector<double> mdl8((size_t)E * (MODEL_ROW_BYTES / 8) * NS), lev((size_t)2 * 4 * std::max<int64_t>(ntot, 1));
-    fastdiv = true;
-    for (int e = 0; e < E; e++) {
-        const double* d6 = mdl.data() + (size_t)e * 6 * NS;
-        double* d8 = mdl8.data() + (size_t)e * (MODEL_ROW_BYTES / 8) * NS;
-        for (int k = 0; k < NS; k++) {
-            const double lm = d6[k], ls = d6[NS + k], sm = d6[3 * NS + k], lam = d6[4 * NS + k];
-            double* r8 = d8 + (size_t)k * (MODEL_ROW_BYTES / 8);
-            r8[0] = lm; r8[1] = 1.0 / ls; r8[2] = ls; r8[3] = d6[2 * NS + k];
-            r8[4] = sm; r8[5] = 1.0 / sm; r8[6] = lam; r8[7] = d6[5 * NS + k];
-            if (!sane_model_row(lm, ls, sm, lam)) fastdiv = false;   // (ps_sane.h: the range, and why)
-        }
-        const int64_t o = off[e];
-        const int ne = n[e];
-        for (int i = 1; i <= ne; i++) {
-            double* f = lev.data() + 4 * (o + i - 1);
-            double* bk = lev.data() + 4 * (ntot + o + i - 1);
-            const double l3 = 3 * lsd[o + ne - i];
-            f[0] = h_mean[o + i - 1]; f[1] = h_stdv[o + i - 1]; f[2] = l3; f[3] = 1.0 / h_stdv[o + i - 1];
-            bk[0] = h_mean[o + ne - i]; bk[1] = h_stdv[o + ne - i]; bk[2] = l3; bk[3] = 1.0 / h_stdv[o + ne - i];
-        }
-    }
-    for (int64_t t = 0; t < ntot; t++)
-        if (!sane_level(h_mean[t], h_stdv[t])) fastdiv = false;
-    if (getenv("PORESEQ_EXACT_DIV")) fastdiv = false;   // tests: the IEEE-division build of every kernel that computes emissions
-    // one slab: mean, stdv, lsd, ra, rl, ri [ntot each] | model | trans | out
-    const size_t nlev = (size_t)std::max<int64_t>(ntot, 1);
-    const size_t bytes = (6 + 8) * nlev * sizeof(double) + (mdl.size() + mdl8.size() + tr.size() + 2) * sizeof(double) + 256 +
-                         (size_t)std::max(E, 1) * sizeof(JobOut) + 64 * 16;
-    PS_TRY(align_slab_take(rt, bytes, &slab, &slab_cap));
-    last_stream = (void*)rt->stream;
-    // the slab is filled by ONE host-to-device copy: its image is assembled in pinned staging memory first (ten copies and a memset per
-    // region before: 3 000 of a bench step's copy commands)
-    char* img = (char*)rt->stage.alloc(bytes);
-    if (!img) return fail(PS_ERR_NOMEM, "hipHostMalloc (staging arena)");
-    memset(img, 0, bytes);
-    char* p = (char*)slab;
-    auto carve = [&](size_t b) { char* r = p; p += (b + 63) / 64 * 64; return r; };
-    auto put = [&](const void* dev, const void* src, size_t b) { if (b) memcpy(img + ((const char*)dev - (const char*)slab), src, b); };
-    d_mean = (double*)carve(nlev * 8); d_stdv = (double*)carve(nlev * 8); d_lsd = (double*)carve(nlev * 8);
-    d_ra = (double*)carve(nlev * 8); d_rl = (double*)carve(nlev * 8); d_ri = (double*)carve(nlev * 8);
-    d_model = (double*)carve(std::max<size_t>(mdl.size(), 1) * 8); d_trans = (double*)carve(std::max<size_t>(tr.size(), 1) * 8);
-    d_out = (JobOut*)carve((size_t)std::max(E, 1) * sizeof(JobOut));
-    d_model8 = (double*)carve(std::max<size_t>(mdl8.size(), 1) * 8);
-    d_lev[0] = (double*)carve(4 * nlev * 8); d_lev[1] = (double*)carve(4 * nlev * 8);
-    if (ntot) {
-        put(d_mean, h_mean.data(), ntot * 8); put(d_stdv, h_stdv.data(), ntot * 8); put(d_lsd, lsd.data(), ntot * 8);
-        put(d_ra, h_ra.data(), ntot * 8); put(d_rl, h_rl.data(), ntot * 8);
-        put(d_lev[0], lev.data(), 4 * ntot * 8); put(d_lev[1], lev.data() + 4 * ntot, 4 * ntot * 8);
-    }
-    if (E) { put(d_model, mdl.data(), mdl.size() * 8); put(d_trans, tr.data(), tr.size() * 8); put(d_model8, mdl8.data(), mdl8.size() * 8); }
-    PS_HIP(hipMemcpyAsync(slab, img, (size_t)(p - (char*)slab), hipMemcpyHostToDevice, rt->stream));   // (d_out: zeros)
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    // EventData::setData ends with updaterefs() (cpp/EventData.h:223)
-    Batch b;
-    PS_TRY(base_batch(rt, &b, 1, 0));
-    PS_TRY(launch_updaterefs(rt, b.d));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    return PS_OK;
-}
-
-int Align::base_batch(Runtime* rt, Batch* b, int ndir, int lb_extra) {
-    std::vector<JobSpec> specs(E);
-    for (int e = 0; e < E; e++) specs[e] = job(e);
-    return b->build(rt, specs, ndir, lb_extra);
-}
-
-// event e against this AlignData's own sequence, with the event's own reference arrays and result record
-JobSpec Align::job(int e) {
-    JobSpec s;
-    s.a = this; s.ev = e; s.states = &states;
-    s.ra = d_ra + off[e]; s.rl = d_rl + off[e]; s.ri = d_ri + off[e];
-    s.out = d_out + e;
-    return s;
-}
-JobSpec Align::job(int e, const std::vector<int>* other, double* ra, double* rl, double* ri, JobOut* out) {
-    JobSpec s = job(e);   // the event's data; the other sequence's states and the alignment to it on top
-    s.states = other;
-    s.ra = ra + off[e]; s.rl = rl + off[e]; s.ri = ri + off[e];
-    s.out = out;
-    return s;
-}
-
-// device -> host mirror of ref_align / ref_like in two halves, so that several AlignData can share one synchronisation
-int Align::refs_to_host_async(Runtime* rt) {
-    pend_ra = nullptr; pend_rl = nullptr;
-    if (host_refs_valid || !ntot) { host_refs_valid = true; return PS_OK; }
-    last_stream = (void*)rt->stream;
-    PS_TRY(rt->down(&pend_ra, d_ra, (size_t)ntot));
-    PS_TRY(rt->down(&pend_rl, d_rl, (size_t)ntot));
-    return PS_OK;
-}
-void Align::refs_finish() {   // after the stream has been synchronised
-    if (pend_ra) { memcpy(h_ra.data(), pend_ra, ntot * 8); memcpy(h_rl.data(), pend_rl, ntot * 8); }
-    pend_ra = nullptr; pend_rl = nullptr;
-    host_refs_valid = true;
-}
-int Align::refs_to_host(Runtime* rt) {
-    PS_TRY(refs_to_host_async(rt));
-    if (pend_ra) PS_HIP(hipStreamSynchronize(rt->stream));
-    refs_finish();
-    return PS_OK;
-}
-
-// ps_align_keep_refs / ps_align_new_call (include/poreseq_hip.h): d_ra and d_rl lie next to each other in the slab
-// (Align::create carves them in this order), one copy each way
-int Align::keep_refs(Runtime* rt) {
-    if (!ntot) return PS_OK;
-    if (keep_valid) { restore_due = true; return PS_OK; }   // (kept before and restored by the last new_call: the refs are the kept ones)
-    const size_t span = (size_t)(d_rl - d_ra) + (size_t)ntot;
-    if (!d_keep) PS_HIP(hipMalloc((void**)&d_keep, span * sizeof(double)));
-    last_stream = (void*)rt->stream;
-    PS_HIP(hipMemcpyAsync(d_keep, d_ra, span * sizeof(double), hipMemcpyDeviceToDevice, rt->stream));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    keep_valid = true;
-    restore_due = true;
-    return PS_OK;
-}
-int Align::restore_refs(Runtime* rt) {
-    if (!keep_valid || !restore_due || !ntot) return PS_OK;
-    restore_due = false;
-    const size_t span = (size_t)(d_rl - d_ra) + (size_t)ntot;
-    last_stream = (void*)rt->stream;
-    PS_HIP(hipMemcpyAsync(d_ra, d_keep, span * sizeof(double), hipMemcpyDeviceToDevice, rt->stream));
-    host_refs_valid = false;
-    Batch b;   // ref_index, refstart and refend follow ref_align (k_updaterefs), as after EventData::setData
-    PS_TRY(base_batch(rt, &b, 1, 0));
-    PS_TRY(launch_updaterefs(rt, b.d));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    return PS_OK;
-}
-
+// ------------------------------------------------------------------------------------------ realign
 // forward fill + backtrace + updaterefs of a batch (the body of ScoreAlignments per event,
 // cpp/MakeMutations.cpp:148-195, and of Alignment::update with ndir == 2, cpp/Alignment.cpp:63-73)
 static int sweep_min_default() { static const int v = getenv("PORESEQ_SWEEP_MIN") ? atoi(getenv("PORESEQ_SWEEP_MIN")) : 400; return v; }
@@ -520,203 +320,6 @@ double share_need(const Align* a, int ndir) {
     return add;
 }
 double share_cap(int ndir) { return ndir == 2 ? dense_cap_bytes() : device_share_bytes(); }
-
-// The scores of a batch's jobs, gathered into one array on the device and enqueued for one copy back (instead of one per AlignData)
-int gather_best(Runtime* rt, const Batch& b, double** best) {
-    DBuf& gb = rt->buf("best");
-    PS_TRY(gb.ensure(b.jobs.size() * sizeof(double)));
-    PS_TRY(launch_gather_best(rt, b.d, gb.as<double>()));
-    return rt->down(best, gb.p, b.jobs.size());
-}
-
-// ScoreAlignments, cpp/MakeMutations.cpp:148-195, for several AlignData in one launch chain (independent regions in lock-step)
-int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes) {
-    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
-        return score_alignments_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
-                                      std::vector<double*>(likes.begin() + k0, likes.begin() + k1));
-    };
-    auto need = [&](size_t k) { return share_need(as[k], 1); };
-    if (over_share(as.size(), 1, need)) return in_share_chunks(as.size(), 1, need, sub);   // more matrices than this runtime's share of the device
-    std::vector<JobSpec> specs;
-    for (Align* a : as)
-        for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
-    if (specs.empty()) return PS_OK;
-    Batch b;
-    PS_TRY(b.build(rt, specs, 1, 0));
-    {
-        const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
-        if (rc == PS_SPLIT) return in_halves(as.size(), sub);   // bands wider than share_need guessed: two halves, one after the other
-        PS_TRY(rc);
-    }
-    for (Align* a : as) a->host_refs_valid = false;
-    double* best = nullptr;
-    PS_TRY(gather_best(rt, b, &best));
-    bool any_likes = false;
-    for (size_t k = 0; k < as.size(); k++) if (likes[k]) { any_likes = true; PS_TRY(as[k]->refs_to_host_async(rt)); }
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    {
-        size_t j = 0;
-        for (size_t k = 0; k < as.size(); k++)
-            for (int e = 0; e < as[k]->E; e++) scores[k][e] = std::max(best[j++], 0.0);  // Alignment::getMax, cpp/Alignment.h:127-130
-    }
-    if (any_likes)
-        par_for((int)as.size(), [&](int k) {
-            Align* a = as[k];
-            if (!likes[k]) return;
-            a->refs_finish();
-            for (int e = 0; e < a->E; e++) accumulate_likes(a->h_ra.data() + a->off[e], a->h_rl.data() + a->off[e], a->n[e], (int)a->states.size(), likes[k]);
-        });
-    return PS_OK;
-}
-
-int score_alignments(Runtime* rt, Align* a, double* scores, double* likes) {
-    if (!a->E) return PS_OK;
-    return score_alignments_multi(rt, {a}, {scores}, {likes});
-}
-
-// The descriptors of k_align_stats and k_kmer_stats for the AlignData `as`, whose events are the jobs of `b` in order: one StatJob
-// per event, one StatRegion per AlignData.  groups (k_kmer_stats; null otherwise): per AlignData the events' group ids and the
-// number of groups; the regions' table rows follow each other.  Returns the levels of all events.
-static double stat_descriptors(const std::vector<Align*>& as, const Batch& b, const std::vector<const int32_t*>* groups, const std::vector<int>* ngroups,
-                               std::vector<StatJob>* sj, std::vector<StatRegion>* sr, int* maxE) {
-    sj->assign(b.jobs.size(), StatJob());
-    sr->assign(as.size(), StatRegion());
-    *maxE = 0;
-    double levels = 0;
-    size_t q = 0;
-    int tab = 0;
-    for (size_t k = 0; k < as.size(); k++) {
-        const Align* a = as[k];
-        StatRegion& r = (*sr)[k];
-        r.job0 = (int)q; r.njobs = a->E; r.ngroups = groups ? (*ngroups)[k] : 0; r.tab0 = tab;
-        tab += r.ngroups;
-        *maxE = std::max(*maxE, a->E);
-        for (int e = 0; e < a->E; e++, q++) {
-            const JobD& j = b.jobs[q];
-            StatJob& s = (*sj)[q];
-            s.ra = j.ra; s.mean = a->d_mean + a->off[e]; s.stdv = a->d_stdv + a->off[e]; s.model = a->d_model + (size_t)e * 6 * NS;
-            s.st = j.st; s.n = j.n0; s.S = j.C;
-            s.grp = groups ? (*groups)[k][e] : 0; s.pad = 0;
-            levels += j.n0;
-        }
-    }
-    return levels;
-}
-
-// ps_align_stats / ps_batch_align_stats (include/poreseq_hip.h): with `re`, ScoreAlignments' chain as above and then k_align_stats
-// over the refs the backtrace just wrote; without it k_align_stats over the refs the handles hold, and no DP.  Either way one
-// launch of it for all AlignData, and scores and records return in one copy.  scores[k] may be null.
-int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<double*>& scores, const std::vector<ps_event_stats*>& stats) {
-    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
-        return align_stats_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), re, std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
-                                 std::vector<ps_event_stats*>(stats.begin() + k0, stats.begin() + k1));
-    };
-    auto need = [&](size_t k) { return share_need(as[k], 1); };
-    if (re && over_share(as.size(), 1, need)) return in_share_chunks(as.size(), 1, need, sub);   // (cut between AlignData, as ScoreAlignments is)
-    std::vector<JobSpec> specs;
-    for (Align* a : as)
-        for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
-    if (specs.empty()) return PS_OK;
-    Batch b;   // (also without a realignment: it puts every sequence's states on the device)
-    PS_TRY(b.build(rt, specs, 1, 0));
-    if (re) {
-        const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
-        if (rc == PS_SPLIT) return in_halves(as.size(), sub);
-        PS_TRY(rc);
-        for (Align* a : as) a->host_refs_valid = false;
-    }
-    const size_t nj = specs.size();
-    std::vector<StatJob> sj;
-    std::vector<StatRegion> sr;
-    int maxE = 0;
-    const double bytes = 16.0 * stat_descriptors(as, b, nullptr, nullptr, &sj, &sr, &maxE) + (double)nj * sizeof(ps_event_stats);
-    // descriptors in; records and, behind them, the scores out
-    const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
-    const size_t out_recs = nj * sizeof(ps_event_stats), out_bytes = out_recs + (re ? nj * sizeof(double) : 0);
-    DBuf& din = rt->buf("astats_in");
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(din.ensure(in_bytes));
-    PS_TRY(dout.ensure(out_bytes));
-    PS_TRY(rt->up(din.p, sj.data(), in_jobs));
-    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
-    PS_TRY(launch_align_stats(rt, din.as<StatJob>(), (const StatRegion*)((char*)din.p + in_jobs), (int)sr.size(), maxE, bytes, dout.as<ps_event_stats>()));
-    if (re) PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + out_recs)));
-    void* back = nullptr;
-    PS_TRY(rt->down(&back, dout.p, out_bytes));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    const ps_event_stats* recs = (const ps_event_stats*)back;
-    const double* best = (const double*)((const char*)back + out_recs);
-    size_t q = 0;
-    for (size_t k = 0; k < as.size(); k++)
-        for (int e = 0; e < as[k]->E; e++, q++) {
-            stats[k][e] = recs[q];
-            if (re && scores[k]) scores[k][e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
-        }
-    return PS_OK;
-}
-
-// ps_kmer_stats / ps_batch_kmer_stats (include/poreseq_hip.h): align_stats_multi's shape — the same Batch, the same optional
-// realignment with the same split rules, one launch of k_kmer_stats for all AlignData, tables and scores back in one copy.  A batch
-// whose tables (48 KiB per group) exceed this runtime's share is cut between AlignData as well.  Every as[k] has events or not;
-// tables[k] has ngroups[k] x NS cells and is written in full.
-int kmer_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<const int32_t*>& groups, const std::vector<int>& ngroups,
-                     const std::vector<double*>& scores, const std::vector<ps_kmer_cell*>& tables) {
-    auto sub = [&](size_t k0, size_t k1) {   // regions k0 .. k1 - 1 as a call of their own
-        return kmer_stats_multi(rt, std::vector<Align*>(as.begin() + k0, as.begin() + k1), re, std::vector<const int32_t*>(groups.begin() + k0, groups.begin() + k1),
-                                std::vector<int>(ngroups.begin() + k0, ngroups.begin() + k1), std::vector<double*>(scores.begin() + k0, scores.begin() + k1),
-                                std::vector<ps_kmer_cell*>(tables.begin() + k0, tables.begin() + k1));
-    };
-    size_t rows = 0;
-    int maxG = 0;
-    for (int g : ngroups) { rows += (size_t)g; maxG = std::max(maxG, g); }
-    const size_t out_tabs = rows * NS * sizeof(ps_kmer_cell);
-    if (as.size() > 1 && (double)out_tabs > device_share_bytes()) return in_halves(as.size(), sub);
-    auto need = [&](size_t k) { return share_need(as[k], 1); };
-    if (re && over_share(as.size(), 1, need)) return in_share_chunks(as.size(), 1, need, sub);   // (cut between AlignData, as ScoreAlignments is)
-    std::vector<JobSpec> specs;
-    for (Align* a : as)
-        for (int e = 0; e < a->E; e++) specs.push_back(a->job(e));
-    if (specs.empty()) {
-        for (size_t k = 0; k < as.size(); k++) memset(tables[k], 0, (size_t)ngroups[k] * NS * sizeof(ps_kmer_cell));
-        return PS_OK;
-    }
-    Batch b;   // (also without a realignment: it puts every sequence's states on the device)
-    PS_TRY(b.build(rt, specs, 1, 0));
-    if (re) {
-        const int rc = realign(rt, b, as.size() > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
-        if (rc == PS_SPLIT) return in_halves(as.size(), sub);
-        PS_TRY(rc);
-        for (Align* a : as) a->host_refs_valid = false;
-    }
-    const size_t nj = specs.size();
-    std::vector<StatJob> sj;
-    std::vector<StatRegion> sr;
-    int maxE = 0;
-    const double bytes = 24.0 * stat_descriptors(as, b, &groups, &ngroups, &sj, &sr, &maxE) + (double)out_tabs;
-    // descriptors in; tables and, behind them, the scores out
-    const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
-    const size_t out_bytes = out_tabs + (re ? nj * sizeof(double) : 0);
-    DBuf& din = rt->buf("astats_in");
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(din.ensure(in_bytes));
-    PS_TRY(dout.ensure(out_bytes));
-    PS_TRY(rt->up(din.p, sj.data(), in_jobs));
-    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
-    PS_TRY(launch_kmer_stats(rt, din.as<StatJob>(), (const StatRegion*)((char*)din.p + in_jobs), (int)sr.size(), maxG, bytes, dout.as<ps_kmer_cell>()));
-    if (re) PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + out_tabs)));
-    void* back = nullptr;
-    PS_TRY(rt->down(&back, dout.p, out_bytes));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    const ps_kmer_cell* tabs = (const ps_kmer_cell*)back;
-    const double* best = (const double*)((const char*)back + out_tabs);
-    size_t q = 0;
-    for (size_t k = 0; k < as.size(); k++) {
-        memcpy(tables[k], tabs + (size_t)sr[k].tab0 * NS, (size_t)ngroups[k] * NS * sizeof(ps_kmer_cell));
-        for (int e = 0; e < as[k]->E; e++, q++)
-            if (re && scores[k]) scores[k][e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
-    }
-    return PS_OK;
-}
 
 // One greedy pass of MakeMutations (ps_greedy.h: sort, apply, defer, shift) on the AlignData's sequence
 static int greedy_apply(Align* a, std::vector<Mut>& muts, std::vector<Mut>* later, bool talk) {

@@ -135,16 +135,8 @@ double fwd_job_bytes(const Align* a, int n0, int C);   // device bytes one forwa
 
 constexpr int PS_SPLIT = 1;   // realign(): the matrices would exceed `cap` bytes; nothing was launched, b.P holds the width they need
 int realign(Runtime* rt, Batch& b, double cap = 0.0);
-int score_alignments(Runtime* rt, Align* a, double* scores, double* likes);
 // the *_multi forms run the same call for several AlignData (independent regions) in one launch chain
 void par_for(int n, const std::function<void(int)>& fn);
-int score_alignments_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<double*>& scores, const std::vector<double*>& likes);
-// ps_batch_align_stats: per event the census of ref_align and the sums of the scaling fit (ps_stats.hip), after ScoreAlignments'
-// chain (re) or of the refs as they are; scores[k] may be null (must be without re), stats[k] has E records
-int align_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<double*>& scores, const std::vector<ps_event_stats*>& stats);
-// ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation (ps_stats.hip), the same chain
-int kmer_stats_multi(Runtime* rt, const std::vector<Align*>& as, bool re, const std::vector<const int32_t*>& groups, const std::vector<int>& ngroups,
-                     const std::vector<double*>& scores, const std::vector<ps_kmer_cell*>& tables);
 int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seeds,
                          const std::vector<std::vector<Mut>*>& outs);
 // Every event of an AlignData aligned forward-only to a sequence that is not its own, for any number of such (AlignData, sequence)
@@ -237,6 +229,22 @@ struct EditReq {
 // ScoreMutations (cpp/MakeMutations.cpp:23-69) and its reductions for reqs[0 .. n - 1] in one launch chain (rt: null for a reduction,
 // whose runtime is taken once its arguments are checked and there is an edit to score)
 int score_edits(Runtime* rt, EditKind kind, EditReq* reqs, size_t n);
+// One AlignData of a call that aligns every event to the AlignData's own sequence, forward only (ps_own.cpp): its handle and, of the
+// host outputs below, those the call's OwnKind means.  A lock-step call is an array of these, a sub-batch a sub-range of it.
+struct OwnReq {
+    Align* a = nullptr;
+    double* scores = nullptr;          // [E] the events' scores after a realignment (Score: required; the statistics: optional)
+    double* likes = nullptr;           // Score: [bases] the per-base likelihoods of all events, added up (optional)
+    ps_event_stats* stats = nullptr;   // AlignStats: [E] records
+    // KmerStats: [E] group ids below ngroups, [ngroups][NS] cells, written in full
+    const int32_t* group = nullptr; int ngroups = 0; ps_kmer_cell* table = nullptr;
+};
+// ScoreAlignments (cpp/MakeMutations.cpp:148-195) | ps_batch_align_stats: per event the census of ref_align and the sums of the
+// scaling fit | ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation (ps_stats.hip)
+enum class OwnKind { Score, AlignStats, KmerStats };
+// reqs[0 .. n - 1] in one launch chain.  realign: ScoreAlignments' fills and backtraces first (Score: always); without, the
+// statistics reduce the refs the handles hold and no DP runs
+int own_forward(Runtime* rt, OwnKind kind, bool realign, OwnReq* reqs, size_t n);
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases);

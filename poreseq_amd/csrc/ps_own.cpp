@@ -1,0 +1,141 @@
+// ps_own.cpp — the calls that align every event of an AlignData to its own sequence, forward only: ScoreAlignments
+// (cpp/MakeMutations.cpp:148-195), ps_align_stats and ps_kmer_stats, for several AlignData in lock-step (independent regions in one
+// launch chain).  One request record per AlignData (OwnReq, ps_host.h) and one chain, own_forward: the cuts of a call that does not
+// fit this runtime's share, the batch, the optional realignment, the tail the kinds differ in, the scores.  Batch and realign() are
+// in ps_host.cpp, struct Align in ps_align.cpp, the kernels of the two reductions in ps_stats.hip.
+#include "ps_host.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace ps {
+
+// The scores of a batch's jobs, gathered into one array on the device and enqueued for one copy back (instead of one per AlignData)
+int gather_best(Runtime* rt, const Batch& b, double** best) {
+    DBuf& gb = rt->buf("best");
+    PS_TRY(gb.ensure(b.jobs.size() * sizeof(double)));
+    PS_TRY(launch_gather_best(rt, b.d, gb.as<double>()));
+    return rt->down(best, gb.p, b.jobs.size());
+}
+
+// ScoreAlignments' tail: the scores through "best", ref_align / ref_like of the AlignData that want their likelihoods, one
+// synchronisation; score_likes adds the likelihoods up once the scores are written
+static int score_tail(Runtime* rt, const Batch& b, OwnReq* reqs, size_t n, double** best) {
+    PS_TRY(gather_best(rt, b, best));
+    for (size_t k = 0; k < n; k++) if (reqs[k].likes) PS_TRY(reqs[k].a->refs_to_host_async(rt));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    return PS_OK;
+}
+static void score_likes(OwnReq* reqs, size_t n) {
+    if (std::none_of(reqs, reqs + n, [](const OwnReq& q) { return q.likes != nullptr; })) return;
+    par_for((int)n, [&](int k) {
+        Align* a = reqs[k].a;
+        if (!reqs[k].likes) return;
+        a->refs_finish();
+        for (int e = 0; e < a->E; e++) accumulate_likes(a->h_ra.data() + a->off[e], a->h_rl.data() + a->off[e], a->n[e], (int)a->states.size(), reqs[k].likes);
+    });
+}
+
+// The descriptors of k_align_stats and k_kmer_stats for reqs[0 .. n - 1], whose events are the jobs of `b` in order: one StatJob per
+// event, one StatRegion per AlignData.  kmer: the events' group ids and the numbers of groups count; the regions' table rows follow
+// each other.  Returns the levels of all events.
+static double stat_descriptors(const OwnReq* reqs, size_t n, const Batch& b, bool kmer, std::vector<StatJob>* sj, std::vector<StatRegion>* sr, int* maxE) {
+    sj->assign(b.jobs.size(), StatJob());
+    sr->assign(n, StatRegion());
+    *maxE = 0;
+    double levels = 0;
+    size_t q = 0;
+    int tab = 0;
+    for (size_t k = 0; k < n; k++) {
+        const Align* a = reqs[k].a;
+        StatRegion& r = (*sr)[k];
+        r.job0 = (int)q; r.njobs = a->E; r.ngroups = kmer ? reqs[k].ngroups : 0; r.tab0 = tab;
+        tab += r.ngroups;
+        *maxE = std::max(*maxE, a->E);
+        for (int e = 0; e < a->E; e++, q++) {
+            const JobD& j = b.jobs[q];
+            StatJob& s = (*sj)[q];
+            s.ra = j.ra; s.mean = a->d_mean + a->off[e]; s.stdv = a->d_stdv + a->off[e]; s.model = a->d_model + (size_t)e * 6 * NS;
+            s.st = j.st; s.n = j.n0; s.S = j.C;
+            s.grp = kmer ? reqs[k].group[e] : 0; s.pad = 0;
+            levels += j.n0;
+        }
+    }
+    return levels;
+}
+
+// bytes of the tables of a k-mer call (48 KiB per group), and the most groups of one AlignData
+static size_t table_bytes(const OwnReq* reqs, size_t n, int* maxG = nullptr) {
+    size_t rows = 0;
+    for (size_t k = 0; k < n; k++) { rows += (size_t)reqs[k].ngroups; if (maxG) *maxG = std::max(*maxG, reqs[k].ngroups); }
+    return rows * NS * sizeof(ps_kmer_cell);
+}
+
+// The tail of the two statistics: the descriptors in through "astats_in"; one launch of k_align_stats or k_kmer_stats over the refs
+// the backtrace just wrote (re) or the handles hold; in "astats" the records or tables and, behind them, the scores (re), back in
+// one copy.  *best: the scores in that copy, null without a realignment.
+static int stats_tail(Runtime* rt, bool kmer, bool re, const Batch& b, OwnReq* reqs, size_t n, double** best) {
+    const size_t nj = b.jobs.size();
+    std::vector<StatJob> sj;
+    std::vector<StatRegion> sr;
+    int maxE = 0, maxG = 0;
+    const double levels = stat_descriptors(reqs, n, b, kmer, &sj, &sr, &maxE);
+    const size_t out_main = kmer ? table_bytes(reqs, n, &maxG) : nj * sizeof(ps_event_stats);
+    const double bytes = (kmer ? 24.0 : 16.0) * levels + (double)out_main;
+    const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
+    const size_t out_bytes = out_main + (re ? nj * sizeof(double) : 0);
+    DBuf& din = rt->buf("astats_in");
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(din.ensure(in_bytes));
+    PS_TRY(dout.ensure(out_bytes));
+    PS_TRY(rt->up(din.p, sj.data(), in_jobs));
+    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
+    const StatRegion* dsr = (const StatRegion*)((char*)din.p + in_jobs);
+    if (kmer) PS_TRY(launch_kmer_stats(rt, din.as<StatJob>(), dsr, (int)sr.size(), maxG, bytes, dout.as<ps_kmer_cell>()));
+    else PS_TRY(launch_align_stats(rt, din.as<StatJob>(), dsr, (int)sr.size(), maxE, bytes, dout.as<ps_event_stats>()));
+    if (re) PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + out_main)));
+    void* back = nullptr;
+    PS_TRY(rt->down(&back, dout.p, out_bytes));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    for (size_t k = 0; k < n; k++) {
+        if (kmer) memcpy(reqs[k].table, (const ps_kmer_cell*)back + (size_t)sr[k].tab0 * NS, (size_t)reqs[k].ngroups * NS * sizeof(ps_kmer_cell));
+        else memcpy(reqs[k].stats, (const ps_event_stats*)back + sr[k].job0, (size_t)reqs[k].a->E * sizeof(ps_event_stats));
+    }
+    *best = re ? (double*)((char*)back + out_main) : nullptr;
+    return PS_OK;
+}
+
+int own_forward(Runtime* rt, OwnKind kind, bool re, OwnReq* reqs, size_t n) {
+    const bool kmer = kind == OwnKind::KmerStats;
+    auto sub = [&](size_t k0, size_t k1) { return own_forward(rt, kind, re, reqs + k0, k1 - k0); };   // regions k0 .. k1 - 1 as a call of their own
+    // a k-mer call whose tables exceed this runtime's share is cut between AlignData
+    if (kmer && n > 1 && (double)table_bytes(reqs, n) > device_share_bytes()) return in_halves(n, sub);
+    auto need = [&](size_t k) { return share_need(reqs[k].a, 1); };
+    if (re && over_share(n, 1, need)) return in_share_chunks(n, 1, need, sub);   // more matrices than this runtime's share of the device
+    std::vector<JobSpec> specs;
+    for (size_t k = 0; k < n; k++)
+        for (int e = 0; e < reqs[k].a->E; e++) specs.push_back(reqs[k].a->job(e));
+    if (specs.empty()) {
+        for (size_t k = 0; kmer && k < n; k++) memset(reqs[k].table, 0, (size_t)reqs[k].ngroups * NS * sizeof(ps_kmer_cell));
+        return PS_OK;
+    }
+    Batch b;   // (also without a realignment: it puts every sequence's states on the device)
+    PS_TRY(b.build(rt, specs, 1, 0));
+    if (re) {
+        const int rc = realign(rt, b, n > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
+        if (rc == PS_SPLIT) return in_halves(n, sub);   // bands wider than share_need guessed: two halves, one after the other
+        PS_TRY(rc);
+        for (size_t k = 0; k < n; k++) reqs[k].a->host_refs_valid = false;
+    }
+    double* best = nullptr;
+    if (kind == OwnKind::Score) PS_TRY(score_tail(rt, b, reqs, n, &best));
+    else PS_TRY(stats_tail(rt, kmer, re, b, reqs, n, &best));
+    size_t q = 0;
+    for (size_t k = 0; best && k < n; k++)
+        for (int e = 0; e < reqs[k].a->E; e++, q++)
+            if (reqs[k].scores) reqs[k].scores[e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
+    if (kind == OwnKind::Score) score_likes(reqs, n);
+    return PS_OK;
+}
+
+}  // namespace ps

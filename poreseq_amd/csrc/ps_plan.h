@@ -1,5 +1,5 @@
 // ps_plan.h — the arithmetic of the device-memory plan: pure, host-only, no HIP include.  Shared by the library (ps_mem.cpp decides
-// with it, ps_host.cpp and ps_fwd.cpp size their batches with it) and by a host test of it (tests/native/plan_check.cpp).
+// with it, ps_host.cpp, ps_own.cpp and ps_fwd.cpp size their batches with it) and by a host test of it (tests/native/plan_check.cpp).
 //
 // The plan (309 GB on an MI355X, or this process's fraction of it):
 //   27 %  three slabs of 9 % each for the full forward + backward score matrices of dense ScoreMutations calls

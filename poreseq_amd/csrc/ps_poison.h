@@ -26,7 +26,7 @@ enum class PoisonClass { INDEX = 0, VALUE = 1, EXEMPT = 2 };
 struct PoisonEntry { const char* name; PoisonClass cls; const char* why; };
 
 constexpr PoisonEntry POISON_TABLE[] = {
-    // the DP batch (ps_host.cpp, ps_mem.cpp, ps_kernels.hip)
+    // the DP batch (ps_host.cpp, ps_own.cpp, ps_mem.cpp, ps_kernels.hip)
     {"jobs", PoisonClass::INDEX, "JobD: pointers, sizes, offsets"},
     {"states", PoisonClass::INDEX, "5-mer state ids and their -1 padding"},
     {"lb", PoisonClass::INDEX, "band centres per column"},
@@ -70,7 +70,7 @@ constexpr PoisonEntry POISON_TABLE[] = {
     {"ptable", PoisonClass::INDEX, "ps_point_best carries slots beside the scores"},
     {"support", PoisonClass::INDEX, "records with counts"},
     {"phase", PoisonClass::INDEX, "links, set ids, haplotype tags"},
-    // alignment census (ps_host.cpp)
+    // alignment census and k-mer statistics (ps_own.cpp)
     {"astats_in", PoisonClass::INDEX, "StatJob / StatRegion: pointers and sizes"},
     {"astats", PoisonClass::INDEX, "ps_event_stats and ps_kmer_cell carry counts"},
     // Viterbi (ps_viterbi.hip)

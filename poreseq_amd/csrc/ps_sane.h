@@ -1,5 +1,5 @@
 // ps_sane.h — which event and model tables may take the tabulated-reciprocal (Markstein) build of the emission: pure, host-only, no
-// HIP include.  Shared by the library (ps_host.cpp decides with it at ps_align_create) and by a host test of it
+// HIP include.  Shared by the library (ps_align.cpp decides with it at ps_align_create) and by a host test of it
 // (tests/native/emission_check.cpp), which evaluates both builds of the emission over the corners of what is accepted here.
 //
 // The range (DESIGN.md section 2 derives it).  With a = the numerator, b = the divisor and y = RN(1/b), the sequence

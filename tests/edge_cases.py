@@ -180,7 +180,7 @@ _exe = {}
 
 
 def _native_exe(name, flags=()):
-    """tests/native/<name>.cpp, built once per session (both programs include poreseq_amd/csrc/ps_sane.h: the code ps_host.cpp compiles)"""
+    """tests/native/<name>.cpp, built once per session (both programs include poreseq_amd/csrc/ps_sane.h: the code ps_align.cpp compiles)"""
     if name not in _exe:
         if "dir" not in _exe:
             _exe["dir"] = tempfile.TemporaryDirectory()

@@ -1,6 +1,6 @@
 // emission_check.cpp — test program (tests/test_edge_values.py): the emission log-density of ps_dev.h (emission8) restated in plain
 // C++ both ways — quotients by Markstein's sequence on tabulated reciprocals y = RN(1/b), and by IEEE division — over a grid of
-// everything the host's predicate (poreseq_amd/csrc/ps_sane.h, the same header ps_host.cpp decides with) accepts: each divisor
+// everything the host's predicate (poreseq_amd/csrc/ps_sane.h, the same header ps_align.cpp decides with) accepts: each divisor
 // from just inside the lower bound to just inside the upper, numerators that make a1, a2 and t zero, subnormal, about 1, 1e150, 1e200
 // and overflowing, lambda from 0 to past its bound.  For every ACCEPTED tuple the two must have identical bits, or both be NaN.
 // Prints the counts; exit status 1 on any mismatch.  `emission_check old` evaluates the predicate the library had before
