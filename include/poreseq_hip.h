@@ -337,9 +337,9 @@ int ps_score_mutation_phase(ps_align* a, const ps_muts* muts, int32_t window, do
  *   Order of the adds (a host can reproduce the bits, as for ps_event_hap): partial t = +0.0 takes the qualifying levels
  *       i = t, t + 256, t + 512, ... ascending; the 256 partials are then added into +0.0 for t = 0 .. 255.
  * The batch form is one launch for all regions; a batch whose realignment does not fit device memory is cut between AlignData,
- * never inside one.  Not part of the reference's interface.  Not built: drift (the ABI carries no level times) and transition
- * parameters (they need the backtrace's moves, not the array).  The stdv channel's scale_sd / var_sd and per-k-mer model
- * re-estimation are fitted from ps_kmer_stats' tables (below). */
+ * never inside one.  Not part of the reference's interface.  Not built: drift (the ABI carries no level times) and sd_stdv per
+ * k-mer.  The stdv channel's scale_sd / var_sd and per-k-mer model re-estimation are fitted from ps_kmer_stats' tables, the
+ * transition parameters from the backtrace's moves, which the array cannot carry: ps_move_stats (both below). */
 typedef struct ps_event_stats {
     int32_t n_levels, n_aligned, n_insert, n_unaligned;
     int32_t n_step, n_stay, n_extend, n_jump, n_back;
@@ -380,6 +380,55 @@ typedef struct ps_kmer_cell {
 } ps_kmer_cell;   /* 48 bytes, no padding (C has one name space for types and functions: the record cannot carry the call's name) */
 int ps_kmer_stats(ps_align* a, int32_t realign, const int32_t* groups /* [E] */, int32_t n_groups,
                   double* scores /* [E] or NULL */, ps_kmer_cell* table /* [n_groups][1024] */);
+
+/* The moves of the backtrace, per event, counted on the device (k_move_stats): what a fit of the transition probabilities
+ * skip / stay / extend / insert needs and ref_align cannot carry — the backtrace writes -1 for U_INSERT and UL_IGNORE alike
+ * (cpp/Alignment.cpp:559-573), a repeated column does not say whether U_STAY or U_EXTEND made it, and a skipped column next to
+ * an inserted level is ambiguous.  The fit is a few lines on the host (poreseq_amd.util.fit_transitions).
+ *
+ * The call always realigns: it is ps_score_alignments' chain, bit for bit — forward fill, then backtrace per event — with one
+ * more kernel between the walk and the kernel that turns the walk's records into ref_like.  `scores` (may be NULL) gets the bits
+ * ps_score_alignments returns; ref_align and ref_like stay in the handle as after any scoring call (a resident driver announces
+ * the call with ps_align_new_call + ps_align_keep_refs, as for ps_align_stats with realign != 0); records, per-level arrays and
+ * scores come back in one device-to-host copy.  A NULL `moves` is PS_ERR_BAD_ARG.  An AlignData without events is PS_OK and
+ * launches nothing.  An AlignData marked non-finite runs like every scoring call.
+ *
+ * One event's record.  The walk (cpp/Alignment.cpp:537-605) starts on the forward matrix' best cell (top_level, top_col) =
+ * (maxScore.i, maxScore.j), both 0 when the best score is not > 0, and steps until it reaches row 0 or a cell whose score is
+ * <= 0 (end_kind 0) or a cell whose step is Z_IMPLICIT (end_kind 1); low_col is the column of that cell, which the walk does
+ * not record.  Every step but L_SKIP and the change from the main to the stay matrix records one level; the levels recorded are
+ * low_level .. top_level without a hole (low_level = 0 and all counts 0 when there is none).
+ *   n_match, n_ignore, n_insert, n_stay, n_extend   recorded levels by the step that recorded them: UL_MATCH, UL_IGNORE, U_INSERT,
+ *       U_STAY (taken in the stay matrix), U_EXTEND.
+ *   Skips.  Between the record of level i (column j_i) and that of level i - 1 the walk takes (j_i - dj_i) - j_(i-1) L_SKIP steps,
+ *       dj = 1 for MATCH / IGNORE and 0 for INSERT / STAY / EXTEND; above the record of top_level it takes top_col - j_top, below
+ *       that of low_level (j_low - dj_low) - low_col.  Each of these that is > 0 is one maximal run: n_skip_runs counts them,
+ *       max_skip is the longest, n_skip_cols their sum.
+ *   inert   the reference's stripe_width == 0 for this call (realign_width 0, or no aligned level): the refs were left alone,
+ *       n_levels is the event's level count and every other field is 0.
+ * Per level, when asked for: step[e][i] is the reference's move code of the step that recorded level i + 1 — 1 MATCH, 2 INSERT,
+ * 3 IGNORE, 4 STAY, 5 EXTEND — and 0 for a level not on the path (L_SKIP records nothing); col[e][i] is the column of the cell it
+ * was recorded from, also for INSERT and IGNORE where ref_align says -1, and 0 off the path.  `step` and `col` are arrays of
+ * n_events pointers, entry e to n_levels(e) elements (an entry may be NULL for an event without levels); either may be NULL.
+ * Invariants:
+ *   n_match + n_ignore + n_insert + n_stay + n_extend == top_level - low_level + 1   when a level was recorded;
+ *   n_match + n_ignore + n_skip_cols == top_col - low_col;
+ *   against the ps_event_stats record of the refs the same call leaves, for a record that is not inert:
+ *       n_match + n_stay + n_extend == n_aligned   and   n_ignore + n_insert == n_insert there.
+ * Counts are integers and max_skip is a maximum: no order of the adds to define.  The batch form is one launch chain with one
+ * launch of k_move_stats and one copy back; a batch whose matrices do not fit device memory is cut between AlignData, never
+ * inside one.  Not part of the reference's interface.  Not built: a fit of lik_offset. */
+typedef struct ps_event_moves {
+    int32_t n_levels, inert;
+    int32_t top_level, top_col;
+    int32_t low_level, low_col;
+    int32_t end_kind;
+    int32_t n_match, n_ignore, n_insert, n_stay, n_extend;
+    int32_t n_skip_runs, max_skip;
+    int64_t n_skip_cols;
+} ps_event_moves;   /* 64 bytes, no padding */
+int ps_move_stats(ps_align* a, double* scores /* [E] or NULL */, ps_event_moves* moves /* [E] */,
+                  uint8_t* const* step /* [E] of [n_e], or NULL */, int32_t* const* col /* [E] of [n_e], or NULL */);
 
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
@@ -451,6 +500,9 @@ int ps_batch_align_stats(int32_t n, ps_align* const* a, int32_t realign, double*
 /* ps_kmer_stats for every AlignData in one launch chain, ONE launch of k_kmer_stats and one copy back: groups[i] has n_events(i) ids (may be NULL for an AlignData without events), n_groups[i] is 1 .. 256, table[i] has n_groups[i] x 1024 records (never NULL); scores as in ps_batch_align_stats. */
 int ps_batch_kmer_stats(int32_t n, ps_align* const* a, int32_t realign, const int32_t* const* groups, const int32_t* n_groups /* [n] */,
                         double* const* scores, ps_kmer_cell* const* table);
+/* ps_move_stats for every AlignData in one launch chain, ONE launch of k_move_stats and one copy back: moves[i] has n_events(i) records (never NULL, also for an AlignData without events); scores[i] — entries or the whole array may be NULL — has n_events(i) entries; step[i] / col[i] — entries or whole arrays may be NULL — are ps_move_stats' arrays of n_events(i) pointers. */
+int ps_batch_move_stats(int32_t n, ps_align* const* a, double* const* scores, ps_event_moves* const* moves,
+                        uint8_t* const* const* step, int32_t* const* const* col);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -555,7 +607,8 @@ int ps_set_device_fraction(double fraction);
  * "link" = k_link: 8 per (event, edit) read, 32 window per edit written, "phase" = k_phase: 32 window per edit read, 16 per edit written,
  * "haptag" = k_haptag: 8 per (event, edit) and 16 per edit read, 24 max_sets per event written,
  * "align_stats" = k_align_stats: 16 per level read, 112 per event written,
- * "kmer_stats" = k_kmer_stats: 24 per level read, 48 * 1024 * n_groups per region written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
+ * "kmer_stats" = k_kmer_stats: 24 per level read, 48 * 1024 * n_groups per region written,
+ * "move_stats" = k_move_stats: 8 per level read, 64 per event and, with the per-level arrays, 5 per level written) since reset; host-side launch counts by form under "sweep_w2", "sweep_w4", "sweep_kept", "sw_pk8", "slab",
  * "fill_pair" / "fill_pair_fwd" / "fill_cmp" / "fill_512" / "fill_1024" / "fill_wide" (which form a k_fill launch took), "score_g7" .. "score_g64"
  * (k_score's size classes) and "fill_ieee" / "sweep_ieee" / "score_ieee" (launches that took the IEEE-division build);
  * Smith-Waterman batches by traceback form under "sw_lists", "sw_summary", "sw_map"; "remap" = k_remap launches and "variant_chunks" =

@@ -65,6 +65,11 @@ EVENT_STATS = np.dtype([(k, np.int32) for k in ("n_levels", "n_aligned", "n_inse
                                                 "n_back", "n_nostate", "n_fit", "first_col", "last_col", "reserved")] +
                        [("n_gap_cols", np.int64)] + [(k, np.float64) for k in ("sw", "swm", "swmm", "swr", "swmr", "swrr")])
 
+# ps_event_moves (64 bytes, no padding): one event's backtrace moves, what move_stats / batch_move_stats hand out
+EVENT_MOVES = np.dtype([(k, np.int32) for k in ("n_levels", "inert", "top_level", "top_col", "low_level", "low_col", "end_kind", "n_match", "n_ignore",
+                                                "n_insert", "n_stay", "n_extend", "n_skip_runs", "max_skip")] + [("n_skip_cols", np.int64)])
+MOVE_NAMES = ("", "MATCH", "INSERT", "IGNORE", "STAY", "EXTEND")   # the step codes of the per-level array (0: not on the path)
+
 # ps_kmer_cell (48 bytes, no padding): one (event group, 5-mer state) of the tables kmer_stats / batch_kmer_stats hand out
 KMER_STATS = np.dtype([("n", np.int64)] + [(k, np.float64) for k in ("sz", "szz", "sp", "spu", "spv")])
 KMER_MAX_GROUPS = 256
@@ -136,6 +141,9 @@ SYMBOLS = {
     "ps_batch_align_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(c_dp), C.POINTER(C.c_void_p)]),
     "ps_kmer_stats": (C.c_int, [C.c_void_p, C.c_int32, c_i32p, C.c_int32, c_dp, C.c_void_p]),
     "ps_batch_kmer_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(c_i32p), c_i32p, C.POINTER(c_dp), C.POINTER(C.c_void_p)]),
+    "ps_move_stats": (C.c_int, [C.c_void_p, c_dp, C.c_void_p, C.POINTER(c_u8p), C.POINTER(c_i32p)]),
+    "ps_batch_move_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_dp), C.POINTER(C.c_void_p), C.POINTER(C.POINTER(c_u8p)),
+                                      C.POINTER(C.POINTER(c_i32p))]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -178,9 +186,10 @@ SYMBOLS = {
 # score_mutation_deltas and the re-aligned refs on the host, util.support_from_deltas, and PSAlign.ScoreMutationGenotypes does the
 # same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas;
 # PSAlign.AlignStats reduces the refs the library holds with util.align_stats_from_refs, after its score_alignments, and
-# PSAlign.KmerStats does the same with util.kmer_stats_from_refs).
+# PSAlign.KmerStats does the same with util.kmer_stats_from_refs; PSAlign.MoveStats walks the tables of the library's debug_fill
+# with util.moves_from_tables).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_kmer_stats", "ps_batch_kmer_stats", "ps_align_stats", "ps_batch_align_stats","ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
+OPTIONAL = frozenset(["ps_move_stats", "ps_batch_move_stats", "ps_kmer_stats", "ps_batch_kmer_stats", "ps_align_stats", "ps_batch_align_stats","ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
                       "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes",
                       "ps_score_mutation_phase", "ps_batch_score_mutation_phase"])
@@ -568,6 +577,42 @@ class CApi:
         sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores]) if realign else None
         self.check(self.lib.ps_batch_kmer_stats(R, self._harr(hs), 1 if realign else 0, gp, ng.ctypes.data_as(c_i32p), sp, tp))
         return [(scores[i][:int(e)] if realign else None, tabs[i]) for i, e in enumerate(n_events)]
+
+    def move_stats(self, h, n_levels, levels=False):
+        """-> (scores float64 [E], records EVENT_MOVES [E][, step, col]): ps_move_stats of one AlignData whose events have
+        n_levels[e] levels"""
+        return self.batch_move_stats([h], [n_levels], levels)[0]
+
+    def batch_move_stats(self, hs, n_levels, levels=False):
+        """ps_batch_move_stats over the AlignData `hs`, n_levels[i][e] the levels of event e of AlignData i: ScoreAlignments' chain
+        with one launch of k_move_stats between the backtrace walk and the kernel that overwrites its records, one copy back ->
+        [(scores float64 [E] — score_alignments' bits —, records EVENT_MOVES [E])], with levels=True [(scores, records, step, col)]:
+        per event a uint8 array of move codes (MOVE_NAMES; 0 off the path) and an int32 array of the columns the levels were
+        recorded from (include/poreseq_hip.h has the definition).  The realignment stays in the handles."""
+        self._need("ps_batch_move_stats")
+        R = len(hs)
+        nl = [[int(v) for v in np.asarray(n, dtype=np.int64).reshape(-1)] for n in n_levels]
+        recs = [np.zeros(max(len(n), 1), dtype=EVENT_MOVES) for n in nl]      # (one spare record: never a null pointer)
+        scores = [np.zeros(max(len(n), 1), dtype=np.float64) for n in nl]
+        rp = (C.c_void_p * max(R, 1))(*[r.ctypes.data_as(C.c_void_p) for r in recs])
+        sp = (c_dp * max(R, 1))(*[_dp(a) for a in scores])
+        stp = clp = None
+        if levels:
+            step = [[np.zeros(max(v, 1), dtype=np.uint8) for v in n] for n in nl]
+            col = [[np.zeros(max(v, 1), dtype=np.int32) for v in n] for n in nl]
+            se = [(c_u8p * max(len(n), 1))(*[a.ctypes.data_as(c_u8p) for a in st]) for n, st in zip(nl, step)]
+            ce = [(c_i32p * max(len(n), 1))(*[a.ctypes.data_as(c_i32p) for a in cl]) for n, cl in zip(nl, col)]
+            stp = (C.POINTER(c_u8p) * max(R, 1))(*[C.cast(x, C.POINTER(c_u8p)) for x in se])
+            clp = (C.POINTER(c_i32p) * max(R, 1))(*[C.cast(x, C.POINTER(c_i32p)) for x in ce])
+        self.check(self.lib.ps_batch_move_stats(R, self._harr(hs), sp, rp, stp, clp))
+        out = []
+        for i, n in enumerate(nl):
+            E = len(n)
+            if levels:
+                out.append((scores[i][:E], recs[i][:E], [a[:v] for a, v in zip(step[i], n)], [a[:v] for a, v in zip(col[i], n)]))
+            else:
+                out.append((scores[i][:E], recs[i][:E]))
+        return out
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

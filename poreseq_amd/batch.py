@@ -245,6 +245,50 @@ class RegionBatch:
                 self.drop([i])
         return fits
 
+    def MoveStats(self, idx=None, levels=False):
+        """PSAlign.MoveStats for the regions `idx` in lock-step: ONE ps_batch_move_stats call — the launch chain of ScoreEvents over
+        all regions with one k_move_stats launch over all their events inside it, one copy back.  Returns one (scores float64 [E],
+        records _capi.EVENT_MOVES [E][, step, col]) per region; sequences and events are not modified (a resident handle's refs
+        come out as they went in)."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        hs = self._open(idx, keep=True)
+        try:
+            if "ps_batch_move_stats" in self.api.missing:
+                return [poreseqcpp._move_stats_on(self.api, h, self.pas[i].events, self.pas[i].params, bool(levels))
+                        for i, h in zip(idx, hs)]
+            return self.api.batch_move_stats(hs, [[len(ev.mean) for ev in self.pas[i].events] for i in idx], bool(levels))
+        finally:
+            self._close(idx, hs, write_back=False)
+
+    def RefitTransitions(self, idx=None, pool=True, params=None, **fit_kw):
+        """PSAlign.RefitTransitions for the regions `idx`: one lock-step MoveStats, then util.fit_transitions and PSEvent.setparams
+        on the Python events.  pool=True (the regions carry reads of the same run) pools the records of all regions per strand and
+        fits once for all of them; pool=False fits every region on its own records.  `params` as PSAlign.RefitTransitions takes
+        it; None: every region's own pa.params (pool=True: those of the first region).  A resident AlignData holds the transition
+        probabilities it was created with, so the handles of the regions are written back (sync) and dropped; the next call
+        rebuilds them.  Returns one util.TransitionFit per region (with pool=True the same one)."""
+        from .util import strand_groups
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        recs = [r for _, r in self.MoveStats(idx)]
+        grps = [strand_groups(self.pas[i].events) for i in idx]
+        if pool:
+            events = [ev for i in idx for ev in self.pas[i].events]
+            fit = poreseqcpp._refit_transitions(events, np.concatenate(recs), [g for gs in grps for g in gs],
+                                                 self.pas[idx[0]].params if params is None else params, fit_kw)
+            fits = [fit] * len(idx)
+        else:
+            fits = [poreseqcpp._refit_transitions(self.pas[i].events, r, g, self.pas[i].params if params is None else params, fit_kw)
+                    for i, r, g in zip(idx, recs, grps)]
+        for i in idx:
+            if i in self._h:
+                self.sync([i])
+                self.drop([i])
+        return fits
+
     def ScoreSequences(self, seqs_per_region, idx=None):
         """PSAlign.ScoreSequences for the regions `idx` on their resident AlignData, all regions' sequences in one chain:
         seqs_per_region[k] are the candidate sequences of region idx[k] (may be empty).  Returns one ndarray

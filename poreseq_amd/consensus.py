@@ -57,7 +57,19 @@ def _refit_kmers_kw(refit_kmers):
     return dict(refit_kmers) if isinstance(refit_kmers, dict) else {}
 
 
-def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None, recalibrate=None, refit_kmers=False):
+def _refit_transitions_kw(refit_transitions):
+    """None / False: no transition refit; True: the defaults; a dict: keyword arguments of RefitTransitions (util.fit_transitions')"""
+    if refit_transitions is None or refit_transitions is False:
+        return None
+    return dict(refit_transitions) if isinstance(refit_transitions, dict) else {}
+
+
+def _rates_fitted(fit):
+    return sum(1 for k in fit.rates if fit.flags.get(k) != 'empty')
+
+
+def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, test=False, qualities=None, recalibrate=None, refit_kmers=False,
+                     refit_transitions=False):
     """Run the consensus schedule in place on `pa`; returns (sequence, accuracy_vs_refseq).
 
     The call sequence is the reference's (Mutate.py:39-101) and has to be: a region with fewer than 5 events is handed
@@ -81,6 +93,11 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     mean, level variance and stdv-channel mean re-estimated on the alignment to the start sequence (util.fit_kmers), in place on
     the events' models — and logs ("RefitKmers", k-mers fitted over the groups, sequence).  False or None is the schedule as it is
     without the argument.  What it does to accuracy on real data is unmeasured.
+    `refit_transitions` (not in the reference; off by default): True, or a dict of keyword arguments for it, runs one
+    `pa.RefitTransitions(params)` after the two refits above and before Mutate('self') — skip / stay / extend / insert per strand
+    re-estimated from the moves of the backtrace on the start sequence (util.fit_transitions), set on the events through setparams
+    — and logs ("RefitTransitions", rates fitted, sequence).  False or None is the schedule as it is without the argument.  What
+    it does to accuracy on real data is unmeasured.
     """
     params = pa.params if params is None else params
     pa.params.setdefault('verbose', 0)
@@ -114,6 +131,10 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
     if refit is not None:
         fitted = call("RefitKmers", lambda: sum(f.n_fitted for f in pa.RefitKmers(**refit)))
         _report(verbose, "refitted %d k-mer rows" % fitted)
+    retr = _refit_transitions_kw(refit_transitions)
+    if retr is not None:
+        fitted = call("RefitTransitions", lambda: _rates_fitted(pa.RefitTransitions(params=params, **retr)))
+        _report(verbose, "refitted %d transition rates" % fitted)
     call("Mutate:self", lambda: pa.Mutate(reps=reps))
     if verbose > 0:
         _report(verbose, "identity after seeding from the reads: %.1f%%" % identity(pa.sequence, refseq)[0])
@@ -143,7 +164,7 @@ def consensus_region(pa, params=None, reps=4, verbose=0, refseq=None, log=None, 
 
 
 def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=None, resident=True, test=False, accuracies=None,
-                      qualities=None, recalibrate=None, refit_kmers=False):
+                      qualities=None, recalibrate=None, refit_kmers=False, refit_transitions=False):
     """The consensus schedule of `consensus_region` for several independent regions in lock-step (poreseq_amd.batch):
     every PSAlign call of the schedule is issued once for all regions that still take part in it, so each phase is one
     launch chain on the GPU.  Returns [(sequence, accuracy)] in the order of `pas`; each entry equals what
@@ -165,6 +186,9 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
     `refit_kmers`: as consensus_region takes it; one lock-step RegionBatch.RefitKmers(pool=False) over all refined regions — every
     region fitted on its own table, as consensus_region does — after the recalibration and before Mutate('self'), logged per region
     as ("RefitKmers", k-mers fitted over the groups, sequence).  Unmeasured on real data.
+    `refit_transitions`: as consensus_region takes it; one lock-step RegionBatch.RefitTransitions(pool=False) over all refined regions
+    — every region fitted on its own records, as consensus_region does — after the two refits above and before Mutate('self'),
+    logged per region as ("RefitTransitions", rates fitted, sequence).  Unmeasured on real data.
     """
     from .batch import RegionBatch
     n = len(pas)
@@ -209,6 +233,7 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
                 raise
         recal = _recalibrate_kw(recalibrate)
         refit = _refit_kmers_kw(refit_kmers)
+        retr = _refit_transitions_kw(refit_transitions)
         with (batch if batch is not None else RegionBatch(pas, resident=resident)) as rb:
             if recal is not None:
                 for i, fits in zip(todo, rb.Recalibrate(todo, **recal)):
@@ -216,6 +241,9 @@ def consensus_regions(pas, params=None, reps=4, refseqs=None, logs=None, batch=N
             if refit is not None:
                 for i, fits in zip(todo, rb.RefitKmers(todo, pool=False, **refit)):
                     note(i, "RefitKmers", sum(f.n_fitted for f in fits))
+            if retr is not None:
+                for i, fit in zip(todo, rb.RefitTransitions(todo, pool=False, params=params, **retr)):
+                    note(i, "RefitTransitions", _rates_fitted(fit))
             tot = rb.Mutate(todo, reps=reps)
             for i in todo:
                 note(i, "Mutate:self", tot[i])
@@ -499,7 +527,7 @@ def variant_sequences(pa, variants, out=None):
     return variantscores
 
 
-def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None, in_flight=1, lock_step=False, test=False):
+def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None, in_flight=1, lock_step=False, test=False, estimate=False):
     """Transition-parameter search of `poreseq train` (cmdline.py:246-267): every iteration runs the consensus schedule
     (reps = 10) once per candidate parameter set (VaryParams: 16 of them) on the same region and keeps the most accurate.
 
@@ -520,8 +548,16 @@ def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None,
     `test` is handed to the consensus schedule of every candidate, in all three modes.  The reference's command line runs
     its candidates with test = not --descend (cmdline.py:242-244), i.e. `poreseq train` corresponds to test=True here and
     `poreseq train --descend` to the default, test=False.
+
+    `estimate` (not in the reference; off by default): the search starts from the transition probabilities fitted to the moves of
+    one forward pass — make_pa(params).RefitTransitions(params), util.fit_transitions — instead of the given ones; every other
+    key of `params` stays.  Unmeasured on real data.
     """
     from .util import VaryParams, SaveParams
+    if estimate:
+        fit = make_pa(params).RefitTransitions(params=params)
+        params = dict(params)
+        params.update({k: fit.params[k] for k in fit.rates})
     best_accs = []
     for it in range(iters):
         cands = paramlists[it] if paramlists is not None else VaryParams(params)

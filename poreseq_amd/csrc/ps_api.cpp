@@ -296,6 +296,29 @@ int ps_kmer_stats(ps_align* a, int32_t realign, const int32_t* groups, int32_t n
     if (!table) return fail(PS_ERR_BAD_ARG, "ps_kmer_stats: null table");
     return ps_batch_kmer_stats(1, &a, realign, &groups, &n_groups, &scores, &table);
 }
+int ps_batch_move_stats(int32_t n, ps_align* const* a, double* const* scores, ps_event_moves* const* moves, uint8_t* const* const* step,
+                        int32_t* const* const* col) {
+    const std::string who = "ps_batch_move_stats";
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n) PS_TRY(stats_output(who, "moves", moves));
+    std::vector<OwnReq> rq(n);
+    for (int i = 0; i < n; i++) {
+        PS_TRY(stats_output(who, "moves", moves[i]));
+        PS_TRY(stats_scores(who, 1, scores, i, &rq[i]));
+        rq[i].a = as[i]; rq[i].moves = moves[i];
+        rq[i].step = step ? step[i] : nullptr; rq[i].col = col ? col[i] : nullptr;
+        for (int e = 0; e < as[i]->E; e++)
+            if (as[i]->n[e] > 0 && ((rq[i].step && !rq[i].step[e]) || (rq[i].col && !rq[i].col[e])))
+                return fail(PS_ERR_BAD_ARG, who + ": null per-level array of event " + std::to_string(e));
+    }
+    return stats_run(OwnKind::MoveStats, 1, rq);
+}
+int ps_move_stats(ps_align* a, double* scores, ps_event_moves* moves, uint8_t* const* step, int32_t* const* col) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_move_stats: null handle");
+    if (!moves) return fail(PS_ERR_BAD_ARG, "ps_move_stats: null moves");
+    return ps_batch_move_stats(1, &a, &scores, &moves, &step, &col);
+}
 int ps_batch_find_mutations(int32_t n, ps_align* const* a, const ps_seqs* const* seeds, ps_muts** out) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));

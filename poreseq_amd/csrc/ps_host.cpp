@@ -297,7 +297,7 @@ int realign(Runtime* rt, Batch& b, double cap) {
     }
     if (rt->prof_on) { rt->prof["fill"].bytes += b.fill_alg_bytes(); rt->prof["fill"].units += (double)b.d.njobs * b.ndir; }
     PS_TRY(launch_fill(rt, b.d, b.jobs, b.ndir, b.maxS, b.P, b.ncols));
-    PS_TRY(launch_backtrace(rt, b.d, b.maxn));
+    PS_TRY(launch_backtrace(rt, b.d, b.maxn, b.moves));
     PS_TRY(launch_updaterefs(rt, b.d));
     return PS_OK;
 }

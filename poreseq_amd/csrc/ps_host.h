@@ -54,6 +54,7 @@ struct Batch {
     char* ext = nullptr;          // full matrices go here (a slab) instead of the runtime's own pools
     size_t ext_bytes = 0;
     std::vector<int> nkeep;       // [2 * job + direction]
+    MoveRun moves;                // forward-only batches: k_move_stats behind the walk (ps_move_stats); unset: today's chain
     int build(Runtime* rt, const std::vector<JobSpec>& specs, int ndir, int lb_extra);
     int place(Runtime* rt, int P, bool can_split = false);
     double fill_alg_bytes() const;
@@ -238,11 +239,14 @@ struct OwnReq {
     ps_event_stats* stats = nullptr;   // AlignStats: [E] records
     // KmerStats: [E] group ids below ngroups, [ngroups][NS] cells, written in full
     const int32_t* group = nullptr; int ngroups = 0; ps_kmer_cell* table = nullptr;
+    // MoveStats: [E] records; [E] pointers to [n_e] step codes / columns each (either may be null, and so may an entry)
+    ps_event_moves* moves = nullptr; uint8_t* const* step = nullptr; int32_t* const* col = nullptr;
 };
 // ScoreAlignments (cpp/MakeMutations.cpp:148-195) | ps_batch_align_stats: per event the census of ref_align and the sums of the
-// scaling fit | ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation (ps_stats.hip)
-enum class OwnKind { Score, AlignStats, KmerStats };
-// reqs[0 .. n - 1] in one launch chain.  realign: ScoreAlignments' fills and backtraces first (Score: always); without, the
+// scaling fit | ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation | ps_batch_move_stats:
+// per event the backtrace's moves, counted between the walk and the kernel that overwrites its records (ps_stats.hip)
+enum class OwnKind { Score, AlignStats, KmerStats, MoveStats };
+// reqs[0 .. n - 1] in one launch chain.  realign: ScoreAlignments' fills and backtraces first (Score, MoveStats: always); without, the
 // statistics reduce the refs the handles hold and no DP runs
 int own_forward(Runtime* rt, OwnKind kind, bool realign, OwnReq* reqs, size_t n);
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out);

@@ -222,7 +222,8 @@ int launch_updaterefs(Runtime* rt, const BatchD& b);
 int launch_lb(Runtime* rt, const BatchD& b, int which /*0: lb_off, 1: lbn_off*/, int maxlbn);
 int launch_lo(Runtime* rt, const BatchD& b, int ndir, int64_t maxS);
 int launch_fill(Runtime* rt, const BatchD& b, const std::vector<JobD>& jobs, int ndir, int64_t maxS, int P, int64_t ncols);
-int launch_backtrace(Runtime* rt, const BatchD& b, int maxn);
+struct MoveRun;
+int launch_backtrace(Runtime* rt, const BatchD& b, int maxn, const MoveRun& moves);   // moves: k_move_stats between the walk and k_fill_like, when asked for
 int launch_prefix(Runtime* rt, const BatchD& b, int ndir);
 
 struct ScoreArgs {
@@ -331,6 +332,26 @@ int launch_align_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_r
 constexpr int KMER_TILE = 512;     // levels staged in LDS per step
 constexpr int KMER_BLOCKS = 4;     // workgroups per (region, group): 256 k-mers each
 int launch_kmer_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxG, double alg_bytes, ps_kmer_cell* d_out);
+// The backtrace's moves (ps_stats.hip, ps_move_stats): one event as k_move_stats sees it — the walk's records in ref_like's slot
+// (bt_walk, ps_dev.h), where the walk started and stopped, and where the per-level arrays go (null: not asked for)
+struct MoveJob {
+    const long long* rec;   // [n] column << 4 | step code << 1 | matrix of every recorded level, 0 elsewhere
+    const JobOut* out;      // bi / bj, term_i / term_w, inert
+    uint8_t* step;          // NULL, or [n]
+    int32_t* col;           // NULL, or [n]
+    int n, pad;
+};
+// A batch's request for k_move_stats, on the host-side Batch: the kernel runs between the walk and the first kernel that
+// overwrites the walk's records, with arguments of its own (BatchD and JobD stay what they are).  jobs == nullptr: not asked for.
+struct MoveRun {
+    const MoveJob* jobs = nullptr;        // device, one per job of the batch, in job order
+    const StatRegion* regs = nullptr;     // device, one per AlignData (job0, njobs)
+    int nregs = 0, maxE = 0;
+    ps_event_moves* out = nullptr;        // device, [jobs]
+    double alg_bytes = 0.0;
+};
+// grid (maxE, nregs): out[job] for every job of every region; counted in the profile as "move_stats".  No-op without a request.
+int launch_move_stats(Runtime* rt, const MoveRun& mv);
 
 // Smith-Waterman (kernels: ps_sw.hip, host side: ps_swhost.cpp)
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,

@@ -950,10 +950,11 @@ int launch_prefix(Runtime* rt, const BatchD& b, int ndir) {
     return PS_OK;
 }
 
-int launch_backtrace(Runtime* rt, const BatchD& b, int maxn) {
+int launch_backtrace(Runtime* rt, const BatchD& b, int maxn, const MoveRun& moves) {
     if (!b.njobs) return PS_OK;
     hipLaunchKernelGGL(k_backtrace, dim3(b.njobs), dim3(256), 0, rt->stream, b);
     PS_LAUNCH_CHECK();
+    PS_TRY(launch_move_stats(rt, moves));   // (reads the walk's records: before k_fill_like turns them into scores)
     if (maxn > 0) {
         hipLaunchKernelGGL(k_fill_like, dim3((maxn + 255) / 256, b.njobs), dim3(256), 0, rt->stream, b);
         PS_LAUNCH_CHECK();

@@ -1,8 +1,9 @@
 // ps_own.cpp — the calls that align every event of an AlignData to its own sequence, forward only: ScoreAlignments
-// (cpp/MakeMutations.cpp:148-195), ps_align_stats and ps_kmer_stats, for several AlignData in lock-step (independent regions in one
+// (cpp/MakeMutations.cpp:148-195), ps_align_stats, ps_kmer_stats and ps_move_stats, for several AlignData in lock-step (independent regions in one
 // launch chain).  One request record per AlignData (OwnReq, ps_host.h) and one chain, own_forward: the cuts of a call that does not
-// fit this runtime's share, the batch, the optional realignment, the tail the kinds differ in, the scores.  Batch and realign() are
-// in ps_host.cpp, struct Align in ps_align.cpp, the kernels of the two reductions in ps_stats.hip.
+// fit this runtime's share, the batch, the optional realignment (with k_move_stats inside it for ps_move_stats, whose outputs are
+// placed before it), the tail the kinds differ in, the scores.  Batch and realign() are
+// in ps_host.cpp, struct Align in ps_align.cpp, the kernels of the three reductions in ps_stats.hip.
 #include "ps_host.h"
 
 #include <algorithm>
@@ -105,6 +106,74 @@ static int stats_tail(Runtime* rt, bool kmer, bool re, const Batch& b, OwnReq* r
     return PS_OK;
 }
 
+// ps_move_stats: k_move_stats runs INSIDE the realignment, between the walk and the kernel that overwrites the walk's records, so
+// its descriptors (through "astats_in") and its outputs (in "astats": the records, the scores, then the per-level columns and step
+// codes when a request wants them) are placed before realign() runs; no kernel of that chain touches either pool.
+struct MovePlan {
+    size_t nj = 0, levels = 0, sc_off = 0, col_off = 0, step_off = 0, out_bytes = 0;
+    bool per_level = false;
+    std::vector<size_t> lev_off;   // of every job in the per-level arrays
+};
+static int moves_place(Runtime* rt, Batch& b, const OwnReq* reqs, size_t n, MovePlan* mp) {
+    mp->nj = b.jobs.size();
+    std::vector<MoveJob> mj(mp->nj);
+    std::vector<StatRegion> sr(n);
+    int maxE = 0;
+    for (size_t k = 0; k < n; k++) mp->per_level |= reqs[k].step || reqs[k].col;
+    mp->lev_off.assign(mp->nj, 0);
+    for (size_t q = 0; q < mp->nj; q++) { mp->lev_off[q] = mp->levels; mp->levels += (size_t)b.jobs[q].n0; }
+    mp->sc_off = mp->nj * sizeof(ps_event_moves);
+    mp->col_off = mp->sc_off + mp->nj * sizeof(double);
+    mp->step_off = mp->col_off + (mp->per_level ? mp->levels * sizeof(int32_t) : 0);
+    mp->out_bytes = mp->step_off + (mp->per_level ? mp->levels : 0);
+    const size_t in_jobs = mp->nj * sizeof(MoveJob), in_bytes = in_jobs + n * sizeof(StatRegion);
+    DBuf& din = rt->buf("astats_in");
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(din.ensure(in_bytes));
+    PS_TRY(dout.ensure(mp->out_bytes));
+    size_t q = 0;
+    for (size_t k = 0; k < n; k++) {
+        const Align* a = reqs[k].a;
+        sr[k].job0 = (int)q; sr[k].njobs = a->E; sr[k].ngroups = 0; sr[k].tab0 = 0;
+        maxE = std::max(maxE, a->E);
+        for (int e = 0; e < a->E; e++, q++) {
+            const JobD& j = b.jobs[q];
+            MoveJob& m = mj[q];
+            m.rec = (const long long*)j.rl; m.out = j.out; m.n = j.n0; m.pad = 0;
+            m.col = reqs[k].col ? (int32_t*)((char*)dout.p + mp->col_off) + mp->lev_off[q] : nullptr;
+            m.step = reqs[k].step ? (uint8_t*)dout.p + mp->step_off + mp->lev_off[q] : nullptr;
+        }
+    }
+    PS_TRY(rt->up(din.p, mj.data(), in_jobs));
+    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), n * sizeof(StatRegion)));
+    b.moves.jobs = din.as<MoveJob>();
+    b.moves.regs = (const StatRegion*)((char*)din.p + in_jobs);
+    b.moves.nregs = (int)n; b.moves.maxE = maxE;
+    b.moves.out = dout.as<ps_event_moves>();
+    b.moves.alg_bytes = (mp->per_level ? 13.0 : 8.0) * (double)mp->levels + (double)mp->sc_off;
+    return PS_OK;
+}
+// and its tail: the scores behind the records, everything back in one copy, the requests' arrays filled
+static int moves_tail(Runtime* rt, const Batch& b, const MovePlan& mp, OwnReq* reqs, size_t n, double** best) {
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + mp.sc_off)));
+    void* back = nullptr;
+    PS_TRY(rt->down(&back, dout.p, mp.out_bytes));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    size_t q = 0;
+    for (size_t k = 0; k < n; k++) {
+        const Align* a = reqs[k].a;
+        memcpy(reqs[k].moves, (const ps_event_moves*)back + q, (size_t)a->E * sizeof(ps_event_moves));
+        for (int e = 0; e < a->E; e++, q++) {
+            const size_t ne = (size_t)a->n[e];
+            if (reqs[k].col && reqs[k].col[e]) memcpy(reqs[k].col[e], (const int32_t*)((const char*)back + mp.col_off) + mp.lev_off[q], ne * sizeof(int32_t));
+            if (reqs[k].step && reqs[k].step[e]) memcpy(reqs[k].step[e], (const uint8_t*)back + mp.step_off + mp.lev_off[q], ne);
+        }
+    }
+    *best = (double*)((char*)back + mp.sc_off);
+    return PS_OK;
+}
+
 int own_forward(Runtime* rt, OwnKind kind, bool re, OwnReq* reqs, size_t n) {
     const bool kmer = kind == OwnKind::KmerStats;
     auto sub = [&](size_t k0, size_t k1) { return own_forward(rt, kind, re, reqs + k0, k1 - k0); };   // regions k0 .. k1 - 1 as a call of their own
@@ -121,6 +190,8 @@ int own_forward(Runtime* rt, OwnKind kind, bool re, OwnReq* reqs, size_t n) {
     }
     Batch b;   // (also without a realignment: it puts every sequence's states on the device)
     PS_TRY(b.build(rt, specs, 1, 0));
+    MovePlan mp;
+    if (kind == OwnKind::MoveStats) PS_TRY(moves_place(rt, b, reqs, n, &mp));
     if (re) {
         const int rc = realign(rt, b, n > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
         if (rc == PS_SPLIT) return in_halves(n, sub);   // bands wider than share_need guessed: two halves, one after the other
@@ -129,6 +200,7 @@ int own_forward(Runtime* rt, OwnKind kind, bool re, OwnReq* reqs, size_t n) {
     }
     double* best = nullptr;
     if (kind == OwnKind::Score) PS_TRY(score_tail(rt, b, reqs, n, &best));
+    else if (kind == OwnKind::MoveStats) PS_TRY(moves_tail(rt, b, mp, reqs, n, &best));
     else PS_TRY(stats_tail(rt, kmer, re, b, reqs, n, &best));
     size_t q = 0;
     for (size_t k = 0; best && k < n; k++)

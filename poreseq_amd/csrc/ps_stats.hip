@@ -1,4 +1,4 @@
-// ps_stats.hip — ps_align_stats and ps_kmer_stats.  ps_align_stats: the census of an event's ref_align array and the sufficient statistics of a shift / scale refit
+// ps_stats.hip — ps_align_stats, ps_kmer_stats and ps_move_stats.  ps_align_stats: the census of an event's ref_align array and the sufficient statistics of a shift / scale refit
 // of its model, reduced on the device (include/poreseq_hip.h has the definition of a record; this file follows it line by line).
 //
 //   k_align_stats   grid (events of the largest AlignData, AlignData), 256 threads per event, as the reductions of ps_edit.hip
@@ -28,10 +28,24 @@
 // workgroups on the chip instead of two, and each does a quarter of the divisions), KMER_TILE = 512: LDS 512 x (4 + 3 x 8) =
 // 14 336 bytes per workgroup, so LDS (160 KiB per CU) admits more workgroups per CU than the four the guides advise to plan
 // for; a larger tile would only save barriers (two per 512 walk steps already).
-#include "ps_internal.h"
+//
+//   k_move_stats    grid (events of the largest AlignData, AlignData), 256 threads per event: ps_move_stats' records
+//
+// Runs between the backtrace walker and the kernel that turns the walker's records into ref_like (launch_backtrace, sweep_run),
+// and reads those records: per recorded level column << 4 | step code << 1 | matrix, in ref_like's slot, 0 for a level not on
+// the path (bt_walk, ps_dev.h, clears every level first), and in the job's result record the cell the walk started from (bi, bj)
+// and the one it stopped on (term_i, term_w).  One pass over 8 bytes per level in coalesced tiles of 256; only the levels in
+// (term_i, bi] are read.  A level classifies its own step; the L_SKIP steps are not recorded and are counted from the columns:
+// above the record of level i the walk skipped from where the record of level i + 1 left it — that record comes from the next
+// lane by a cross-lane move (the last lane of a wavefront loads it: one more 8-byte load per 64 levels, from a line its
+// neighbours just fetched), for the top level it is the start cell — and the lowest recorded level adds the skips down to the
+// cell the walk stopped on.  So no tile carries anything to the next and the tile loop has no barrier.  Counts are integers and
+// max_skip a maximum, reduced in any order: registers, then the wavefront, then four LDS words per count.
+#include "ps_dev.h"
 
 namespace ps {
 
+static_assert(sizeof(ps_event_moves) == 64, "ps_event_moves has no padding");
 static_assert(sizeof(ps_event_stats) == 112, "ps_event_stats has no padding");
 static_assert(sizeof(ps_kmer_cell) == 48, "ps_kmer_cell has no padding");
 static_assert(KMER_BLOCKS * 256 == NS && KMER_TILE % 256 == 0 && KMER_TILE % 16 == 0, "a thread per k-mer, the walk takes sixteen ids per step");
@@ -219,7 +233,94 @@ __global__ __launch_bounds__(256) void k_kmer_stats(const StatJob* __restrict__ 
     o->n = n; o->sz = sz; o->szz = szz; o->sp = sp; o->spu = spu; o->spv = spv;
 }
 
+constexpr int MV_NCNT = 7;   // n_match, n_ignore, n_insert, n_stay, n_extend, n_skip_runs, max_skip
+
+__device__ inline int wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+// columns the step recorded in `w` moves to the left: 1 for MATCH / IGNORE, 0 for INSERT / STAY / EXTEND
+__device__ inline int move_dj(long long w) {
+    const unsigned st = (unsigned)(w >> 1) & 7u;
+    return (st == M_MATCH || st == M_IGNORE) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_move_stats(const MoveJob* __restrict__ J, const StatRegion* __restrict__ R, ps_event_moves* __restrict__ out) {
+    const StatRegion rg = R[blockIdx.y];
+    if ((int)blockIdx.x >= rg.njobs) return;   // (the same for every thread of the block)
+    const MoveJob j = J[rg.job0 + blockIdx.x];
+    const JobOut O = *j.out;
+    __shared__ int s_cnt[MV_NCNT][4];
+    __shared__ long long s_cols[4];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    // inert: the walker left at once (refs and records untouched, term_i / term_w stale); no positive score: it walked nothing
+    const bool walked = !O.inert && O.bi > 0;
+    const int top = walked ? min(O.bi, j.n) : 0, bj = walked ? O.bj : 0;
+    const int low = walked ? clampi(O.term_i, 0, top) : 0;   // levels low + 1 .. top were recorded
+    const int low_col = walked ? (O.term_w >> 3) : 0;
+    int n_m = 0, n_ig = 0, n_in = 0, n_st = 0, n_ex = 0, n_run = 0, mx = 0;
+    long long cols = 0;
+    // (with the per-level arrays every level is visited, since the levels off the path get their zeros here)
+    const bool per_level = j.step || j.col;
+    const int first = per_level ? 0 : (low / 256) * 256, last = per_level ? j.n : top;
+    for (int base = first; base < last; base += 256) {
+        const int i = base + t + 1;   // the level, 1-based
+        const bool on = i > low && i <= top;
+        const long long rec = on ? j.rec[i - 1] : 0ll;
+        // the record of level i + 1: the next lane's, or — last lane of the wavefront — loaded
+        long long up = (lane == 63 && on && i < top) ? j.rec[i] : 0ll;
+        const long long nxt = __shfl_down(rec, 1, 64);
+        if (lane != 63) up = nxt;
+        const int st = (int)(rec >> 1) & 7, c = (int)(rec >> 4);
+        if (i <= j.n) {
+            if (j.step) j.step[i - 1] = (uint8_t)st;
+            if (j.col) j.col[i - 1] = c;
+        }
+        if (!on) continue;
+        n_m += st == (int)M_MATCH; n_ig += st == (int)M_IGNORE; n_in += st == (int)M_INSERT;
+        n_st += st == (int)M_STAY; n_ex += st == (int)M_EXTEND;
+        const int above = (i == top ? bj : (int)(up >> 4) - move_dj(up)) - c;
+        const int below = i == low + 1 ? (c - move_dj(rec)) - low_col : 0;
+        n_run += (above > 0) + (below > 0);
+        mx = max(mx, max(above, below));
+        cols += above + below;
+    }
+    {
+        const int c0 = wave_sum(n_m), c1 = wave_sum(n_ig), c2 = wave_sum(n_in), c3 = wave_sum(n_st), c4 = wave_sum(n_ex), c5 = wave_sum(n_run);
+        const int c6 = wave_max(mx);
+        const long long g = wave_sum(cols);
+        if (lane == 0) {
+            s_cnt[0][w] = c0; s_cnt[1][w] = c1; s_cnt[2][w] = c2; s_cnt[3][w] = c3; s_cnt[4][w] = c4; s_cnt[5][w] = c5; s_cnt[6][w] = c6;
+            s_cols[w] = g;
+        }
+    }
+    __syncthreads();
+    if (t == 0) {
+        auto cnt = [&](int k) { return s_cnt[k][0] + s_cnt[k][1] + s_cnt[k][2] + s_cnt[k][3]; };
+        ps_event_moves m;
+        m.n_levels = j.n; m.inert = O.inert ? 1 : 0;
+        m.top_level = top; m.top_col = bj;
+        m.low_level = top > low ? low + 1 : 0; m.low_col = low_col;
+        m.end_kind = walked ? (O.term_w & 1) : 0;
+        m.n_match = cnt(0); m.n_ignore = cnt(1); m.n_insert = cnt(2); m.n_stay = cnt(3); m.n_extend = cnt(4);
+        m.n_skip_runs = cnt(5);
+        m.max_skip = max(max(s_cnt[6][0], s_cnt[6][1]), max(s_cnt[6][2], s_cnt[6][3]));
+        m.n_skip_cols = s_cols[0] + s_cols[1] + s_cols[2] + s_cols[3];
+        out[rg.job0 + blockIdx.x] = m;
+    }
+}
+
 }  // namespace
+
+int launch_move_stats(Runtime* rt, const MoveRun& mv) {
+    if (!mv.jobs || mv.nregs <= 0 || mv.maxE <= 0) return PS_OK;
+    prof_begin(rt);
+    hipLaunchKernelGGL(k_move_stats, dim3(mv.maxE, mv.nregs), dim3(256), 0, rt->stream, mv.jobs, mv.regs, mv.out);
+    PS_LAUNCH_CHECK();
+    prof_end(rt, "move_stats", mv.alg_bytes);
+    return PS_OK;
+}
 
 int launch_kmer_stats(Runtime* rt, const StatJob* d_jobs, const StatRegion* d_regs, int nregs, int maxG, double alg_bytes, ps_kmer_cell* d_out) {
     if (nregs <= 0 || maxG <= 0) return PS_OK;

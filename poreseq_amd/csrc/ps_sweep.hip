@@ -475,6 +475,7 @@ int sweep_run(Runtime* rt, Batch& bt) {
 #undef PS_X
     }
     PS_LAUNCH_CHECK();
+    PS_TRY(launch_move_stats(rt, bt.moves));   // (reads the walk's records: before k_like_b turns them into scores)
     if (bt.maxn > 0) {
         with_fastdiv(b.fastdiv, [&](auto fd) {
             hipLaunchKernelGGL(k_like_a<fd.value>, dim3((bt.maxn + 255) / 256, b.njobs), dim3(256), 0, rt->stream, b);

@@ -14,6 +14,7 @@ from . import _capi
 from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, support_from_deltas, genotypes_from_deltas, check_alt_frac, phase_from_deltas, check_phase_args
 from .util import align_stats_from_refs, fit_scaling, apply_scaling
 from .util import kmer_groups, kmer_stats_from_refs, fit_kmers, apply_kmers
+from .util import moves_from_tables, fit_transitions, strand_groups
 
 
 def _api():
@@ -159,6 +160,57 @@ def _kmer_stats_on(api, h, events, grp, G, realign):
     return scores, kmer_stats_from_refs(states, events, refs, grp, G)
 
 
+def _move_stats_on(api, h, events, params, levels):
+    """(scores float64 [E], records _capi.EVENT_MOVES [E][, step, col]) of the AlignData `h`, whose events are `events` and whose
+    parameters `params`: ps_move_stats, or — a library without the entry point — the literal walk (util.moves_from_tables) of the
+    forward tables its debug_fill hands out, taken on a scratch AlignData with the sequence and the ref_align that `h` holds (a
+    checker's debug_fill backtraces into the handle it is given), and then
+    its score_alignments on `h`, which leaves the refs a scoring call leaves.  An event the reference would not walk
+    (realign_width 0, or no aligned level) gets the inert record."""
+    E = len(events)
+    nl = [len(ev.mean) for ev in events]
+    if "ps_move_stats" not in api.missing:
+        return api.move_stats(h, nl, levels)
+    recs = np.zeros(E, dtype=_capi.EVENT_MOVES)
+    step = [np.zeros(n, dtype=np.uint8) for n in nl]
+    col = [np.zeros(n, dtype=np.int32) for n in nl]
+    sequence = api.align_sequence(h)                  # (what the handle holds now: a resident one may be ahead of the Python objects)
+    S = len(api.seq_to_states(sequence))
+    width = int(params.get('realign_width', 300))      # (cpp/AlignUtil.h:64: the default of a call that sets none)
+    held = []
+    for ev, ra in zip(events, api.align_event_refs(h, E)):
+        ev = copy.copy(ev)
+        ev.ref_align = ra
+        held.append(ev)
+    scratch = api.align_create(sequence, held, params)
+    try:
+        for e, ev in enumerate(held):
+            recs[e]["n_levels"] = nl[e]
+            with np.errstate(invalid='ignore'):
+                walks = width != 0 and bool(np.any(ev.ref_align > 0))
+            if not walks:
+                recs[e]["inert"] = 1
+                continue
+            recs[e], step[e], col[e], _, _ = moves_from_tables(*api.debug_fill(scratch, e, 0, nl[e], S))
+    finally:
+        api.align_destroy(scratch)
+    scores = api.score_alignments(h, E)
+    return (scores, recs, step, col) if levels else (scores, recs)
+
+
+def _refit_transitions(events, records, groups, params, fit_kw):
+    """util.fit_transitions of the records, applied through PSEvent.setparams to every event -> the fit"""
+    base = dict(params) if params is not None else {}
+    for ev, g in zip(events, groups):      # the rates the events carry now, where `params` does not say
+        for name in ("skip", "stay", "extend", "insert"):
+            base.setdefault(name + ("_c" if g else "_t"), float(getattr(ev.model, 'prob_' + name)))
+    fit = fit_transitions(records, groups, base, **fit_kw)
+    keys = {k: fit.params[k] for k in fit.rates}
+    for ev in events:
+        ev.setparams(keys)
+    return fit
+
+
 def _refit_kmers(events, grp, fits):
     """apply_kmers of every event's group's fit, in place on the events' models -> the events whose model changed"""
     changed, seen = 0, set()
@@ -288,6 +340,27 @@ class PSAlign:
         fits = fit_kmers(table, **fit_kw)
         _refit_kmers(self.events, grp, fits)
         return fits
+
+    def MoveStats(self, levels=False):
+        """Per event the moves of its backtrace (ps_move_stats): (scores, records[, step, col]).  Every event is aligned as
+        ScoreEvents does — scores are ScoreEvents' bits, as float64 [E] — and, on the device, between the backtrace walk and the
+        kernel that overwrites its records, the moves of the path are counted (k_move_stats): records is a structured array
+        (_capi.EVENT_MOVES [E]) with the cell the walk started from and stopped on, the recorded levels by move (match, ignore,
+        insert, stay, extend) and the skips (runs, the longest, columns), for util.fit_transitions.  levels=True adds per event a
+        uint8 array of move codes (_capi.MOVE_NAMES; 0: not on the path) and an int32 array of the columns the levels were
+        recorded on — also for the inserted and ignored levels, where ref_align says -1.  Like ScoreEvents it does not write
+        ref_align back; `self` is not modified.  A library without the entry point (the test-suite's checkers) walks its
+        debug_fill tables: `util.moves_from_tables`."""
+        with PSAlign._Data(self) as d:
+            return _move_stats_on(d.api, d.h, self.events, self.params, bool(levels))
+
+    def RefitTransitions(self, params=None, **fit_kw):
+        """Re-estimate the transition probabilities on the alignment to self.sequence: one MoveStats() pass, util.fit_transitions
+        (**fit_kw) pooled per strand, starting from `params` ('skip_t' .. 'insert_c'; None: self.params; what it lacks is read off the events' models),
+        and PSEvent.setparams IN PLACE on every event.  Returns the util.TransitionFit.  Sequence, ref_align, ref_like and the
+        models' level tables are not touched.  What this does to consensus accuracy on real data has not been measured."""
+        _, records = self.MoveStats()
+        return _refit_transitions(self.events, records, strand_groups(self.events), self.params if params is None else params, fit_kw)
 
     def ScoreSequences(self, seqs):
         """ndarray [len(seqs)][len(events)]: row s is what `pav = self.Copy(); pav.RealignTo(seqs[s]); pav.ScoreEvents()` returns,

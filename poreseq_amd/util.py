@@ -783,3 +783,149 @@ def apply_scaling_sd(event, a, D=1.0):
     m.sd_mean = np.asarray(m.sd_mean, dtype=np.float64) * float(a)
     m.sd_stdv = np.asarray(m.sd_stdv, dtype=np.float64) * (float(a) ** 1.5 * float(D) ** 0.5)
     return event
+
+
+# ---- the backtrace's moves (ps_move_stats) and the transition rates fitted from them ---------------------------------------------
+def moves_from_tables(main, stay, step_main, step_stay):
+    """One event's backtrace, walked literally (cpp/Alignment.cpp:537-605) on the forward tables that `debug_fill` hands out —
+    main / stay scores and their step codes, [levels + 1, states + 1], NaN outside the band — the definition of ps_move_stats in
+    Python and the path of a library without the entry point.  The walk starts on the first maximum of the main scores that is
+    > 0, columns before rows (the order the fill meets the cells in, cpp/Alignment.cpp:158, 270), and ends on row 0, on a score
+    <= 0 or on a Z_IMPLICIT step.  Returns (record, step, col, ref_align, ref_like): the _capi.EVENT_MOVES record (shape (); `inert`
+    is the caller's to set: the tables do not say whether the reference would have walked at all), per level the move code that
+    recorded it (1 MATCH, 2 INSERT, 3 IGNORE, 4 STAY, 5 EXTEND, 0 off the path) and the column it was recorded on, and the
+    ref_align / ref_like arrays the reference's backtrace writes.  Skips are counted step by step, a run ending at any other step."""
+    import numpy as np
+    from ._capi import EVENT_MOVES
+    main, stay = np.asarray(main, dtype=np.float64), np.asarray(stay, dtype=np.float64)
+    sm, ss = np.asarray(step_main), np.asarray(step_stay)
+    n = main.shape[0] - 1
+    rec = np.zeros((), dtype=EVENT_MOVES)
+    step, col = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.int32)
+    ra, rl = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+    rec["n_levels"] = n
+    # MaxInfo starts at (score 0, cell 0, 0) and moves on a strictly larger score only, column by column, rows ascending
+    with np.errstate(invalid='ignore'):
+        cand = np.where(main > 0, main, -np.inf).T      # [column, row]; NaN and scores <= 0 never win
+    i = j = 0
+    if cand.size and np.max(cand) > 0:
+        j, i = np.unravel_index(int(np.argmax(cand)), cand.shape)   # (argmax: the first maximum in column-major order)
+        i, j = int(i), int(j)
+    rec["top_level"], rec["top_col"] = i, j
+    counts = {1: 0, 2: 0, 3: 0, 4: 0, 5: 0}
+    run = runs = longest = skipped = 0
+    arr = kind = 0
+
+    def close_run():
+        nonlocal run, runs, longest
+        if run:
+            runs += 1
+            longest = max(longest, run)
+        run = 0
+
+    low = 0
+    while i > 0:
+        st = int((ss if arr else sm)[i, j])
+        score = (stay if arr else main)[i, j]
+        if np.isnan(score):
+            raise ValueError("moves_from_tables: the walk left the band at level %d, column %d" % (i, j))
+        if score <= 0.0:
+            break
+        if st == 0:                       # L_SKIP
+            run += 1
+            skipped += 1
+            j -= 1
+            continue
+        close_run()
+        if st == 4 and arr == 0:          # U_STAY on the main matrix: over to the stay matrix, same cell
+            arr = 1
+            continue
+        if st not in counts:              # Z_IMPLICIT (or an unknown code): the walk ends here
+            kind = 1 if st == 255 else 0
+            break
+        counts[st] += 1
+        step[i - 1], col[i - 1] = st, j
+        ra[i - 1] = -1.0 if st in (2, 3) else float(j)
+        rl[i - 1] = score
+        low = i
+        if st == 4:
+            arr = 0
+        i -= 1
+        if st in (1, 3):
+            j -= 1
+    close_run()
+    rec["low_level"], rec["low_col"], rec["end_kind"] = low, j, kind
+    rec["n_match"], rec["n_insert"], rec["n_ignore"], rec["n_stay"], rec["n_extend"] = counts[1], counts[2], counts[3], counts[4], counts[5]
+    rec["n_skip_runs"], rec["max_skip"], rec["n_skip_cols"] = runs, longest, skipped
+    return rec, step, col, ra, rl
+
+
+TRANSITION_RATES = ("skip", "stay", "extend", "insert")
+
+
+class TransitionFit(object):
+    """fit_transitions' result: params (a copy of the given parameters with the fitted rates under 'skip_t' .. 'insert_c'), rates
+    {key: value before the clamp}, counts {key: (numerator, denominator)} and flags {key: 'clamped' | 'empty'} for the rates that
+    a limit cut or that had no observation (those keep the given value)"""
+    __slots__ = ("params", "rates", "counts", "flags")
+
+    def __init__(self, params, rates, counts, flags):
+        self.params, self.rates, self.counts, self.flags = params, rates, counts, flags
+
+    @property
+    def ok(self):
+        return not self.flags
+
+    def __repr__(self):
+        return "TransitionFit(%s%s)" % (", ".join("%s=%.4g" % (k, self.params[k]) for k in sorted(self.rates)),
+                                        "; flagged: " + ", ".join(sorted(self.flags)) if self.flags else "")
+
+
+def fit_transitions(records, groups, params, prior=100.0, lo=1e-3, hi=0.5, suffixes=("_t", "_c")):
+    """The transition probabilities of `params` re-estimated from ps_move_stats records (_capi.EVENT_MOVES [E]): the frequencies of
+    the moves on the backtrace's paths, pooled per group — groups[e] is the group of record e, by default use the strand (0
+    template, 1 complement), which gives the keys 'skip_t' .. 'insert_c' through `suffixes`.  With L = n_match + n_ignore +
+    n_insert + n_stay + n_extend (the recorded levels) and Ccol = n_match + n_ignore + n_skip_cols (the columns the path crossed):
+        skip = n_skip_cols / Ccol;  stay = n_stay / L;  extend = n_extend / (n_stay + n_extend);  insert = (n_insert + n_ignore) / L
+    Each rate is shrunk towards the parameter as it is by `prior` pseudo-observations, (num + prior cur) / (den + prior), and
+    clamped to [lo, hi]; a rate that was clamped is flagged 'clamped', one without an observation (denominator 0: an empty group,
+    or no stay to extend) keeps the given value and is flagged 'empty' — fit_kmers' convention.  `lo`, `hi` and `prior` are guards
+    with documented defaults, not measurements.  A key `params` lacks is taken from DEFAULT_PARAMS.
+    These are path frequencies (Viterbi training) of a score that is no normalised probability (lik_offset is added per matched
+    level), not maximum-likelihood estimates.  Host only.  Returns a TransitionFit."""
+    import numpy as np
+    rec = np.asarray(records).reshape(-1)
+    grp = np.asarray(list(groups), dtype=np.int64).reshape(-1)
+    if grp.size != rec.size:
+        raise ValueError("fit_transitions: %d group ids for %d records" % (grp.size, rec.size))
+    if grp.size and (grp.min() < 0 or grp.max() >= len(suffixes)):
+        raise ValueError("fit_transitions: group ids must lie in 0 .. %d" % (len(suffixes) - 1))
+    if not (0.0 <= float(lo) <= float(hi)) or float(prior) < 0:
+        raise ValueError("fit_transitions: need 0 <= lo <= hi and prior >= 0")
+    out, rates, counts, flags = dict(params), {}, {}, {}
+    for g, suf in enumerate(suffixes):
+        r = rec[grp == g]
+        tot = {k: int(np.sum(r[k], dtype=np.int64)) for k in ("n_match", "n_ignore", "n_insert", "n_stay", "n_extend", "n_skip_cols")}
+        L = tot["n_match"] + tot["n_ignore"] + tot["n_insert"] + tot["n_stay"] + tot["n_extend"]
+        ccol = tot["n_match"] + tot["n_ignore"] + tot["n_skip_cols"]
+        frac = {"skip": (tot["n_skip_cols"], ccol), "stay": (tot["n_stay"], L), "extend": (tot["n_extend"], tot["n_stay"] + tot["n_extend"]),
+                "insert": (tot["n_insert"] + tot["n_ignore"], L)}
+        for name in TRANSITION_RATES:
+            key = name + suf
+            cur = float(params[key]) if key in params else float(DEFAULT_PARAMS[key])
+            num, den = frac[name]
+            counts[key] = (num, den)
+            if den <= 0:
+                rates[key], out[key], flags[key] = cur, cur, 'empty'
+                continue
+            v = (num + float(prior) * cur) / (den + float(prior))
+            rates[key] = v
+            out[key] = min(max(v, float(lo)), float(hi))
+            if out[key] != v:
+                flags[key] = 'clamped'
+    return TransitionFit(out, rates, counts, flags)
+
+
+def strand_groups(events):
+    """the default grouping of fit_transitions: 0 for a template event, 1 for a complement one (ev.model.complement)"""
+    return [1 if getattr(ev.model, 'complement', False) else 0 for ev in events]
