@@ -182,19 +182,25 @@ int ps_make_mutations(ps_align* a, const ps_muts* in, int32_t* nb) {
     *nb = n;
     return PS_OK;
 }
-// ViterbiMutate on emissions that are -infinity or NaN: a position whose candidates are all NaN leaves the back-pointer -1 behind
-// (k_vit_steps), which the back-trace would index with — refused
-static int viterbi_refuses(const Align& a, const char* call) {
-    if (a.nonfinite.empty()) return PS_OK;
-    return fail(PS_ERR_BAD_ARG, std::string(call) + ": " + a.nonfinite + " (ViterbiMutate needs finite levels with stdv > 0 and a model with positive deviations)");
-}
 int ps_viterbi_mutate(ps_align* a, int32_t nkeep, double skip, double stay, double mmin, double mmax,
                       int32_t verbose, ps_seqs** out) {
-    if (!a || !out || a->a.E == 0 || nkeep < 0) return fail(PS_ERR_BAD_ARG, "ps_viterbi_mutate");
-    PS_TRY(viterbi_refuses(a->a, "ps_viterbi_mutate"));
-    NEED_RT();
+    if (!a || !out) return fail(PS_ERR_BAD_ARG, "ps_viterbi_mutate");
     std::unique_ptr<ps_seqs> s(new ps_seqs());
-    PS_TRY(viterbi_mutate(rt, &a->a, nkeep, skip, stay, mmin, mmax, &s->v, verbose != 0));
+    VitCall call;
+    call.nkeep = nkeep; call.skip = skip; call.stay = stay; call.mmin = mmin; call.mmax = mmax;
+    call.who = "ps_viterbi_mutate"; call.lockstep = false;
+    VitReq q;
+    q.a = &a->a; q.out = &s->v;
+    PS_TRY(viterbi_mutate(nullptr, call, &q, 1));
+    if (verbose) {
+        // the reference's progress line (cpp/Viterbi.cpp:258-259, 357-370): "Viterbi", a dot whenever the reference position passes a
+        // multiple of 200, a newline.  The positions walked: from the first event's start to where no event is aligned any more —
+        // counted here from the sequence length (the walk itself runs on the device)
+        fputs("Viterbi", stderr);
+        for (size_t k = 200; k <= a->a.bases.size(); k += 200) fputc('.', stderr);
+        fputc('\n', stderr);
+        fflush(stderr);
+    }
     *out = s.release();
     return PS_OK;
 }
@@ -460,15 +466,12 @@ int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, i
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
     if (n && !out) return fail(PS_ERR_BAD_ARG, "ps_batch_viterbi_mutate");
-    if (nkeep < 0) return fail(PS_ERR_BAD_ARG, "ps_batch_viterbi_mutate: nkeep");
-    for (Align* x : as) if (x->E == 0) return fail(PS_ERR_BAD_ARG, "ps_batch_viterbi_mutate: no events");
-    for (Align* x : as) PS_TRY(viterbi_refuses(*x, "ps_batch_viterbi_mutate"));
-    NEED_RT();
     std::vector<std::unique_ptr<ps_seqs>> s(n);
-    std::vector<RandState*> rs(n, nullptr);
-    std::vector<std::vector<std::string>*> o(n);
-    for (int i = 0; i < n; i++) { s[i].reset(new ps_seqs()); o[i] = &s[i]->v; rs[i] = (rng && rng[i]) ? rng[i]->s : nullptr; }
-    PS_TRY(viterbi_mutate_multi(rt, as, rs, nkeep, skip, stay, mmin, mmax, o));
+    std::vector<VitReq> rq(n);
+    for (int i = 0; i < n; i++) { s[i].reset(new ps_seqs()); rq[i].a = as[i]; rq[i].rng = (rng && rng[i]) ? rng[i]->s : nullptr; rq[i].out = &s[i]->v; }
+    VitCall call;
+    call.nkeep = nkeep; call.skip = skip; call.stay = stay; call.mmin = mmin; call.mmax = mmax;
+    PS_TRY(viterbi_mutate(nullptr, call, rq.data(), rq.size()));
     for (int i = 0; i < n; i++) out[i] = s[i].release();
     return PS_OK;
 }
@@ -544,10 +547,7 @@ int ps_debug_viterbi(int32_t n, ps_align* const* a, int32_t build, int32_t nkeep
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
     if (nkeep < 0 || build < 0 || build > 3 || cap_T < 0 || (n && !T)) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi");
-    for (Align* x : as) if (x->E == 0) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: no events");
-    for (Align* x : as) PS_TRY(viterbi_refuses(*x, "ps_debug_viterbi"));
-    NEED_RT();
-    return debug_viterbi(rt, as, build, nkeep, skip, stay, mmin, mmax, cap_T, T, obs, bp, lik_final, fwd, paths);
+    return debug_viterbi(as, build, nkeep, skip, stay, mmin, mmax, cap_T, T, obs, bp, lik_final, fwd, paths);
 }
 int ps_debug_viterbi_steps(int32_t R, const int32_t* T, const double* obs, const double* rnd, int32_t nkeep, double skip, double stay,
                            double mmin, double mmax, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {

@@ -83,15 +83,18 @@ int debug_fill(Runtime* rt, Align* a, int ev, int dir, double* main, double* sta
 
 // ViterbiMutate of a batch of AlignData as ps_batch_viterbi_mutate runs it (vit_gather, emission kernel, steps, log, trace; deviates from
 // the calling thread's generator), with the device tables tapped.  Outputs per region at a row pitch of cap_T.
-int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
+int debug_viterbi(const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
                   int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths) {
     const int R = (int)as.size();
     VitTap tap;
     tap.obs_build = build;
     std::vector<std::vector<std::string>> seqs(R);
-    std::vector<std::vector<std::string>*> outs(R);
-    for (int r = 0; r < R; r++) outs[r] = &seqs[r];
-    PS_TRY(viterbi_mutate_multi(rt, as, std::vector<RandState*>(R, nullptr), nkeep, skip, stay, mmin, mmax, outs, &tap, "ps_debug_viterbi"));
+    std::vector<VitReq> rq(R);
+    for (int r = 0; r < R; r++) { rq[r].a = as[r]; rq[r].out = &seqs[r]; }
+    VitCall call;
+    call.nkeep = nkeep; call.skip = skip; call.stay = stay; call.mmin = mmin; call.mmax = mmax;
+    call.who = "ps_debug_viterbi"; call.tap = &tap;
+    PS_TRY(viterbi_mutate(nullptr, call, rq.data(), rq.size()));
     for (int r = 0; r < R; r++) T[r] = tap.T[r];
     for (int r = 0; r < R; r++) if (tap.T[r] > cap_T) return fail(PS_ERR_BAD_ARG, "ps_debug_viterbi: a region has more positions than cap_T");
     const int np = std::max(nkeep, 1);
@@ -102,9 +105,9 @@ int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nke
         if (bp && n) memcpy(bp + to, tap.bp.data() + t_off * NS, n * sizeof(short));
         if (fwd && n && !tap.fwd.empty()) memcpy(fwd + to, tap.fwd.data() + t_off * NS, n * sizeof(double));
         if (lik_final) memcpy(lik_final + (size_t)r * NS, tap.lik_final.data() + (size_t)r * NS, NS * sizeof(double));
-        if (paths)
-            for (size_t k = 0; k < tap.paths[r].size(); k++)
-                for (int i = 0; i < tap.T[r]; i++) paths[((size_t)r * np + k) * cap_T + i] = (int16_t)tap.paths[r][k][i];
+        if (paths)   // (rows of T at a pitch of cap_T)
+            for (size_t k = 0; k * tap.T[r] < tap.paths[r].size(); k++)
+                memcpy(paths + ((size_t)r * np + k) * cap_T, tap.paths[r].data() + k * tap.T[r], (size_t)tap.T[r] * sizeof(int16_t));
         t_off += tap.T[r];
     }
     return PS_OK;
@@ -135,8 +138,10 @@ int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs,
     }
     VitTap tap;
     tap.obs_rows = obs;
-    std::vector<std::vector<std::vector<int>>> pt;
-    PS_TRY(viterbi_device_multi(rt, regs, nkeep, skip, stay, mmin, mmax, &pt, &tap, "ps_debug_viterbi_steps"));
+    VitCall call;
+    call.nkeep = nkeep; call.skip = skip; call.stay = stay; call.mmin = mmin; call.mmax = mmax;
+    call.who = "ps_debug_viterbi_steps"; call.tap = &tap;
+    PS_TRY(viterbi_batch(rt, call, regs.data(), regs.size()));
     if (bp && !tap.bp.empty()) memcpy(bp, tap.bp.data(), tap.bp.size() * sizeof(short));
     if (fwd && !tap.fwd.empty()) memcpy(fwd, tap.fwd.data(), tap.fwd.size() * sizeof(double));
     if (lik_final) memcpy(lik_final, tap.lik_final.data(), (size_t)R * NS * sizeof(double));
@@ -144,8 +149,7 @@ int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs,
         const int np = std::max(nkeep, 1);
         t_off = 0;
         for (int r = 0; r < R; r++) {
-            for (size_t k = 0; k < tap.paths[r].size(); k++)
-                for (int i = 0; i < T[r]; i++) paths[(size_t)np * t_off + k * T[r] + i] = (int16_t)tap.paths[r][k][i];
+            if (!tap.paths[r].empty()) memcpy(paths + (size_t)np * t_off, tap.paths[r].data(), tap.paths[r].size() * sizeof(int16_t));
             t_off += T[r];
         }
     }

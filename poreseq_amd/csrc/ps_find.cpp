@@ -1,6 +1,5 @@
-// ps_find.cpp — FindMutations (cpp/FindMutations.cpp:24-186), MapAlignments (cpp/EventUtil.cpp:12-55),
-// fillinds (cpp/swlib.cpp:342-365) and the host part of ViterbiMutate (cpp/Viterbi.cpp:239-426).
-// The alignments, Smith-Waterman matrices and the Viterbi recursion run on the GPU; what is left
+// ps_find.cpp — FindMutations (cpp/FindMutations.cpp:24-186), MapAlignments (cpp/EventUtil.cpp:12-55) and
+// fillinds (cpp/swlib.cpp:342-365).  The alignments and the Smith-Waterman matrices run on the GPU; what is left
 // here is the reference's list / index bookkeeping.
 #include <algorithm>
 #include <cmath>
@@ -257,224 +256,6 @@ int find_mutations_multi(Runtime* rt, const std::vector<Align*>& as, const std::
 
 int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds, std::vector<Mut>* out) {
     return find_mutations_multi(rt, {a}, {&seeds}, {out});
-}
-
-// ---------------------------------------------------------------------------------------------
-inline int succ(int st, int k, int j) { return ((st << (2 * j)) & (NS - 1)) + k; }   // cpp/Viterbi.h:31-32
-inline char base_at(int st, int k) { return "ACGT"[3 & (st >> (2 * (4 - k)))]; }    // cpp/Viterbi.h:35-39
-
-// StatesToSequence, cpp/Viterbi.cpp:171-237
-static std::string path_to_bases(const std::vector<int>& st) {
-    std::string s;
-    int cur = st[0];
-    s.push_back(base_at(cur, 0));
-    for (size_t i = 1; i < st.size(); i++) {
-        if (cur == st[i]) continue;
-        bool hit = false;
-        for (int n = 1; n <= 4 && !hit; n++)
-            for (int k = 0; k < (1 << (2 * n)); k++)
-                if (succ(cur, k, n) == st[i]) {
-                    for (int b = 1; b <= n; b++) s.push_back(base_at(cur, b));
-                    cur = st[i]; hit = true; break;
-                }
-        if (!hit) { cur = st[i]; s.push_back(base_at(cur, 0)); }
-    }
-    for (int b = 1; b <= 4; b++) s.push_back(base_at(cur, b));
-    return s;
-}
-
-// rand() of a fresh process, per region: glibc's reentrant random_r() on a 128-byte TYPE_3 state is the generator behind
-// rand() minus the process-wide lock.  A state is either the calling thread's (ps_srand / ps_rand_draw, the single-handle
-// ABI) or an explicit ps_rng object that a lock-step driver keeps per region (include/poreseq_hip.h).
-struct RandState {
-    random_data rd;
-    char st[128];
-    bool init = false;
-};
-namespace { thread_local RandState t_rand; }
-static void rs_seed(RandState* r, unsigned seed) {
-    memset(&r->rd, 0, sizeof(r->rd));
-    initstate_r(seed, r->st, sizeof(r->st), &r->rd);
-    r->init = true;
-}
-static int rs_next(RandState* r) {
-    if (!r->init) rs_seed(r, 1);
-    int32_t v = 0;
-    random_r(&r->rd, &v);
-    return (int)v;
-}
-void rand_seed(unsigned seed) { rs_seed(&t_rand, seed); }
-int rand_next() { return rs_next(&t_rand); }
-RandState* rand_state_new(unsigned seed) { RandState* r = new RandState(); rs_seed(r, seed); return r; }
-void rand_state_free(RandState* r) { delete r; }
-void rand_state_seed(RandState* r, unsigned seed) { rs_seed(r, seed); }
-int rand_state_next(RandState* r) { return rs_next(r ? r : &t_rand); }
-
-namespace {
-// host part of ViterbiMutate for one AlignData: which reference positions are kept and the mean level per (position, event)
-struct VitGather { std::vector<double> obsin; int T = 0; };
-}  // namespace
-
-// The walk runs from the smallest refstart to the largest refend, both (int)ref_align of an aligned level (cpp/EventData.h:135-136):
-// an entry that is not below 2^31, +inf included, has no defined conversion and would send vit_gather towards 2^31 — refused, naming
-// the event and the level (region < 0: not a lock-step call).  The DP and the census take any double (include/poreseq_hip.h).
-static int vit_refuses_refs(const Align& a, const char* who, int region) {
-    for (int e = 0; e < a.E; e++) {
-        const double* ra = a.h_ra.data() + a.off[e];
-        for (int t = 0; t < a.n[e]; t++)
-            if (ra[t] >= 2147483648.0) {
-                char val[64];
-                snprintf(val, sizeof(val), "%g", ra[t]);
-                return fail(PS_ERR_BAD_ARG, std::string(who) + ": " + (region >= 0 ? "region " + std::to_string(region) + ": " : std::string()) + "event " + std::to_string(e) +
-                                                ", level " + std::to_string(t) + ": ref_align = " + val + " is not below 2^31 (ViterbiMutate walks the positions from (int)ref_align)");
-            }
-    }
-    return PS_OK;
-}
-
-static void vit_gather(const Align* a, const double* h_ri, const JobOut* info, VitGather* g) {
-    const int E = a->E;
-    // first level whose ref_index equals an integer position (std::find in getrefstates, cpp/EventData.h:192),
-    // as a flat table per event indexed by position + 1 (positions outside [-1, maxpos] never match)
-    // (extrapolated ref_index values past refend can be integers too and do take part, so the table
-    // spans every integer-valued entry).  The table starts at position -1: a read without an aligned level has refstart = -1, the
-    // walk then begins there, and std::find meets the -1 markers that an un-interpolated hole keeps (behind an aligned level 0,
-    // cpp/EventData.h:157) or a head that the line through the end levels crosses at -1; no position lies below -1.
-    int maxpos = 0;
-    for (int e = 0; e < E; e++) {
-        if (!info[e].has_index) continue;
-        const double* ri = h_ri + a->off[e];
-        for (int t = 0; t < a->n[e]; t++) {
-            const double v = ri[t];
-            if (v >= 0.0 && v < 1e9 && v == std::floor(v)) maxpos = std::max(maxpos, (int)v);
-        }
-    }
-    std::vector<std::vector<int>> first(E);
-    for (int e = 0; e < E; e++) {
-        if (!info[e].has_index) continue;  // empty ref_index: getrefstates finds nothing
-        first[e].assign((size_t)maxpos + 2, -1);
-        const double* ri = h_ri + a->off[e];
-        for (int t = 0; t < a->n[e]; t++) {
-            const double v = ri[t];
-            if (v >= -1.0 && v <= (double)maxpos && v == std::floor(v)) {
-                int& slot = first[e][(size_t)((int)v + 1)];
-                if (slot < 0) slot = t;
-            }
-        }
-    }
-    auto rstart = [&](int e) { return info[e].has_index ? info[e].refstart : -1; };
-    auto rend = [&](int e) { return info[e].has_index ? info[e].refend : -1; };
-    int refind = rstart(0);
-    for (int e = 0; e < E; e++) refind = std::min(refind, rstart(e));
-    std::vector<double>& obsin = g->obsin;
-    int T = 0;
-    while (true) {
-        int nl = 0, nal = 0;
-        const size_t at = obsin.size();
-        obsin.resize(at + (size_t)E * 4, 0.0);
-        for (int e = 0; e < E; e++) {
-            if (refind < -1 || refind > maxpos || first[e].empty() || first[e][refind + 1] < 0) continue;
-            const double* ra = a->h_ra.data() + a->off[e];
-            const double* mean = a->h_mean.data() + a->off[e];
-            const double* stdv = a->h_stdv.data() + a->off[e];
-            int t = first[e][refind + 1], cnt = 1;
-            // getrefstates keeps following levels while ref_align <= refind, using those > 0 (cpp/EventData.h:197-201)
-            double lsum = 0, ssum = 0;
-            lsum += mean[t]; ssum += stdv[t];
-            for (t++; t < a->n[e] && ra[t] <= refind; t++)
-                if (ra[t] > 0) { lsum += mean[t]; ssum += stdv[t]; cnt++; }
-            const double lvl = lsum / cnt, sd = ssum / cnt;
-            nl++;
-            double* o = obsin.data() + at + (size_t)e * 4;
-            o[0] = lvl; o[1] = sd; o[2] = std::log(sd); o[3] = 1.0;
-        }
-        for (int e = 0; e < E; e++) if (refind >= rstart(e) && refind <= rend(e)) nal++;
-        if (nl <= nal * 0.2) {
-            obsin.resize(at);
-            if (nal == 0) break;
-            refind++;
-            continue;
-        }
-        T++;
-        refind++;
-    }
-    g->T = T;
-}
-
-// uniform deviates in the reference's call order: for each kept path, one per back-step (cpp/Viterbi.cpp:108)
-static void vit_draw(void* rng, double* rnd, size_t n) {
-    RandState* r = (RandState*)rng;
-    for (size_t k = 0; k < n; k++) rnd[k] = rand_state_next(r) / (double(RAND_MAX) + 1);
-}
-
-// ViterbiMutate (cpp/Viterbi.cpp:239-426) for several AlignData in lock-step; rngs[r] = the region's generator (nullptr: the
-// calling thread's); tap: the device tables for ps_debug_viterbi (ps_internal.h), a null pointer otherwise
-int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
-                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap, const char* who, bool lockstep) {
-    Tick tk("viterbi_mutate");
-    const int R = (int)as.size();
-    for (int r = 0; r < R; r++) outs[r]->clear();
-    // host mirrors of ref_align / ref_index / refstart / refend
-    std::vector<double*> h_ri(R, nullptr);
-    std::vector<JobOut*> info(R, nullptr);
-    for (int r = 0; r < R; r++) {
-        PS_TRY(as[r]->refs_to_host_async(rt));
-        as[r]->last_stream = (void*)rt->stream;
-        PS_TRY(rt->down(&h_ri[r], as[r]->d_ri, (size_t)as[r]->ntot));
-        PS_TRY(rt->down(&info[r], as[r]->d_out, (size_t)as[r]->E));
-    }
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    for (int r = 0; r < R; r++) as[r]->refs_finish();
-    tk.lap("refs D2H");
-    for (int r = 0; r < R; r++) PS_TRY(vit_refuses_refs(*as[r], who, lockstep ? r : -1));   // on the host copy, before any kernel of the call
-    std::vector<VitGather> gath(R);
-    par_for(R, [&](int r) { vit_gather(as[r], h_ri[r], info[r], &gath[r]); });
-    tk.lap("gather levels");
-    std::vector<VitRegionH> regs(R);
-    for (int r = 0; r < R; r++) {
-        regs[r].E = as[r]->E; regs[r].T = gath[r].T; regs[r].obsin = gath[r].obsin.data(); regs[r].d_model = as[r]->d_model;
-        as[r]->last_stream = (void*)rt->stream;   // (the Viterbi kernels read the model tables in the AlignData's slab)
-        regs[r].rng = rngs[r]; regs[r].draw = vit_draw;
-        regs[r].index = lockstep ? r : -1;
-    }
-    std::vector<std::vector<std::vector<int>>> paths;
-    {
-        // sub-batches of regions that fit this runtime's device share (obs, trimmed means, back-pointers and forward
-        // probabilities: 26 KB per position; ~270 MB per 10 kb region); the regions' generators keep the results the same however
-        // the batch is cut; a sub-batch the device has no memory for is cut in two
-        auto need = [&](size_t k) { return 26.0 * 1024.0 * (double)regs[k].T + 32.0 * (double)regs[k].T * regs[k].E; };
-        double cap = std::max(1e9, PLAN_VITERBI_FRAC * device_share_bytes());   // (the tables live in the runtime's matrix pool, which no alignment uses during this call)
-        for (size_t k0 = 0; k0 < regs.size();) {
-            size_t k1 = k0;
-            double acc = 0;
-            for (; k1 < regs.size(); k1++) { const double add = need(k1); if (k1 > k0 && acc + add > cap) break; acc += add; }
-            std::vector<std::vector<std::vector<int>>> part;
-            const int rc = viterbi_device_multi(rt, std::vector<VitRegionH>(regs.begin() + k0, regs.begin() + k1), nkeep, skip, stay, mmin, mmax, &part, tap, who);
-            if (rc == PS_ERR_NOMEM && k1 - k0 > 1) { cap *= 0.5; continue; }   // (nothing of this sub-batch has been drawn yet: allocation comes first)
-            PS_TRY(rc);
-            for (auto& pr : part) paths.push_back(std::move(pr));
-            k0 = k1;
-        }
-    }
-    tk.lap("device");
-    par_for(R, [&](int r) { for (auto& p : paths[r]) outs[r]->push_back(path_to_bases(p)); });
-    tk.lap("paths to bases");
-    return PS_OK;
-}
-
-int viterbi_mutate(Runtime* rt, Align* a, int nkeep, double skip, double stay, double mmin, double mmax,
-                   std::vector<std::string>* out, bool verbose) {
-    const int rc = viterbi_mutate_multi(rt, {a}, {nullptr}, nkeep, skip, stay, mmin, mmax, {out}, nullptr, "ps_viterbi_mutate", false);
-    if (verbose && rc == PS_OK) {
-        // the reference's progress line (cpp/Viterbi.cpp:258-259, 357-370): "Viterbi", a dot whenever the reference position passes a
-        // multiple of 200, a newline.  The positions walked: from the first event's start to where no event is aligned any more —
-        // counted here from the sequence length (the walk itself runs on the device)
-        fputs("Viterbi", stderr);
-        for (size_t k = 200; k <= a->bases.size(); k += 200) fputc('.', stderr);
-        fputc('\n', stderr);
-        fflush(stderr);
-    }
-    return rc;
 }
 
 }  // namespace ps

@@ -2,7 +2,7 @@
 // runs for a batch, in which form), what a lock-step call may take of the device (guess_slots, share_need, share_cap), and
 // MakeMutations (cpp/MakeMutations.cpp).  struct Align — AlignData — is in ps_align.cpp; ScoreAlignments and the two statistics
 // calls, one chain over the events' own sequences, in ps_own.cpp; ScoreMutations and its reductions — the edit-scoring chain — in
-// ps_score.cpp, the edit plans in ps_editplan.h, FindMutations in ps_find.cpp.  The runtime, its streams and par_for
+// ps_score.cpp, the edit plans in ps_editplan.h, FindMutations in ps_find.cpp, ViterbiMutate's host chain in ps_vit.cpp.  The runtime, its streams and par_for
 // are in ps_runtime.cpp; device memory — pools, shares, slabs, the AlignData slab cache — in ps_mem.cpp, its arithmetic in ps_plan.h.
 // All dynamic-programming arithmetic runs in the HIP kernels (ps_kernels.hip, ps_edit.hip, ps_sw.hip,
 // ps_viterbi.hip); there is no CPU implementation of it in this library.

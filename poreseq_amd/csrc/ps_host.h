@@ -19,7 +19,7 @@ struct Tick {
 
 struct Align;
 
-void rand_seed(unsigned seed);   // per-thread generator of ViterbiMutate's deviates (ps_find.cpp)
+void rand_seed(unsigned seed);   // per-thread generator of ViterbiMutate's deviates (ps_vit.cpp)
 int rand_next();
 struct RandState;                // an explicit generator state (one per region of a lock-step driver)
 RandState* rand_state_new(unsigned seed);
@@ -162,9 +162,6 @@ int gather_best(Runtime* rt, const Batch& b, double** best);   // the jobs' maxi
 // accuracy[r][s] = swalign's identity in % (may be nullptr); no AlignData is modified (ps_variant.hip)
 int score_sequences_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<const std::vector<std::string>*>& seqs,
                           const std::vector<double*>& scores, const std::vector<double*>& accuracy);
-int viterbi_mutate_multi(Runtime* rt, const std::vector<Align*>& as, const std::vector<RandState*>& rngs, int nkeep, double skip, double stay,
-                         double mmin, double mmax, const std::vector<std::vector<std::string>*>& outs, VitTap* tap = nullptr, const char* who = "ps_batch_viterbi_mutate", bool lockstep = true);
-// (who, lockstep: the entry point, and whether a region index, that a refusal of the deterministic back-trace names)
 std::string info_string();   // process-wide state in one line (ps_info)
 struct MemInfo { size_t slabs = 0, slab_bytes = 0; int slabs_planned = 0; long long pool_bytes = 0; };
 MemInfo mem_info();          // ps_mem.cpp's part of it: slabs allocated (and their bytes) of how many, bytes in the pools of this process
@@ -253,13 +250,32 @@ int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::ve
 void find_point_mutations(const Align* a, std::vector<Mut>* out);
 int make_mutations(Runtime* rt, Align* a, std::vector<Mut> muts, int* nbases);
 int find_mutations(Runtime* rt, Align* a, const std::vector<std::string>& seeds, std::vector<Mut>* out);
-int viterbi_mutate(Runtime* rt, Align* a, int nkeep, double skip, double stay, double mmin, double mmax,
-                   std::vector<std::string>* out, bool verbose = false);
+// One ViterbiMutate call (ps_vit.cpp): its arguments, the entry point and whether a refusal names a region index (a lock-step
+// call), and the table tap of the test hooks (ps_internal.h), null in production
+struct VitCall {
+    int nkeep = 0;
+    double skip = 0.0, stay = 0.0, mmin = 0.0, mmax = 0.0;
+    const char* who = "ps_batch_viterbi_mutate";
+    bool lockstep = true;
+    VitTap* tap = nullptr;
+};
+// and one AlignData of it: its handle, its generator (null: the calling thread's) and where its sequences go.  A lock-step call is an
+// array of these.
+struct VitReq {
+    Align* a = nullptr;
+    RandState* rng = nullptr;
+    std::vector<std::string>* out = nullptr;
+};
+// ViterbiMutate (cpp/Viterbi.cpp:239-426) for reqs[0 .. n - 1] in as few launch chains as the share allows (rt: null, the runtime is
+// taken once the arguments are checked)
+int viterbi_mutate(Runtime* rt, const VitCall& call, VitReq* reqs, size_t n);
+// one sub-batch of it on the device: regs[0 .. n - 1] through emissions, steps and back-traces into their `paths`
+int viterbi_batch(Runtime* rt, const VitCall& call, VitRegionH* regs, size_t n);
 int debug_fill(Runtime* rt, Align* a, int ev, int dir, double* main, double* stay, uint8_t* sm, uint8_t* ss);
 // ps_debug_poison (ps_mem.cpp): overwrites the scratch memory the calling thread's next call could find left over (ps_poison.h)
 int debug_poison(Runtime* rt, uint32_t index_word, uint64_t value_word, ps_poison_report* rep, int32_t cap, int32_t* n_rep);
 // ps_debug_viterbi / ps_debug_viterbi_steps (include/poreseq_hip.h): the tables of a ViterbiMutate call
-int debug_viterbi(Runtime* rt, const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
+int debug_viterbi(const std::vector<Align*>& as, int build, int nkeep, double skip, double stay, double mmin, double mmax,
                   int64_t cap_T, int32_t* T, double* obs, int16_t* bp, double* lik_final, double* fwd, int16_t* paths);
 int debug_viterbi_steps(Runtime* rt, int R, const int32_t* T, const double* obs, const double* rnd, int nkeep, double skip, double stay,
                         double mmin, double mmax, int16_t* bp, double* lik_final, double* fwd, int16_t* paths);

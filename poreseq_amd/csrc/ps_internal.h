@@ -358,7 +358,14 @@ int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* sc
               std::vector<int>* inds1, std::vector<int>* inds2);
 void sw_band_counters(int64_t out[5]);   // band mode: pairs banded, fell back, maxima near a band edge, band cells, full-matrix cells
 
-// Viterbi (ps_viterbi.hip): one region of a batched ViterbiMutate call, host side
+// Viterbi (kernels and launchers: ps_viterbi.hip, the chain: ps_vit.cpp).  One region (AlignData) of a sub-batch as the kernels see it
+struct VitReg {
+    const double* model;   // [E][6][1024]
+    int E, T;              // events, reference positions kept
+    int64_t in_off;        // into obsin (doubles)
+    int64_t t_off;         // first position of the region in obs / eobs / bp / lfwd (rows of 1024)
+};
+// and on the host: what the chain reads of it and where its paths go.  A call is one array of these, a sub-batch a sub-range of it.
 struct VitRegionH {
     int E = 0, T = 0;
     int index = -1;                      // of the region in the caller's lock-step batch, named in a refusal (-1: not a batch)
@@ -366,10 +373,11 @@ struct VitRegionH {
     const double* d_model = nullptr;     // device, [E][6][1024]
     void* rng = nullptr;                 // the region's generator state, handed to draw()
     void (*draw)(void* rng, double* out /*[nkeep][T]*/, size_t n) = nullptr;
+    std::vector<int16_t> paths;          // out: [max(nkeep, 1)][T] states; empty for a region without positions
 };
-// Table tap of viterbi_device_multi for the test hooks ps_debug_viterbi / ps_debug_viterbi_steps (ps_debug.cpp): a null pointer in
+// Table tap of viterbi_batch for the test hooks ps_debug_viterbi / ps_debug_viterbi_steps (ps_debug.cpp): a null pointer in
 // production.  The same launches, grids and buffers run whether it is set or not; with a tap the tables are also copied to the
-// host.  Results are appended (viterbi_mutate_multi may cut a batch into several device calls), regions in batch order.
+// host.  Results are appended (viterbi_mutate may cut a batch into several sub-batches), regions in batch order.
 struct VitTap {
     int obs_build = 0;                  // in: emission build: 0 the library's choice, 1 k_vit_obs_lds, 2 k_vit_obs<64>, 3 k_vit_obs<256>
     const double* obs_rows = nullptr;   // in: [sum T][1024] emission rows from the caller; the emission kernel is skipped, exp(obs) is formed on the host
@@ -378,11 +386,16 @@ struct VitTap {
     std::vector<short> bp;              // [sum T][1024]
     std::vector<double> lik_final;      // [regions][1024]
     std::vector<double> fwd;            // [sum T][1024] as k_vit_steps wrote it, before k_vit_log (nkeep > 0 only: no forward table otherwise)
-    std::vector<std::vector<std::vector<int>>> paths;   // per region [nkeep or 1][T] states
+    std::vector<std::vector<int16_t>> paths;   // per region [nkeep or 1][T] states, as VitRegionH.paths
 };
-int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, int nkeep, double skip, double stay, double mmin, double mmax,
-                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap = nullptr, const char* who = "ViterbiMutate");
-// (who: the entry point a refusal of the deterministic back-trace names, ps_vitpath.h)
+bool vit_obs_lds_ok();   // k_vit_obs_lds can have its dynamic LDS (asked once per process)
+// emission build 1 k_vit_obs_lds | 2 k_vit_obs<64> | 3 k_vit_obs<256> over ttot positions (counted in the profile as vit_obs_lds / vit_obs_64 / vit_obs_256)
+void launch_vit_obs(Runtime* rt, int build, const VitReg* d_regs, const int* d_posreg, const double* d_in, int64_t ttot, int maxE, double* d_obs, double* d_eobs);
+int launch_vit_steps(Runtime* rt, const VitReg* d_regs, int R, const double* d_obs, const double* d_eobs, double skip, double stay, short* d_bp, double* d_fwd,
+                     double* d_lik, bool keep_fwd);
+// k_vit_log over the forward table, then k_vit_trace: nkeep back-traces per region
+int launch_vit_trace(Runtime* rt, const VitReg* d_regs, int R, int64_t ttot, int nkeep, double* d_fwd, const int* d_start, double skip, double stay,
+                     const double* d_att, const double* d_rnd, short* d_path);
 
 void prof_flush(Runtime* rt);   // deferred mode: read the queued event pairs (drains the stream)
 void prof_begin(Runtime* rt);

@@ -1,5 +1,5 @@
 // ps_plan.h — the arithmetic of the device-memory plan: pure, host-only, no HIP include.  Shared by the library (ps_mem.cpp decides
-// with it, ps_host.cpp, ps_own.cpp and ps_fwd.cpp size their batches with it) and by a host test of it (tests/native/plan_check.cpp).
+// with it, ps_host.cpp, ps_own.cpp, ps_fwd.cpp and ps_vit.cpp size their batches with it) and by a host test of it (tests/native/plan_check.cpp).
 //
 // The plan (309 GB on an MI355X, or this process's fraction of it):
 //   27 %  three slabs of 9 % each for the full forward + backward score matrices of dense ScoreMutations calls
@@ -30,6 +30,7 @@ constexpr int PLAN_MIN_RUNTIMES = 4;          // the device is divided by at lea
 constexpr double PLAN_OVER_GUESS = 1.2;       // realign()'s cap for a batch sized on a guess: the real matrices may come out a fifth over the share
 constexpr int PLAN_SW_PART = 8;               // Smith-Waterman checkpoints: at most an eighth of the share per launch
 constexpr double PLAN_VITERBI_FRAC = 0.9;     // Viterbi tables: all of the matrix pool but a tenth (no alignment uses it during that call)
+constexpr double PLAN_VITERBI_FLOOR = 1e9;    // ... and no sub-batch of them is cut below this, however small the share
 
 // ---- ceilings of the pools' sum (all runtimes + slabs), of this process's part of the device ----------------------------------
 constexpr double PLAN_POOL_CEILING = 0.94;    // no buffer grows into the last 6 %: PS_ERR_NOMEM instead of the HSA runtime's abort

@@ -73,7 +73,7 @@ constexpr PoisonEntry POISON_TABLE[] = {
     // alignment census and k-mer statistics (ps_own.cpp)
     {"astats_in", PoisonClass::INDEX, "StatJob / StatRegion: pointers and sizes"},
     {"astats", PoisonClass::INDEX, "ps_event_stats and ps_kmer_cell carry counts"},
-    // Viterbi (ps_viterbi.hip)
+    // Viterbi (placed by viterbi_batch, ps_vit.cpp; the kernels: ps_viterbi.hip)
     {"vit_regs", PoisonClass::INDEX, "VitReg: pointers, sizes, offsets"},
     {"vit_posreg", PoisonClass::INDEX, "region of every position"},
     {"vit_in", PoisonClass::INDEX, "the fourth double of every record is the `present` flag"},

@@ -1,8 +1,12 @@
-// ps_viterbi.hip — the 1024-state consensus Viterbi of ViterbiMutate (cpp/Viterbi.cpp:239-426).
+// ps_viterbi.hip — the 1024-state consensus Viterbi of ViterbiMutate (cpp/Viterbi.cpp:239-426): the kernels and their
+// launchers.  The chain that calls them — sizes, pools, uploads, deviates, the two tails — is ps_vit.cpp.
 //
 //   k_vit_obs    per reference position: emissions of all 1024 5-mers for every contributing
 //                event, ascending sort across events, drop the lowest quarter, mean
-//                (cpp/Viterbi.cpp:272-349) — chip-wide, one block per position.
+//                (cpp/Viterbi.cpp:272-349) — chip-wide, one block per position.  k_vit_obs<64> and
+//                k_vit_obs<256> sort in a private array, k_vit_obs_lds in a column of LDS: one body
+//                written twice, because the compiler schedules a shared body differently from either
+//                (profiles/viterbi_chain.md).
 //   k_vit_steps  the sequential part (V_LIK::V_LIK, cpp/Viterbi.cpp:39-102): one 1024-lane
 //                workgroup, state vectors double-buffered in LDS.  The 4 + 16 + 64 predecessors
 //                of a destination state depend only on its low bits, so the per-family maximum,
@@ -10,6 +14,7 @@
 //                (336 families) instead of once per state.  The first-strict-maximum rule of the
 //                reference is kept exactly: a destination state falls back to the plain ordered scan in
 //                the (sub-ulp) case where a value just below the family maximum would round to the same sum.
+//   k_vit_log    the forward vectors to their logarithms in place, chip-wide, ahead of the back-traces.
 //   k_vit_trace  nkeep stochastic back-traces (randbp, cpp/Viterbi.cpp:105-131), one block each;
 //                the uniform deviates are drawn on the host from libc rand() in the reference's
 //                call order.
@@ -20,7 +25,6 @@
 #include <atomic>
 
 #include "ps_internal.h"
-#include "ps_vitpath.h"
 
 namespace ps {
 
@@ -32,14 +36,6 @@ __device__ __forceinline__ double emission_v(const ModelRowV& m, double x, doubl
     l += 0.5 * (m.llam - 3 * lsd - log2pi - e * e * m.lam / sd);
     return l;
 }
-
-// one region (AlignData) of a batched ViterbiMutate call
-struct VitReg {
-    const double* model;   // [E][6][1024]
-    int E, T;              // events, reference positions kept
-    int64_t in_off;        // into obsin (doubles)
-    int64_t t_off;         // first position of the region in obs / eobs / bp / lfwd (rows of 1024)
-};
 
 // obsin[t][e][4] = {level mean, sd mean, log(sd mean), present}; obs[t][1024].  VMAXE = events one thread can sort in its
 // private array: 64 covers the reference's max_coverage of 30 reads (60 events); 256 is the slow build for deeper stacks
@@ -415,160 +411,45 @@ __global__ __launch_bounds__(VT_THREADS) void k_vit_trace(const VitReg* __restri
     }
 }
 
-int viterbi_device_multi(Runtime* rt, const std::vector<VitRegionH>& regions, int nkeep, double skip, double stay, double mmin, double mmax,
-                         std::vector<std::vector<std::vector<int>>>* paths, VitTap* tap, const char* who) {
-    const int R = (int)regions.size();
-    paths->assign(R, {});
-    std::vector<VitReg> regs(R);
-    int64_t ttot = 0, intot = 0;
-    int maxE = 0;
-    for (int r = 0; r < R; r++) {
-        regs[r].model = regions[r].d_model; regs[r].E = regions[r].E; regs[r].T = regions[r].T;
-        regs[r].in_off = intot; regs[r].t_off = ttot;
-        intot += (int64_t)regions[r].T * regions[r].E * 4; ttot += regions[r].T;
-        maxE = std::max(maxE, regions[r].E);
+// ---- launchers: the chain that calls them is viterbi_batch (ps_vit.cpp), which also holds the profile's "viterbi" bracket ----
+
+// The LDS column sort needs 144 KB of dynamic LDS at 72 events: whether the attribute can be had, asked once per process.  When
+// it cannot, the private-array kernels serve.
+bool vit_obs_lds_ok() {
+    static std::atomic<int> attr(0);   // 0: untried, 1: granted, -1: refused
+    if (attr.load(std::memory_order_acquire) == 0) {
+        const hipError_t e = hipFuncSetAttribute((const void*)k_vit_obs_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) (void)hipGetLastError();
+        attr.store(e == hipSuccess ? 1 : -1, std::memory_order_release);
     }
-    if (tap)
-        for (int r = 0; r < R; r++) { tap->T.push_back(regions[r].T); tap->paths.emplace_back(); tap->lik_final.insert(tap->lik_final.end(), NS, 0.0); }
-    if (ttot <= 0) return PS_OK;
-    if (maxE > 256) return fail(PS_ERR_UNSUPPORTED, "ViterbiMutate: more than 256 events");
-    std::vector<int> pos_reg((size_t)ttot);
-    for (int r = 0; r < R; r++) std::fill(pos_reg.begin() + regs[r].t_off, pos_reg.begin() + regs[r].t_off + regs[r].T, r);
-    PS_TRY(rt->buf("vit_regs").ensure(R * sizeof(VitReg)));
-    PS_TRY(rt->buf("vit_posreg").ensure((size_t)ttot * sizeof(int)));
-    PS_TRY(rt->buf("vit_in").ensure((size_t)std::max<int64_t>(intot, 1) * sizeof(double)));
-    // The position x state tables (8 KB per position and table: 5.3 GB for 20 regions of 10 kb) live in the score-matrix pool: no
-    // alignment is in flight during a ViterbiMutate call, and a runtime that kept them beside the matrices would hold ~2 % of an
-    // MI355X for a phase that is 4 % of a schedule (seven runtimes: 38 GB that the matrices of the other phases can use).
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_obs = al((size_t)ttot * NS * sizeof(double)), b_fwd = al((size_t)(nkeep ? ttot : 1) * NS * sizeof(double)),
-                 b_bp = al((size_t)ttot * NS * sizeof(short));
-    DBuf& arena = rt->buf("rec");
-    PS_TRY(arena.ensure(2 * b_obs + b_fwd + b_bp));
-    PS_TRY(rt->buf("vit_lik").ensure((size_t)R * NS * sizeof(double)));
-    if (nkeep > 0) {   // every allocation of the call before the first deviate is drawn: a caller may cut the batch again on PS_ERR_NOMEM
-        PS_TRY(rt->buf("vit_att").ensure(nkeep * sizeof(double)));
-        PS_TRY(rt->buf("vit_start").ensure(R * sizeof(int)));
-        PS_TRY(rt->buf("vit_rnd").ensure((size_t)nkeep * ttot * sizeof(double)));
-        PS_TRY(rt->buf("vit_path").ensure((size_t)nkeep * ttot * sizeof(short)));
-    }
-    VitReg* d_regs = rt->buf("vit_regs").as<VitReg>();
-    int* d_posreg = rt->buf("vit_posreg").as<int>();
-    double* d_in = rt->buf("vit_in").as<double>();
-    char* abase = (char*)arena.p;
-    double* d_obs = (double*)abase;
-    double* d_eobs = (double*)(abase + b_obs);
-    double* d_fwd = (double*)(abase + 2 * b_obs);
-    short* d_bp = (short*)(abase + 2 * b_obs + b_fwd);
-    double* d_lik = rt->buf("vit_lik").as<double>();
-    PS_TRY(rt->up(d_regs, regs.data(), R * sizeof(VitReg)));
-    PS_TRY(rt->up(d_posreg, pos_reg.data(), (size_t)ttot * sizeof(int)));
-    for (int r = 0; r < R; r++)
-        if (regions[r].T && regions[r].E) PS_TRY(rt->up(d_in + regs[r].in_off, regions[r].obsin, (size_t)regions[r].T * regions[r].E * 4 * sizeof(double)));
-    bool lds_ok = false;
-    if (maxE <= 72) {   // the LDS column sort needs 144 KB of dynamic LDS at 72 events: when the attribute cannot be had, the register / scratch kernels below serve
-        static std::atomic<int> attr(0);   // 0: untried, 1: granted, -1: refused
-        if (attr.load(std::memory_order_acquire) == 0) {
-            const hipError_t e = hipFuncSetAttribute((const void*)k_vit_obs_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) (void)hipGetLastError();
-            attr.store(e == hipSuccess ? 1 : -1, std::memory_order_release);
-        }
-        lds_ok = attr.load(std::memory_order_acquire) == 1;
-    }
-    // emission build: 1 k_vit_obs_lds, 2 k_vit_obs<64>, 3 k_vit_obs<256>; a tap may ask for one that admits the batch's events
-    int build = lds_ok ? 1 : maxE <= 64 ? 2 : 3;
-    if (tap && tap->obs_build) {
-        build = tap->obs_build;
-        if (build < 1 || build > 3 || (build == 1 && !lds_ok) || (build == 2 && maxE > 64))
-            return fail(PS_ERR_BAD_ARG, "ViterbiMutate: the emission build asked for does not take this many events");
-    }
-    prof_begin(rt);
-    if (rt->prof_on && !(tap && tap->obs_rows)) rt->prof[build == 1 ? "vit_obs_lds" : (build == 2 ? "vit_obs_64" : "vit_obs_256")].launches++;   // (which emission build ran: a host-side count, no event pair)
-    if (tap && tap->obs_rows) {   // rows from the caller instead of the emission kernel (ps_debug_viterbi_steps)
-        std::vector<double> eo((size_t)ttot * NS);
-        for (size_t k = 0; k < eo.size(); k++) eo[k] = std::exp(tap->obs_rows[k]);
-        PS_TRY(rt->up(d_obs, tap->obs_rows, eo.size() * sizeof(double)));
-        PS_TRY(rt->up(d_eobs, eo.data(), eo.size() * sizeof(double)));
-    } else if (build == 1)
+    return attr.load(std::memory_order_acquire) == 1;
+}
+
+// emission build: 1 k_vit_obs_lds, 2 k_vit_obs<64>, 3 k_vit_obs<256>; grid: the ttot positions of the sub-batch
+void launch_vit_obs(Runtime* rt, int build, const VitReg* d_regs, const int* d_posreg, const double* d_in, int64_t ttot, int maxE, double* d_obs, double* d_eobs) {
+    if (rt->prof_on) rt->prof[build == 1 ? "vit_obs_lds" : (build == 2 ? "vit_obs_64" : "vit_obs_256")].launches++;   // (which emission build ran: a host-side count, no event pair)
+    if (build == 1)
         hipLaunchKernelGGL(k_vit_obs_lds, dim3((unsigned)ttot), dim3(256), (size_t)256 * std::max(maxE, 1) * sizeof(double), rt->stream, d_regs, d_posreg, d_in,
                            std::log(2 * M_PI), d_obs, d_eobs);
     else if (build == 2) hipLaunchKernelGGL(k_vit_obs<64>, dim3((unsigned)ttot), dim3(256), 0, rt->stream, d_regs, d_posreg, d_in, std::log(2 * M_PI), d_obs, d_eobs);
     else hipLaunchKernelGGL(k_vit_obs<256>, dim3((unsigned)ttot), dim3(256), 0, rt->stream, d_regs, d_posreg, d_in, std::log(2 * M_PI), d_obs, d_eobs);
+}
+
+// the recursion, one workgroup per region; checks this launch and the emission build's before it
+int launch_vit_steps(Runtime* rt, const VitReg* d_regs, int R, const double* d_obs, const double* d_eobs, double skip, double stay, short* d_bp, double* d_fwd,
+                     double* d_lik, bool keep_fwd) {
     hipLaunchKernelGGL(k_vit_steps, dim3(R), dim3(1024), 0, rt->stream, d_regs, d_obs, d_eobs, skip, stay, std::log(skip), std::log(stay),
-                       std::log(0.25), d_bp, d_fwd, d_lik, nkeep ? 1 : 0);
+                       std::log(0.25), d_bp, d_fwd, d_lik, keep_fwd ? 1 : 0);
     PS_LAUNCH_CHECK();
-    double* lik = nullptr;
-    PS_TRY(rt->down(&lik, d_lik, (size_t)R * NS));
-    double *tap_obs = nullptr, *tap_fwd = nullptr;
-    short* tap_bp = nullptr;
-    if (tap) {   // the tables as the kernels left them: the forward vectors before k_vit_log overwrites them
-        PS_TRY(rt->down(&tap_obs, d_obs, (size_t)ttot * NS));
-        PS_TRY(rt->down(&tap_bp, d_bp, (size_t)ttot * NS));
-        if (nkeep > 0) PS_TRY(rt->down(&tap_fwd, d_fwd, (size_t)ttot * NS));
-    }
-    // the uniform deviates of the stochastic back-traces are drawn on the host while the recursion runs: per region in the
-    // reference's call order (for each kept path, one per back-step, cpp/Viterbi.cpp:108) from the region's own generator
-    double* h_rand = nullptr;
-    if (nkeep > 0) {
-        h_rand = (double*)rt->stage.alloc((size_t)nkeep * ttot * sizeof(double));
-        if (!h_rand) return fail(PS_ERR_NOMEM, "hipHostMalloc (staging arena)");
-        for (int r = 0; r < R; r++) regions[r].draw(regions[r].rng, h_rand + (size_t)nkeep * regs[r].t_off, (size_t)nkeep * regions[r].T);
-    }
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    if (tap) {
-        tap->obs.insert(tap->obs.end(), tap_obs, tap_obs + (size_t)ttot * NS);
-        tap->bp.insert(tap->bp.end(), tap_bp, tap_bp + (size_t)ttot * NS);
-        if (tap_fwd) tap->fwd.insert(tap->fwd.end(), tap_fwd, tap_fwd + (size_t)ttot * NS);
-        for (int r = 0; r < R; r++)   // (a region without positions keeps its zeros: k_vit_steps writes nothing for it)
-            if (regions[r].T) std::copy(lik + (size_t)r * NS, lik + (size_t)(r + 1) * NS, tap->lik_final.end() - (size_t)(R - r) * NS);
-    }
-    std::vector<int> starts(R, 0);
-    for (int r = 0; r < R; r++) starts[r] = (int)(std::max_element(lik + (size_t)r * NS, lik + (size_t)(r + 1) * NS) - (lik + (size_t)r * NS));
-    if (nkeep == 0) {
-        short* bp = nullptr;
-        PS_TRY(rt->down(&bp, d_bp, (size_t)ttot * NS));
-        PS_HIP(hipStreamSynchronize(rt->stream));
-        prof_end(rt, "viterbi", (double)ttot * NS * (8.0 * maxE + 8 + 2));
-        for (int r = 0; r < R; r++) {
-            if (!regions[r].T) continue;
-            std::vector<int> p(regions[r].T);
-            // a back-pointer of -1 on the path (a dead max-plus row) refuses the whole call
-            const int64_t dead = vit_follow_bp(bp, regs[r].t_off, regions[r].T, NS, starts[r], p.data());
-            if (dead >= 0) {
-                paths->assign(R, {});
-                return fail(PS_ERR_BAD_ARG, std::string(who) + ": " + (regions[r].index >= 0 ? "region " + std::to_string(regions[r].index) + ": " : std::string()) +
-                                                "no state is reachable at kept position " + std::to_string(dead) +
-                                                " (every emission there is -inf or below -1e300, or the running scores have passed -1e300)");
-            }
-            (*paths)[r].push_back(p);
-        }
-        if (tap) std::copy(paths->begin(), paths->end(), tap->paths.end() - R);
-        return PS_OK;
-    }
-    std::vector<double> att(nkeep);
-    for (int k = 0; k < nkeep; k++) att[k] = mmin + (mmax - mmin) * k / (double)nkeep;
-    PS_TRY(rt->up(rt->buf("vit_att").p, att.data(), nkeep * sizeof(double)));
-    PS_TRY(rt->up(rt->buf("vit_start").p, starts.data(), R * sizeof(int)));
-    PS_HIP(hipMemcpyAsync(rt->buf("vit_rnd").p, h_rand, (size_t)nkeep * ttot * sizeof(double), hipMemcpyHostToDevice, rt->stream));
+    return PS_OK;
+}
+
+// the forward table to logarithms in place, then nkeep back-traces per region
+int launch_vit_trace(Runtime* rt, const VitReg* d_regs, int R, int64_t ttot, int nkeep, double* d_fwd, const int* d_start, double skip, double stay,
+                     const double* d_att, const double* d_rnd, short* d_path) {
     hipLaunchKernelGGL(k_vit_log, dim3((unsigned)(((size_t)ttot * NS + 255) / 256)), dim3(256), 0, rt->stream, d_fwd, (size_t)ttot * NS);
-    hipLaunchKernelGGL(k_vit_trace, dim3(nkeep, R), dim3(VT_THREADS), 0, rt->stream, d_regs, d_fwd, rt->buf("vit_start").as<int>(), skip, stay,
-                       rt->buf("vit_att").as<double>(), rt->buf("vit_rnd").as<double>(), rt->buf("vit_path").as<short>());
+    hipLaunchKernelGGL(k_vit_trace, dim3(nkeep, R), dim3(VT_THREADS), 0, rt->stream, d_regs, d_fwd, d_start, skip, stay, d_att, d_rnd, d_path);
     PS_LAUNCH_CHECK();
-    prof_end(rt, "viterbi", (double)ttot * NS * (8.0 * maxE + 8 + 2 + 8 + 8.0 * nkeep));
-    short* hp = nullptr;
-    PS_TRY(rt->down(&hp, rt->buf("vit_path").p, (size_t)nkeep * ttot));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    for (int r = 0; r < R; r++) {
-        const int T = regions[r].T;
-        if (!T) continue;
-        const short* rp = hp + (size_t)nkeep * regs[r].t_off;
-        for (int k = 0; k < nkeep; k++) {
-            std::vector<int> p(T);
-            for (int i = 0; i < T; i++) p[i] = rp[(size_t)k * T + i];
-            (*paths)[r].push_back(p);
-        }
-    }
-    if (tap) std::copy(paths->begin(), paths->end(), tap->paths.end() - R);
     return PS_OK;
 }
 

@@ -1,5 +1,5 @@
 // ps_vitpath.h — the deterministic back-trace of ViterbiMutate (nkeep == 0) over the back-pointer table k_vit_steps leaves behind.
-// Pure host code without a dependency: viterbi_device_multi (ps_viterbi.hip) and tests/native/vitpath_check.cpp both compile it.
+// Pure host code without a dependency: the deterministic tail of viterbi_batch (ps_vit.cpp) and tests/native/vitpath_check.cpp both compile it.
 //
 // The rule ("Finite outliers"): p[T - 1] = start, p[i - 1] = bp[i][p[i]] for i = T - 1 .. 1.  bp[0][.] is
 // never followed, so T = 1 always has a path.  A back-pointer of -1 means that no predecessor of that state scored above -1e300
