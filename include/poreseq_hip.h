@@ -430,6 +430,53 @@ typedef struct ps_event_moves {
 int ps_move_stats(ps_align* a, double* scores /* [E] or NULL */, ps_event_moves* moves /* [E] */,
                   uint8_t* const* step /* [E] of [n_e], or NULL */, int32_t* const* col /* [E] of [n_e], or NULL */);
 
+/* Posterior move counts: the sum over ALL alignments in an event's band, and the expected number of each move under it — where
+ * ps_move_stats counts the moves of the one best path.  No backtrace runs and nothing of the handle changes: ref_align, ref_like,
+ * what ps_align_keep_refs keeps and the host copies stay what they were.
+ *
+ * The lattice is the forward fill's own, for an event on the refs it carries when the call begins:
+ *   columns j = 1 .. C, C = n_states; band rows i0(j) .. i1(j) of cpp/Alignment.cpp:127-148 with stripe_width = realign_width
+ *       (exactly the non-NaN pattern of ps_debug_fill, direction 0); the blank column 0 with rows 0 .. n0;
+ *   obs(i, j) the fill's emission, lik_offset and the log_stdv[n0 - i] quirk (cpp/Alignment.cpp:169-173) included.
+ * The recursion is the reference's (cpp/Alignment.cpp:189-267) with every max / > chain replaced by log-sum-exp, (+):
+ *   the blank column and every column whose state is < 0 (calloc'd, returned early): M = S = 0 on all their rows.  These cells are
+ *       constants: nothing flows through them, and they are not part of logz.
+ *   S(i, j) = 0 (+) (M(i-1, j) + obs + lik_stay) (+) (S(i-1, j) + obs + lik_extend)   for i > i0(j); the 0 is the calloc'd floor.
+ *   S(i0, j) = -infinity.
+ *   M(i, j) = 0 (+) skip (+) match (+) ignore (+) insert (+) S(i, j), with ONE floor term 0, and with p0 .. p1 the previous
+ *       column's band and Mp its M:
+ *       skip   = Mp(i) + lik_skip;
+ *       match  = Mp(i-1) + obs;
+ *       ignore = Mp(i-1) + lik_insert, present only when p0 < i <= p1;
+ *       insert = M(i-1, j) + lik_insert, present only when i > i0;
+ *       Mp(r) is the previous column's M(r) when the row tested lies in its band — p0 <= i <= p1 for skip, p0 < i <= p1 for
+ *       match — and the implicit 0 otherwise (cpp/Alignment.cpp:200-225).  An absent candidate adds nothing.
+ *   logz = (+) of M(i, j) over all band cells of the columns with a valid state; an event without such a cell has logz = 0 and
+ *       all counts 0.
+ *   e_skip, e_match, e_ignore, e_insert, e_stay, e_extend: for each move the sum over cells of exp(F(pred) + w + beta(cell) -
+ *       logz), F(pred) the forward value the move starts from (0 for a constant or implicit one: implicit skips and matches are
+ *       counted), w the move's term, beta the adjoint (backward) quantity of the same lattice — the log-sum of what follows a
+ *       cell, with the 1 of "the path ends here" in M of the columns with a state: beta_M(c) = 0 (+) the moves out of M(c),
+ *       beta_S(c) = beta_M(c) (+) the extend out of S(c).
+ *   n_cells the band cells of the columns with a valid state, n_cols those columns.
+ *   Per level, when asked for: emit[e][i-1] the expected number of emitting arrivals (match + stay + extend, over all columns) at
+ *       level i, col[e][i-1] their posterior mean column (NaN where emit is 0).  `emit` and `col` are arrays of n_events pointers,
+ *       entry e to n_levels(e) doubles (an entry may be NULL for an event without levels); both NULL, or both given.
+ *   inert   ps_move_stats' rule (realign_width 0, no aligned level, no level at all): n_levels is the event's level count, every
+ *       other field 0 and the event's per-level arrays are not written.
+ * FP64, log domain; sums run in a fixed order (per lane, then lanes in order): two runs give the same bytes.  A band footprint of
+ * more than 1024 rows on one anti-diagonal (realign_width > 511 on a long read) is PS_ERR_UNSUPPORTED, an AlignData marked
+ * non-finite PS_ERR_BAD_ARG, as for ps_viterbi_mutate; the handle stays usable.  A batch whose tables — (n0 + C + 25) x slots x 16
+ * bytes per event — exceed the calling thread's share of the device is cut between AlignData; one AlignData over the share is
+ * PS_ERR_NOMEM.  Not part of the reference's interface.  Not built: posterior-weighted k-mer statistics, a fit of lik_offset. */
+typedef struct ps_event_posterior {
+    int32_t n_levels, inert, n_cols, pad;
+    int64_t n_cells;
+    double logz, e_skip, e_match, e_ignore, e_insert, e_stay, e_extend;
+} ps_event_posterior;   /* 80 bytes, no padding */
+int ps_posterior_stats(ps_align* a, ps_event_posterior* stats /* [E] */, double* const* emit /* [E] of [n_e], or NULL */,
+                       double* const* col /* [E] of [n_e], or NULL */);
+
 /* ViterbiMutate (cpp/Viterbi.h:67-68, cpp/Viterbi.cpp:239-426).  The nkeep > 0 stochastic back-traces draw
  * rand() / (RAND_MAX + 1.0) in the reference's call order (cpp/Viterbi.cpp:108).  The reference never seeds
  * libc rand() and runs one process per region, so every region sees the generator of a fresh process.  The
@@ -503,6 +550,9 @@ int ps_batch_kmer_stats(int32_t n, ps_align* const* a, int32_t realign, const in
 /* ps_move_stats for every AlignData in one launch chain, ONE launch of k_move_stats and one copy back: moves[i] has n_events(i) records (never NULL, also for an AlignData without events); scores[i] — entries or the whole array may be NULL — has n_events(i) entries; step[i] / col[i] — entries or whole arrays may be NULL — are ps_move_stats' arrays of n_events(i) pointers. */
 int ps_batch_move_stats(int32_t n, ps_align* const* a, double* const* scores, ps_event_moves* const* moves,
                         uint8_t* const* const* step, int32_t* const* const* col);
+/* ps_posterior_stats for every AlignData in one launch chain — the band stage, k_post_fwd, k_post_bwd — and one copy back: stats[i] has n_events(i) records (never NULL, also for an AlignData without events); emit[i] / col[i] — whole arrays may be NULL, both or neither — are ps_posterior_stats' arrays of n_events(i) pointers. */
+int ps_batch_posterior_stats(int32_t n, ps_align* const* a, ps_event_posterior* const* stats, double* const* const* emit,
+                             double* const* const* col);
 /* ViterbiMutate: rng[i] may be NULL (the calling thread's generator, as ps_viterbi_mutate). */
 int ps_batch_viterbi_mutate(int32_t n, ps_align* const* a, ps_rng* const* rng, int32_t nkeep, double skip_prob,
                             double stay_prob, double mut_min, double mut_max, ps_seqs** out);
@@ -553,6 +603,10 @@ int ps_debug_poison(uint32_t index_word, uint64_t value_word, ps_poison_report* 
  * (backtrace, cpp/Alignment.cpp:516-624); for direction 1 they are zero. */
 int ps_debug_fill(ps_align* a, int32_t ev, int32_t direction, double* main, double* stay,
                   uint8_t* step_main, uint8_t* step_stay);
+/* The forward log tables of ps_posterior_stats for one event, as k_post_fwd left them: main = M and stay = S (may be NULL), dense
+ * (n_levels+1) x (n_states+1), NaN outside the band, 0 in the blank column and in the columns without a state, -infinity for S on a
+ * band's first row; shaped like ps_debug_fill's.  An inert event has the blank column only.  The checkers do not export it. */
+int ps_debug_posterior(ps_align* a, int32_t ev, double* main, double* stay);
 /* The tables of ViterbiMutate (cpp/Viterbi.cpp:239-426) for n AlignData, run as ps_batch_viterbi_mutate runs them (same launches,
  * deviates from the calling thread's generator).  obs_build selects the emission kernel: 0 = the library's choice, 1 = k_vit_obs_lds
  * (at most 72 events), 2 = k_vit_obs<64> (at most 64), 3 = k_vit_obs<256>; PS_ERR_BAD_ARG for a build that cannot take the batch's

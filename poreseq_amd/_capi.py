@@ -69,6 +69,11 @@ EVENT_STATS = np.dtype([(k, np.int32) for k in ("n_levels", "n_aligned", "n_inse
 EVENT_MOVES = np.dtype([(k, np.int32) for k in ("n_levels", "inert", "top_level", "top_col", "low_level", "low_col", "end_kind", "n_match", "n_ignore",
                                                 "n_insert", "n_stay", "n_extend", "n_skip_runs", "max_skip")] + [("n_skip_cols", np.int64)])
 MOVE_NAMES = ("", "MATCH", "INSERT", "IGNORE", "STAY", "EXTEND")   # the step codes of the per-level array (0: not on the path)
+# ps_event_posterior (80 bytes, no padding): one event's sum over all alignments in its band and the expected moves under it, what
+# posterior_stats / batch_posterior_stats hand out
+EVENT_POSTERIOR = np.dtype([(k, np.int32) for k in ("n_levels", "inert", "n_cols", "pad")] + [("n_cells", np.int64)] +
+                           [(k, np.float64) for k in ("logz", "e_skip", "e_match", "e_ignore", "e_insert", "e_stay", "e_extend")])
+POSTERIOR_COUNTS = ("e_skip", "e_match", "e_ignore", "e_insert", "e_stay", "e_extend")
 
 # ps_kmer_cell (48 bytes, no padding): one (event group, 5-mer state) of the tables kmer_stats / batch_kmer_stats hand out
 KMER_STATS = np.dtype([("n", np.int64)] + [(k, np.float64) for k in ("sz", "szz", "sp", "spu", "spv")])
@@ -144,6 +149,10 @@ SYMBOLS = {
     "ps_move_stats": (C.c_int, [C.c_void_p, c_dp, C.c_void_p, C.POINTER(c_u8p), C.POINTER(c_i32p)]),
     "ps_batch_move_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_dp), C.POINTER(C.c_void_p), C.POINTER(C.POINTER(c_u8p)),
                                       C.POINTER(C.POINTER(c_i32p))]),
+    "ps_posterior_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(c_dp), C.POINTER(c_dp)]),
+    "ps_batch_posterior_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.POINTER(c_dp)),
+                                           C.POINTER(C.POINTER(c_dp))]),
+    "ps_debug_posterior": (C.c_int, [C.c_void_p, C.c_int32, c_dp, c_dp]),
     "ps_viterbi_mutate": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_double, C.c_int32, C.POINTER(C.c_void_p)]),
     "ps_srand": (C.c_int, [C.c_uint32]),
@@ -187,9 +196,10 @@ SYMBOLS = {
 # same with util.genotypes_from_deltas on top; PSAlign.ScoreMutationPhase reduces the same two with util.phase_from_deltas;
 # PSAlign.AlignStats reduces the refs the library holds with util.align_stats_from_refs, after its score_alignments, and
 # PSAlign.KmerStats does the same with util.kmer_stats_from_refs; PSAlign.MoveStats walks the tables of the library's debug_fill
-# with util.moves_from_tables).
+# with util.moves_from_tables; PSAlign.PosteriorStats runs util.posterior_from_emissions — the definition — on the band pattern of
+# the library's debug_fill; ps_debug_posterior has no substitute).
 # The Viterbi table hooks have no substitute: on a checker built without them the wrappers raise PoreseqError.
-OPTIONAL = frozenset(["ps_move_stats", "ps_batch_move_stats", "ps_kmer_stats", "ps_batch_kmer_stats", "ps_align_stats", "ps_batch_align_stats","ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
+OPTIONAL = frozenset(["ps_posterior_stats", "ps_batch_posterior_stats", "ps_debug_posterior", "ps_move_stats", "ps_batch_move_stats", "ps_kmer_stats", "ps_batch_kmer_stats", "ps_align_stats", "ps_batch_align_stats","ps_align_keep_refs", "ps_batch_sw_summary", "ps_score_sequences", "ps_batch_score_sequences", "ps_debug_viterbi", "ps_debug_viterbi_steps", "ps_debug_poison",
                       "ps_point_table", "ps_batch_point_table", "ps_score_mutation_support", "ps_batch_score_mutation_support",
                       "ps_score_mutation_genotypes", "ps_batch_score_mutation_genotypes",
                       "ps_score_mutation_phase", "ps_batch_score_mutation_phase"])
@@ -613,6 +623,49 @@ class CApi:
             else:
                 out.append((scores[i][:E], recs[i][:E]))
         return out
+
+    def posterior_stats(self, h, n_levels, levels=False):
+        """-> records EVENT_POSTERIOR [E] (levels=True: (records, emit, col)): ps_posterior_stats of one AlignData whose events
+        have n_levels[e] levels"""
+        return self.batch_posterior_stats([h], [n_levels], levels)[0]
+
+    def batch_posterior_stats(self, hs, n_levels, levels=False):
+        """ps_batch_posterior_stats over the AlignData `hs`, n_levels[i][e] the levels of event e of AlignData i: the band stage of
+        the fills, k_post_fwd and k_post_bwd over all events, one copy back -> [records EVENT_POSTERIOR [E]], with levels=True
+        [(records, emit, col)]: per event two float64 arrays, the expected number of emitting arrivals at every level and their
+        posterior mean column (NaN where there is none; an inert event keeps zeros and NaN).  include/poreseq_hip.h has the
+        definition.  Nothing of the handles changes."""
+        self._need("ps_batch_posterior_stats")
+        R = len(hs)
+        nl = [[int(v) for v in np.asarray(n, dtype=np.int64).reshape(-1)] for n in n_levels]
+        recs = [np.zeros(max(len(n), 1), dtype=EVENT_POSTERIOR) for n in nl]      # (one spare record: never a null pointer)
+        rp = (C.c_void_p * max(R, 1))(*[r.ctypes.data_as(C.c_void_p) for r in recs])
+        emp = clp = None
+        if levels:
+            emit = [[np.zeros(max(v, 1)) for v in n] for n in nl]
+            col = [[np.full(max(v, 1), np.nan) for v in n] for n in nl]
+            ee = [(c_dp * max(len(n), 1))(*[_dp(a) for a in em]) for n, em in zip(nl, emit)]
+            ce = [(c_dp * max(len(n), 1))(*[_dp(a) for a in cl]) for n, cl in zip(nl, col)]
+            emp = (C.POINTER(c_dp) * max(R, 1))(*[C.cast(x, C.POINTER(c_dp)) for x in ee])
+            clp = (C.POINTER(c_dp) * max(R, 1))(*[C.cast(x, C.POINTER(c_dp)) for x in ce])
+        self.check(self.lib.ps_batch_posterior_stats(R, self._harr(hs), rp, emp, clp))
+        out = []
+        for i, n in enumerate(nl):
+            E = len(n)
+            if levels:
+                out.append((recs[i][:E], [a[:v] for a, v in zip(emit[i], n)], [a[:v] for a, v in zip(col[i], n)]))
+            else:
+                out.append(recs[i][:E])
+        return out
+
+    def debug_posterior(self, h, ev, n_levels, n_states):
+        """the forward log tables of ps_posterior_stats for one event (ps_debug_posterior): (main, stay), [n_levels + 1][n_states + 1],
+        NaN outside the band"""
+        self._need("ps_debug_posterior")
+        shape = (n_levels + 1, n_states + 1)
+        main, stay = np.zeros(shape), np.zeros(shape)
+        self.check(self.lib.ps_debug_posterior(h, ev, _dp(main), _dp(stay)))
+        return main, stay
 
     def make_mutations(self, h, hm):
         nb = C.c_int32(0)

@@ -262,17 +262,57 @@ class RegionBatch:
         finally:
             self._close(idx, hs, write_back=False)
 
-    def RefitTransitions(self, idx=None, pool=True, params=None, **fit_kw):
+    def PosteriorStats(self, idx=None, levels=False):
+        """PSAlign.PosteriorStats for the regions `idx` in lock-step: ONE ps_batch_posterior_stats call — the band stage of the fills,
+        k_post_fwd and k_post_bwd over all regions' events, one copy back.  Returns one records array (_capi.EVENT_POSTERIOR [E]) per
+        region, with levels=True one (records, emit, col); no backtrace runs, and sequences, events and a resident handle's refs
+        are not modified."""
+        idx = list(range(len(self.pas))) if idx is None else list(idx)
+        if not idx:
+            return []
+        hs = self._open(idx)
+        try:
+            if "ps_batch_posterior_stats" in self.api.missing:
+                return [poreseqcpp._posterior_stats_on(self.api, h, self.pas[i].events, self.pas[i].params, bool(levels))
+                        for i, h in zip(idx, hs)]
+            return self.api.batch_posterior_stats(hs, [[len(ev.mean) for ev in self.pas[i].events] for i in idx], bool(levels))
+        finally:
+            self._close(idx, hs, write_back=False)
+
+    def _refit_posterior(self, idx, pool, params, iters, fit_kw):
+        """RefitTransitions(posterior=True): every round is one lock-step PosteriorStats; the handles are dropped after every round,
+        since a resident AlignData holds the transition probabilities it was created with"""
+        def stats(ids):
+            def run():
+                out = self.PosteriorStats(ids)
+                for i in ids:
+                    if i in self._h:
+                        self.sync([i])
+                        self.drop([i])
+                return out
+            return run
+        if pool:
+            fit = poreseqcpp._refit_posterior(stats(idx), [self.pas[i].events for i in idx],
+                                              self.pas[idx[0]].params if params is None else params, iters, fit_kw)
+            return [fit] * len(idx)
+        return [poreseqcpp._refit_posterior(stats([i]), [self.pas[i].events], self.pas[i].params if params is None else params, iters, fit_kw)
+                for i in idx]
+
+    def RefitTransitions(self, idx=None, pool=True, params=None, posterior=False, iters=1, **fit_kw):
         """PSAlign.RefitTransitions for the regions `idx`: one lock-step MoveStats, then util.fit_transitions and PSEvent.setparams
         on the Python events.  pool=True (the regions carry reads of the same run) pools the records of all regions per strand and
         fits once for all of them; pool=False fits every region on its own records.  `params` as PSAlign.RefitTransitions takes
         it; None: every region's own pa.params (pool=True: those of the first region).  A resident AlignData holds the transition
         probabilities it was created with, so the handles of the regions are written back (sync) and dropped; the next call
-        rebuilds them.  Returns one util.TransitionFit per region (with pool=True the same one)."""
+        rebuilds them.  Returns one util.TransitionFit per region (with pool=True the same one).  posterior=True fits expected
+        counts (PosteriorStats, util.fit_transitions_soft) in `iters` rounds, as PSAlign.RefitTransitions does: with pool=True every
+        round is one lock-step call over all regions, with pool=False the regions are fitted one after the other."""
         from .util import strand_groups
         idx = list(range(len(self.pas))) if idx is None else list(idx)
         if not idx:
             return []
+        if posterior:
+            return self._refit_posterior(idx, pool, params, iters, fit_kw)
         recs = [r for _, r in self.MoveStats(idx)]
         grps = [strand_groups(self.pas[i].events) for i in idx]
         if pool:

@@ -58,7 +58,8 @@ def _refit_kmers_kw(refit_kmers):
 
 
 def _refit_transitions_kw(refit_transitions):
-    """None / False: no transition refit; True: the defaults; a dict: keyword arguments of RefitTransitions (util.fit_transitions')"""
+    """None / False: no transition refit; True: the defaults; a dict: keyword arguments of RefitTransitions (util.fit_transitions',
+    and 'posterior': True / 'iters' for the fit of expected counts)"""
     if refit_transitions is None or refit_transitions is False:
         return None
     return dict(refit_transitions) if isinstance(refit_transitions, dict) else {}
@@ -551,11 +552,12 @@ def train(make_pa, params, refseq, iters=1, reps=10, save=None, paramlists=None,
 
     `estimate` (not in the reference; off by default): the search starts from the transition probabilities fitted to the moves of
     one forward pass — make_pa(params).RefitTransitions(params), util.fit_transitions — instead of the given ones; every other
-    key of `params` stays.  Unmeasured on real data.
+    key of `params` stays.  estimate='posterior' fits the EXPECTED moves under the sum over all alignments in the bands instead
+    (RefitTransitions(posterior=True), util.fit_transitions_soft).  Both unmeasured on real data.
     """
     from .util import VaryParams, SaveParams
     if estimate:
-        fit = make_pa(params).RefitTransitions(params=params)
+        fit = make_pa(params).RefitTransitions(params=params, posterior=estimate == 'posterior')
         params = dict(params)
         params.update({k: fit.params[k] for k in fit.rates})
     best_accs = []

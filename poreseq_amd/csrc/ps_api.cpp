@@ -325,6 +325,31 @@ int ps_move_stats(ps_align* a, double* scores, ps_event_moves* moves, uint8_t* c
     if (!moves) return fail(PS_ERR_BAD_ARG, "ps_move_stats: null moves");
     return ps_batch_move_stats(1, &a, &scores, &moves, &step, &col);
 }
+int ps_batch_posterior_stats(int32_t n, ps_align* const* a, ps_event_posterior* const* stats, double* const* const* emit, double* const* const* col) {
+    const std::string who = "ps_batch_posterior_stats";
+    std::vector<Align*> as;
+    PS_TRY(batch_handles(n, a, &as));
+    if (n) PS_TRY(stats_output(who, "stats", stats));
+    if ((emit == nullptr) != (col == nullptr)) return fail(PS_ERR_BAD_ARG, who + ": emit and col go together");
+    std::vector<OwnReq> rq(n);
+    for (int i = 0; i < n; i++) {
+        PS_TRY(stats_output(who, "stats", stats[i]));
+        if (!as[i]->nonfinite.empty())
+            return fail(PS_ERR_BAD_ARG, who + ": " + as[i]->nonfinite + " (the sum over alignments needs finite levels with stdv > 0 and a model with positive deviations)");
+        rq[i].a = as[i]; rq[i].post = stats[i];
+        rq[i].emit = emit ? emit[i] : nullptr; rq[i].pcol = col ? col[i] : nullptr;
+        if ((rq[i].emit == nullptr) != (rq[i].pcol == nullptr)) return fail(PS_ERR_BAD_ARG, who + ": emit and col go together");
+        for (int e = 0; e < as[i]->E; e++)
+            if (as[i]->n[e] > 0 && rq[i].emit && (!rq[i].emit[e] || !rq[i].pcol[e]))
+                return fail(PS_ERR_BAD_ARG, who + ": null per-level array of event " + std::to_string(e));
+    }
+    return stats_run(OwnKind::Posterior, 0, rq);
+}
+int ps_posterior_stats(ps_align* a, ps_event_posterior* stats, double* const* emit, double* const* col) {
+    if (!a) return fail(PS_ERR_BAD_ARG, "ps_posterior_stats: null handle");
+    if (!stats) return fail(PS_ERR_BAD_ARG, "ps_posterior_stats: null stats");
+    return ps_batch_posterior_stats(1, &a, &stats, emit ? &emit : nullptr, col ? &col : nullptr);
+}
 int ps_batch_find_mutations(int32_t n, ps_align* const* a, const ps_seqs* const* seeds, ps_muts** out) {
     std::vector<Align*> as;
     PS_TRY(batch_handles(n, a, &as));
@@ -531,6 +556,12 @@ int ps_debug_sw_band(int64_t* out) {
     if (!out) return fail(PS_ERR_BAD_ARG, "ps_debug_sw_band");
     sw_band_counters(out);
     return PS_OK;
+}
+int ps_debug_posterior(ps_align* a, int32_t e, double* main, double* stay) {
+    if (!a || e < 0 || e >= a->a.E || !main) return fail(PS_ERR_BAD_ARG, "ps_debug_posterior");
+    if (!a->a.nonfinite.empty()) return fail(PS_ERR_BAD_ARG, "ps_debug_posterior: " + a->a.nonfinite);
+    NEED_RT();
+    return debug_posterior(rt, &a->a, e, main, stay);
 }
 int ps_debug_fill(ps_align* a, int32_t e, int32_t dir, double* main, double* stay, uint8_t* sm, uint8_t* ss) {
     if (!a || e < 0 || e >= a->a.E || !main || dir < 0 || dir > 1) return fail(PS_ERR_BAD_ARG, "ps_debug_fill");

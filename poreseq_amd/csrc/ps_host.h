@@ -238,11 +238,15 @@ struct OwnReq {
     const int32_t* group = nullptr; int ngroups = 0; ps_kmer_cell* table = nullptr;
     // MoveStats: [E] records; [E] pointers to [n_e] step codes / columns each (either may be null, and so may an entry)
     ps_event_moves* moves = nullptr; uint8_t* const* step = nullptr; int32_t* const* col = nullptr;
+    // Posterior: [E] records; [E] pointers to [n_e] doubles each, both or neither (an entry may be null for an event without levels)
+    ps_event_posterior* post = nullptr; double* const* emit = nullptr; double* const* pcol = nullptr;
 };
 // ScoreAlignments (cpp/MakeMutations.cpp:148-195) | ps_batch_align_stats: per event the census of ref_align and the sums of the
 // scaling fit | ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation | ps_batch_move_stats:
-// per event the backtrace's moves, counted between the walk and the kernel that overwrites its records (ps_stats.hip)
-enum class OwnKind { Score, AlignStats, KmerStats, MoveStats };
+// per event the backtrace's moves, counted between the walk and the kernel that overwrites its records (ps_stats.hip) |
+// ps_batch_posterior_stats: per event the sum over all alignments in its band and the expected moves under it (ps_post.hip) — the
+// band stage of the fills, k_post_fwd, k_post_bwd; no backtrace, the handles' refs stay what they are (`realign` is ignored)
+enum class OwnKind { Score, AlignStats, KmerStats, MoveStats, Posterior };
 // reqs[0 .. n - 1] in one launch chain.  realign: ScoreAlignments' fills and backtraces first (Score, MoveStats: always); without, the
 // statistics reduce the refs the handles hold and no DP runs
 int own_forward(Runtime* rt, OwnKind kind, bool realign, OwnReq* reqs, size_t n);
@@ -272,6 +276,8 @@ int viterbi_mutate(Runtime* rt, const VitCall& call, VitReq* reqs, size_t n);
 // one sub-batch of it on the device: regs[0 .. n - 1] through emissions, steps and back-traces into their `paths`
 int viterbi_batch(Runtime* rt, const VitCall& call, VitRegionH* regs, size_t n);
 int debug_fill(Runtime* rt, Align* a, int ev, int dir, double* main, double* stay, uint8_t* sm, uint8_t* ss);
+// ps_debug_posterior (ps_own.cpp): the chain of a Posterior call for one event, its forward tables un-skewed
+int debug_posterior(Runtime* rt, Align* a, int ev, double* main, double* stay);
 // ps_debug_poison (ps_mem.cpp): overwrites the scratch memory the calling thread's next call could find left over (ps_poison.h)
 int debug_poison(Runtime* rt, uint32_t index_word, uint64_t value_word, ps_poison_report* rep, int32_t cap, int32_t* n_rep);
 // ps_debug_viterbi / ps_debug_viterbi_steps (include/poreseq_hip.h): the tables of a ViterbiMutate call

@@ -353,6 +353,18 @@ struct MoveRun {
 // grid (maxE, nregs): out[job] for every job of every region; counted in the profile as "move_stats".  No-op without a request.
 int launch_move_stats(Runtime* rt, const MoveRun& mv);
 
+// Posterior move counts (ps_post.hip, ps_posterior_stats): where one event's per-level arrays go (both null: not asked for), and its
+// per-row sums: scratch of the two kernels, reduced in row order so that no result depends on the slots per anti-diagonal
+struct PostJob {
+    double* emit;   // NULL, or [n]
+    double* col;    // NULL, or [n]
+    double* row;    // [n][8]
+};
+constexpr int POST_MAX_SLOTS = 1024;   // slots per anti-diagonal of the posterior kernels: one lane each, one workgroup per event
+// k_post_fwd, then k_post_bwd, one workgroup of P threads per job of the batch (its skewed records placed, JobD.P = P, a multiple of
+// 64 up to POST_MAX_SLOTS): out[job] in full; counted in the profile as "post_fwd" / "post_bwd", `cells` band cells for its bytes
+int launch_post(Runtime* rt, const BatchD& b, int P, const PostJob* d_jobs, ps_event_posterior* d_out, double cells);
+
 // Smith-Waterman (kernels: ps_sw.hip, host side: ps_swhost.cpp)
 int sw_device(Runtime* rt, const std::string& s1, const std::string& s2, int* score, double* accuracy,
               std::vector<int>* inds1, std::vector<int>* inds2);

@@ -1,5 +1,6 @@
 // ps_own.cpp — the calls that align every event of an AlignData to its own sequence, forward only: ScoreAlignments
-// (cpp/MakeMutations.cpp:148-195), ps_align_stats, ps_kmer_stats and ps_move_stats, for several AlignData in lock-step (independent regions in one
+// (cpp/MakeMutations.cpp:148-195), ps_align_stats, ps_kmer_stats, ps_move_stats and — a chain of its own below, posterior():
+// sum-product fills instead of a realignment — ps_posterior_stats, for several AlignData in lock-step (independent regions in one
 // launch chain).  One request record per AlignData (OwnReq, ps_host.h) and one chain, own_forward: the cuts of a call that does not
 // fit this runtime's share, the batch, the optional realignment (with k_move_stats inside it for ps_move_stats, whose outputs are
 // placed before it), the tail the kinds differ in, the scores.  Batch and realign() are
@@ -7,6 +8,7 @@
 #include "ps_host.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace ps {
@@ -174,7 +176,147 @@ static int moves_tail(Runtime* rt, const Batch& b, const MovePlan& mp, OwnReq* r
     return PS_OK;
 }
 
+// ---- ps_posterior_stats: the band stage of the fills, k_post_fwd and k_post_bwd (ps_post.hip) over skewed {M, S} records in "rec";
+// the descriptors through "astats_in"; in "astats" the records and, behind them, the per-level arrays, back in one copy.  No
+// backtrace and no updaterefs: nothing of the handles changes.
+// bytes of the records of one AlignData at P slots per anti-diagonal: (n0 + C + 25) x P x 16 per event (matrix_cells, ps_plan.h)
+static double post_need(const Align* a, int P) {
+    double t = 0;
+    for (int e = 0; e < a->E; e++) t += (double)matrix_cells((int64_t)a->n[e] + (int64_t)a->states.size() + 1, P) * sizeof(double2);
+    return t;
+}
+static int post_slots(int footprint) { return (std::max(footprint, 1) + 63) / 64 * 64; }
+// k_begin's inert latch, k_lb, k_lo and the 4-byte footprint read-back that sizes P; then the records placed.  PS_SPLIT (can_split)
+// or PS_ERR_NOMEM when they exceed `cap` bytes; nothing of the fill was launched then, b.P holds the slots they need.
+static int post_place(Runtime* rt, Batch& b, double cap, bool can_split) {
+    PS_TRY(launch_begin(rt, b.d));
+    PS_TRY(launch_lb(rt, b.d, 0, b.maxlbn));
+    PS_TRY(launch_lo(rt, b.d, 1, b.maxS));
+    int* w = nullptr;
+    PS_TRY(rt->down(&w, b.d.maxw, (size_t)1));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    const int P = post_slots(*w);
+    if (P > POST_MAX_SLOTS)
+        return fail(PS_ERR_UNSUPPORTED, "posterior: band footprint of " + std::to_string(*w) + " rows on one anti-diagonal: more than one lane per row of one workgroup holds (" +
+                                        std::to_string(POST_MAX_SLOTS) + "); realign_width up to " + std::to_string((POST_MAX_SLOTS - 1) / 2) + " fits for any input");
+    int64_t tot = 0;
+    for (JobD& j : b.jobs) { j.P = P; j.K = 0; j.mat_off[0] = tot + (int64_t)MAT_FRONT * P; tot += matrix_cells(j.S, P); }
+    b.P = P; b.cells = tot;
+    const double bytes = (double)tot * sizeof(double2);
+    if (cap > 0 && bytes > cap) {
+        if (can_split) return PS_SPLIT;
+        return fail(PS_ERR_NOMEM, "posterior: the forward tables of this AlignData need " + std::to_string((size_t)(bytes / 1048576.0) + 1) + " MB at " + std::to_string(P) +
+                                  " slots per anti-diagonal, this thread's share of the device is " + std::to_string((size_t)(cap / 1048576.0)) + " MB");
+    }
+    void *prec = nullptr, *pflg = nullptr;
+    const int rc = ensure_matrix_pools(rt, b, (size_t)std::max<int64_t>(tot, 1) * sizeof(double2), 0, can_split, &prec, &pflg);
+    if (rc == PS_ERR_NOMEM && can_split) return PS_SPLIT;
+    PS_TRY(rc);
+    PS_TRY(rt->up(rt->buf("jobs").p, b.jobs.data(), b.jobs.size() * sizeof(JobD)));   // JobD.P, JobD.mat_off
+    b.d.rec = (double2*)prec; b.d.flg = nullptr;
+    return PS_OK;
+}
+static double post_cells(const Batch& b) {
+    double t = 0;
+    for (const JobD& j : b.jobs) t += (double)j.C * std::min<double>(2.0 * j.W + 1, j.n0);
+    return t;
+}
+static int posterior(Runtime* rt, OwnReq* reqs, size_t n) {
+    auto sub = [&](size_t k0, size_t k1) { return posterior(rt, reqs + k0, k1 - k0); };
+    auto need = [&](size_t k) { return post_need(reqs[k].a, post_slots(guess_slots(reqs[k].a))); };
+    if (n > 1 && over_share(n, 1, need)) return in_share_chunks(n, 1, need, sub);
+    std::vector<JobSpec> specs;
+    for (size_t k = 0; k < n; k++)
+        for (int e = 0; e < reqs[k].a->E; e++) specs.push_back(reqs[k].a->job(e));
+    if (specs.empty()) return PS_OK;
+    Batch b;
+    PS_TRY(b.build(rt, specs, 1, 0));
+    {
+        const int rc = post_place(rt, b, n > 1 ? PLAN_OVER_GUESS * share_cap(1) : share_cap(1), n > 1);
+        if (rc == PS_SPLIT) return in_halves(n, sub);   // bands wider than guessed: two halves, one after the other
+        PS_TRY(rc);
+    }
+    const size_t nj = b.jobs.size();
+    bool per_level = false;
+    for (size_t k = 0; k < n; k++) per_level |= reqs[k].emit != nullptr;
+    std::vector<size_t> lev_off(nj, 0);
+    size_t levels = 0;
+    for (size_t q = 0; q < nj; q++) { lev_off[q] = levels; levels += (size_t)b.jobs[q].n0; }
+    const size_t emit_off = nj * sizeof(ps_event_posterior), col_off = emit_off + (per_level ? levels * sizeof(double) : 0);
+    const size_t out_bytes = col_off + (per_level ? levels * sizeof(double) : 0);   // what comes back; behind it the kernels' per-row sums
+    DBuf& din = rt->buf("astats_in");
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(din.ensure(nj * sizeof(PostJob)));
+    PS_TRY(dout.ensure(out_bytes + levels * 8 * sizeof(double)));
+    std::vector<PostJob> pj(nj);
+    size_t q = 0;
+    for (size_t k = 0; k < n; k++)
+        for (int e = 0; e < reqs[k].a->E; e++, q++) {
+            pj[q].emit = reqs[k].emit ? (double*)((char*)dout.p + emit_off) + lev_off[q] : nullptr;
+            pj[q].col = reqs[k].emit ? (double*)((char*)dout.p + col_off) + lev_off[q] : nullptr;
+            pj[q].row = (double*)((char*)dout.p + out_bytes) + lev_off[q] * 8;
+        }
+    PS_TRY(rt->up(din.p, pj.data(), nj * sizeof(PostJob)));
+    PS_TRY(launch_post(rt, b.d, b.P, din.as<PostJob>(), dout.as<ps_event_posterior>(), post_cells(b)));
+    void* back = nullptr;
+    PS_TRY(rt->down(&back, dout.p, out_bytes));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    q = 0;
+    for (size_t k = 0; k < n; k++) {
+        const Align* a = reqs[k].a;
+        memcpy(reqs[k].post, (const ps_event_posterior*)back + q, (size_t)a->E * sizeof(ps_event_posterior));
+        for (int e = 0; e < a->E; e++, q++) {
+            if (!reqs[k].emit || reqs[k].post[e].inert || !a->n[e]) continue;   // (an inert event's arrays were not written)
+            const size_t ne = (size_t)a->n[e];
+            if (reqs[k].emit[e]) memcpy(reqs[k].emit[e], (const double*)((const char*)back + emit_off) + lev_off[q], ne * sizeof(double));
+            if (reqs[k].pcol[e]) memcpy(reqs[k].pcol[e], (const double*)((const char*)back + col_off) + lev_off[q], ne * sizeof(double));
+        }
+    }
+    return PS_OK;
+}
+
+// ps_debug_posterior: the same chain for one event, then its records un-skewed (the band per column from the lb table, as debug_fill)
+int debug_posterior(Runtime* rt, Align* a, int ev, double* main, double* stay) {
+    const std::vector<JobSpec> specs(1, a->job(ev));
+    Batch b;
+    PS_TRY(b.build(rt, specs, 1, 0));
+    PS_TRY(post_place(rt, b, share_cap(1), false));
+    DBuf& din = rt->buf("astats_in");
+    DBuf& dout = rt->buf("astats");
+    PS_TRY(din.ensure(sizeof(PostJob)));
+    PS_TRY(dout.ensure(128 + (size_t)a->n[ev] * 8 * sizeof(double)));
+    const PostJob none = {nullptr, nullptr, (double*)((char*)dout.p + 128)};
+    PS_TRY(rt->up(din.p, &none, sizeof(none)));
+    PS_TRY(launch_post(rt, b.d, b.P, din.as<PostJob>(), dout.as<ps_event_posterior>(), post_cells(b)));
+    const JobD& J = b.jobs[0];
+    const int n0 = J.n0, C = J.C, P = J.P;
+    const size_t ld = (size_t)C + 1, tot = ((size_t)n0 + 1) * ld;
+    const double nan = std::nan("");
+    for (size_t k = 0; k < tot; k++) { main[k] = nan; if (stay) stay[k] = nan; }
+    for (int i = 0; i <= n0; i++) { main[(size_t)i * ld] = 0.0; if (stay) stay[(size_t)i * ld] = 0.0; }   // the blank column
+    ps_event_posterior rec0;
+    std::vector<int> lb(J.lbn);
+    std::vector<double2> rec((size_t)J.S * P);
+    PS_HIP(hipMemcpyAsync(&rec0, dout.p, sizeof(rec0), hipMemcpyDeviceToHost, rt->stream));
+    PS_HIP(hipMemcpyAsync(lb.data(), b.d.lb + J.lb_off, J.lbn * sizeof(int), hipMemcpyDeviceToHost, rt->stream));
+    PS_HIP(hipMemcpyAsync(rec.data(), b.d.rec + J.mat_off[0], rec.size() * sizeof(double2), hipMemcpyDeviceToHost, rt->stream));
+    PS_HIP(hipStreamSynchronize(rt->stream));
+    if (rec0.inert) return PS_OK;
+    for (int c = 1; c <= C; c++) {
+        const int v = lb[c];
+        const int ce = std::min(std::max(v < 0 ? 1 : v, 1), n0);
+        const int i0 = std::max(1, ce - J.W), i1 = std::min(n0, ce + J.W);
+        for (int i = i0; i <= i1; i++) {
+            const size_t to = (size_t)i * ld + c, at = (size_t)(i + c) * P + (i % P);
+            main[to] = rec[at].x;
+            if (stay) stay[to] = rec[at].y;
+        }
+    }
+    return PS_OK;
+}
+
 int own_forward(Runtime* rt, OwnKind kind, bool re, OwnReq* reqs, size_t n) {
+    if (kind == OwnKind::Posterior) return posterior(rt, reqs, n);
     const bool kmer = kind == OwnKind::KmerStats;
     auto sub = [&](size_t k0, size_t k1) { return own_forward(rt, kind, re, reqs + k0, k1 - k0); };   // regions k0 .. k1 - 1 as a call of their own
     // a k-mer call whose tables exceed this runtime's share is cut between AlignData

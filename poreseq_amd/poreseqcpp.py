@@ -7,6 +7,7 @@ the C ABI of include/poreseq_hip.h, served by hand-written HIP kernels
 call raises if libporeseq_hip.so is missing or no MI355X-class device is usable.
 """
 import copy
+import math
 
 import numpy as np
 
@@ -15,6 +16,7 @@ from .util import MutationInfo, MutationScore, support_groups, spans_from_refs, 
 from .util import align_stats_from_refs, fit_scaling, apply_scaling
 from .util import kmer_groups, kmer_stats_from_refs, fit_kmers, apply_kmers
 from .util import moves_from_tables, fit_transitions, strand_groups
+from .util import fill_emissions, posterior_from_emissions, fit_transitions_soft
 
 
 def _api():
@@ -198,16 +200,77 @@ def _move_stats_on(api, h, events, params, levels):
     return (scores, recs, step, col) if levels else (scores, recs)
 
 
-def _refit_transitions(events, records, groups, params, fit_kw):
-    """util.fit_transitions of the records, applied through PSEvent.setparams to every event -> the fit"""
+def _posterior_stats_on(api, h, events, params, levels):
+    """records _capi.EVENT_POSTERIOR [E] (levels: (records, emit, col)) of the AlignData `h`, whose events are `events` and whose
+    parameters `params`: ps_posterior_stats, or — a library without the entry point — the definition itself,
+    util.posterior_from_emissions, on util.fill_emissions and the band pattern of the forward tables the library's debug_fill hands
+    out, taken on a scratch AlignData with the sequence and the ref_align that `h` holds.  `h` is not touched.  An event the
+    reference would not fill (realign_width 0, no aligned level, no level) gets the inert record."""
+    E = len(events)
+    nl = [len(ev.mean) for ev in events]
+    if "ps_posterior_stats" not in api.missing:
+        return api.posterior_stats(h, nl, levels)
+    recs = np.zeros(E, dtype=_capi.EVENT_POSTERIOR)
+    emit = [np.zeros(n) for n in nl]
+    col = [np.full(n, np.nan) for n in nl]
+    sequence = api.align_sequence(h)
+    states = api.seq_to_states(sequence)
+    valid = np.concatenate([[False], np.asarray(states) >= 0])
+    width = int(params.get('realign_width', 300))
+    held = []
+    for ev, ra in zip(events, api.align_event_refs(h, E)):
+        ev = copy.copy(ev)
+        ev.ref_align = ra
+        held.append(ev)
+    scratch = api.align_create(sequence, held, params)
+    try:
+        for e, ev in enumerate(held):
+            recs[e]["n_levels"] = nl[e]
+            with np.errstate(invalid='ignore'):
+                fills = width != 0 and nl[e] > 0 and bool(np.any(ev.ref_align > 0))
+            if not fills:
+                recs[e]["inert"] = 1
+                continue
+            mask = ~np.isnan(api.debug_fill(scratch, e, 0, nl[e], len(states))[0])
+            lik = [math.log(float(getattr(ev.model, 'prob_' + r))) for r in ("skip", "stay", "extend", "insert")]
+            res = posterior_from_emissions(fill_emissions(ev, states, params), mask, valid, *lik, levels=levels)
+            recs[e] = res.record(nl[e])
+            if levels:
+                emit[e], col[e] = np.asarray(res.emit, dtype=np.float64), np.asarray(res.col, dtype=np.float64)
+    finally:
+        api.align_destroy(scratch)
+    return (recs, emit, col) if levels else recs
+
+
+def _refit_transitions(events, records, groups, params, fit_kw, soft=False):
+    """util.fit_transitions (soft: util.fit_transitions_soft) of the records, applied through PSEvent.setparams to every event ->
+    the fit"""
     base = dict(params) if params is not None else {}
     for ev, g in zip(events, groups):      # the rates the events carry now, where `params` does not say
         for name in ("skip", "stay", "extend", "insert"):
             base.setdefault(name + ("_c" if g else "_t"), float(getattr(ev.model, 'prob_' + name)))
-    fit = fit_transitions(records, groups, base, **fit_kw)
+    fit = (fit_transitions_soft if soft else fit_transitions)(records, groups, base, **fit_kw)
     keys = {k: fit.params[k] for k in fit.rates}
     for ev in events:
         ev.setparams(keys)
+    return fit
+
+
+def _refit_posterior(stats, events_per_region, params, iters, fit_kw):
+    """`iters` rounds of {stats() -> one EVENT_POSTERIOR array per region, util.fit_transitions_soft pooled over the regions per
+    strand, setparams on every event}: round k starts from the rates round k - 1 set.  -> the last fit, with `logz`: the summed
+    logz before every round"""
+    if int(iters) < 1:
+        raise ValueError("RefitTransitions(posterior=True): iters must be >= 1")
+    events = [ev for evs in events_per_region for ev in evs]
+    groups = strand_groups(events)
+    cur, logz, fit = params, [], None
+    for _ in range(int(iters)):
+        records = np.concatenate(stats())
+        logz.append(math.fsum(float(v) for v in records["logz"]))
+        fit = _refit_transitions(events, records, groups, cur, fit_kw, soft=True)
+        cur = fit.params
+    fit.logz = logz
     return fit
 
 
@@ -354,13 +417,33 @@ class PSAlign:
         with PSAlign._Data(self) as d:
             return _move_stats_on(d.api, d.h, self.events, self.params, bool(levels))
 
-    def RefitTransitions(self, params=None, **fit_kw):
+    def PosteriorStats(self, levels=False):
+        """Per event the sum over ALL alignments in its band and the expected number of each move under it (ps_posterior_stats):
+        records[, emit, col].  The lattice is the forward fill's on the refs the events carry; its recursion is the reference's
+        with every maximum replaced by a log-sum (k_post_fwd), and a backward pass over the same cells weights every move by its
+        posterior (k_post_bwd).  records is a structured array (_capi.EVENT_POSTERIOR [E]): logz — the marginal score, >= the
+        event's ScoreEvents score —, e_skip .. e_extend for util.fit_transitions_soft, n_cells, n_cols, and inert = 1 with zeros for
+        an event the reference would not fill.  levels=True adds per event two float64 arrays: the expected number of emitting
+        arrivals at every level and their posterior mean column (NaN where there is none).  No backtrace runs; `self` is not
+        modified.  A library without the entry point (the test-suite's checkers) runs the definition,
+        `util.posterior_from_emissions`, on its debug_fill's band pattern."""
+        with PSAlign._Data(self) as d:
+            return _posterior_stats_on(d.api, d.h, self.events, self.params, bool(levels))
+
+    def RefitTransitions(self, params=None, posterior=False, iters=1, **fit_kw):
         """Re-estimate the transition probabilities on the alignment to self.sequence: one MoveStats() pass, util.fit_transitions
         (**fit_kw) pooled per strand, starting from `params` ('skip_t' .. 'insert_c'; None: self.params; what it lacks is read off the events' models),
         and PSEvent.setparams IN PLACE on every event.  Returns the util.TransitionFit.  Sequence, ref_align, ref_like and the
-        models' level tables are not touched.  What this does to consensus accuracy on real data has not been measured."""
-        _, records = self.MoveStats()
-        return _refit_transitions(self.events, records, strand_groups(self.events), self.params if params is None else params, fit_kw)
+        models' level tables are not touched.  What this does to consensus accuracy on real data has not been measured.
+        posterior=True fits expected counts instead of the best path's: `iters` rounds of PosteriorStats() ->
+        util.fit_transitions_soft(**fit_kw) -> setparams, every round starting from the rates the round before set (the bands do not
+        move: a round is one call, no backtrace).  The fit returned is the last round's and gains `logz`, the list of the summed
+        logz of all events before every round.  Equally unmeasured on real data."""
+        base = self.params if params is None else params
+        if not posterior:
+            _, records = self.MoveStats()
+            return _refit_transitions(self.events, records, strand_groups(self.events), base, fit_kw)
+        return _refit_posterior(lambda: [self.PosteriorStats()], [self.events], base, iters, fit_kw)
 
     def ScoreSequences(self, seqs):
         """ndarray [len(seqs)][len(events)]: row s is what `pav = self.Copy(); pav.RealignTo(seqs[s]); pav.ScoreEvents()` returns,

@@ -866,11 +866,13 @@ TRANSITION_RATES = ("skip", "stay", "extend", "insert")
 class TransitionFit(object):
     """fit_transitions' result: params (a copy of the given parameters with the fitted rates under 'skip_t' .. 'insert_c'), rates
     {key: value before the clamp}, counts {key: (numerator, denominator)} and flags {key: 'clamped' | 'empty'} for the rates that
-    a limit cut or that had no observation (those keep the given value)"""
-    __slots__ = ("params", "rates", "counts", "flags")
+    a limit cut or that had no observation (those keep the given value); logz: None, or — RefitTransitions(posterior=True) — the
+    summed logz of all events before every round"""
+    __slots__ = ("params", "rates", "counts", "flags", "logz")
 
     def __init__(self, params, rates, counts, flags):
         self.params, self.rates, self.counts, self.flags = params, rates, counts, flags
+        self.logz = None
 
     @property
     def ok(self):
@@ -894,18 +896,32 @@ def fit_transitions(records, groups, params, prior=100.0, lo=1e-3, hi=0.5, suffi
     These are path frequencies (Viterbi training) of a score that is no normalised probability (lik_offset is added per matched
     level), not maximum-likelihood estimates.  Host only.  Returns a TransitionFit."""
     import numpy as np
+    return _fit_rates("fit_transitions", records, groups, params, prior, lo, hi, suffixes, _MOVE_FIELDS,
+                      lambda col: int(np.sum(col, dtype=np.int64)))
+
+
+# the six totals of a rate fit and the fields they are summed from: ps_event_moves' integers, ps_event_posterior's expectations
+_FIT_TOTALS = ("n_match", "n_ignore", "n_insert", "n_stay", "n_extend", "n_skip_cols")
+_MOVE_FIELDS = _FIT_TOTALS
+_SOFT_FIELDS = ("e_match", "e_ignore", "e_insert", "e_stay", "e_extend", "e_skip")
+
+
+def _fit_rates(who, records, groups, params, prior, lo, hi, suffixes, fields, total):
+    """the one body of fit_transitions and fit_transitions_soft: `fields` names the six totals in the records, `total` sums one
+    column of a group (to a Python int for counts, to a float for expectations)"""
+    import numpy as np
     rec = np.asarray(records).reshape(-1)
     grp = np.asarray(list(groups), dtype=np.int64).reshape(-1)
     if grp.size != rec.size:
-        raise ValueError("fit_transitions: %d group ids for %d records" % (grp.size, rec.size))
+        raise ValueError("%s: %d group ids for %d records" % (who, grp.size, rec.size))
     if grp.size and (grp.min() < 0 or grp.max() >= len(suffixes)):
-        raise ValueError("fit_transitions: group ids must lie in 0 .. %d" % (len(suffixes) - 1))
+        raise ValueError("%s: group ids must lie in 0 .. %d" % (who, len(suffixes) - 1))
     if not (0.0 <= float(lo) <= float(hi)) or float(prior) < 0:
-        raise ValueError("fit_transitions: need 0 <= lo <= hi and prior >= 0")
+        raise ValueError("%s: need 0 <= lo <= hi and prior >= 0" % who)
     out, rates, counts, flags = dict(params), {}, {}, {}
     for g, suf in enumerate(suffixes):
         r = rec[grp == g]
-        tot = {k: int(np.sum(r[k], dtype=np.int64)) for k in ("n_match", "n_ignore", "n_insert", "n_stay", "n_extend", "n_skip_cols")}
+        tot = {k: total(r[f]) for k, f in zip(_FIT_TOTALS, fields)}
         L = tot["n_match"] + tot["n_ignore"] + tot["n_insert"] + tot["n_stay"] + tot["n_extend"]
         ccol = tot["n_match"] + tot["n_ignore"] + tot["n_skip_cols"]
         frac = {"skip": (tot["n_skip_cols"], ccol), "stay": (tot["n_stay"], L), "extend": (tot["n_extend"], tot["n_stay"] + tot["n_extend"]),
@@ -926,6 +942,215 @@ def fit_transitions(records, groups, params, prior=100.0, lo=1e-3, hi=0.5, suffi
     return TransitionFit(out, rates, counts, flags)
 
 
+def fit_transitions_soft(records, groups, params, prior=100.0, lo=1e-3, hi=0.5, suffixes=("_t", "_c")):
+    """fit_transitions on EXPECTED move counts: `records` are ps_posterior_stats records (_capi.EVENT_POSTERIOR [E]), whose e_skip ..
+    e_extend are the expected numbers of each move under the sum over all alignments in the band (posterior_from_emissions).  The
+    formulas, the shrinkage by `prior`, the clamps and the flags are fit_transitions' own (one body, _fit_rates), with e_match,
+    e_ignore, e_insert, e_stay, e_extend in the places of the n_ fields and e_skip in that of n_skip_cols:
+        skip = e_skip / (e_match + e_ignore + e_skip);  stay = e_stay / L;  extend = e_extend / (e_stay + e_extend);
+        insert = (e_insert + e_ignore) / L,   L = e_match + e_ignore + e_insert + e_stay + e_extend
+    Totals are summed with math.fsum (correctly rounded, whatever the order of the records).  On integer-valued expectations the result is fit_transitions'.  One round of
+    a Baum-Welch-like re-estimation of a score that is no normalised probability (the floor terms and lik_offset), not a
+    maximum-likelihood estimate; what it does to consensus accuracy on real data has not been measured.  Host only."""
+    import math
+    return _fit_rates("fit_transitions_soft", records, groups, params, prior, lo, hi, suffixes, _SOFT_FIELDS,
+                      lambda col: math.fsum(float(v) for v in col))
+
+
 def strand_groups(events):
     """the default grouping of fit_transitions: 0 for a template event, 1 for a complement one (ev.model.complement)"""
     return [1 if getattr(ev.model, 'complement', False) else 0 for ev in events]
+
+
+# ---- posterior move counts: the sum over all alignments in the band (ps_posterior_stats) ------------------------------------------
+LOG2PI = 1.8378770664093453      # log(2 pi) as the library forms it (cpp/AlignUtil.h:24)
+REF_INF = 1e300                   # the reference's "inf" (cpp/AlignUtil.h:20): the floor of a band's first stay cell in 'max' mode
+
+
+class Posterior(object):
+    """posterior_from_emissions' result.  logz (sum mode; the best score in 'max' mode), counts {e_skip, e_match, e_ignore, e_insert,
+    e_stay, e_extend} (sum mode), n_cells / n_cols (band cells of the columns with a state, and those columns), main / stay (the
+    forward tables [n0 + 1][C + 1], NaN outside the band, 0 in the blank column and in columns without a state), emit / col (per
+    level, when asked for)"""
+    __slots__ = ("logz", "counts", "n_cells", "n_cols", "main", "stay", "emit", "col")
+
+    def record(self, n_levels, inert=0):
+        """the _capi.EVENT_POSTERIOR record of this result (float64)"""
+        import numpy as np
+        from ._capi import EVENT_POSTERIOR
+        r = np.zeros((), dtype=EVENT_POSTERIOR)
+        r["n_levels"], r["inert"], r["n_cols"], r["n_cells"], r["logz"] = n_levels, inert, self.n_cols, self.n_cells, float(self.logz)
+        for k, v in self.counts.items():
+            r[k] = float(v)
+        return r
+
+
+def fill_emissions(event, states, params):
+    """obs [n0 + 1][C + 1] float64: the forward fill's emission of every level of `event` against every state of `states` (row 0,
+    column 0 and the columns without a state: 0), operation for operation as the library forms it (cpp/AlignUtil.h:34-53,
+    cpp/Alignment.cpp:169-173): logarithms and pow(., 3) through libm, lambda = pow(sd_mean, 3) / (sd_stdv * sd_stdv), the level's
+    log stdv MIRRORED — row i takes 3 log(stdv[n0 - i]), sic — and lik_offset added last."""
+    import math
+    import numpy as np
+    m = event.model
+    lm, ls = np.asarray(m.level_mean, dtype=np.float64), np.asarray(m.level_stdv, dtype=np.float64)
+    sm, ss = np.asarray(m.sd_mean, dtype=np.float64), np.asarray(m.sd_stdv, dtype=np.float64)
+    with np.errstate(all='ignore'):
+        lam = np.array([math.pow(a, 3) / (b * b) if b != 0 else float('nan') for a, b in zip(sm.tolist(), ss.tolist())])
+        log_lev = np.array([math.log(x) if x > 0 else float('nan') for x in ls.tolist()])
+        log_lam = np.array([math.log(x) if x > 0 else float('nan') for x in lam.tolist()])
+    mean, stdv = np.asarray(event.mean, dtype=np.float64), np.asarray(event.stdv, dtype=np.float64)
+    n0 = mean.size
+    st = np.asarray(states, dtype=np.int64).reshape(-1)
+    C = st.size
+    obs = np.zeros((n0 + 1, C + 1))
+    ok = np.nonzero(st >= 0)[0]
+    if not n0 or not ok.size:
+        return obs
+    k = st[ok]
+    lsd3 = 3.0 * np.array([math.log(x) if x > 0 else float('nan') for x in stdv.tolist()])[::-1]      # row i: 3 log stdv[n0 - i]
+    off = float(params.get('lik_offset', DEFAULT_PARAMS['lik_offset']))
+    with np.errstate(all='ignore'):
+        d = (mean[:, None] - lm[k][None, :]) / ls[k][None, :]
+        l = -0.5 * (d * d + LOG2PI) - log_lev[k][None, :]
+        e = (stdv[:, None] - sm[k][None, :]) / sm[k][None, :]
+        q = (e * e * lam[k][None, :]) / stdv[:, None]
+        g = 0.5 * (log_lam[k][None, :] - lsd3[:, None] - LOG2PI - q)
+        l = l + g
+        l = l + off
+    obs[1:, ok + 1] = l
+    return obs
+
+
+def posterior_from_emissions(obs, mask, valid, lik_skip, lik_stay, lik_extend, lik_insert, semiring='sum', dtype=None, levels=False, counts=True):
+    """The sum-product (or, semiring='max', the reference's max-plus) fill of one event's band, and the expected move counts under
+    it: the definition of ps_posterior_stats (include/poreseq_hip.h) in numpy.
+      obs    [n0 + 1][C + 1] emissions (fill_emissions); read inside the band of the columns with a state only
+      mask   [n0 + 1][C + 1] bool: the cells the forward fill holds — column 0 the blank column, rows 0 .. n0; column j the rows
+             i0(j) .. i1(j) (the non-NaN pattern of debug_fill, direction 0)
+      valid  [C + 1] bool: column j has a 5-mer state (valid[0] is ignored: the blank column has none)
+      lik_*  the four log transition probabilities
+    The recursion is cpp/Alignment.cpp:189-267 with (+) = log-sum-exp in place of every max ('max': max).  A column without a state
+    and the blank column hold M = S = 0 on their rows, constants through which nothing flows.  In a column with a state, with the
+    previous column's band p0 .. p1 and Mp its M (0 where the text says "implicit"):
+      S(i, j) = 0 (+) (M(i-1, j) + obs + lik_stay) (+) (S(i-1, j) + obs + lik_extend)   for i > i0;   S(i0, j) = -inf ('max': -1e300)
+      M(i, j) = 0 (+) skip (+) match (+) ignore (+) insert (+) S(i, j)
+      skip = Mp(i) + lik_skip (Mp = 0 unless p0 <= i <= p1);  match = Mp(i-1) + obs (Mp = 0 unless p0 < i <= p1);
+      ignore = Mp(i-1) + lik_insert, only when p0 < i <= p1;  insert = M(i-1, j) + lik_insert, only when i > i0
+      logz = (+) of M over the band cells of the columns with a state (0 when there is none)
+    The expected count of a move is the sum over cells of exp(F(pred) + w + beta(cell) - logz), F(pred) = 0 for a constant or
+    implicit predecessor, beta the backward quantity of the same lattice: beta_M(c) = 0 (the path ends here) (+) every move out of
+    M(c), beta_S(c) = beta_M(c) (+) the extend out of S(c).  With levels=True, emit[i-1] is the expected number of emitting arrivals
+    (match + stay + extend) at level i and col[i-1] their posterior mean column (NaN where emit is 0).
+    Cells of one anti-diagonal do not depend on each other; the recursion runs over anti-diagonals, vectorised along each.
+    dtype: numpy float64 (default) or longdouble.  counts=False stops after logz (no backward pass; counts stay 0).  Returns a
+    Posterior."""
+    import numpy as np
+    ft = np.dtype(np.float64 if dtype is None else dtype).type
+    if semiring not in ('sum', 'max'):
+        raise ValueError("posterior_from_emissions: semiring must be 'sum' or 'max'")
+    mask = np.asarray(mask, dtype=bool)
+    n0, C = mask.shape[0] - 1, mask.shape[1] - 1
+    ok = np.asarray(valid, dtype=bool).reshape(-1).copy()
+    if ok.size != C + 1 or np.asarray(obs).shape != mask.shape:
+        raise ValueError("posterior_from_emissions: shapes of obs, mask and valid do not fit")
+    ok[0] = False
+    NINF = ft(-np.inf)
+    lsk, lst, lex, lin = ft(lik_skip), ft(lik_stay), ft(lik_extend), ft(lik_insert)
+    # everything padded by one row and one column on the far side, so that (i + 1, j + 1) always exists
+    mk = np.zeros((n0 + 2, C + 2), dtype=bool)
+    mk[:n0 + 1, :C + 1] = mask
+    live = mk.copy()
+    live[:, :C + 1] &= ok[None, :]
+    live[:, 0] = False
+    o = np.zeros((n0 + 2, C + 2), dtype=ft)
+    with np.errstate(invalid='ignore'):
+        o[:n0 + 1, :C + 1] = np.where(live[:n0 + 1, :C + 1], np.asarray(obs), 0.0)
+    FM = np.zeros((n0 + 2, C + 2), dtype=ft)      # read as Mp: 0 outside the band and in the constant columns
+    FS = np.zeros((n0 + 2, C + 2), dtype=ft)
+
+    def lse(terms):
+        t = np.stack(terms)
+        if semiring == 'max':
+            return np.max(t, axis=0)
+        m = np.max(t, axis=0)
+        with np.errstate(invalid='ignore'):
+            return m + np.log(np.sum(np.exp(t - m[None, :]), axis=0))
+
+    ci, cj = np.nonzero(live)
+    order = np.argsort(ci + cj, kind='stable')
+    ci, cj = ci[order], cj[order]
+    cuts = np.nonzero(np.diff(ci + cj))[0] + 1
+    diags = list(zip(np.split(ci, cuts), np.split(cj, cuts))) if ci.size else []
+    up_ok = np.zeros_like(mk)
+    up_ok[1:, :] = mk[:-1, :]
+    up_ok &= live                                   # i > i0: the cell above is in the column's band
+    dg_ok = np.zeros_like(mk)
+    dg_ok[1:, 1:] = mk[1:, :-1] & mk[:-1, :-1]      # p0 < i <= p1
+    dg_ok &= live
+    top_floor = ft(-REF_INF) if semiring == 'max' else NINF
+    zero = ft(0.0)
+    for ii, jj in diags:
+        ob = o[ii, jj]
+        u, d = up_ok[ii, jj], dg_ok[ii, jj]
+        D = np.where(d, FM[ii - 1, jj - 1], zero)
+        um, us = FM[ii - 1, jj], FS[ii - 1, jj]
+        z = np.zeros(ii.size, dtype=ft)
+        s_in = lse([z, np.where(u, um + ob + lst, NINF), np.where(u, us + ob + lex, NINF)])
+        S = np.where(u, s_in, top_floor)
+        M = lse([z, FM[ii, jj - 1] + lsk, D + ob, np.where(d, D + lin, NINF), np.where(u, um + lin, NINF), S])
+        FM[ii, jj], FS[ii, jj] = M, S
+    res = Posterior()
+    nan = ft(np.nan)
+    res.main = np.where(mask, FM[:n0 + 1, :C + 1], nan)
+    res.stay = np.where(mask, FS[:n0 + 1, :C + 1], nan)
+    res.n_cells = int(ci.size)
+    res.n_cols = int(np.count_nonzero(np.any(live, axis=0)))
+    res.counts = dict.fromkeys(("e_skip", "e_match", "e_ignore", "e_insert", "e_stay", "e_extend"), ft(0.0))
+    res.emit = res.col = None
+    if levels:
+        res.emit, res.col = np.zeros(n0, dtype=ft), np.full(n0, nan, dtype=ft)
+    if not ci.size:
+        res.logz = ft(0.0)
+        return res
+    cells = FM[ci, cj]
+    if semiring == 'max':
+        res.logz = max(ft(0.0), np.max(cells))
+        return res
+    top = np.max(cells)
+    logz = top + np.log(np.sum(np.exp(cells - top)))
+    res.logz = logz
+    if not counts:
+        return res
+    # backward: beta over descending anti-diagonals; -inf wherever nothing flows (outside the band, constant columns)
+    BM = np.full((n0 + 2, C + 2), NINF, dtype=ft)
+    BS = np.full((n0 + 2, C + 2), NINF, dtype=ft)
+    for ii, jj in reversed(diags):
+        dn = mk[ii + 1, jj]                          # i + 1 <= i1(j): the match / ignore into (i + 1, j + 1) reads this cell, not the implicit 0
+        bd = BM[ii + 1, jj + 1]
+        z = np.zeros(ii.size, dtype=ft)
+        bm = lse([z, BM[ii, jj + 1] + lsk, np.where(dn, bd + o[ii + 1, jj + 1], NINF), np.where(dn, bd + lin, NINF),
+                  BM[ii + 1, jj] + lin, BS[ii + 1, jj] + o[ii + 1, jj] + lst])
+        BM[ii, jj] = bm
+        BS[ii, jj] = lse([bm, BS[ii + 1, jj] + o[ii + 1, jj] + lex])
+    ob, bM, bS = o[ci, cj], BM[ci, cj] - logz, BS[ci, cj] - logz
+    u, d = up_ok[ci, cj], dg_ok[ci, cj]
+    D = np.where(d, FM[ci - 1, cj - 1], zero)
+    with np.errstate(invalid='ignore'):
+        w_skip = np.exp(FM[ci, cj - 1] + lsk + bM)
+        w_match = np.exp(D + ob + bM)
+        w_ign = np.where(d, np.exp(D + lin + bM), zero)
+        w_ins = np.where(u, np.exp(FM[ci - 1, cj] + lin + bM), zero)
+        w_stay = np.where(u, np.exp(FM[ci - 1, cj] + ob + lst + bS), zero)
+        w_ext = np.where(u, np.exp(FS[ci - 1, cj] + ob + lex + bS), zero)
+    res.counts = {"e_skip": np.sum(w_skip), "e_match": np.sum(w_match), "e_ignore": np.sum(w_ign), "e_insert": np.sum(w_ins),
+                  "e_stay": np.sum(w_stay), "e_extend": np.sum(w_ext)}
+    if levels:
+        w = w_match + w_stay + w_ext
+        emit = np.zeros(n0 + 2, dtype=ft)
+        colw = np.zeros(n0 + 2, dtype=ft)
+        np.add.at(emit, ci, w)
+        np.add.at(colw, ci, w * cj.astype(ft))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            res.emit, res.col = emit[1:n0 + 1], np.where(emit[1:n0 + 1] > 0, colw[1:n0 + 1] / emit[1:n0 + 1], nan)
+    return res
