@@ -30,7 +30,8 @@ def _want_hw_queues():
     read when the HIP runtime starts, so it is exported here, at import — but only when nobody has set it and nothing in the process
     has opened the GPU yet (torch.cuda.is_available(), another HIP library ...: the variable would be ignored, and the library, told
     that it is in force, would put every stream on one priority level: seven streams on four queues).  PORESEQ_HWQ_SET_BY_PACKAGE=1
-    tells the library that the value can be trusted; otherwise it deals its streams over the device's priority levels
+    tells the library that the value can be trusted; where HIP runs on its default instead, the library gives each stream a private
+    queue (a CU-masked stream) within a budget, and deals the rest over the device's priority levels
     (ps_runtime.cpp, hwq_mode; `poreseq_amd._capi.load_hip().info()` says which mode a process is in)."""
     if "GPU_MAX_HW_QUEUES" in _os.environ:
         return

@@ -166,7 +166,7 @@ std::string info_string();   // process-wide state in one line (ps_info)
 struct MemInfo { size_t slabs = 0, slab_bytes = 0; int slabs_planned = 0; long long pool_bytes = 0; };
 MemInfo mem_info();          // ps_mem.cpp's part of it: slabs allocated (and their bytes) of how many, bytes in the pools of this process
 void for_idle_runtimes(const std::function<void(Runtime&)>& fn);   // fn on every runtime no thread owns, under the free list's lock
-int hwq_mode(std::string* why);   // 1: every stream on one priority level (a hardware queue each), 0: streams dealt over the levels
+int hwq_mode(std::string* why);   // 1: every stream on one priority level (a hardware queue each), 0: streams dealt over the levels, 2: a private queue per stream within a budget, the rest dealt
 int peak_runtimes();   // most host threads that ever owned a runtime at the same time
 int live_runtimes();   // host threads that currently own a runtime
 int guess_slots(const Align* a);   // anti-diagonal footprint realign() will probably choose

@@ -104,6 +104,41 @@ static int hwq_from_exec_env() {
     }();
     return v;
 }
+// Private queues.  Where HIP runs on its default of four pooled queues per level, a runtime's stream is created with a CU mask of
+// the whole device instead: the HIP runtime gives a stream with a CU mask a hardware queue of its own, outside the pool that
+// GPU_MAX_HW_QUEUES limits, on the normal priority level.  The process holds at most PORESEQ_PRIVATE_QUEUES of them (default and
+// ceiling 16, what the package asks HIP for; 0 switches them off), times the device fraction when several ranks share a GPU.
+// A runtime keeps its stream for the life of the process (free list above), so the count follows the most runtimes alive at once.
+namespace {
+std::atomic<int> g_pq_held(0);   // runtimes whose stream holds a private queue
+std::atomic<int> g_pq_fell(0);   // runtimes that were dealt a priority level instead (budget spent, or the create failed)
+}  // namespace
+static int private_queue_knob() {
+    static const int v = [] { const char* e = getenv("PORESEQ_PRIVATE_QUEUES"); return e ? std::max(0, std::min(atoi(e), 16)) : 16; }();
+    return v;
+}
+static int private_queue_budget() {
+    const int k = private_queue_knob();
+    return k > 0 ? std::max(1, (int)(k * device_fraction() + 1e-9)) : 0;
+}
+// a stream on a queue of its own when the budget has one left (false: the caller deals a priority level)
+static bool private_stream(hipStream_t* st, int cus) {
+    const int budget = private_queue_budget();
+    int held = g_pq_held.load();
+    bool mine = false;
+    while (cus > 0 && held < budget && !(mine = g_pq_held.compare_exchange_weak(held, held + 1))) {}
+    if (mine) {
+        std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0xffffffffu);   // (ROC_GLOBAL_CU_MASK still applies: HIP intersects the two)
+        if (cus % 32) mask.back() = (1u << (cus % 32)) - 1u;
+        if (hipExtStreamCreateWithCUMask(st, (uint32_t)mask.size(), mask.data()) == hipSuccess) return true;
+        (void)hipGetLastError();
+        *st = nullptr;
+        g_pq_held--;
+    }
+    g_pq_fell++;
+    return false;
+}
+
 int hwq_mode(std::string* why) {
     static int mode = -1;
     static std::string reason;
@@ -117,11 +152,9 @@ int hwq_mode(std::string* why) {
         else if (getenv("PORESEQ_PRIORITY_LEVELS")) { mode = 0; reason = "streams dealt over the priority levels (PORESEQ_PRIORITY_LEVELS)"; }
         else if (hwq_from_exec_env() >= 8) { mode = 1; reason = "one priority level, a hardware queue per stream (GPU_MAX_HW_QUEUES=" + std::to_string(hwq_from_exec_env()) + " in the process's start-up environment)"; }
         else if (now >= 8 && pk && atoi(pk) == 1) { mode = 1; reason = "one priority level, a hardware queue per stream (GPU_MAX_HW_QUEUES=" + std::to_string(now) + " exported by the poreseq_amd package before HIP started)"; }
-        else {
-            mode = 0;
-            reason = now >= 8 ? "streams dealt over the priority levels (GPU_MAX_HW_QUEUES=" + std::to_string(now) + " appeared after start-up without the package's guarantee that HIP had not started: not trusted)"
-                              : "streams dealt over the priority levels (HIP's default of 4 hardware queues per level)";
-        }
+        else if (now >= 8) { mode = 0; reason = "streams dealt over the priority levels (GPU_MAX_HW_QUEUES=" + std::to_string(now) + " appeared after start-up without the package's guarantee that HIP had not started: not trusted)"; }
+        else if (private_queue_knob() > 0) { mode = 2; reason = "a private hardware queue per stream (CU-masked streams beside HIP's default of 4 hardware queues per level)"; }
+        else { mode = 0; reason = "streams dealt over the priority levels (HIP's default of 4 hardware queues per level; private queues switched off by PORESEQ_PRIVATE_QUEUES=0)"; }
     }
     if (why) *why = reason;
     return mode;
@@ -186,13 +219,19 @@ int runtime(Runtime** out) {
             // batches on one level = seven streams on four queues, three kernels in flight on average, 108 kb/s.
             //  * GPU_MAX_HW_QUEUES >= 8 in force (hwq_mode() above: in the environment the process started with, or exported by the
             //    poreseq_amd package before HIP started): every runtime's stream on the default level, a queue each — 146-147 kb/s.
-            //  * otherwise the streams are dealt round-robin to the device's three priority levels, not for the priorities' sake but
+            //  * a value that is not trusted, no private queue to be had (below), or PORESEQ_PRIORITY_LEVELS: the streams are dealt
+            //    round-robin to the device's three priority levels, not for the priorities' sake but
             //    for the 3 x 4 queues: 141 kb/s — the two or three batches on the lowest level finish ~0.8 s after the others
             //    (profiles/r03_d_sweep_forms.md).
+            //  * HIP on its default (no value, or one below 8): a private queue per runtime while the budget lasts (private_stream()
+            //    above: a stream with a CU mask of the whole device; it is blocking with respect to the null stream, which the library
+            //    never enqueues on); runtimes beyond the budget are dealt as in the second case (profiles/stream_queues.md).
             // (PORESEQ_ONE_PRIORITY=1 forces the default level, PORESEQ_PRIORITY_LEVELS=1 the dealing.)
             auto make_stream = [&](hipStream_t* st) {
                 static std::atomic<int> seq(0);
-                const bool one = hwq_mode(nullptr) == 1;
+                const int mode = hwq_mode(nullptr);
+                if (mode == 2 && private_stream(st, prop.multiProcessorCount)) return hipSuccess;
+                const bool one = mode == 1;
                 int lo = 0, hi = 0;
                 if (!one && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo > hi)
                     return hipStreamCreateWithPriority(st, hipStreamNonBlocking, hi + seq++ % (lo - hi + 1));
@@ -339,7 +378,11 @@ void par_for(int n, const std::function<void(int)>& fn) {
 // one line about the process-wide state of the library (ps_info): stream / hardware-queue mode, runtimes, memory plan
 std::string info_string() {
     std::string why;
-    (void)hwq_mode(&why);
+    if (hwq_mode(&why) == 2) {   // how many runtimes hold a private queue, how many were dealt a priority level instead
+        const int held = g_pq_held.load(), fell = g_pq_fell.load();
+        why += ": " + std::to_string(held) + " private (budget " + std::to_string(private_queue_budget()) + ") on one priority level, " +
+               (fell ? std::to_string(fell) + " fell back and are dealt over the priority levels" : std::string("none fell back"));
+    }
     const MemInfo m = mem_info();
     char buf[512];
     snprintf(buf, sizeof buf, "; device fraction of this process %.3f; runtimes: %d live, %d peak; share per runtime %.1f GB; slabs for full score matrices: %zu of %d allocated (%.1f GB, %.1f GB each by plan); device pools of this process %.1f GB",
