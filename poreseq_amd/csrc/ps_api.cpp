@@ -250,6 +250,12 @@ static int stats_scores(const std::string& who, int32_t realign, double* const* 
     q->scores = scores[i];
     return PS_OK;
 }
+// What ps_batch_move_stats and ps_batch_posterior_stats check alike: an event with levels has an array wherever its AlignData passes them
+static int stats_levels(const std::string& who, const Align* a, const void* const* x, const void* const* y) {
+    for (int e = 0; e < a->E; e++)
+        if (a->n[e] > 0 && ((x && !x[e]) || (y && !y[e]))) return fail(PS_ERR_BAD_ARG, who + ": null per-level array of event " + std::to_string(e));
+    return PS_OK;
+}
 // and their end: no events anywhere launches nothing and takes no runtime (the tables of the k-mer call are all zero)
 static int stats_run(OwnKind kind, int32_t realign, std::vector<OwnReq>& rq) {
     if (std::none_of(rq.begin(), rq.end(), [](const OwnReq& q) { return q.a->E > 0; })) {
@@ -314,9 +320,7 @@ int ps_batch_move_stats(int32_t n, ps_align* const* a, double* const* scores, ps
         PS_TRY(stats_scores(who, 1, scores, i, &rq[i]));
         rq[i].a = as[i]; rq[i].moves = moves[i];
         rq[i].step = step ? step[i] : nullptr; rq[i].col = col ? col[i] : nullptr;
-        for (int e = 0; e < as[i]->E; e++)
-            if (as[i]->n[e] > 0 && ((rq[i].step && !rq[i].step[e]) || (rq[i].col && !rq[i].col[e])))
-                return fail(PS_ERR_BAD_ARG, who + ": null per-level array of event " + std::to_string(e));
+        PS_TRY(stats_levels(who, as[i], (const void* const*)rq[i].step, (const void* const*)rq[i].col));
     }
     return stats_run(OwnKind::MoveStats, 1, rq);
 }
@@ -339,9 +343,7 @@ int ps_batch_posterior_stats(int32_t n, ps_align* const* a, ps_event_posterior* 
         rq[i].a = as[i]; rq[i].post = stats[i];
         rq[i].emit = emit ? emit[i] : nullptr; rq[i].pcol = col ? col[i] : nullptr;
         if ((rq[i].emit == nullptr) != (rq[i].pcol == nullptr)) return fail(PS_ERR_BAD_ARG, who + ": emit and col go together");
-        for (int e = 0; e < as[i]->E; e++)
-            if (as[i]->n[e] > 0 && rq[i].emit && (!rq[i].emit[e] || !rq[i].pcol[e]))
-                return fail(PS_ERR_BAD_ARG, who + ": null per-level array of event " + std::to_string(e));
+        PS_TRY(stats_levels(who, as[i], (const void* const*)rq[i].emit, (const void* const*)rq[i].pcol));
     }
     return stats_run(OwnKind::Posterior, 0, rq);
 }

@@ -5,6 +5,7 @@
 #include <functional>
 
 #include "ps_internal.h"
+#include "ps_ownplan.h"   // OwnKind and the output plan of the own-sequence statistics (host-only, no HIP)
 
 namespace ps {
 
@@ -245,10 +246,9 @@ struct OwnReq {
 // scaling fit | ps_batch_kmer_stats: per AlignData, event group and 5-mer state the sums of a model re-estimation | ps_batch_move_stats:
 // per event the backtrace's moves, counted between the walk and the kernel that overwrites its records (ps_stats.hip) |
 // ps_batch_posterior_stats: per event the sum over all alignments in its band and the expected moves under it (ps_post.hip) — the
-// band stage of the fills, k_post_fwd, k_post_bwd; no backtrace, the handles' refs stay what they are (`realign` is ignored)
-enum class OwnKind { Score, AlignStats, KmerStats, MoveStats, Posterior };
-// reqs[0 .. n - 1] in one launch chain.  realign: ScoreAlignments' fills and backtraces first (Score, MoveStats: always); without, the
-// statistics reduce the refs the handles hold and no DP runs
+// band stage of the fills, k_post_fwd, k_post_bwd; no backtrace, the handles' refs stay what they are (`realign` is ignored): enum
+// class OwnKind { Score, AlignStats, KmerStats, MoveStats, Posterior }, ps_ownplan.h.  reqs[0 .. n - 1] in one launch chain.  realign:
+// ScoreAlignments' fills and backtraces first (Score, MoveStats: always); without, the statistics reduce the refs the handles hold
 int own_forward(Runtime* rt, OwnKind kind, bool realign, OwnReq* reqs, size_t n);
 int score_mutations(Runtime* rt, Align* a, const std::vector<Mut>& muts, std::vector<Mut>* out);
 void find_point_mutations(const Align* a, std::vector<Mut>* out);

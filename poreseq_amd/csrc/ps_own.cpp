@@ -1,10 +1,10 @@
 // ps_own.cpp — the calls that align every event of an AlignData to its own sequence, forward only: ScoreAlignments
-// (cpp/MakeMutations.cpp:148-195), ps_align_stats, ps_kmer_stats, ps_move_stats and — a chain of its own below, posterior():
-// sum-product fills instead of a realignment — ps_posterior_stats, for several AlignData in lock-step (independent regions in one
-// launch chain).  One request record per AlignData (OwnReq, ps_host.h) and one chain, own_forward: the cuts of a call that does not
-// fit this runtime's share, the batch, the optional realignment (with k_move_stats inside it for ps_move_stats, whose outputs are
-// placed before it), the tail the kinds differ in, the scores.  Batch and realign() are
-// in ps_host.cpp, struct Align in ps_align.cpp, the kernels of the three reductions in ps_stats.hip.
+// (cpp/MakeMutations.cpp:148-195), ps_align_stats, ps_kmer_stats, ps_move_stats and ps_posterior_stats, for several AlignData in
+// lock-step (independent regions in one launch chain).  One request record per AlignData (OwnReq, ps_host.h), one statement of
+// where the statistics' outputs lie in "astats" (OwnPlan, ps_ownplan.h) and one chain, own_forward, in stages: cut (a call that does
+// not fit this runtime's share), jobs, batch, plan, place, fills (the optional realignment, with k_move_stats inside it for
+// ps_move_stats; sum-product fills for ps_posterior_stats), reduce, fetch, scatter.  Batch and realign() are in ps_host.cpp,
+// struct Align in ps_align.cpp, the kernels of the three reductions in ps_stats.hip, those of the posterior call in ps_post.hip.
 #include "ps_host.h"
 
 #include <algorithm>
@@ -39,146 +39,8 @@ static void score_likes(OwnReq* reqs, size_t n) {
     });
 }
 
-// The descriptors of k_align_stats and k_kmer_stats for reqs[0 .. n - 1], whose events are the jobs of `b` in order: one StatJob per
-// event, one StatRegion per AlignData.  kmer: the events' group ids and the numbers of groups count; the regions' table rows follow
-// each other.  Returns the levels of all events.
-static double stat_descriptors(const OwnReq* reqs, size_t n, const Batch& b, bool kmer, std::vector<StatJob>* sj, std::vector<StatRegion>* sr, int* maxE) {
-    sj->assign(b.jobs.size(), StatJob());
-    sr->assign(n, StatRegion());
-    *maxE = 0;
-    double levels = 0;
-    size_t q = 0;
-    int tab = 0;
-    for (size_t k = 0; k < n; k++) {
-        const Align* a = reqs[k].a;
-        StatRegion& r = (*sr)[k];
-        r.job0 = (int)q; r.njobs = a->E; r.ngroups = kmer ? reqs[k].ngroups : 0; r.tab0 = tab;
-        tab += r.ngroups;
-        *maxE = std::max(*maxE, a->E);
-        for (int e = 0; e < a->E; e++, q++) {
-            const JobD& j = b.jobs[q];
-            StatJob& s = (*sj)[q];
-            s.ra = j.ra; s.mean = a->d_mean + a->off[e]; s.stdv = a->d_stdv + a->off[e]; s.model = a->d_model + (size_t)e * 6 * NS;
-            s.st = j.st; s.n = j.n0; s.S = j.C;
-            s.grp = kmer ? reqs[k].group[e] : 0; s.pad = 0;
-            levels += j.n0;
-        }
-    }
-    return levels;
-}
-
-// bytes of the tables of a k-mer call (48 KiB per group), and the most groups of one AlignData
-static size_t table_bytes(const OwnReq* reqs, size_t n, int* maxG = nullptr) {
-    size_t rows = 0;
-    for (size_t k = 0; k < n; k++) { rows += (size_t)reqs[k].ngroups; if (maxG) *maxG = std::max(*maxG, reqs[k].ngroups); }
-    return rows * NS * sizeof(ps_kmer_cell);
-}
-
-// The tail of the two statistics: the descriptors in through "astats_in"; one launch of k_align_stats or k_kmer_stats over the refs
-// the backtrace just wrote (re) or the handles hold; in "astats" the records or tables and, behind them, the scores (re), back in
-// one copy.  *best: the scores in that copy, null without a realignment.
-static int stats_tail(Runtime* rt, bool kmer, bool re, const Batch& b, OwnReq* reqs, size_t n, double** best) {
-    const size_t nj = b.jobs.size();
-    std::vector<StatJob> sj;
-    std::vector<StatRegion> sr;
-    int maxE = 0, maxG = 0;
-    const double levels = stat_descriptors(reqs, n, b, kmer, &sj, &sr, &maxE);
-    const size_t out_main = kmer ? table_bytes(reqs, n, &maxG) : nj * sizeof(ps_event_stats);
-    const double bytes = (kmer ? 24.0 : 16.0) * levels + (double)out_main;
-    const size_t in_jobs = nj * sizeof(StatJob), in_bytes = in_jobs + sr.size() * sizeof(StatRegion);
-    const size_t out_bytes = out_main + (re ? nj * sizeof(double) : 0);
-    DBuf& din = rt->buf("astats_in");
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(din.ensure(in_bytes));
-    PS_TRY(dout.ensure(out_bytes));
-    PS_TRY(rt->up(din.p, sj.data(), in_jobs));
-    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
-    const StatRegion* dsr = (const StatRegion*)((char*)din.p + in_jobs);
-    if (kmer) PS_TRY(launch_kmer_stats(rt, din.as<StatJob>(), dsr, (int)sr.size(), maxG, bytes, dout.as<ps_kmer_cell>()));
-    else PS_TRY(launch_align_stats(rt, din.as<StatJob>(), dsr, (int)sr.size(), maxE, bytes, dout.as<ps_event_stats>()));
-    if (re) PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + out_main)));
-    void* back = nullptr;
-    PS_TRY(rt->down(&back, dout.p, out_bytes));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    for (size_t k = 0; k < n; k++) {
-        if (kmer) memcpy(reqs[k].table, (const ps_kmer_cell*)back + (size_t)sr[k].tab0 * NS, (size_t)reqs[k].ngroups * NS * sizeof(ps_kmer_cell));
-        else memcpy(reqs[k].stats, (const ps_event_stats*)back + sr[k].job0, (size_t)reqs[k].a->E * sizeof(ps_event_stats));
-    }
-    *best = re ? (double*)((char*)back + out_main) : nullptr;
-    return PS_OK;
-}
-
-// ps_move_stats: k_move_stats runs INSIDE the realignment, between the walk and the kernel that overwrites the walk's records, so
-// its descriptors (through "astats_in") and its outputs (in "astats": the records, the scores, then the per-level columns and step
-// codes when a request wants them) are placed before realign() runs; no kernel of that chain touches either pool.
-struct MovePlan {
-    size_t nj = 0, levels = 0, sc_off = 0, col_off = 0, step_off = 0, out_bytes = 0;
-    bool per_level = false;
-    std::vector<size_t> lev_off;   // of every job in the per-level arrays
-};
-static int moves_place(Runtime* rt, Batch& b, const OwnReq* reqs, size_t n, MovePlan* mp) {
-    mp->nj = b.jobs.size();
-    std::vector<MoveJob> mj(mp->nj);
-    std::vector<StatRegion> sr(n);
-    int maxE = 0;
-    for (size_t k = 0; k < n; k++) mp->per_level |= reqs[k].step || reqs[k].col;
-    mp->lev_off.assign(mp->nj, 0);
-    for (size_t q = 0; q < mp->nj; q++) { mp->lev_off[q] = mp->levels; mp->levels += (size_t)b.jobs[q].n0; }
-    mp->sc_off = mp->nj * sizeof(ps_event_moves);
-    mp->col_off = mp->sc_off + mp->nj * sizeof(double);
-    mp->step_off = mp->col_off + (mp->per_level ? mp->levels * sizeof(int32_t) : 0);
-    mp->out_bytes = mp->step_off + (mp->per_level ? mp->levels : 0);
-    const size_t in_jobs = mp->nj * sizeof(MoveJob), in_bytes = in_jobs + n * sizeof(StatRegion);
-    DBuf& din = rt->buf("astats_in");
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(din.ensure(in_bytes));
-    PS_TRY(dout.ensure(mp->out_bytes));
-    size_t q = 0;
-    for (size_t k = 0; k < n; k++) {
-        const Align* a = reqs[k].a;
-        sr[k].job0 = (int)q; sr[k].njobs = a->E; sr[k].ngroups = 0; sr[k].tab0 = 0;
-        maxE = std::max(maxE, a->E);
-        for (int e = 0; e < a->E; e++, q++) {
-            const JobD& j = b.jobs[q];
-            MoveJob& m = mj[q];
-            m.rec = (const long long*)j.rl; m.out = j.out; m.n = j.n0; m.pad = 0;
-            m.col = reqs[k].col ? (int32_t*)((char*)dout.p + mp->col_off) + mp->lev_off[q] : nullptr;
-            m.step = reqs[k].step ? (uint8_t*)dout.p + mp->step_off + mp->lev_off[q] : nullptr;
-        }
-    }
-    PS_TRY(rt->up(din.p, mj.data(), in_jobs));
-    PS_TRY(rt->up((char*)din.p + in_jobs, sr.data(), n * sizeof(StatRegion)));
-    b.moves.jobs = din.as<MoveJob>();
-    b.moves.regs = (const StatRegion*)((char*)din.p + in_jobs);
-    b.moves.nregs = (int)n; b.moves.maxE = maxE;
-    b.moves.out = dout.as<ps_event_moves>();
-    b.moves.alg_bytes = (mp->per_level ? 13.0 : 8.0) * (double)mp->levels + (double)mp->sc_off;
-    return PS_OK;
-}
-// and its tail: the scores behind the records, everything back in one copy, the requests' arrays filled
-static int moves_tail(Runtime* rt, const Batch& b, const MovePlan& mp, OwnReq* reqs, size_t n, double** best) {
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(launch_gather_best(rt, b.d, (double*)((char*)dout.p + mp.sc_off)));
-    void* back = nullptr;
-    PS_TRY(rt->down(&back, dout.p, mp.out_bytes));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    size_t q = 0;
-    for (size_t k = 0; k < n; k++) {
-        const Align* a = reqs[k].a;
-        memcpy(reqs[k].moves, (const ps_event_moves*)back + q, (size_t)a->E * sizeof(ps_event_moves));
-        for (int e = 0; e < a->E; e++, q++) {
-            const size_t ne = (size_t)a->n[e];
-            if (reqs[k].col && reqs[k].col[e]) memcpy(reqs[k].col[e], (const int32_t*)((const char*)back + mp.col_off) + mp.lev_off[q], ne * sizeof(int32_t));
-            if (reqs[k].step && reqs[k].step[e]) memcpy(reqs[k].step[e], (const uint8_t*)back + mp.step_off + mp.lev_off[q], ne);
-        }
-    }
-    *best = (double*)((char*)back + mp.sc_off);
-    return PS_OK;
-}
-
-// ---- ps_posterior_stats: the band stage of the fills, k_post_fwd and k_post_bwd (ps_post.hip) over skewed {M, S} records in "rec";
-// the descriptors through "astats_in"; in "astats" the records and, behind them, the per-level arrays, back in one copy.  No
-// backtrace and no updaterefs: nothing of the handles changes.
+// ---- ps_posterior_stats' fills: the band stage, then k_post_fwd and k_post_bwd (ps_post.hip) over skewed {M, S} records in "rec".
+// No backtrace and no updaterefs: nothing of the handles changes.
 // bytes of the records of one AlignData at P slots per anti-diagonal: (n0 + C + 25) x P x 16 per event (matrix_cells, ps_plan.h)
 static double post_need(const Align* a, int P) {
     double t = 0;
@@ -216,63 +78,112 @@ static int post_place(Runtime* rt, Batch& b, double cap, bool can_split) {
     b.d.rec = (double2*)prec; b.d.flg = nullptr;
     return PS_OK;
 }
-static double post_cells(const Batch& b) {
-    double t = 0;
-    for (const JobD& j : b.jobs) t += (double)j.C * std::min<double>(2.0 * j.W + 1, j.n0);
-    return t;
-}
-static int posterior(Runtime* rt, OwnReq* reqs, size_t n) {
-    auto sub = [&](size_t k0, size_t k1) { return posterior(rt, reqs + k0, k1 - k0); };
-    auto need = [&](size_t k) { return post_need(reqs[k].a, post_slots(guess_slots(reqs[k].a))); };
-    if (n > 1 && over_share(n, 1, need)) return in_share_chunks(n, 1, need, sub);
-    std::vector<JobSpec> specs;
-    for (size_t k = 0; k < n; k++)
-        for (int e = 0; e < reqs[k].a->E; e++) specs.push_back(reqs[k].a->job(e));
-    if (specs.empty()) return PS_OK;
-    Batch b;
-    PS_TRY(b.build(rt, specs, 1, 0));
-    {
-        const int rc = post_place(rt, b, n > 1 ? PLAN_OVER_GUESS * share_cap(1) : share_cap(1), n > 1);
-        if (rc == PS_SPLIT) return in_halves(n, sub);   // bands wider than guessed: two halves, one after the other
-        PS_TRY(rc);
+
+// ---- the chain.  One call, or one sub-batch of it, on its way through the stages below, which fill it in this order
+struct OwnChain {
+    Runtime* rt; OwnKind kind; bool re;
+    OwnReq* r; size_t n;   // r[0 .. n - 1]
+    OwnView view; OwnPlan plan;
+    Batch b;     // (also without a realignment: it puts every sequence's states on the device)
+    DBuf *din = nullptr, *dout = nullptr;   // "astats_in", "astats"
+    const StatRegion* d_regs = nullptr;     // behind the job descriptors in "astats_in"
+    char* back = nullptr;                   // the copy of "astats" on the host
+    OwnChain(Runtime* rt_, OwnKind kind_, bool re_, OwnReq* r_, size_t n_) : rt(rt_), kind(kind_), re(re_), r(r_), n(n_) {
+        view.kind = kind; view.re = re;
+        for (size_t k = 0; k < n; k++) view.regs.push_back({r[k].a->E, r[k].ngroups, r[k].step || r[k].col || r[k].emit});
     }
-    const size_t nj = b.jobs.size();
-    bool per_level = false;
-    for (size_t k = 0; k < n; k++) per_level |= reqs[k].emit != nullptr;
-    std::vector<size_t> lev_off(nj, 0);
-    size_t levels = 0;
-    for (size_t q = 0; q < nj; q++) { lev_off[q] = levels; levels += (size_t)b.jobs[q].n0; }
-    const size_t emit_off = nj * sizeof(ps_event_posterior), col_off = emit_off + (per_level ? levels * sizeof(double) : 0);
-    const size_t out_bytes = col_off + (per_level ? levels * sizeof(double) : 0);   // what comes back; behind it the kernels' per-row sums
-    DBuf& din = rt->buf("astats_in");
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(din.ensure(nj * sizeof(PostJob)));
-    PS_TRY(dout.ensure(out_bytes + levels * 8 * sizeof(double)));
-    std::vector<PostJob> pj(nj);
-    size_t q = 0;
-    for (size_t k = 0; k < n; k++)
-        for (int e = 0; e < reqs[k].a->E; e++, q++) {
-            pj[q].emit = reqs[k].emit ? (double*)((char*)dout.p + emit_off) + lev_off[q] : nullptr;
-            pj[q].col = reqs[k].emit ? (double*)((char*)dout.p + col_off) + lev_off[q] : nullptr;
-            pj[q].row = (double*)((char*)dout.p + out_bytes) + lev_off[q] * 8;
-        }
-    PS_TRY(rt->up(din.p, pj.data(), nj * sizeof(PostJob)));
-    PS_TRY(launch_post(rt, b.d, b.P, din.as<PostJob>(), dout.as<ps_event_posterior>(), post_cells(b)));
-    void* back = nullptr;
-    PS_TRY(rt->down(&back, dout.p, out_bytes));
-    PS_HIP(hipStreamSynchronize(rt->stream));
-    q = 0;
-    for (size_t k = 0; k < n; k++) {
-        const Align* a = reqs[k].a;
-        memcpy(reqs[k].post, (const ps_event_posterior*)back + q, (size_t)a->E * sizeof(ps_event_posterior));
-        for (int e = 0; e < a->E; e++, q++) {
-            if (!reqs[k].emit || reqs[k].post[e].inert || !a->n[e]) continue;   // (an inert event's arrays were not written)
-            const size_t ne = (size_t)a->n[e];
-            if (reqs[k].emit[e]) memcpy(reqs[k].emit[e], (const double*)((const char*)back + emit_off) + lev_off[q], ne * sizeof(double));
-            if (reqs[k].pcol[e]) memcpy(reqs[k].pcol[e], (const double*)((const char*)back + col_off) + lev_off[q], ne * sizeof(double));
-        }
+    bool kmer() const { return kind == OwnKind::KmerStats; }
+    bool moves() const { return kind == OwnKind::MoveStats; }
+    bool post() const { return kind == OwnKind::Posterior; }
+};
+// the one walk over the events of r[0 .. n - 1], which are the jobs of the chain's batch in order: f(region k, event e, job q)
+template <class F> static void for_each_job(const OwnReq* r, size_t n, F&& f) {
+    for (size_t k = 0, q = 0; k < n; k++)
+        for (int e = 0; e < r[k].a->E; e++, q++) f(k, e, q);
+}
+
+// ---- stage: place.  Both pools sized; through "astats_in" one descriptor per job (StatJob, MoveJob or PostJob) and, behind them, one
+// StatRegion per AlignData (none for the posterior kernels), every address into "astats" from the plan.  Before the fills for every kind:
+// k_move_stats runs INSIDE the realignment, between the walk and the kernel that overwrites its records; no kernel there touches either pool.
+static int place(OwnChain& c) {
+    const OwnPlan& p = c.plan;
+    std::vector<StatJob> sj(c.moves() || c.post() ? 0 : p.nj);
+    std::vector<MoveJob> mj(c.moves() ? p.nj : 0);
+    std::vector<PostJob> pj(c.post() ? p.nj : 0);
+    std::vector<StatRegion> sr(c.post() ? 0 : c.n);
+    const size_t in_jobs = sj.size() * sizeof(StatJob) + mj.size() * sizeof(MoveJob) + pj.size() * sizeof(PostJob);
+    c.din = &c.rt->buf("astats_in"); c.dout = &c.rt->buf("astats");
+    PS_TRY(c.din->ensure(in_jobs + sr.size() * sizeof(StatRegion)));
+    PS_TRY(c.dout->ensure(p.ensure_bytes));
+    void* out = c.dout->p;
+    for (size_t k = 0; k < sr.size(); k++) sr[k] = {p.job0[k], c.r[k].a->E, c.kmer() ? c.r[k].ngroups : 0, p.tab0[k]};
+    for_each_job(c.r, c.n, [&](size_t k, int e, size_t q) {
+        const OwnReq& r = c.r[k]; const Align* a = r.a; const JobD& j = c.b.jobs[q];
+        if (c.post()) pj[q] = {r.emit ? p.level<double>(out, OO_EMIT, q) : nullptr, r.emit ? p.level<double>(out, OO_PCOL, q) : nullptr, p.level<double>(out, OO_ROW, q, 8)};
+        else if (c.moves()) mj[q] = {(const long long*)j.rl, j.out, r.step ? p.level<uint8_t>(out, OO_STEP, q) : nullptr, r.col ? p.level<int32_t>(out, OO_COL, q) : nullptr, j.n0, 0};
+        else sj[q] = {j.ra, a->d_mean + a->off[e], a->d_model + (size_t)e * 6 * NS, j.st, j.n0, j.C, a->d_stdv + a->off[e], c.kmer() ? r.group[e] : 0, 0};
+    });
+    PS_TRY(c.rt->up(c.din->p, c.post() ? (const void*)pj.data() : c.moves() ? (const void*)mj.data() : (const void*)sj.data(), in_jobs));
+    if (!sr.empty()) PS_TRY(c.rt->up((char*)c.din->p + in_jobs, sr.data(), sr.size() * sizeof(StatRegion)));
+    c.d_regs = (const StatRegion*)((char*)c.din->p + in_jobs);
+    if (c.moves()) {
+        MoveRun& m = c.b.moves;
+        m.jobs = c.din->as<MoveJob>(); m.regs = c.d_regs; m.nregs = (int)c.n; m.maxE = p.maxE;
+        m.out = p.item<ps_event_moves>(out, OO_MAIN); m.alg_bytes = p.alg_bytes;
     }
     return PS_OK;
+}
+
+// ---- stage: fills.  PS_SPLIT when the bands came out wider than the cut guessed; nothing of the fill was launched then.  A
+// realignment of one region is never split (cap 0); a lone posterior region gets the whole share and is refused beyond it.
+// host_refs_valid goes only after a realignment: the posterior fills change nothing of the handles.
+static int fills(OwnChain& c) {
+    if (c.post()) {
+        PS_TRY(post_place(c.rt, c.b, c.n > 1 ? PLAN_OVER_GUESS * share_cap(1) : share_cap(1), c.n > 1));
+        return launch_post(c.rt, c.b.d, c.b.P, c.din->as<PostJob>(), c.plan.item<ps_event_posterior>(c.dout->p, OO_MAIN), c.plan.alg_bytes);
+    }
+    if (!c.re) return PS_OK;
+    PS_TRY(realign(c.rt, c.b, c.n > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0));
+    for (size_t k = 0; k < c.n; k++) c.r[k].a->host_refs_valid = false;
+    return PS_OK;
+}
+
+// ---- stage: reduce.  One launch of k_align_stats or k_kmer_stats over the refs the backtrace just wrote or the handles hold
+// (k_move_stats ran inside the realignment, the posterior kernels are their own reduction), and the scores behind the records
+static int reduce(OwnChain& c) {
+    const OwnPlan& p = c.plan;
+    void* out = c.dout->p;
+    if (c.kmer()) PS_TRY(launch_kmer_stats(c.rt, c.din->as<StatJob>(), c.d_regs, (int)c.n, p.maxG, p.alg_bytes, p.item<ps_kmer_cell>(out, OO_MAIN)));
+    else if (c.kind == OwnKind::AlignStats) PS_TRY(launch_align_stats(c.rt, c.din->as<StatJob>(), c.d_regs, (int)c.n, p.maxE, p.alg_bytes, p.item<ps_event_stats>(out, OO_MAIN)));
+    if (p.bytes[OO_SCORES]) PS_TRY(launch_gather_best(c.rt, c.b.d, p.item<double>(out, OO_SCORES)));
+    return PS_OK;
+}
+
+// ---- stages: fetch, one copy and one synchronisation, and scatter: every output of the plan that a caller wants goes to its array
+static int fetch(OwnChain& c) {
+    PS_TRY(c.rt->down((void**)&c.back, c.dout->p, c.plan.back_bytes));
+    PS_HIP(hipStreamSynchronize(c.rt->stream));
+    return PS_OK;
+}
+static void scatter(OwnChain& c) {
+    const OwnPlan& p = c.plan;
+    const size_t rec = own_out_elem(c.kind, OO_MAIN);
+    for (size_t k = 0; k < c.n; k++) {
+        const OwnReq& r = c.r[k];
+        void* host = c.kmer() ? (void*)r.table : c.moves() ? (void*)r.moves : c.post() ? (void*)r.post : (void*)r.stats;
+        const size_t i0 = c.kmer() ? (size_t)p.tab0[k] * NS : (size_t)p.job0[k], cnt = c.kmer() ? (size_t)r.ngroups * NS : (size_t)r.a->E;
+        memcpy(host, p.item<char>(c.back, OO_MAIN, i0 * rec), cnt * rec);
+    }
+    if (!p.per_level) return;
+    for_each_job(c.r, c.n, [&](size_t k, int e, size_t q) {
+        const OwnReq& r = c.r[k]; const size_t ne = (size_t)r.a->n[e];
+        auto put = [&](void* to, OwnOut o) { const size_t el = own_out_elem(c.kind, o); if (to) memcpy(to, p.level<char>(c.back, o, q, el), ne * el); };
+        if (r.col) put(r.col[e], OO_COL);
+        if (r.step) put(r.step[e], OO_STEP);
+        if (!r.emit || r.post[e].inert || !ne) return;   // (an inert event's arrays were not written)
+        put(r.emit[e], OO_EMIT);
+        put(r.pcol[e], OO_PCOL);
+    });
 }
 
 // ps_debug_posterior: the same chain for one event, then its records un-skewed (the band per column from the lb table, as debug_fill)
@@ -281,14 +192,16 @@ int debug_posterior(Runtime* rt, Align* a, int ev, double* main, double* stay) {
     Batch b;
     PS_TRY(b.build(rt, specs, 1, 0));
     PS_TRY(post_place(rt, b, share_cap(1), false));
-    DBuf& din = rt->buf("astats_in");
-    DBuf& dout = rt->buf("astats");
-    PS_TRY(din.ensure(sizeof(PostJob)));
-    PS_TRY(dout.ensure(128 + (size_t)a->n[ev] * 8 * sizeof(double)));
-    const PostJob none = {nullptr, nullptr, (double*)((char*)dout.p + 128)};
-    PS_TRY(rt->up(din.p, &none, sizeof(none)));
-    PS_TRY(launch_post(rt, b.d, b.P, din.as<PostJob>(), dout.as<ps_event_posterior>(), post_cells(b)));
     const JobD& J = b.jobs[0];
+    OwnView view;   // a one-event call without per-level arrays
+    view.kind = OwnKind::Posterior; view.regs.push_back({1, 0, false}); view.jobs.push_back({J.n0, J.C, J.W});
+    const OwnPlan plan = lay_out(view);
+    DBuf &din = rt->buf("astats_in"), &dout = rt->buf("astats");
+    PS_TRY(din.ensure(sizeof(PostJob)));
+    PS_TRY(dout.ensure(plan.ensure_bytes));
+    const PostJob none = {nullptr, nullptr, plan.level<double>(dout.p, OO_ROW, 0, 8)};
+    PS_TRY(rt->up(din.p, &none, sizeof(none)));
+    PS_TRY(launch_post(rt, b.d, b.P, din.as<PostJob>(), plan.item<ps_event_posterior>(dout.p, OO_MAIN), plan.alg_bytes));
     const int n0 = J.n0, C = J.C, P = J.P;
     const size_t ld = (size_t)C + 1, tot = ((size_t)n0 + 1) * ld;
     const double nan = std::nan("");
@@ -316,38 +229,35 @@ int debug_posterior(Runtime* rt, Align* a, int ev, double* main, double* stay) {
 }
 
 int own_forward(Runtime* rt, OwnKind kind, bool re, OwnReq* reqs, size_t n) {
-    if (kind == OwnKind::Posterior) return posterior(rt, reqs, n);
-    const bool kmer = kind == OwnKind::KmerStats;
+    OwnChain c(rt, kind, re, reqs, n);
     auto sub = [&](size_t k0, size_t k1) { return own_forward(rt, kind, re, reqs + k0, k1 - k0); };   // regions k0 .. k1 - 1 as a call of their own
-    // a k-mer call whose tables exceed this runtime's share is cut between AlignData
-    if (kmer && n > 1 && (double)table_bytes(reqs, n) > device_share_bytes()) return in_halves(n, sub);
-    auto need = [&](size_t k) { return share_need(reqs[k].a, 1); };
-    if (re && over_share(n, 1, need)) return in_share_chunks(n, 1, need, sub);   // more matrices than this runtime's share of the device
+    // ---- cut.  A k-mer call whose tables exceed this runtime's share is halved between AlignData; fills — a realignment only when
+    // it runs — are cut to the share on a guess of their matrices (share_need) or forward tables (post_need)
+    if (c.kmer() && n > 1 && (double)lay_out(c.view).bytes[OO_MAIN] > device_share_bytes()) return in_halves(n, sub);
+    auto need = [&](size_t k) { return c.post() ? post_need(reqs[k].a, post_slots(guess_slots(reqs[k].a))) : share_need(reqs[k].a, 1); };
+    if ((re || c.post()) && over_share(n, 1, need)) return in_share_chunks(n, 1, need, sub);
+    // ---- jobs, batch
     std::vector<JobSpec> specs;
-    for (size_t k = 0; k < n; k++)
-        for (int e = 0; e < reqs[k].a->E; e++) specs.push_back(reqs[k].a->job(e));
-    if (specs.empty()) {
-        for (size_t k = 0; kmer && k < n; k++) memset(reqs[k].table, 0, (size_t)reqs[k].ngroups * NS * sizeof(ps_kmer_cell));
+    for_each_job(reqs, n, [&](size_t k, int e, size_t) { specs.push_back(reqs[k].a->job(e)); });
+    if (specs.empty()) {   // (the tables of a k-mer call without events: zeroed here)
+        for (size_t k = 0; c.kmer() && k < n; k++) memset(reqs[k].table, 0, (size_t)reqs[k].ngroups * NS * sizeof(ps_kmer_cell));
         return PS_OK;
     }
-    Batch b;   // (also without a realignment: it puts every sequence's states on the device)
-    PS_TRY(b.build(rt, specs, 1, 0));
-    MovePlan mp;
-    if (kind == OwnKind::MoveStats) PS_TRY(moves_place(rt, b, reqs, n, &mp));
-    if (re) {
-        const int rc = realign(rt, b, n > 1 ? PLAN_OVER_GUESS * device_share_bytes() : 0.0);
-        if (rc == PS_SPLIT) return in_halves(n, sub);   // bands wider than share_need guessed: two halves, one after the other
-        PS_TRY(rc);
-        for (size_t k = 0; k < n; k++) reqs[k].a->host_refs_valid = false;
+    PS_TRY(c.b.build(rt, specs, 1, 0));
+    // ---- plan, place: the statistics' outputs in "astats" (ScoreAlignments has none there: its scores go through "best")
+    if (kind != OwnKind::Score) {
+        for (const JobD& j : c.b.jobs) c.view.jobs.push_back({j.n0, j.C, j.W});
+        c.plan = lay_out(c.view);
+        PS_TRY(place(c));
     }
+    if (const int rc = fills(c)) return rc == PS_SPLIT ? in_halves(n, sub) : rc;   // bands wider than guessed: two halves, one after the other
     double* best = nullptr;
-    if (kind == OwnKind::Score) PS_TRY(score_tail(rt, b, reqs, n, &best));
-    else if (kind == OwnKind::MoveStats) PS_TRY(moves_tail(rt, b, mp, reqs, n, &best));
-    else PS_TRY(stats_tail(rt, kmer, re, b, reqs, n, &best));
-    size_t q = 0;
-    for (size_t k = 0; best && k < n; k++)
-        for (int e = 0; e < reqs[k].a->E; e++, q++)
-            if (reqs[k].scores) reqs[k].scores[e] = std::max(best[q], 0.0);   // Alignment::getMax, cpp/Alignment.h:127-130
+    if (kind == OwnKind::Score) PS_TRY(score_tail(rt, c.b, reqs, n, &best));
+    else {
+        PS_TRY(reduce(c)); PS_TRY(fetch(c)); scatter(c);
+        if (c.plan.bytes[OO_SCORES]) best = c.plan.item<double>(c.back, OO_SCORES);
+    }
+    if (best) for_each_job(reqs, n, [&](size_t k, int e, size_t q) { if (reqs[k].scores) reqs[k].scores[e] = std::max(best[q], 0.0); });   // Alignment::getMax, cpp/Alignment.h:127-130
     if (kind == OwnKind::Score) score_likes(reqs, n);
     return PS_OK;
 }
